@@ -7,9 +7,12 @@ A "step" is one pass of the hot path over one batch of B synthetic KITTI-shaped 
 Inputs are resident in HBM before the timed region.  N>1: one process per GPU (one client per GPU,
 independent streams, no data-path collective => weak scaling); launched by torch.distributed.run.
 
-Prints ONE JSON line (rank 0).  `roofline` is for the kernel with the largest share of device time,
-measured with HIP events on the library's own stream; `cpu_baseline` is the CPU oracle (a port of the
-reference algorithm, 2 threads like the reference's left/right extraction threads) on a bounded sample.
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the K steps and prints the headline
+(`value`, `ms_per_step`); everything else is measured with --full only: `roofline` (the kernel with the
+largest share of device time, HIP events on the library's own stream), `cpu_baseline` (the CPU oracle, a
+port of the reference algorithm, 2 threads like the reference's left/right extraction threads, on a
+bounded sample), the repeats, host-buffer, map-push, BA, 1080p, latency and client-loop legs.
+--dump-outputs DIR writes what the last timed step computed (a fixed sample of its frames) as .npy files.
 """
 import argparse
 import json
@@ -387,7 +390,7 @@ def ba_cpu_summary(rec):
 
 def compact_line(out):
     """The line the driver parses, below 8 KB: notes, per-kernel tables and the figures already carried by roofline.ba_config5 / cpu_baseline.ba_same_size dropped
-    (the long form: stderr, gpurun_out/bench_full.json, or --full)."""
+    (the long form: stderr with --full, the file of --record, or the line itself with --long-line)."""
     drop = {"note", "kernels", "structure", "sample_note", "generator_s", "record_bytes", "staging_s", "per_level", "source", "whole_step", "alone_unsplit_avg_us",
             "bytes_in", "bytes_out", "calls", "n_left", "n_matched", "p90_ms", "mean", "checks_passed", "kernels_alone_us_B1", "whole_box_extrapolated"}
 
@@ -420,6 +423,28 @@ def compact_line(out):
     return c
 
 
+DUMP_FRAMES = 32            # frames of the last step's output written by --dump-outputs (~0.6 MB each as float32)
+
+
+def dump_outputs(h, B, d):
+    """--dump-outputs: what the timed path handed its caller in the last step (StereoFrontend.fetch of each frame), for a fixed, seeded sample of the step's
+    B frames, as float32 / float64 .npy files: per-frame counts, keypoints (x, y, size, angle, response, octave, class_id), descriptor bytes, u_right, depth."""
+    os.makedirs(d, exist_ok=True)
+    idx = np.sort(np.random.default_rng(0).choice(B, size=min(B, DUMP_FRAMES), replace=False))
+    res = [h.fetch(int(f)) for f in idx]
+    kp = lambda k: np.stack([k[n].astype(np.float32) for n in k.dtype.names], 1).reshape(-1, len(k.dtype.names))
+    arrs = dict(frames=idx.astype(np.float64),
+                n_matched=np.array([o["n_matched"] for o in res], np.float64),
+                left_counts=np.array([len(o["kl"]) for o in res], np.float64), right_counts=np.array([len(o["kr"]) for o in res], np.float64),
+                left_keypoints=np.concatenate([kp(o["kl"]) for o in res]), right_keypoints=np.concatenate([kp(o["kr"]) for o in res]),
+                left_descriptors=np.concatenate([o["dl"].astype(np.float32) for o in res]).reshape(-1, 32),
+                right_descriptors=np.concatenate([o["dr"].astype(np.float32) for o in res]).reshape(-1, 32),
+                u_right=np.concatenate([o["u_right"] for o in res]).astype(np.float32), depth=np.concatenate([o["depth"] for o in res]).astype(np.float32))
+    assert sum(a.nbytes for a in arrs.values()) < 64 << 20
+    for k, a in arrs.items():
+        np.save(os.path.join(d, k + ".npy"), a)
+
+
 def main():
     if len(sys.argv) >= 5 and sys.argv[1] == "--cpu-worker":          # one client of cpu_baseline's throughput sample (no GPU, no torch)
         import corbload
@@ -434,15 +459,25 @@ def main():
     ap.add_argument("--steps", type=int, default=32)
     ap.add_argument("--warmup", type=int, default=4)
     ap.add_argument("--batch", type=int, default=512, help="stereo frames per step (per GPU); a run is issued as two part-batches, see corb_run_parts")
-    ap.add_argument("--cpu-frames", type=int, default=96, help="frames of the CPU baseline sample (0 = skip)")
-    ap.add_argument("--no-profile", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="only the timed region (for rocprofv3 runs: no stand-alone kernel timing, no host-buffer / map-push / BA / replay legs)")
+    ap.add_argument("--cpu-frames", type=int, default=96, help="with --full: frames of the CPU baseline sample (0 = skip)")
+    ap.add_argument("--no-profile", action="store_true", help="with --full: no HIP-event pairs in the timed region (no roofline)")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: only the timed region and its roofline (for rocprofv3 runs: no stand-alone kernel timing, no host-buffer / map-push / BA / replay legs)")
     ap.add_argument("--inflight", type=int, default=1, help="batches in flight per GPU (independent handles/streams, steps alternate between them)")
-    ap.add_argument("--ba-cpu-kf", type=int, default=150, help="keyframes/client (x8) of the BA problem that is solved on the GPU AND on the CPU oracle (0 = skip)")
-    ap.add_argument("--replay-frames", type=int, default=400, help="frames of the configs[2] client-loop replay (0 = skip)")
-    ap.add_argument("--full", action="store_true", help="print the long record (every note and per-kernel table, ~16 KB) as the line instead of the compact one (< 8 KB)")
-    ap.add_argument("--ba-kf", type=int, default=6250, help="keyframes/client (x8) of the config-5-size BA problem, GPU only (0 = skip)")
+    ap.add_argument("--ba-cpu-kf", type=int, default=150, help="with --full: keyframes/client (x8) of the BA problem that is solved on the GPU AND on the CPU oracle (0 = skip)")
+    ap.add_argument("--replay-frames", type=int, default=400, help="with --full: frames of the configs[2] client-loop replay (0 = skip)")
+    ap.add_argument("--full", action="store_true", help="besides the headline, measure everything else: roofline (event pairs in the timed region), repeats, host buffers, map push, "
+                                                         "CPU baselines, BA, 1080p, latency and client loop; the long record (~16 KB) goes to stderr")
+    ap.add_argument("--long-line", action="store_true", help="print the long record (every note and per-kernel table) as the line instead of the compact one (< 8 KB)")
+    ap.add_argument("--record", metavar="FILE", help="also write the long record to FILE")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last step computed (a fixed sample of %d frames) as DIR/<name>.npy" % DUMP_FRAMES)
+    ap.add_argument("--ba-kf", type=int, default=6250, help="with --full: keyframes/client (x8) of the config-5-size BA problem, GPU only (0 = skip)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    profile = args.full and not args.no_profile          # a plain run times the steps alone: no event pairs, no legs beside the headline
+    if not args.full or args.no_extras:
+        args.no_extras = True
+        args.cpu_frames = 0; args.ba_cpu_kf = 0; args.ba_kf = 0; args.replay_frames = 0
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` without a launcher: start the N ranks ourselves, one per GPU, exactly as the driver's torch.distributed.run line does
@@ -508,7 +543,7 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    if not args.no_profile:
+    if profile:
         for h in sfs:
             h.orb.profile(True); h.orb.profile(False)      # creates the profiler's event pool outside the timed region
     for i in range(warm_steps):
@@ -521,21 +556,21 @@ def main():
     PROF_AT = 4                                         # timestamps, no marker packets) -- steps 4, 12, 20 ...: NOT step 0, whose first part-batch meets an empty GPU after
     for i in range(args.steps):                          # the barrier (its FAST launch ran 0.9 instead of 1.4 ms and pulled the average 10 % under rocprofv3's)
         h = sfs[i % NH]                                  # K steps; step i runs on handle i % NH (own streams)
-        if not args.no_profile:
+        if profile:
             h.orb.profile((i // NH) % PROF_EVERY == PROF_AT % PROF_EVERY if args.steps > PROF_AT else i == args.steps - 1)
         h.run(B)
     for h in sfs:
         h.sync()
     barrier()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(sfs[(args.steps - 1) % NH], B, args.dump_outputs)
     prof = {}
-    if args.no_extras:
-        args.cpu_frames = 0; args.ba_cpu_kf = 0; args.ba_kf = 0; args.replay_frames = 0
     if world > 1:
         # N > 1 is the scaling run: the CPU baselines, the BA legs and the client replay are single-GPU records (rank 0 at N = 1 only); what N ranks add is the
         # weak-scaling figure and the map push between them -- and the other ranks must not sit in the final barrier while rank 0 spends minutes on extras
         args.cpu_frames = 0; args.ba_cpu_kf = 0; args.ba_kf = 0; args.replay_frames = 0
-    if not args.no_profile:
+    if profile:
         for h in sfs:
             for k, v in h.orb.profile_read().items():
                 a = prof.get(k, (0.0, 0)); prof[k] = (a[0] + v[0], a[1] + v[1])
@@ -774,47 +809,46 @@ def main():
                                  for k, v in sorted(prof.items(), key=lambda kv: -kv[1][0])},
                         alone_unsplit_avg_us=alone, dominant_by="time alone on the GPU" if alone else "time inside the pipeline")
         # never `value`: the same step with the images handed over as host buffers and every result fetched (one copy each way)
-        packed = np.ascontiguousarray(np.stack([np.stack(frames[s % distinct]) for s in range(B)]))
-        hb_out = sf.fetch_batch(0, B)
-        def host_step():
-            sf.upload_batch(0, packed); sf.run(B); sf.fetch_batch(0, B, hb_out)
-        NHB = 0 if args.no_extras else 5
-        if NHB:
+        host_buffers = None
+        if not args.no_extras:
+            packed = np.ascontiguousarray(np.stack([np.stack(frames[s % distinct]) for s in range(B)]))
+            hb_out = sf.fetch_batch(0, B)
+            def host_step():
+                sf.upload_batch(0, packed); sf.run(B); sf.fetch_batch(0, B, hb_out)
+            NHB = 5
             host_step()
-        t1 = time.perf_counter()
-        for _ in range(NHB):
-            host_step()
-        hb_dt = (time.perf_counter() - t1) / max(NHB, 1) or 1e-9
-        host_buffers = dict(value=round(B / hb_dt, 1), unit="stereo frames/s", ms_per_step=round(hb_dt * 1e3, 3),
-                            note="PCIe-inclusive: %.1f MB in + %.1f MB out per step, pageable host memory, transfers and compute serialised" % (
-                                packed.nbytes / 1e6, sum(v.nbytes for v in hb_out.values()) / 1e6))
-        # the same with page-locked buffers and TWO handles in a software pipeline: while one handle's results travel back, the other
-        # handle's images travel in and its kernels run (what a server fed from the network would do)
-        try:
-            if args.no_extras:
-                raise RuntimeError("skipped (--no-extras)")
-            sf_b = corb.StereoFrontend(nfeatures=KITTI["nfeatures"], width=KITTI["width"], height=KITTI["height"], max_frames=B, fx=KITTI["fx"], bf=KITTI["bf"], device=dev_index)
-            pin_in = corb.pinned_empty(packed.shape, np.uint8); pin_in[...] = packed
-            pin_out = [dict((k, corb.pinned_empty(v.shape, v.dtype)) for k, v in hb_out.items()) for _ in range(2)]
-            pair = [sf, sf_b]
-            def pipe(n):
-                pair[0].upload_batch(0, pin_in); pair[0].run(B)
-                for i in range(n):
-                    pair[(i + 1) & 1].upload_batch(0, pin_in); pair[(i + 1) & 1].run(B)
-                    pair[i & 1].fetch_batch(0, B, pin_out[i & 1])
-                pair[n & 1].sync()
-            pipe(3)
-            ok = all(np.array_equal(pin_out[j]["counts"], hb_out["counts"]) and np.array_equal(pin_out[j]["desc"][0][: hb_out["counts"][0]], hb_out["desc"][0][: hb_out["counts"][0]]) for j in range(2))
-            t1 = time.perf_counter(); NP = 12
-            pipe(NP)
-            pp_dt = (time.perf_counter() - t1) / (NP + 1)
-            host_buffers["pipelined"] = dict(value=round(B / pp_dt, 1), unit="stereo frames/s", ms_per_batch=round(pp_dt * 1e3, 3), verified=bool(ok),
-                                             h2d_GBps=round(packed.nbytes / pp_dt / 1e9, 1), d2h_GBps=round(sum(v.nbytes for v in hb_out.values()) / pp_dt / 1e9, 1),
-                                             note="page-locked host buffers, two handles: transfers of one batch overlap the kernels of the other; "
-                                                  "bound by the host link (h2d_GBps = image bytes per second over PCIe), not by the kernels")
-            sf_b.close()
-        except Exception as e:
-            host_buffers["pipelined"] = dict(error=str(e)[:200])
+            t1 = time.perf_counter()
+            for _ in range(NHB):
+                host_step()
+            hb_dt = (time.perf_counter() - t1) / NHB
+            host_buffers = dict(value=round(B / hb_dt, 1), unit="stereo frames/s", ms_per_step=round(hb_dt * 1e3, 3),
+                                note="PCIe-inclusive: %.1f MB in + %.1f MB out per step, pageable host memory, transfers and compute serialised" % (
+                                    packed.nbytes / 1e6, sum(v.nbytes for v in hb_out.values()) / 1e6))
+            # the same with page-locked buffers and TWO handles in a software pipeline: while one handle's results travel back, the other
+            # handle's images travel in and its kernels run (what a server fed from the network would do)
+            try:
+                sf_b = corb.StereoFrontend(nfeatures=KITTI["nfeatures"], width=KITTI["width"], height=KITTI["height"], max_frames=B, fx=KITTI["fx"], bf=KITTI["bf"], device=dev_index)
+                pin_in = corb.pinned_empty(packed.shape, np.uint8); pin_in[...] = packed
+                pin_out = [dict((k, corb.pinned_empty(v.shape, v.dtype)) for k, v in hb_out.items()) for _ in range(2)]
+                pair = [sf, sf_b]
+                def pipe(n):
+                    pair[0].upload_batch(0, pin_in); pair[0].run(B)
+                    for i in range(n):
+                        pair[(i + 1) & 1].upload_batch(0, pin_in); pair[(i + 1) & 1].run(B)
+                        pair[i & 1].fetch_batch(0, B, pin_out[i & 1])
+                    pair[n & 1].sync()
+                pipe(3)
+                ok = all(np.array_equal(pin_out[j]["counts"], hb_out["counts"]) and np.array_equal(pin_out[j]["desc"][0][: hb_out["counts"][0]], hb_out["desc"][0][: hb_out["counts"][0]]) for j in range(2))
+                t1 = time.perf_counter(); NP = 12
+                pipe(NP)
+                pp_dt = (time.perf_counter() - t1) / (NP + 1)
+                host_buffers["pipelined"] = dict(value=round(B / pp_dt, 1), unit="stereo frames/s", ms_per_batch=round(pp_dt * 1e3, 3), verified=bool(ok),
+                                                 h2d_GBps=round(packed.nbytes / pp_dt / 1e9, 1), d2h_GBps=round(sum(v.nbytes for v in hb_out.values()) / pp_dt / 1e9, 1),
+                                                 note="page-locked host buffers, two handles: transfers of one batch overlap the kernels of the other; "
+                                                      "bound by the host link (h2d_GBps = image bytes per second over PCIe), not by the kernels")
+                sf_b.close()
+            except Exception as e:
+                host_buffers["pipelined"] = dict(error=str(e)[:200])
         cpu = cpu_baseline(args.cpu_frames, synth, seed0) if args.cpu_frames > 0 else None
         ba = ba_bench(corb, synth, dev_index, args.ba_cpu_kf, args.ba_kf) if (args.ba_cpu_kf > 0 or args.ba_kf > 0) else None
         hd = None; latency = None
@@ -882,20 +916,22 @@ def main():
         }
         # BASELINE.json's metric has two halves.  The second (global-BA LM iterations/s on the fused 8-client map, configs[4]'s size) goes where the driver's record keeps
         # objects whole -- `roofline` and `cpu_baseline` -- and the line itself stays below 8 KB: the long form (every note, the per-kernel tables)
-        # is written to stderr and to gpurun_out/bench_full.json; `--full` prints it as the line instead
+        # is written to stderr by --full and to the file of --record; `--long-line` prints it as the line instead
         if ba and isinstance(out["roofline"], dict) and "config5" in ba:
             out["roofline"]["ba_config5"] = ba_summary(ba["config5"])
         if ba and isinstance(out["cpu_baseline"], dict) and "same_size" in ba:
             out["cpu_baseline"]["ba_same_size"] = ba_cpu_summary(ba["same_size"])
         full_line = json.dumps(out)
-        try:
-            os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
-            with open(os.path.join(ROOT, "gpurun_out", "bench_full.json"), "w") as f:
-                f.write(full_line + "\n")
-        except OSError:
-            pass
-        if not args.full:
-            print(full_line, file=sys.stderr)
+        if args.record:
+            try:
+                os.makedirs(os.path.dirname(os.path.abspath(args.record)), exist_ok=True)
+                with open(args.record, "w") as f:
+                    f.write(full_line + "\n")
+            except OSError:
+                pass
+        if not args.long_line:
+            if args.full:
+                print(full_line, file=sys.stderr)
             out = compact_line(out)
         sys.stdout.flush()
         try:
@@ -904,7 +940,7 @@ def main():
         except Exception:
             pass
         os.dup2(real_stdout, 1)
-        print(json.dumps(out, separators=(",", ":")) if not args.full else full_line); sys.stdout.flush()
+        print(json.dumps(out, separators=(",", ":")) if not args.long_line else full_line); sys.stdout.flush()
     if abandon:                                          # a collective of the abandoned leg may still be pending: no barrier, no destructors
         sys.stdout.flush(); sys.stderr.flush(); os._exit(0)
     for h in sfs:

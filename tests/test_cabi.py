@@ -120,3 +120,36 @@ def test_bench_line_stays_below_eight_kilobytes_and_carries_both_metrics():
     assert c["config"] == d["config"]
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data"):
         assert k in c
+
+
+def test_bench_dump_outputs_writes_a_fixed_float_sample(tmp_path):
+    """bench.py --dump-outputs: the last step's results of a fixed, seeded sample of the step's frames, float32 / float64 only, below 64 MB, the same from run to run
+    (a stand-in handle returns per-frame results in StereoFrontend.fetch's form)."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    b = importlib.util.module_from_spec(spec); spec.loader.exec_module(b)
+    kp_dtype = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4"), ("response", "<f4"), ("octave", "<i4"), ("class_id", "<i4")])
+
+    class Handle:
+        def fetch(self, f):
+            r = np.random.default_rng(f); nl, nr = 5 + f % 7, 3 + f % 5
+            kl = np.zeros(nl, kp_dtype); kl["x"] = r.random(nl) * 1241; kl["octave"] = r.integers(0, 8, nl)
+            kr = np.zeros(nr, kp_dtype); kr["y"] = r.random(nr) * 376
+            return dict(kl=kl, dl=r.integers(0, 256, (nl, 32), dtype=np.uint8), kr=kr, dr=r.integers(0, 256, (nr, 32), dtype=np.uint8),
+                        u_right=r.random(nl).astype(np.float32), depth=r.random(nl).astype(np.float32), n_matched=f % 4)
+
+    B = 512
+    b.dump_outputs(Handle(), B, str(tmp_path / "a"))
+    b.dump_outputs(Handle(), B, str(tmp_path / "b"))
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(os.listdir(tmp_path / "b")) and "left_keypoints.npy" in names and "u_right.npy" in names
+    arrs = dict((n, np.load(str(tmp_path / "a" / n))) for n in names)
+    assert all(a.dtype in (np.float32, np.float64) for a in arrs.values()) and sum(a.nbytes for a in arrs.values()) < 64 << 20
+    for n in names:
+        assert np.array_equal(arrs[n], np.load(str(tmp_path / "b" / n)))
+    fr = arrs["frames.npy"].astype(int)
+    assert len(fr) == b.DUMP_FRAMES and len(set(fr)) == len(fr) and fr.min() >= 0 and fr.max() < B
+    h = Handle()
+    assert arrs["left_counts.npy"].tolist() == [len(h.fetch(int(f))["kl"]) for f in fr]
+    assert arrs["left_keypoints.npy"].shape == (int(arrs["left_counts.npy"].sum()), 7) and arrs["left_descriptors.npy"].shape == (int(arrs["left_counts.npy"].sum()), 32)
+    assert np.array_equal(arrs["left_descriptors.npy"][: len(h.fetch(int(fr[0]))["dl"])], h.fetch(int(fr[0]))["dl"].astype(np.float32))

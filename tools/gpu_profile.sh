@@ -6,7 +6,7 @@ TAG=$1
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 OUT=gpurun_out/$TAG; RAW=/tmp/corb_prof_$TAG
 mkdir -p $OUT $RAW
-CMD="python bench.py --no-extras --steps 32 --warmup 4"
+CMD="python bench.py --full --no-extras --steps 32 --warmup 4"
 timeout 240 rocprofv3 --kernel-trace --stats -d $RAW -o stats -- $CMD > $OUT/bench_under_rocprof.json 2> $RAW/stats.log
 python tools/rocprof_summary.py $RAW/stats_results.db $OUT/kernel_stats.txt > /dev/null
 CMD="python bench.py --no-extras --steps 32 --warmup 1 --no-profile"      # same frames per step (hence images per launch) as the default bench line

@@ -3,10 +3,11 @@
 # usage (on the GPU box, via gpurun): tools/gpu_quick.sh [pytest selection...]
 sel=${@:-tests/test_gpu_orb.py}
 timeout 900 python -m pytest $sel -x -q 2>&1 | tail -4
-timeout 400 python bench.py --cpu-frames 0 --ba-cpu-kf 0 --ba-kf 0 --replay-frames 0 > gpurun_out/quick.json 2> gpurun_out/quick.err || tail -5 gpurun_out/quick.err
-python - <<'PY'
-import json
-d = json.loads(open('gpurun_out/quick.json').read())
+OUT=${QUICK_OUT:-${TMPDIR:-/tmp}}
+timeout 400 python bench.py --full --cpu-frames 0 --ba-cpu-kf 0 --ba-kf 0 --replay-frames 0 > $OUT/quick.json 2> $OUT/quick.err || tail -5 $OUT/quick.err
+QUICK_JSON=$OUT/quick.json python - <<'PY'
+import json, os
+d = json.loads(open(os.environ['QUICK_JSON']).read())
 r = d['roofline']
 print('fps', d['value'], 'ms/step', d['ms_per_step'])
 print({k: v['avg_us'] for k, v in r['kernels'].items()})
