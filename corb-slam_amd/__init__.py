@@ -35,6 +35,8 @@ EXPORTS = [
     "corb_mp_store_create", "corb_mp_store_destroy", "corb_mp_store_record_bytes", "corb_mp_store_put_host", "corb_mp_store_get",
     "corb_comm_create_local", "corb_comm_rank", "corb_comm_world", "corb_map_push_ex", "corb_map_push_plan", "corb_map_push_messages", "corb_comm_test_rccl_exchange", "corb_map_push_setup", "corb_map_push_begin", "corb_map_push_wait", "corb_rebase_map_store", "corb_ba_solve_store", "corb_local_ba_store", "corb_fuse_store", "corb_search_by_projection_scw_store", "corb_ba_solve_devflat", "corb_kf_store_put_batch", "corb_spd_solve",
     "corb_mp_store_build_index", "corb_kf_store_count", "corb_track_search_last_frame", "corb_track_pose_optimization", "corb_track_search_local_points", "corb_kf_store_put_frame",
+    "corb_rgbd_create", "corb_rgbd_destroy", "corb_rgbd_orb", "corb_rgbd_upload_batch", "corb_rgbd_run", "corb_rgbd_sync", "corb_rgbd_fetch_batch",
+    "corb_rgbd_frame_layout", "corb_rgbd_frames", "corb_rgbd_image_bounds", "corb_kf_store_put_from_rgbd",
 ]
 
 
@@ -50,6 +52,19 @@ class OrbConfig(C.Structure):
 
 class StereoConfig(C.Structure):
     _fields_ = [("orb", OrbConfig), ("max_frames", C.c_int32), ("fx", C.c_float), ("bf", C.c_float)]
+
+
+SENSOR_MONOCULAR, SENSOR_RGBD = 0, 2            # include/corb_accel.h: CORB_SENSOR_*
+DEPTH_U16, DEPTH_F32 = 0, 1                     # CORB_DEPTH_*
+
+
+class CameraConfig(C.Structure):
+    _fields_ = [("orb", OrbConfig), ("max_frames", C.c_int32), ("sensor", C.c_int32), ("channels", C.c_int32), ("rgb", C.c_int32)] + \
+               [(k, C.c_float) for k in ("fx", "fy", "cx", "cy", "k1", "k2", "p1", "p2", "k3", "bf", "depth_map_factor")] + [("depth_format", C.c_int32)]
+
+
+class RgbdFrameLayout(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ("capacity", "frame_bytes", "input_bytes", "off_keys", "off_keys_un", "off_desc", "off_u_right", "off_depth")]
 
 
 class KernelTime(C.Structure):
@@ -278,6 +293,17 @@ def load():
     L.corb_fuse_store.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(TrackCamera), C.c_void_p, C.c_float, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
     L.corb_local_ba_store.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(BAStage), C.c_int, C.c_float, C.c_int, C.c_void_p,
                                       C.POINTER(_BAResult), C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(BAOptions)]
+    L.corb_rgbd_create.argtypes = [C.POINTER(CameraConfig), C.POINTER(C.c_void_p)]
+    L.corb_rgbd_destroy.argtypes = [C.c_void_p]; L.corb_rgbd_destroy.restype = None
+    L.corb_rgbd_orb.argtypes = [C.c_void_p]; L.corb_rgbd_orb.restype = C.c_void_p
+    L.corb_rgbd_upload_batch.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+    L.corb_rgbd_run.argtypes = [C.c_void_p, C.c_int]
+    L.corb_rgbd_sync.argtypes = [C.c_void_p]
+    L.corb_rgbd_fetch_batch.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 6
+    L.corb_rgbd_frame_layout.argtypes = [C.c_void_p, C.POINTER(RgbdFrameLayout)]
+    L.corb_rgbd_frames.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.corb_rgbd_image_bounds.argtypes = [C.c_void_p, C.c_void_p]
+    L.corb_kf_store_put_from_rgbd.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_uint64]
     _lib = L
     return L
 
@@ -508,6 +534,107 @@ class StereoFrontend:
         n, nm = C.c_int(), C.c_int()
         _chk(self.L.corb_stereo_fetch_matches(self.h, frame, _p(ur), _p(dp), self.orb.cap, C.byref(n), C.byref(nm)), "fetch_matches")
         return dict(kl=kl, dl=dl, kr=kr, dr=dr, u_right=ur[: n.value].copy(), depth=dp[: n.value].copy(), n_matched=nm.value)
+
+
+class RgbdFrontend:
+    """Frame::Frame(RGB-D) / Frame::Frame(monocular) hot path (corbslam_client/src/Frame.cc:119-228) with the input conversions of
+    Tracking::GrabImageRGBD / GrabImageMonocular (Tracking.cc:206-264): colour -> grey, extraction, UndistortKeyPoints, ComputeStereoFromRGBD.
+    Defaults: TUM1's RGB-D settings file.  One frame of input = colour [height][width][channels] (or [height][width] grey) followed by the depth image
+    [height][width] (uint16 or float32, RGB-D only); pack_input builds the block."""
+
+    def __init__(self, nfeatures=1000, scaleFactor=1.2, nlevels=8, iniThFAST=20, minThFAST=7, width=640, height=480, max_frames=1,
+                 sensor=SENSOR_RGBD, channels=3, rgb=1, fx=517.306408, fy=516.469215, cx=318.643040, cy=255.313989,
+                 k1=0.262383, k2=-0.953104, p1=-0.005358, p2=0.002628, k3=1.163314, bf=40.0, depth_map_factor=5000.0, depth_format=DEPTH_U16, device=0):
+        self.L = load()
+        cfg = CameraConfig(OrbConfig(nfeatures, scaleFactor, nlevels, iniThFAST, minThFAST, width, height, 0, device), max_frames, sensor, channels, rgb,
+                           fx, fy, cx, cy, k1, k2, p1, p2, k3, bf, depth_map_factor, depth_format)
+        h = C.c_void_p()
+        _chk(self.L.corb_rgbd_create(C.byref(cfg), C.byref(h)), "corb_rgbd_create")
+        self.h = h
+        self.max_frames, self.width, self.height, self.channels = max_frames, width, height, channels
+        self.sensor, self.depth_format = sensor, depth_format
+        self.orb = ORBextractor(nfeatures, scaleFactor, nlevels, iniThFAST, minThFAST, width, height, max_frames, device, _handle=self.L.corb_rgbd_orb(h))
+        self.layout = self.frame_layout()
+
+    def close(self):
+        if self.h:
+            self.L.corb_rgbd_destroy(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def pack_input(self, frames):
+        """frames: list of (colour, depth) pairs (depth None for monocular) -> uint8 [n][input_bytes]"""
+        out = np.zeros((len(frames), self.layout.input_bytes), np.uint8)
+        for i, (col, dep) in enumerate(frames):
+            b = np.ascontiguousarray(col, np.uint8).reshape(-1).view(np.uint8)
+            out[i, : b.size] = b
+            if self.sensor == SENSOR_RGBD:
+                d = np.ascontiguousarray(dep, np.float32 if self.depth_format == DEPTH_F32 else np.uint16).reshape(-1).view(np.uint8)
+                out[i, b.size: b.size + d.size] = d
+        return out
+
+    def upload_batch(self, first, packed):
+        """packed: uint8 [n][input_bytes], C-contiguous (pack_input)"""
+        assert packed.flags["C_CONTIGUOUS"] and packed.dtype == np.uint8 and packed.size == packed.shape[0] * self.layout.input_bytes
+        _chk(self.L.corb_rgbd_upload_batch(self.h, first, packed.shape[0], _p(packed)), "corb_rgbd_upload_batch")
+
+    def run(self, n_frames):
+        _chk(self.L.corb_rgbd_run(self.h, n_frames), "corb_rgbd_run")
+
+    def sync(self):
+        _chk(self.L.corb_rgbd_sync(self.h), "corb_rgbd_sync")
+
+    def fetch_batch(self, first, n):
+        """strided results of frames first .. first+n-1: keys / keys_un [n][cap], desc [n][cap][32], u_right / depth [n][cap], counts [n]"""
+        cap = self.layout.capacity
+        out = dict(keys=np.zeros((n, cap), KP_DTYPE), keys_un=np.zeros((n, cap), KP_DTYPE), desc=np.zeros((n, cap, 32), np.uint8),
+                   u_right=np.zeros((n, cap), np.float32), depth=np.zeros((n, cap), np.float32), counts=np.zeros(n, np.int32))
+        _chk(self.L.corb_rgbd_fetch_batch(self.h, first, n, _p(out["keys"]), _p(out["keys_un"]), _p(out["desc"]), _p(out["u_right"]), _p(out["depth"]),
+                                          _p(out["counts"])), "corb_rgbd_fetch_batch")
+        return out
+
+    def fetch(self, frame):
+        """frame `frame`'s results after run + sync: dict(keys, keys_un, desc, u_right, depth)"""
+        o = self.fetch_batch(frame, 1)
+        n = int(o["counts"][0])
+        return dict(keys=o["keys"][0, :n].copy(), keys_un=o["keys_un"][0, :n].copy(), desc=o["desc"][0, :n].copy(), u_right=o["u_right"][0, :n].copy(),
+                    depth=o["depth"][0, :n].copy())
+
+    def frame_layout(self):
+        lay = RgbdFrameLayout()
+        _chk(self.L.corb_rgbd_frame_layout(self.h, C.byref(lay)), "corb_rgbd_frame_layout")
+        return lay
+
+    def frames(self, packed, result=None, timing=None):
+        """corb_rgbd_frames: the n frames of `packed` (uint8 [n][input_bytes]) in ONE call; result: n * frame_bytes bytes (page-locked: pinned_empty);
+        timing: a StereoFrameTiming to fill.  Returns the result block (parse with unpack_frame)."""
+        assert packed.flags["C_CONTIGUOUS"] and packed.dtype == np.uint8
+        n = packed.shape[0]
+        if result is None:
+            result = np.zeros(n * self.layout.frame_bytes, np.uint8)
+        _chk(self.L.corb_rgbd_frames(self.h, n, _p(packed), _p(result), C.byref(timing) if timing is not None else None), "corb_rgbd_frames")
+        return result
+
+    def unpack_frame(self, result, f=0):
+        """views into frame f's block of a corb_rgbd_frames result"""
+        lay = self.layout
+        b = result[f * lay.frame_bytes: (f + 1) * lay.frame_bytes]
+        n, status = (int(x) for x in b[:8].view(np.int32))
+        kp = lambda off: b[off: off + n * KP_DTYPE.itemsize].view(KP_DTYPE)
+        f32 = lambda off: b[off: off + 4 * n].view(np.float32)
+        return dict(keys=kp(lay.off_keys), keys_un=kp(lay.off_keys_un), desc=b[lay.off_desc: lay.off_desc + 32 * n].reshape(n, 32),
+                    u_right=f32(lay.off_u_right), depth=f32(lay.off_depth), status=status)
+
+    def bounds(self):
+        """Frame::ComputeImageBounds: (mnMinX, mnMaxX, mnMinY, mnMaxY) as float32"""
+        out = np.zeros(4, np.float32)
+        _chk(self.L.corb_rgbd_image_bounds(self.h, _p(out)), "corb_rgbd_image_bounds")
+        return out
 
 
 def _fv(node_id, offset, idx, keep):
@@ -854,6 +981,10 @@ class KeyFrameStore:
 
     def put_from_stereo(self, slot, sf, frame, keyframe_id=0):
         _chk(load().corb_kf_store_put_from_stereo(self.h, slot, sf.h, frame, keyframe_id), "corb_kf_store_put_from_stereo")
+
+    def put_from_rgbd(self, slot, fe, frame, keyframe_id=0):
+        """slot <- mvKeysUn / descriptors / mvuRight / mvDepth of frame `frame` of a RgbdFrontend (device-to-device)"""
+        _chk(load().corb_kf_store_put_from_rgbd(self.h, slot, fe.h, frame, keyframe_id), "corb_kf_store_put_from_rgbd")
 
     def put(self, slot, kp, desc, u_right=None, depth=None, keyframe_id=0):
         kp = np.ascontiguousarray(kp, KP_DTYPE); desc = np.ascontiguousarray(desc, np.uint8)

@@ -117,6 +117,8 @@ __device__ __forceinline__ void corb_xcd_remap(int& unit, int& img)
 struct CorbStereoDeviceFrame { const CorbKeyPoint* kp; const uint8_t* desc; const float* u_right; const float* depth; const int* count; int cap; hipStream_t stream; int device; };
 struct CorbStereo;
 int corb_stereo_device_frame(CorbStereo* h, int frame, CorbStereoDeviceFrame* out);
+struct CorbRgbd;
+int corb_rgbd_device_frame(CorbRgbd* h, int frame, CorbStereoDeviceFrame* out);      // kp = mvKeysUn (corb_cam.cpp)
 
 // kernel launchers (orb_kernels.hip / match_kernels.hip); all asynchronous on `stream`
 struct CorbProfiler;

@@ -76,13 +76,12 @@ static int refresh_host(CorbKfStore* s, int slot)
     return CORB_OK;
 }
 
-extern "C" int corb_kf_store_put_from_stereo(CorbKfStore* s, int slot, CorbStereo* sf, int frame, uint64_t id)
+// slot <- a front-end frame's device arrays (device-to-device, on the front-end's stream)
+static int kf_put_device_frame(CorbKfStore* s, int slot, const CorbStereoDeviceFrame& f, uint64_t id, const char* who)
 {
-    int rc = slot_ok(s, slot, "corb_kf_store_put_from_stereo"); if (rc) return rc;
-    CorbStereoDeviceFrame f;
-    if (corb_stereo_device_frame(sf, frame, &f) != CORB_OK || f.device != s->device) { corb_set_error("corb_kf_store_put_from_stereo: bad front-end / frame / device"); return CORB_ERR_ARG; }
-    if (f.cap > s->F) { corb_set_error("corb_kf_store_put_from_stereo: the front-end holds up to %d features per image, the store %d", f.cap, s->F); return CORB_ERR_CAPACITY; }
-    rc = corb_select_device(s->device); if (rc) return rc;
+    if (f.device != s->device) { corb_set_error("%s: bad front-end / frame / device", who); return CORB_ERR_ARG; }
+    if (f.cap > s->F) { corb_set_error("%s: the front-end holds up to %d features per image, the store %d", who, f.cap, s->F); return CORB_ERR_CAPACITY; }
+    int rc = corb_select_device(s->device); if (rc) return rc;
     std::lock_guard<std::mutex> lk(s->mu);
     // on the front-end's stream, behind its run; the store's own stream then waits for the copy
     corb_launch_kf_pack(f.kp, f.desc, f.u_right, f.depth, f.count, -1, id, s->rec(slot), s->F, f.stream);
@@ -91,6 +90,22 @@ extern "C" int corb_kf_store_put_from_stereo(CorbKfStore* s, int slot, CorbStere
     HIPCHK(hipStreamWaitEvent(s->stream, s->ev, 0));
     s->host[slot].header_valid = false;
     return CORB_OK;
+}
+
+extern "C" int corb_kf_store_put_from_stereo(CorbKfStore* s, int slot, CorbStereo* sf, int frame, uint64_t id)
+{
+    int rc = slot_ok(s, slot, "corb_kf_store_put_from_stereo"); if (rc) return rc;
+    CorbStereoDeviceFrame f;
+    if (corb_stereo_device_frame(sf, frame, &f) != CORB_OK) { corb_set_error("corb_kf_store_put_from_stereo: bad front-end / frame / device"); return CORB_ERR_ARG; }
+    return kf_put_device_frame(s, slot, f, id, "corb_kf_store_put_from_stereo");
+}
+
+extern "C" int corb_kf_store_put_from_rgbd(CorbKfStore* s, int slot, CorbRgbd* h, int frame, uint64_t id)
+{
+    int rc = slot_ok(s, slot, "corb_kf_store_put_from_rgbd"); if (rc) return rc;
+    CorbStereoDeviceFrame f;
+    if (corb_rgbd_device_frame(h, frame, &f) != CORB_OK) { corb_set_error("corb_kf_store_put_from_rgbd: bad front-end / frame / device"); return CORB_ERR_ARG; }
+    return kf_put_device_frame(s, slot, f, id, "corb_kf_store_put_from_rgbd");
 }
 
 static int kf_put_host(CorbKfStore* s, int slot, const CorbKeyPoint* kp, const uint8_t* desc, const float* u_right, const float* depth, int n, uint64_t id, const CorbKeyFrameMeta* meta,

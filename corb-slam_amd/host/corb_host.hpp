@@ -148,6 +148,63 @@ private:
     CorbStereo* h_ = nullptr; int max_frames_, cap_;
 };
 
+// Frame::Frame(RGB-D) / Frame::Frame(monocular) (Frame.cc:119-228) with Tracking::GrabImageRGBD / GrabImageMonocular's input conversions (Tracking.cc:206-264).
+// cfg: the settings file's camera and ORB values (CorbCameraConfig); one frame of input = colour (or grey) image, then the depth image (RGB-D), tightly packed.
+class RgbdFrontend {
+public:
+    struct FrameResult { std::vector<KeyPoint> mvKeys, mvKeysUn; Descriptors mDescriptors; std::vector<float> mvuRight, mvDepth; float mnMinX = 0, mnMaxX = 0, mnMinY = 0, mnMaxY = 0; };
+    explicit RgbdFrontend(const CorbCameraConfig& cfg)
+    {
+        check(corb_rgbd_create(&cfg, &h_), "corb_rgbd_create");
+        check(corb_rgbd_frame_layout(h_, &lay_), "corb_rgbd_frame_layout");
+        check(corb_rgbd_image_bounds(h_, bounds_), "corb_rgbd_image_bounds");
+    }
+    ~RgbdFrontend() { corb_rgbd_destroy(h_); }
+    RgbdFrontend(const RgbdFrontend&) = delete;
+    RgbdFrontend& operator=(const RgbdFrontend&) = delete;
+    const CorbRgbdFrameLayout& FrameLayout() const { return lay_; }
+    int InputBytes() const { return lay_.input_bytes; }
+    int Capacity() const { return lay_.capacity; }
+    // Frame::ComputeImageBounds of the calibration: {mnMinX, mnMaxX, mnMinY, mnMaxY}
+    void Bounds(float out[4]) const { for (int i = 0; i < 4; i++) out[i] = bounds_[i]; }
+    // the per-frame call (corb_rgbd_frames): nFrames inputs in, nFrames result blocks of FrameLayout().frame_bytes out, one synchronisation
+    void Frames(int nFrames, const uint8_t* input, void* resultBlocks, CorbStereoFrameTiming* timing = nullptr) { check(corb_rgbd_frames(h_, nFrames, input, resultBlocks, timing), "corb_rgbd_frames"); }
+    FrameResult FromBlock(const void* block) const
+    {
+        const uint8_t* b = static_cast<const uint8_t*>(block);
+        const size_t n = (size_t)reinterpret_cast<const int32_t*>(b)[0];
+        FrameResult r;
+        r.mvKeys.assign(reinterpret_cast<const KeyPoint*>(b + lay_.off_keys), reinterpret_cast<const KeyPoint*>(b + lay_.off_keys) + n);
+        r.mvKeysUn.assign(reinterpret_cast<const KeyPoint*>(b + lay_.off_keys_un), reinterpret_cast<const KeyPoint*>(b + lay_.off_keys_un) + n);
+        r.mDescriptors.data.assign(b + lay_.off_desc, b + lay_.off_desc + 32 * n);
+        r.mvuRight.assign(reinterpret_cast<const float*>(b + lay_.off_u_right), reinterpret_cast<const float*>(b + lay_.off_u_right) + n);
+        r.mvDepth.assign(reinterpret_cast<const float*>(b + lay_.off_depth), reinterpret_cast<const float*>(b + lay_.off_depth) + n);
+        r.mnMinX = bounds_[0]; r.mnMaxX = bounds_[1]; r.mnMinY = bounds_[2]; r.mnMaxY = bounds_[3];
+        return r;
+    }
+    // one frame: Frames(1, ...) into a block this object keeps
+    FrameResult ProcessFrame(const uint8_t* input)
+    {
+        block_.resize((size_t)lay_.frame_bytes);
+        Frames(1, input, block_.data());
+        return FromBlock(block_.data());
+    }
+    // batches: one upload + conversion kernel, an asynchronous run of frames 0 .. n-1, strided results (Capacity() entries per frame)
+    void UploadBatch(int firstFrame, int nFrames, const uint8_t* input) { check(corb_rgbd_upload_batch(h_, firstFrame, nFrames, input), "corb_rgbd_upload_batch"); }
+    void Run(int nFrames) { check(corb_rgbd_run(h_, nFrames), "corb_rgbd_run"); }
+    void Sync() { check(corb_rgbd_sync(h_), "corb_rgbd_sync"); }
+    void FetchBatch(int firstFrame, int nFrames, KeyPoint* keys, KeyPoint* keysUn, uint8_t* descriptors, float* uRight, float* depth, int32_t* counts)
+    {
+        check(corb_rgbd_fetch_batch(h_, firstFrame, nFrames, keys, keysUn, descriptors, uRight, depth, counts), "corb_rgbd_fetch_batch");
+    }
+    CorbRgbd* handle() const { return h_; }
+private:
+    CorbRgbd* h_ = nullptr;
+    CorbRgbdFrameLayout lay_{};
+    float bounds_[4] = {0, 0, 0, 0};
+    std::vector<uint8_t> block_;
+};
+
 // DBoW2::FeatureVector = std::map<NodeId, std::vector<unsigned>>, flattened in ascending node order
 struct FeatureVector {
     std::vector<uint32_t> node_id, idx; std::vector<int32_t> offset{0};

@@ -710,3 +710,37 @@ def frustum_view(Tcw, world, normal, min_distance, max_distance, fx, fy, cx, cy,
     out["proj_x"] = np.where(ok, u, 0); out["proj_y"] = np.where(ok, v, 0); out["proj_xr"] = np.where(ok, u - f(bf) * invz, 0)
     out["view_cos"] = np.where(ok, view, 0); out["level"] = np.where(ok, lvl, 0)
     return out
+
+
+def rgbd_frame(idx, w=640, h=480, channels=3):
+    """TUM-shaped synthetic RGB-D frame: (colour [h][w][channels] uint8 -- [h][w] for one channel --, depth [h][w] uint16).
+    The three colour channels carry the same texture with different gains, offsets and noise, so that the grey conversion weighs them; a fourth
+    channel (alpha) is noise the conversion must ignore.  The depth is a smooth surface of 0.1 .. 4 m at 5000 counts per metre with holes (0), a
+    band of near values (1 .. 40 counts), saturated pixels (65535) and isolated far pixels."""
+    rng = np.random.default_rng(SEED0 + 0x4D000 + int(idx))
+    grey, _ = stereo_pair(3000 + int(idx), w=w, h=h)
+    g = grey.astype(np.float32)
+    chans = []
+    for gain, off in ((1.0, 0.0), (0.7, 40.0), (0.45, 90.0)):
+        n = rng.integers(-9, 10, size=(h, w)).astype(np.float32)
+        chans.append(np.clip(np.rint(g * gain + off + n), 0, 255).astype(np.uint8))
+    chans.append(rng.integers(0, 256, size=(h, w), dtype=np.uint8))
+    colour = grey.copy() if channels == 1 else np.ascontiguousarray(np.stack(chans[:channels], axis=-1))
+    depth = (500.0 + 19500.0 * _value_noise(rng, h, w, 48)).astype(np.uint16)
+    for _ in range(12):                                       # holes
+        rw_, rh_ = int(rng.integers(10, 80)), int(rng.integers(10, 60))
+        x, y = int(rng.integers(0, w - rw_)), int(rng.integers(0, h - rh_))
+        depth[y:y + rh_, x:x + rw_] = 0
+    depth[h // 3: h // 3 + 24, :] = rng.integers(1, 41, size=(24, w))      # near band
+    sat = rng.random((h, w)) < 0.04
+    depth[sat] = 65535
+    zero = rng.random((h, w)) < 0.04
+    depth[zero] = 0
+    return colour, depth
+
+
+def mono_frame(idx, w=752, h=480, channels=1):
+    """EuRoC-shaped synthetic monocular frame: [h][w] uint8 (channels = 1) or [h][w][channels] colour built like rgbd_frame's"""
+    if channels == 1:
+        return stereo_pair(5000 + int(idx), w=w, h=h)[0]
+    return rgbd_frame(5000 + int(idx), w=w, h=h, channels=channels)[0]

@@ -166,6 +166,59 @@ typedef struct CorbStereoFrameTiming { float ms_upload, ms_kernels, ms_download;
 int corb_stereo_frame_layout(CorbStereo* h, CorbStereoFrameLayout* out);
 int corb_stereo_frames(CorbStereo* h, int n_frames, const uint8_t* images, void* result, CorbStereoFrameTiming* timing);
 
+/* ============================ RGB-D and monocular front-end ===============================
+ * One client's per-frame work in Frame::Frame(RGB-D) (C/src/Frame.cc:119-172) and Frame::Frame(monocular) (:174-228) with the input conversions of
+ * Tracking::GrabImageRGBD / GrabImageMonocular (C/src/Tracking.cc:206-264), for a batch of `max_frames` frames per launch:
+ *   1. colour -> grey as cvtColor RGB2GRAY / BGR2GRAY / RGBA2GRAY / BGRA2GRAY (chosen by `rgb` and `channels`; one channel is used as it is)
+ *   2. ORBextractor::operator() on the grey image (the handle's extractor, corb_rgbd_orb)
+ *   3. Frame::UndistortKeyPoints -> keys_un (mvKeysUn; = keys when k1 == 0)
+ *   4. RGB-D: depth at the distorted keypoint, scaled as Mat::convertTo(CV_32F, 1 / DepthMapFactor) does, and Frame::ComputeStereoFromRGBD -> u_right
+ *      (mvuRight) and depth (mvDepth), -1 where the depth is not > 0; monocular: both -1
+ * Frame f uses image slot f of the extractor.  Input of one frame: the colour image (height x width x channels bytes, tightly packed) followed, for
+ * RGB-D, by the depth image (height x width uint16 or float32, tightly packed); corb_rgbd_frame_layout().input_bytes bytes per frame. */
+#define CORB_SENSOR_MONOCULAR 0      /* System::MONOCULAR */
+#define CORB_SENSOR_RGBD      2      /* System::RGBD */
+#define CORB_DEPTH_U16        0      /* depth image CV_16U (TUM's PNGs) */
+#define CORB_DEPTH_F32        1      /* depth image CV_32F */
+typedef struct CorbRgbd CorbRgbd;
+typedef struct CorbCameraConfig {
+    CorbOrbConfig orb;                /* max_images is ignored: the handle sizes its extractor to max_frames */
+    int32_t max_frames;
+    int32_t sensor;                   /* CORB_SENSOR_MONOCULAR / CORB_SENSOR_RGBD */
+    int32_t channels;                 /* bytes per input pixel: 1 (grey), 3 (RGB / BGR), 4 (RGBA / BGRA) */
+    int32_t rgb;                      /* Camera.RGB: 1 = RGB(A) order, 0 = BGR(A) order (ignored for one channel) */
+    float fx, fy, cx, cy;             /* Camera.fx .. Camera.cy */
+    float k1, k2, p1, p2, k3;         /* Camera.k1 .. Camera.k3 (k3 = 0: the 4-coefficient model, Tracking.cc:65-75) */
+    float bf;                         /* Camera.bf (RGB-D) */
+    float depth_map_factor;           /* DepthMapFactor as in the settings file; the handle applies Tracking.cc:141-145 (|.| < 1e-5 -> 1, else 1 / value) */
+    int32_t depth_format;             /* CORB_DEPTH_U16 / CORB_DEPTH_F32 (RGB-D) */
+} CorbCameraConfig;
+int corb_rgbd_create(const CorbCameraConfig* cfg, CorbRgbd** out);
+void corb_rgbd_destroy(CorbRgbd* h);
+CorbOrb* corb_rgbd_orb(CorbRgbd* h);                 /* the underlying batched extractor (borrowed): corb_orb_pyramid_level, corb_orb_tables ... */
+/* frames first .. first+n-1 from ONE contiguous block of n * input_bytes bytes (one copy + one conversion kernel, asynchronous) */
+int corb_rgbd_upload_batch(CorbRgbd* h, int first_frame, int n_frames, const uint8_t* input);
+int corb_rgbd_run(CorbRgbd* h, int n_frames);        /* async: frames 0 .. n-1: extraction, undistortion, depth */
+int corb_rgbd_sync(CorbRgbd* h);                     /* CORB_ERR_OVERFLOW if a frame overflowed an internal buffer */
+/* results of frames first .. first+n-1, strided by capacity = corb_orb_capacity(corb_rgbd_orb(h)) per frame: keys / keys_un [n][capacity],
+ * desc [n][capacity][32], u_right / depth [n][capacity], counts [n]; any array but counts may be NULL; one synchronisation */
+int corb_rgbd_fetch_batch(CorbRgbd* h, int first_frame, int n_frames, CorbKeyPoint* keys, CorbKeyPoint* keys_un, uint8_t* desc, float* u_right, float* depth,
+                          int32_t* counts);
+/* corb_rgbd_frames: the per-frame call of a client (Tracking::GrabImageRGBD / GrabImageMonocular), like corb_stereo_frames: one host-to-device transfer of
+ * the n inputs, the kernel chain (one captured hipGraph per n, one stream), ONE device-to-host transfer of n result blocks, ONE synchronisation.
+ *   result : n blocks of frame_bytes bytes; block f: int32 n (keypoints), status (0 = ok, else CORB_ERR_OVERFLOW), then at their offsets
+ *            CorbKeyPoint[capacity] mvKeys, CorbKeyPoint[capacity] mvKeysUn, uint8[capacity][32] mDescriptors, float[capacity] mvuRight, float[capacity] mvDepth;
+ *            only the first n entries of a section are written.
+ * timing (may be NULL): device milliseconds of upload / kernels / download. */
+typedef struct CorbRgbdFrameLayout {
+    int32_t capacity, frame_bytes, input_bytes;
+    int32_t off_keys, off_keys_un, off_desc, off_u_right, off_depth;
+} CorbRgbdFrameLayout;
+int corb_rgbd_frame_layout(CorbRgbd* h, CorbRgbdFrameLayout* out);
+int corb_rgbd_frames(CorbRgbd* h, int n_frames, const uint8_t* input, void* result, CorbStereoFrameTiming* timing);
+/* Frame::ComputeImageBounds (C/src/Frame.cc:440-468) of the handle's calibration: out = {mnMinX, mnMaxX, mnMinY, mnMaxY} */
+int corb_rgbd_image_bounds(CorbRgbd* h, float out[4]);
+
 /* per-kernel device timing (HIP events on the handle's own stream).  enable, run, sync, then read. */
 typedef struct CorbKernelTime {
     char name[48];
@@ -488,6 +541,9 @@ int corb_kf_store_record_bytes(const CorbKfStore* s);                 /* bytes o
 /* slot <- left keypoints / descriptors / mvuRight / mvDepth of frame `frame` of a stereo front-end after corb_stereo_run (device-to-device, asynchronous on
  * the front-end's stream; the store's later calls wait for it) */
 int corb_kf_store_put_from_stereo(CorbKfStore* s, int slot, CorbStereo* sf, int frame, uint64_t keyframe_id);
+/* slot <- mvKeysUn / descriptors / mvuRight / mvDepth of frame `frame` of an RGB-D / monocular front-end after corb_rgbd_run or corb_rgbd_frames (device-to-device,
+ * asynchronous on the front-end's stream, like corb_kf_store_put_from_stereo) */
+int corb_kf_store_put_from_rgbd(CorbKfStore* s, int slot, CorbRgbd* h, int frame, uint64_t keyframe_id);
 /* slot <- host arrays (adapters / tests); any pointer except kp / desc may be NULL (u_right, depth default to -1) */
 int corb_kf_store_put_host(CorbKfStore* s, int slot, const CorbKeyPoint* kp, const uint8_t* desc, const float* u_right, const float* depth, int n, uint64_t keyframe_id);
 /* the parts the host computes: DBoW2 FeatureVector (Frame::ComputeBoW, C/src/Frame.cc:397-406) and the per-feature "vpMapPoints[i] && !isBad()" flags */
