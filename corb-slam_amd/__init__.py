@@ -867,7 +867,7 @@ class Optimizer:
         sp = None if stop is None else (C.cast(C.byref(one), C.c_void_p) if stop == "before" else C.cast(C.byref(res, _BAResult.iters_done.offset), C.c_void_p))
         _chk(load().corb_ba_solve_staged(C.byref(prob), st, len(stages), sp, C.byref(res), _p(outl), device, C.byref(opt)), "corb_ba_solve_staged")
         return dict(poses=oposes.reshape(-1, 4, 4), points=opoints, outlier=outl[: len(edges)].copy(), iters_done=res.iters_done,
-                    trials=res.trials_total, ms_total=res.ms_total, device_route=bool(res.reserved0))
+                    trials=res.trials_total, ms_total=res.ms_total, device_route=bool(res.reserved0), solver=res.solver_used)
 
     @staticmethod
     def LocalBundleAdjustment(*args, **kw):

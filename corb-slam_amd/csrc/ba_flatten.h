@@ -6,6 +6,7 @@
 #define FLAT_MAXROW  2      //         most blocks in one block row
 #define FLAT_PAIRS   1      //         sum over the free landmarks of (free-keyframe observations)^2: an upper bound of the Schur pair lists' length (local windows)
 #define FLAT_NSCAL   4
+#define FLAT_MAX_STAGES 15  // classification stages a staged solve may take the device route with (corb_ba_staged_device_wanted); FlatStageList holds them all
 
 struct BAFlattenDev {
     // the problem (device arrays; edges grouped by point)
@@ -46,4 +47,4 @@ void flat_launch_counts(const BAFlattenDev& d, const int* extra, int* out, hipSt
 // outlier[e_src[j]] = 1 for every flattened edge j that is not in the active set
 void flat_launch_outliers(const unsigned char* active, const int* e_src, int nE, unsigned char* outlier, hipStream_t s);
 // outlier[e] of the problem's edges between a fixed keyframe and a fixed map point (outside the flattened graph): the depth test of the classification stages that ran
-void flat_launch_fixed_edge_outliers(const BAFlattenDev& d, const CorbBAStage* used, int n_used, unsigned char* outlier, hipStream_t s);
+int flat_launch_fixed_edge_outliers(const BAFlattenDev& d, const CorbBAStage* used, int n_used, unsigned char* outlier, hipStream_t s);     // -1: more than FLAT_MAX_STAGES stages

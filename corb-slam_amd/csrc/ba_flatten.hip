@@ -416,7 +416,8 @@ void flat_launch_outliers(const unsigned char* active, const int* e_src, int nE,
 // An edge between a fixed keyframe and a fixed map point is not part of the flattened graph (g2o does not activate it, sparse_optimizer.cpp:234: its error is never computed,
 // its chi2 stays 0) -- but the callers' classification loops still visit it and apply isDepthPositive() to it (Optimizer.cc:722-748, 768-797).  Neither vertex moves, so the
 // verdict follows from the inputs: the classification stages are replayed on the constant depth (the device route left these edges at outlier = 0).
-struct FlatStageList { int n; int check_depth[8]; int allow_reactivate[8]; };
+struct FlatStageList { int n; int check_depth[FLAT_MAX_STAGES]; int allow_reactivate[FLAT_MAX_STAGES]; };
+static_assert(sizeof(FlatStageList) == sizeof(int) * (1 + 2 * FLAT_MAX_STAGES), "FlatStageList must hold every stage corb_ba_staged_device_wanted admits");
 __global__ __launch_bounds__(256) void flat_fixed_edge_outliers_kernel(BAFlattenDev d, FlatStageList st, unsigned char* __restrict__ outlier)
 {
     const int e = blockIdx.x * 256 + threadIdx.x;
@@ -432,11 +433,13 @@ __global__ __launch_bounds__(256) void flat_fixed_edge_outliers_kernel(BAFlatten
     }
     outlier[e] = active ? 0 : 1;
 }
-void flat_launch_fixed_edge_outliers(const BAFlattenDev& d, const CorbBAStage* used, int n_used, unsigned char* outlier, hipStream_t s)
+int flat_launch_fixed_edge_outliers(const BAFlattenDev& d, const CorbBAStage* used, int n_used, unsigned char* outlier, hipStream_t s)
 {
-    FlatStageList st; st.n = n_used < 8 ? n_used : 8;
+    if (n_used < 0 || n_used > FLAT_MAX_STAGES) return -1;                 // (corb_ba_staged_device_wanted admits at most FLAT_MAX_STAGES: every stage that ran is replayed)
+    FlatStageList st; st.n = n_used;
     for (int k = 0; k < st.n; k++) { st.check_depth[k] = used[k].check_depth; st.allow_reactivate[k] = used[k].allow_reactivate; }
     if (d.E > 0 && st.n > 0) hipLaunchKernelGGL(flat_fixed_edge_outliers_kernel, dim3((d.E + 255) / 256), dim3(256), 0, s, d, st, outlier);
+    return 0;
 }
 void flat_launch_rows(const BAFlattenDev& d, int nP, bool fill, hipStream_t s)
 {

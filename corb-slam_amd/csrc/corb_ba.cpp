@@ -1934,7 +1934,7 @@ int corb_ba_solve_device(const CorbBADeviceProblem* dp, int iterations, int robu
 bool corb_ba_staged_device_wanted(const CorbBAStage* stages, int n_stages)
 {
     static const bool host_route = getenv("CORB_LBA_HOST_FLATTEN") != nullptr;      // (the round-4 route -- problem to the host, host flattening --: for A/B timing)
-    if (host_route || n_stages < 1 || n_stages > 15) return false;
+    if (host_route || n_stages < 1 || n_stages > FLAT_MAX_STAGES) return false;     // (flat_launch_fixed_edge_outliers replays every stage that ran)
     for (int s = 1; s < n_stages; s++) if (stages[s].reset_estimates) return false;
     return true;
 }
@@ -2086,7 +2086,10 @@ static int ba_staged_window(BASession& sess, const CorbBADeviceProblem* dp, cons
     flat_launch_state_out(d, s);
     HIPCHK(hipMemsetAsync(d_outlier, 0, (size_t)n_edges, s));
     flat_launch_outliers(sess.d_act + (size_t)sess.cur_set * nE, d.e_src, nE, d_outlier, s);
-    if (nE != n_edges) { BAFlattenDev dd = d; dd.E = n_edges; flat_launch_fixed_edge_outliers(dd, used_stages.data(), (int)used_stages.size(), d_outlier, s); }      // (edges between two fixed vertices)
+    if (nE != n_edges) {                                   // (edges between two fixed vertices)
+        BAFlattenDev dd = d; dd.E = n_edges;
+        if (flat_launch_fixed_edge_outliers(dd, used_stages.data(), (int)used_stages.size(), d_outlier, s)) { corb_set_error("staged BA: %d stages, the device route replays at most %d", (int)used_stages.size(), FLAT_MAX_STAGES); return CORB_ERR_ARG; }
+    }
     HIPCHK(hipGetLastError());
     if (n_opt > 1) {
         static thread_local std::vector<uint8_t> set; set.resize((size_t)nE);

@@ -60,14 +60,15 @@ struct Arena {
 int run_projection(const CorbFrameView* F, int nq, const void* qdesc, const CorbTrackedPoint* mp, const CorbLastPoint* last,
                    const CorbProjPose* pose, float th, float nnratio, int ratio_test, int check_ori, int32_t* match, int* n_matches, int device)
 {
-    if (!F || !match || !n_matches || F->n < 0 || nq < 0 || F->nlevels < 1 || F->nlevels > CORB_MAX_LEVELS || !(F->max_x > F->min_x) || !(F->max_y > F->min_y) ||
+    if (!F || !match || !n_matches || F->n < 0 || nq < 0 || F->nlevels < 1 || F->nlevels > CORB_MAX_LEVELS ||
         (F->n > 0 && (!F->keys_un || !F->u_right || !F->desc || !F->claimed)) || !F->scale || (nq > 0 && !qdesc)) {
         corb_set_error("projection matcher: bad argument"); return CORB_ERR_ARG;
     }
     if (F->n > 6000 || nq > 60000) { corb_set_error("projection matcher: frame too large (%d features)", F->n); return CORB_ERR_ARG; }
     *n_matches = 0;
     for (int i = 0; i < F->n; i++) match[i] = -1;
-    if (F->n == 0 || nq == 0) return CORB_OK;
+    if (F->n == 0 || nq == 0) return CORB_OK;          // (before the bounds test: a featureless frame's view may leave its bounds at zero; nothing to match either way)
+    if (!(F->max_x > F->min_x) || !(F->max_y > F->min_y)) { corb_set_error("projection matcher: empty image bounds"); return CORB_ERR_ARG; }
     int rc = corb_select_device(device); if (rc) return rc;
     const int n = F->n;
     Arena ar;
@@ -109,14 +110,15 @@ int run_projection(const CorbFrameView* F, int nq, const void* qdesc, const Corb
 int run_points(const CorbKeyFrameView* K, const uint8_t* claimed, const CorbMapPointView* pts, const uint8_t* qdesc, int nq, const CorbProjTf& tf,
                int greedy, int check_ori, int th_dist, int chi2_check, int32_t* match, int* n_matches, int32_t* best_idx, int32_t* best_dist, int device)
 {
-    if (!K || K->n < 0 || nq < 0 || K->nlevels < 1 || K->nlevels > CORB_MAX_LEVELS || !(K->max_x > K->min_x) || !(K->max_y > K->min_y) || !K->scale ||
+    if (!K || K->n < 0 || nq < 0 || K->nlevels < 1 || K->nlevels > CORB_MAX_LEVELS || !K->scale ||
         (K->n > 0 && (!K->keys_un || !K->u_right || !K->desc)) || (nq > 0 && (!pts || !qdesc)) || (chi2_check && !K->inv_level_sigma2) || (greedy && K->n > 0 && !claimed)) {
         corb_set_error("keyframe projection matcher: bad argument"); return CORB_ERR_ARG;
     }
     if (K->n > 6000 || nq > 60000) { corb_set_error("keyframe projection matcher: too large (%d features, %d points)", K->n, nq); return CORB_ERR_ARG; }
     if (greedy) { *n_matches = 0; for (int i = 0; i < K->n; i++) match[i] = -1; }
     else for (int i = 0; i < nq; i++) { best_idx[i] = -1; best_dist[i] = 256; }
-    if (K->n == 0 || nq == 0) return CORB_OK;
+    if (K->n == 0 || nq == 0) return CORB_OK;          // (before the bounds test, as in run_projection)
+    if (!(K->max_x > K->min_x) || !(K->max_y > K->min_y)) { corb_set_error("keyframe projection matcher: empty image bounds"); return CORB_ERR_ARG; }
     int rc = corb_select_device(device); if (rc) return rc;
     const int n = K->n;
     Arena ar;
@@ -202,13 +204,14 @@ extern "C" int corb_search_for_initialization(const CorbFrameView* f1, const Cor
                                               int32_t* matches12, int* n_matches, int device)
 {
     if (!f1 || !f2 || !matches12 || !n_matches || f1->n < 0 || f2->n < 0 || (f1->n > 0 && (!f1->keys_un || !f1->desc || !prev_matched)) || (f2->n > 0 && (!f2->keys_un || !f2->desc)) ||
-        !(f2->max_x > f2->min_x) || !(f2->max_y > f2->min_y) || window_size < 0) {
+        window_size < 0) {
         corb_set_error("corb_search_for_initialization: bad argument"); return CORB_ERR_ARG;
     }
     if (f2->n > 6000 || f1->n > 8192) { corb_set_error("corb_search_for_initialization: frame too large (%d / %d features)", f1->n, f2->n); return CORB_ERR_ARG; }
     *n_matches = 0;
     for (int i = 0; i < f1->n; i++) matches12[i] = -1;
-    if (f1->n == 0 || f2->n == 0) return CORB_OK;
+    if (f1->n == 0 || f2->n == 0) return CORB_OK;          // (before the bounds test: the view of a featureless F2 may leave its bounds at zero)
+    if (!(f2->max_x > f2->min_x) || !(f2->max_y > f2->min_y)) { corb_set_error("corb_search_for_initialization: empty image bounds"); return CORB_ERR_ARG; }
     int rc = corb_select_device(device); if (rc) return rc;
     const int n = f2->n, nq = f1->n;
     const int cap = std::min(n, 2048);                     // candidates kept per window (a 2 x 100 px window of a dense frame holds more than the other matchers' 256)

@@ -633,7 +633,7 @@ def map_point_update_normal_and_depth(mp, kfs_by_id, scale_factor):
     mp["normal"] = (normal.astype(np.float64) * (1.0 / n)).astype(np.float32)
 
 
-def local_bundle_adjustment(local_kfs, fixed_kfs, mps, scale_factor=1.2, apply_erase=True, stop=None):
+def local_bundle_adjustment(local_kfs, fixed_kfs, mps, scale_factor=1.2, apply_erase=True, stop=None, stages=None):
     kfs = list(local_kfs) + list(fixed_kfs)
     by_id = {k["id"]: k for k in kfs}
     vidx = {k["id"]: i for i, k in enumerate(kfs)}
@@ -659,7 +659,7 @@ def local_bundle_adjustment(local_kfs, fixed_kfs, mps, scale_factor=1.2, apply_e
         edges[i] = e
     if stop == "before":
         return dict(erase=[], edges=edges)
-    r = ba_solve_staged(poses, pose_fixed, points, point_fixed, edges, 0, 0, 0, 0, 0, LOCAL_BA_STAGES, intr=intr, stop=stop)
+    r = ba_solve_staged(poses, pose_fixed, points, point_fixed, edges, 0, 0, 0, 0, 0, LOCAL_BA_STAGES if stages is None else stages, intr=intr, stop=stop)
     out = np.nonzero(r["outlier"])[0]
     mono = [i for i in out if edges["ur"][i] < 0]; stereo = [i for i in out if edges["ur"][i] >= 0]
     erase = [who[i] for i in mono + stereo]
