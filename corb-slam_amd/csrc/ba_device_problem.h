@@ -1,4 +1,4 @@
-// ba_device_problem.h -- a bundle-adjustment problem whose arrays live in device memory (corb_ba_store.cpp builds it from store records, corb_ba.cpp solves it)
+// ba_device_problem.h -- a bundle-adjustment problem whose arrays live in device memory (corb_ba_store.cpp builds it from store records, corb_ba.cpp / corb_ba_staged.cpp solve it)
 #pragma once
 #include "corb_internal.h"
 

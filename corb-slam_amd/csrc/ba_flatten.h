@@ -1,4 +1,4 @@
-// ba_flatten.h -- argument block of the device-side graph flattening (ba_flatten.hip, driven by corb_ba.cpp: corb_ba_solve_device)
+// ba_flatten.h -- argument block of the device-side graph flattening (ba_flatten.hip, driven by corb_ba.cpp: corb_ba_solve_device and corb_ba_staged.cpp: ba_staged_window through ba_flatten_dev.cpp)
 #pragma once
 #include "corb_internal.h"
 

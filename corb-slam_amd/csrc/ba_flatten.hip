@@ -1,5 +1,5 @@
 // ba_flatten.hip -- the graph flattening of Optimizer::BundleAdjustment on the device.
-// What corb_ba.cpp's host flattening does for a CorbBAProblem in host memory (active-edge filter, g2o's index mapping -- free poses, then free
+// What ba_flatten_host.cpp's host flattening does for a CorbBAProblem in host memory (active-edge filter, g2o's index mapping -- free poses, then free
 // landmarks, ascending: G/core/sparse_optimizer.cpp:166-190 --, edges sorted by landmark with the free-pose edges first, per-keyframe edge lists,
 // block pattern of the reduced camera system: G/core/block_solver.hpp:143-295) for a problem whose arrays already live in device memory
 // (CorbBADeviceProblem: edges grouped by map point, as corb_ba_solve_store derives them from the map-point records).  Same lists, element for element;

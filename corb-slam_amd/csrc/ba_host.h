@@ -1,0 +1,205 @@
+// ba_host.h -- what the host-side translation units of the bundle adjustment share.  Host code only.
+//   corb_ba.cpp          C-ABI entry points of the global BA, the route decision (ba_choose), problem <-> double-precision state
+//   ba_flatten_host.cpp  graph flattening of a CorbBAProblem on the host, upload into a BAFlat
+//   ba_flatten_dev.cpp   the steps of the device flattening (ba_flatten.hip) that the global and the window route share
+//   ba_lm.cpp            the Levenberg-Marquardt driver on a BAFlat
+//   ba_ml_host.cpp       host hierarchy of the multilevel preconditioner
+//   corb_ba_staged.cpp   staged solves (LocalBundleAdjustment): sessions, both window routes
+//   corb_pose.cpp        the fused single-pose optimiser's batches
+//   corb_scratch.cpp     corb_warmup, corb_release_scratch, corb_spd_solve
+#pragma once
+#include "ba_internal.h"
+#include "ba_multilevel.h"
+#include "ba_device_problem.h"
+#include "ba_flatten.h"
+#include "corb_workspace.h"
+#include "device_util.h"
+#include <chrono>
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <memory>
+#include <thread>
+#include <vector>
+
+void corb_set_error(const char* fmt, ...);
+int corb_select_device(int device);
+
+#define HIPCHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { corb_set_error("%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); return CORB_ERR_HIP; } } while (0)
+
+#define BA_TRACE(what) do { static const bool t_ = getenv("CORB_BA_TRACE") != nullptr; if (t_) { fprintf(stderr, "[corb_ba trace] %s\n", what); fflush(stderr); } } while (0)
+struct Lap {                          // CORB_BA_TIMING=1: host-side phase times of a call on stderr (development aid)
+    bool on; const char* fmt; std::chrono::steady_clock::time_point t;
+    explicit Lap(const char* fmt_ = "[corb_ba] %-28s %8.2f ms\n") : on(getenv("CORB_BA_TIMING") != nullptr), fmt(fmt_), t(std::chrono::steady_clock::now()) {}
+    void operator()(const char* what) {
+        if (!on) return;
+        auto n = std::chrono::steady_clock::now();
+        fprintf(stderr, fmt, what, std::chrono::duration<double, std::milli>(n - t).count()); t = n;
+    }
+};
+
+// host flattening of large maps runs on a few worker threads: contiguous index ranges, results identical to the serial order
+template <class F> void parallel_ranges(size_t n, int threads, F fn)
+{
+    if (threads <= 1 || n < 2) { fn(0, (size_t)0, n); return; }
+    std::vector<std::thread> th;
+    for (int t = 0; t < threads; t++) { const size_t b = n * t / threads, e = n * (t + 1) / threads; th.emplace_back([=] { fn(t, b, e); }); }
+    for (auto& x : th) x.join();
+}
+int ba_host_threads(size_t n, bool sort_stage = false);      // ba_flatten_host.cpp
+
+struct Pool : CorbScratch { Pool() : CorbScratch(1) {} };      // bundle adjustment runs in the long-optimisation lane
+
+struct BAState { std::vector<double> q, t, pt; };      // double-precision estimates carried across stages
+
+// The flattened graph in device memory: what the Levenberg-Marquardt loop (ba_lm.cpp) works on.  Filled either by the host flattening of a CorbBAProblem (host
+// arrays in: corb_ba_solve*) or by the device flattening of a CorbBADeviceProblem (ba_flatten.hip: corb_ba_solve_device / corb_ba_solve_store).
+struct BAFlat {
+    int nE = 0, nP = 0, nL = 0;                   // active edges, free poses, free landmarks
+    int nA = 0;                                   // edges of free landmarks (= loff[nL]; the edges of fixed landmarks follow)
+    int nnzb = 0, bsr_max_row = 0, nu = 0;        // blocks of the reduced system, largest block row, blocks on / above the diagonal
+    bool have_pattern = false;
+    size_t pairs_bound = 0;                       // local windows, host flattening: an upper bound of the Schur pair lists' length (0 = not known: the count is read back)
+    int *e_pose = nullptr, *e_point = nullptr, *e_vpose = nullptr, *e_vpoint = nullptr, *loff = nullptr, *lnfree = nullptr, *poff = nullptr, *pedge = nullptr;
+    int *pose_vertex = nullptr, *point_vertex = nullptr, *bsr_rowptr = nullptr, *bsr_col = nullptr, *bsr_diag = nullptr, *uinfo = nullptr, *plm = nullptr;
+    double *e_obs = nullptr, *e_w = nullptr, *cam = nullptr; unsigned char* e_dim = nullptr;
+    double *dq = nullptr, *dq_bak = nullptr;      // estimates: quaternions | translations | points (all vertices), and the push() copy
+    size_t n_q = 0, n_t = 0, n_pt = 0;
+    size_t n_state() const { return n_q + n_t + n_pt; }
+};
+// the estimate block quaternions | translations | points as one host buffer (one copy each way)
+inline void ba_state_pack(const BAState& st, double* blk)
+{
+    if (!st.q.empty()) memcpy(blk, st.q.data(), st.q.size() * 8);
+    if (!st.t.empty()) memcpy(blk + st.q.size(), st.t.data(), st.t.size() * 8);
+    if (!st.pt.empty()) memcpy(blk + st.q.size() + st.t.size(), st.pt.data(), st.pt.size() * 8);
+}
+inline void ba_state_unpack(const double* blk, BAState& st)
+{
+    if (!st.q.empty()) memcpy(st.q.data(), blk, st.q.size() * 8);
+    if (!st.t.empty()) memcpy(st.t.data(), blk + st.q.size(), st.t.size() * 8);
+    if (!st.pt.empty()) memcpy(st.pt.data(), blk + st.q.size() + st.t.size(), st.pt.size() * 8);
+}
+// what the per-edge kernels (error, evaluation, classification) read of a flattened graph: the edges with the weights e_w, the estimates, the intrinsics
+inline CorbBADev ba_edge_view(int nE, const int* e_vpose, const int* e_vpoint, const double* e_obs, const double* e_w, const unsigned char* e_dim,
+                              double* q, double* t, double* pt, const double* cam)
+{
+    CorbBADev d; memset(&d, 0, sizeof(d));
+    d.nE = nE; d.e_vpose = e_vpose; d.e_vpoint = e_vpoint; d.e_obs = e_obs; d.e_w = e_w; d.e_dim = e_dim; d.pose_q = q; d.pose_t = t; d.pt = pt; d.cam = cam;
+    return d;
+}
+inline CorbBADev ba_edge_view(const BAFlat& f, const double* e_w) { return ba_edge_view(f.nE, f.e_vpose, f.e_vpoint, f.e_obs, e_w, f.e_dim, f.dq, f.dq + f.n_q, f.dq + f.n_q + f.n_t, f.cam); }
+
+// pcg_tol: the caller's fixed tolerance, or (pcg_forcing) the default policy: every reduced solve stops at BA_PCG_TOL_LOOSE, and a trial whose accept / reject or
+// lambda decision could depend on the solve's accuracy is continued to BA_PCG_TOL_TIGHT before the decision is taken (ba_lm_device, at the trial's rho).
+// tools/pcg_tol_sweep.py, round 5 (profiles/r05_pcg_tol_sweep.txt; 320 / 1 200 / 4 800 / 20 000 keyframes, 10 LM iterations against a 1e-13 solve): the chi2 after every
+// iteration moves by <= 6e-8 / 3e-7 / 3.2e-6 relative at 1e-8 / 1e-5 / 1e-4 (the parity bar is 1e-4) while the CG iterations fall 902 -> 541 -> 430 at 20 000 keyframes;
+// What binds the loose tolerance is lambda, not chi2: where rho falls into the steep part of the schedule, d lambda / lambda ~ 10 d rho, and rho = (chi2_old - chi2_new) /
+// scale amplifies a relative chi2 error by chi2 / (chi2_old - chi2_new) -- 1e3 in the late iterations.  At 1e-5 a 100-keyframe robust problem's lambda moved by 1.5e-3
+// at its seventh iteration (tests/test_gpu_ba.py compares lambda at 1e-3) -- through the chi2 the EARLIER loose iterations had left, not through that iteration's own
+// solve (continuing it to 1e-8 changed nothing).  1e-6 keeps that at 1.5e-4; the continuation guards the discrete decisions.
+// Two more rules keep the policy away from where NO finite tolerance reproduces an exact solve's decisions: (1) on a plateau -- chi2 flat to 1e-7 and below -- the sign of
+// a trial's gain is rounding noise of whichever solver ran, and one flipped accept moves a weakly observed map point by 1e-2 without moving chi2 (a 10-keyframe robust
+// problem of tests/test_gpu_ba.py: 16 / 17 / 10 trials at 1e-8 / exact / the policy): the tolerance of an iteration follows the relative gain of the iteration before it,
+// tol = clamp(1e-2 gain, 1e-8, BA_PCG_TOL_LOOSE) -- the classical forcing sequence, tight as the iteration converges; (2) the policy applies to the maps the PCG solver is the automatic
+// choice for (more than BA_PCG_FORCING_MIN_POSES free keyframes), where the solve is the cost; a small problem forced onto the PCG solver solves to 1e-8 like before.
+// Round 6 re-examined the cap with the oracle's exact sparse LDL^T at 4 800 (non-robust and Huber) and 12 000 keyframes (tests/golden/ba_config3.json, ba_12k.json):
+// tools/pcg_loose_margins.py, cap 1e-6 / 1e-5 / 1e-4 / 1e-3 (CORB_BA_PCG_LOOSE): chi2 per iteration within 1.6e-8 / 1.4e-7 / 3.1e-7 / 1.7e-5 of those trajectories, lambda
+// identical, estimates within 6e-8 .. 4e-7, counts equal -- >= 300x inside every bar at 1e-4, with 500 -> 308 CG iterations at 50 000 keyframes (solve 72.7 -> 45.6 ms).
+// The goldens are well-conditioned maps.  On noisy maps above 256 keyframes whose LM runs reject trials (tools/pcg_policy_rejections.py: 24 runs against the dense solver,
+// 48 rejected trials) the accept / reject histories stay equal at every cap, but the worst chi2 deviation is 6e-6 at 1e-6 and 3.0e-4 / 7.1e-4 / 3.8e-4 at 1e-5 / 3e-5 /
+// 1e-4 -- outside the 1e-4 parity bar.  The cap stays 1e-6; a caller who knows its maps sets CorbBAOptions.pcg_tol (bench.py reports the 1e-4 figure beside the default's).
+#define BA_PCG_TOL_LOOSE 1e-6
+#define BA_PCG_TOL_TIGHT 1e-8
+#define BA_PCG_FORCING_MIN_POSES 256
+struct BAChoice { int solver = 1, pc_g = 1; double pcg_tol = 1e-8; bool pcg_forcing = false; int pcg_max_iter = 4000; bool fused_small = false, want_pattern = false, multilevel = false; };
+
+// The work arrays and pair lists of a local window's optimize() (dense reduced system, one-workgroup solve), kept by a staged solve's session: the later optimize()
+// calls run on the same graph and take them as they are instead of allocating and building them again.
+struct LMWork { bool ready = false; int n_pairs = 0; CorbBADev d; double* d_partial = nullptr; double* d_scal = nullptr; double* d_chi_partial = nullptr; BALMCtl* d_ctl = nullptr; };
+
+// A staged call (LocalBundleAdjustment: optimize(5), classify, optimize(10)) used to flatten, upload and build the pair lists once per optimize(): with
+// a session the device-resident graph of the FIRST optimize() -- which has every edge active -- serves the later ones: an edge that a classification
+// switched off keeps its place with the weight 0 (J = 0, r = 0, V = 0: it adds exact zeros in the same places of the same sums, i.e. the estimates are
+// those of the re-flattened graph up to the rounding of a zero update of vertices left without an active edge), only the weights and the estimates travel.
+// Round 5: with want_dev the classifications between the optimize() calls run on the device as well (ba_stage_classify_kernel: the active sets, the chi2 every edge
+// had when it last was active and the masked weights stay in device memory), so a staged solve reads NOTHING back until its end -- a local window's call was
+// bound by those round trips (per optimize(): estimates + per-edge chi2 down, fresh chi2 + depth down, weights + estimates up).
+struct BASession {
+    std::unique_ptr<Pool> pool; BAFlat f; BAChoice ch; bool ready = false;
+    std::vector<int> act;             // flattened edge j = edge act[j] of the problem
+    std::vector<double> e_w0;         // its information scale
+    bool covers_all = false;          // every edge of the problem is in the graph (none between two fixed vertices)
+    LMWork work;                      // the first optimize()'s work arrays and pair lists (local windows)
+    bool want_dev = false, dev = false;
+    int n_sets = 0, cur_set = 0;      // active sets on the device: set 0 = every edge (the first optimize()), set k + 1 = after the k-th classification
+    double *d_w0 = nullptr, *d_last = nullptr, *d_e_chi2 = nullptr; unsigned char* d_act = nullptr;
+};
+
+// ---- corb_ba.cpp ----
+int ba_validate(const CorbBAProblem* p, const CorbBAResult* r);
+void ba_result_reset(CorbBAResult* r);                           // the counters, times and certificates of a call; histories and estimate arrays are the caller's
+void ba_intrinsics(const CorbBAProblem* p, int k, float* c5);   // fx fy cx cy bf of pose vertex k: p->intr or the shared camera
+void ba_cam_table(const CorbBAProblem* p, std::vector<double>& cam);
+void ba_state_from_floats(const CorbBAProblem* p, BAState& st);
+void ba_state_to_floats(const CorbBAProblem* p, const BAState& st, const std::vector<uint8_t>& pose_touched, const std::vector<uint8_t>& pt_touched, CorbBAResult* r);
+// the chi2 thresholds are decimal literals (5.991, 7.815) that the reference compares as doubles unless it first narrows chi2 to float
+inline const auto th_double = [](float t) { return std::round((double)t * 1e6) / 1e6; };
+int ba_choose(const CorbBAOptions* opt, int nP, int nE, int nL, BAChoice& ch);
+int ba_optimize_device(const CorbBAProblem* p, const uint8_t* active, BAState& st, int iterations, int robust, volatile int* stop_flag,
+                       CorbBAResult* r, const CorbBAOptions* opt, std::vector<double>* last_chi2,
+                       std::vector<uint8_t>* pose_touched, std::vector<uint8_t>* pt_touched, double delta2, double delta3, BASession* sess = nullptr);
+size_t ba_host_fast_release(int device);                         // the page-locked double buffer of large host calls, if no call holds it: bytes given back
+
+// ---- ba_flatten_host.cpp ----
+// host arrays of a flattened CorbBAProblem (one set per thread, keeping its capacity from call to call)
+struct BAHostFlat {
+    int nP = 0, nL = 0, nE = 0, nnzb = 0, bsr_max_row = 0;
+    std::vector<int> deg, act, pidx, lidx, pose_vertex, point_vertex, cnt, sorted, e_pose, e_point, e_vpose, e_vpoint, loff, lnfree, poff, pedge,
+                     bsr_rowptr, bsr_col, bsr_diag, uinfo, plm, cur, keys;
+    std::vector<double> e_obs, e_w, cam; std::vector<unsigned char> e_dim;
+};
+int ba_flatten_host(const CorbBAProblem* p, const uint8_t* active, const CorbBAOptions* opt, std::vector<uint8_t>* pose_touched, std::vector<uint8_t>* pt_touched,
+                    Lap& lap, BAChoice& ch, BAHostFlat** out);
+int ba_upload_flat(Pool& pool, const BAHostFlat& h, const BAState& st, const BAChoice& ch, BAFlat& f);
+
+// ---- ba_flatten_dev.cpp ----
+int ba_flat_dev_begin(BAFlattenDev& d, const CorbBADeviceProblem* dp, Pool& pool, int** scan_tmp);
+void ba_flat_dev_scans(const BAFlattenDev& d, int* scan_tmp, hipStream_t s);
+inline void ba_flat_dev_counts(BAFlat& f, const int* h) { f.nL = h[0]; f.nE = h[1] + h[2]; f.nP = h[3]; f.nA = h[1]; }      // h: lidx[M], eoffA[M], eoffB[M], pidx[K]
+int ba_flat_dev_alloc(BAFlattenDev& d, BAFlat& f, Pool& pool, bool with_e_src);
+int ba_flat_dev_wire(BAFlattenDev& d, BAFlat& f, Pool& pool);
+void ba_launch_edge_offsets(const CorbBAEdge* edges, int n_edges, int n_points, int* off, hipStream_t s);      // ba_flatten.hip
+
+// ---- ba_ml_host.cpp ----
+struct MLHostLevel {
+    int n = 0, stride = 0, max_row = 0;
+    std::vector<int> rowptr, col;            // pattern of A_k
+    std::vector<int> i0, i1, lo, hi, seg;    // hats over the level below (size n_below: i0, i1; size n: lo, hi, seg = trajectory of every node)
+    std::vector<double> w1;
+};
+// The hierarchy is built on the host from the fine pattern (ba_ml_host: 15 ms at 50 000 keyframes -- on a helper thread, beside the device's pair-list kernels) and
+// left in device memory by ba_ml_upload (pool); m.L == 0: not built (too few keyframes).
+struct MLHostAll {
+    std::vector<int> h_rowptr, h_col;                 // the fine pattern (read back by the caller)
+    std::vector<MLHostLevel> lv; std::vector<int> node_off, p_ptr, p_node, r_ptr, r_pose, ch_begin, ch_ptr; std::vector<double> p_w, r_w; int n_nodes = 0;
+};
+void ba_ml_host(int nP, MLHostAll& H);
+int ba_ml_upload(Pool& pool, int nP, const MLHostAll& H, BAMLDev& m);
+
+// ---- ba_lm.cpp ----
+int ba_lm_device(Pool& pool, BAFlat& f, const BAChoice& ch, int iterations, int robust, volatile int* stop_flag, CorbBAResult* r, double delta2, double delta3,
+                 Lap& lap, double** e_chi2_out, LMWork* work = nullptr);
+
+// ---- corb_pose.cpp ----
+void corb_pose_from_T(const float* T, double* out7);            // out7: quaternion x y z w, translation
+void corb_pose_to_T(const double* p7, float* T);
+void corb_pose_optimization_stages(CorbBAStage* st);
+struct PoseBatch {                       // flattened problems of one launch
+    std::vector<int> edge_off{0}, stage_limit;      // stage_limit: empty = every problem runs all stages
+    std::vector<double> pt, obs, w, cam, pose;
+    std::vector<unsigned char> dim;
+};
+int pose_batch_run(const PoseBatch& b, const CorbBAStage* stages, int n_stages, std::vector<double>& pose_out, std::vector<unsigned char>& active_out,
+                   std::vector<int>& counters, double* ms_total);

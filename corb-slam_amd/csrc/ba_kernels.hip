@@ -1547,7 +1547,7 @@ __device__ __forceinline__ double cg_reduce_parts(const double* part, int n, dou
 // after the ticket's value has come back.  One ticket per GROUP: a single ticket for all workgroups serialised 12 500 same-address atomics (+49 us
 // per kernel at 50 000 keyframes).  The ticket is reset by its last taker.
 // The stop tolerance (|r|^2 <= tol^2 |b|^2) of the solve in progress lives on the device (set by ba_pcg_zero_x_kernel): the captured chunks of CG iterations
-// serve every tolerance, and the LM loop may change it from one trial to the next (corb_ba.cpp: the default policy tightens it after a rejected trial).
+// serve every tolerance, and the LM loop may change it from one trial to the next (ba_lm.cpp: the default policy tightens it after a rejected trial).
 #define CG_TOL2(d) ((d).cg_scal[5])
 #define CG_GROUP 64
 #define CG_TICK_STRIDE 64      // ints between two tickets: one ticket per 256 bytes, so that the groups' atomics go to different L2 channels
@@ -3227,7 +3227,7 @@ int ba_launch_schur_bsr(const CorbBADev& d, double lambda, int nnzb, int* bad, i
     }
     return 0;
 }
-// the solve in progress goes on to a tighter tolerance: the state a stopped solve holds is the state its next iteration starts from (see corb_ba.cpp cg_run)
+// the solve in progress goes on to a tighter tolerance: the state a stopped solve holds is the state its next iteration starts from (see ba_lm.cpp cg_run)
 __global__ void ba_pcg_resume_kernel(CorbBADev d, double tol2) { CG_TOL2(d) = tol2; d.cg_flag[0] = 0; }
 void ba_launch_pcg_resume(const CorbBADev& d, double tol, hipStream_t s) { hipLaunchKernelGGL(ba_pcg_resume_kernel, dim3(1), dim3(1), 0, s, d, tol * tol); }
 void ba_launch_pcg_init(const CorbBADev& d, double tol, hipStream_t s)
@@ -3242,7 +3242,7 @@ void ba_launch_pcg_init(const CorbBADev& d, double tol, hipStream_t s)
 // second stream beside the step kernel, the captured graph carrying both branches: 181 -> 172 us per iteration at 50 000 keyframes, but a graph's cross-stream edges
 // cost ~20 us per iteration -- 1 200 keyframes: 20.7 ms of solve per 10 LM iterations against 11.8 on one stream, crossover near 30 000 -- and the one-launch form
 // matches it at 50 000 within 0.4 % (203.6 vs 202.7 ms per 10 LM iterations) and is faster everywhere below: 4 800 keyframes 39.1 -> 35.3 ms, 1 200: 14.6 -> 12.9.)
-// par0: parity of the first iteration (a continuation after an odd number of iterations: corb_ba.cpp cg_run)
+// par0: parity of the first iteration (a continuation after an odd number of iterations: ba_lm.cpp cg_run)
 void ba_launch_pcg_chunk(const CorbBADev& d, int n_iter, hipStream_t s, int par0)
 {
     const bool ml = d.ml && d.pc_g > 1;

@@ -14,7 +14,7 @@
                                 // 600 keyframes 26.7 / 25.7 ms, 1 200: 33.1 / 25.7, 2 x 800: 37.6 / 34.5, 280 keyframes 20.0 / 10.7 ms, 400: 23.4 / 10.4, 600: 26.7 / 12.1, 1 200: 32.7 / 12.9, 2 000: 35.0 / 14.3 (tools/ml_small.py; 2 048 until late in round 4):
                                 // every map the PCG solver takes
 #define BA_ML_STRIDE0 8          // keyframes per node of the first coarse level (the deeper levels: 4 nodes per node)
-#define BA_ML_WEIGHT 1.0         // default weight of the coarse levels' terms (corb_ba.cpp ml_level_weight)
+#define BA_ML_WEIGHT 1.0         // default weight of the coarse levels' terms (ba_ml_host.cpp ml_level_weight)
 #define BA_ML_CHUNK 128          // entries of a restriction row summed by one wavefront
 #define BA_ML_G 16              // nodes per block-Jacobi block of a coarse level (96 rows: 16 x 16 threads with a 6 x 6 block each in ba_pc_sweep_body)
 struct BAMLLevel {

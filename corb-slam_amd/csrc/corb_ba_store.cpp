@@ -4,27 +4,14 @@
 #include "store_host.h"
 #include "ba_store_internal.h"
 static_assert(sizeof(CorbBAOptions) == 32, "CorbBAOptions: scale_factor fills what was padding -- the struct's size is part of the C-ABI");
-#include "ba_device_problem.h"
-#include <vector>
-#include <chrono>
-#include <cstdio>
-#include <cstdlib>
+#include "ba_host.h"
 #include <algorithm>
-#include <cstring>
-#include <thread>
 #include <atomic>
 
-void corb_set_error(const char* fmt, ...);
-int corb_select_device(int device);
-bool corb_ba_staged_device_wanted(const CorbBAStage* stages, int n_stages);
-#define HIPCHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { corb_set_error("%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); return CORB_ERR_HIP; } } while (0)
+bool corb_ba_staged_device_wanted(const CorbBAStage* stages, int n_stages);      // corb_ba_staged.cpp
 
 namespace {
-struct Lap {                          // CORB_BA_TIMING=1: host-side phase times of a call on stderr (development aid, as in corb_ba.cpp)
-    bool on; std::chrono::steady_clock::time_point t;
-    Lap() : on(getenv("CORB_BA_TIMING") != nullptr), t(std::chrono::steady_clock::now()) {}
-    void operator()(const char* what) { if (!on) return; auto n = std::chrono::steady_clock::now(); fprintf(stderr, "[corb_lba_store] %-24s %8.3f ms\n", what, std::chrono::duration<double, std::milli>(n - t).count()); t = n; }
-};
+const char* const STORE_LAP = "[corb_lba_store] %-24s %8.3f ms\n";      // (Lap: this file's phases are sub-millisecond)
 struct DevBuf {                       // device memory of one call: bumped out of an arena when the caller lends one (the local BA), else hipMalloc'ed (a config-5 global BA
                                       // needs ~1 GB: not taken from the per-device arena, which never shrinks)
     std::vector<void*> ptrs;
@@ -116,9 +103,9 @@ static int check_slots(const char* who, CorbKfStore* kf, const int32_t* kf_slots
     // range and order of a slot list in one pass; lists of a global BA (5 M map points: 2 ms on one thread) on a few threads
     auto scan = [](const int32_t* sl, int n, int cap, bool& in_range, bool& ascending) {
         auto part = [sl, cap](int b, int e, bool& ok, bool& asc) {
-            int lo = 0, hi = 0, desc = 0;                            // branch-free: the loop vectorises
-            for (int i = b; i < e; i++) { const int v = sl[i]; lo |= v >> 31; hi |= (cap - 1 - v) >> 31; desc |= (i > 0 && sl[i - 1] >= v) ? 1 : 0; }
-            ok = !(lo | hi); asc = !desc;
+            int hi = 0, desc = 0;                                    // branch-free: the loop vectorises; the unsigned compare catches negative slots too
+            for (int i = b; i < e; i++) { const int v = sl[i]; hi |= (unsigned)v >= (unsigned)cap ? 1 : 0; desc |= (i > 0 && sl[i - 1] >= v) ? 1 : 0; }
+            ok = !hi; asc = !desc;
         };
         const int nt = n >= (1 << 20) ? (int)std::min(8u, std::max(1u, std::thread::hardware_concurrency())) : 1;
         if (nt <= 1) { part(0, n, in_range, ascending); return; }
@@ -147,7 +134,7 @@ static int check_slots(const char* who, CorbKfStore* kf, const int32_t* kf_slots
 extern "C" int corb_ba_solve_store(CorbKfStore* kf, const int32_t* kf_slots, int n_kf, CorbMpStore* mp, const int32_t* mp_slots, int n_mp,
                                    int iterations, int robust, volatile int* stop_flag, uint64_t loop_kf, CorbBAResult* r, const CorbBAOptions* opt)
 {
-    Lap lap;
+    Lap lap(STORE_LAP);
     int rc = check_slots("corb_ba_solve_store", kf, kf_slots, n_kf, mp, mp_slots, n_mp); if (rc) return rc;
     if (!r || iterations < 0) { corb_set_error("corb_ba_solve_store: bad argument"); return CORB_ERR_ARG; }
     rc = corb_select_device(kf->device); if (rc) return rc;
@@ -189,7 +176,7 @@ extern "C" int corb_local_ba_store(CorbKfStore* kf, const int32_t* kf_slots, int
     r->iters_done = 0; r->trials_total = 0;
     if (stop_flag && *stop_flag) return CORB_OK;                  // if(pbStopFlag) if(*pbStopFlag) return; (Optimizer.cc:706-708): nothing is touched
     rc = corb_select_device(kf->device); if (rc) return rc;
-    Lap lap;
+    Lap lap(STORE_LAP);
     std::lock_guard<std::mutex> lk_kf(kf->mu); std::lock_guard<std::mutex> lk_mp(mp->mu);
     HIPCHK(hipStreamSynchronize(kf->stream)); HIPCHK(hipStreamSynchronize(mp->stream));
     hipStream_t s = mp->stream;

@@ -97,19 +97,19 @@ struct CorbScratch {                         // one BA call's view of the worksp
     template <class T> hipError_t upload(T** out, const T* src, size_t n) { hipError_t e = alloc(out, n); if (e == hipSuccess && n) e = h2d(*out, src, n * sizeof(T)); return e; }
     // several small host arrays as ONE allocation and ONE copy (a synchronous copy of a few KB costs ~15 us each; per-frame calls upload up to a dozen)
     struct Piece { void** dst; const void* src; size_t bytes; };
-    hipError_t upload_block(std::initializer_list<Piece> pieces) {
+    hipError_t upload_block(std::initializer_list<Piece> pieces) { return upload_block(pieces.begin(), pieces.size()); }
+    hipError_t upload_block(const Piece* pieces, size_t n) {
         size_t total = 0;
-        for (const Piece& pc : pieces) total += (pc.bytes + 255) & ~(size_t)255;
+        for (size_t i = 0; i < n; i++) total += (pieces[i].bytes + 255) & ~(size_t)255;
         char* base = nullptr; hipError_t e = alloc(&base, total + 256); if (e != hipSuccess) return e;
-        size_t off = 0;
-        if (char* st = static_cast<char*>(ws->host_take(total))) {
-            for (const Piece& pc : pieces) { if (pc.bytes) memcpy(st + off, pc.src, pc.bytes); *pc.dst = base + off; off += (pc.bytes + 255) & ~(size_t)255; }
-            return total ? hipMemcpyAsync(base, st, total, hipMemcpyHostToDevice, stream) : hipSuccess;
-        }
         static thread_local std::vector<char> blob;
-        blob.resize(total + 1);
-        for (const Piece& pc : pieces) { if (pc.bytes) memcpy(blob.data() + off, pc.src, pc.bytes); *pc.dst = base + off; off += (pc.bytes + 255) & ~(size_t)255; }
-        return total ? hipMemcpy(base, blob.data(), total, hipMemcpyHostToDevice) : hipSuccess;
+        char* st = static_cast<char*>(ws->host_take(total));
+        const bool staged = st != nullptr;
+        if (!staged) { blob.resize(total + 1); st = blob.data(); }
+        size_t off = 0;
+        for (size_t i = 0; i < n; i++) { const Piece& pc = pieces[i]; if (pc.bytes) memcpy(st + off, pc.src, pc.bytes); *pc.dst = base + off; off += (pc.bytes + 255) & ~(size_t)255; }
+        if (!total) return hipSuccess;
+        return staged ? hipMemcpyAsync(base, st, total, hipMemcpyHostToDevice, stream) : hipMemcpy(base, st, total, hipMemcpyHostToDevice);
     }
     template <class T> hipError_t upload(T** out, const std::vector<T>& v) { hipError_t e = alloc(out, v.size()); if (e == hipSuccess && !v.empty()) e = h2d(*out, v.data(), v.size() * sizeof(T)); return e; }
 };

@@ -5,7 +5,7 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 RTOL = 1e-4
-PCG_LOOSE = 1e-6          # corb_ba.cpp: BA_PCG_TOL_LOOSE, the cap of the default policy's forcing sequence (the certificate of a call stays within 10x of it)
+PCG_LOOSE = 1e-6          # ba_host.h: BA_PCG_TOL_LOOSE, the cap of the default policy's forcing sequence (the certificate of a call stays within 10x of it)
 
 
 def _args(prob):

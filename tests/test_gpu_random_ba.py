@@ -112,7 +112,7 @@ def _near(g, r):
 def _route(g):
     """the bucket of a result.  What the result itself tells apart: the solver, the fused optimiser (no block pattern: nnz_blocks = 0) and the coarse levels
     (pc_levels > 0).  The in-LDS solve vs the blocked dense Cholesky and the row-owner Schur kernel vs the plain PCG build are not reported in CorbBAResult: those
-    splits follow the reported free_poses (checked against the case's) at the sizes corb_ba.cpp keys them on, 6 free_poses <= 128 and BA_ROW_MIN_POSES"""
+    splits follow the reported free_poses (checked against the case's) at the sizes ba_lm.cpp keys them on, 6 free_poses <= 128 and BA_ROW_MIN_POSES"""
     s = g["structure"]
     if g["solver"] == 1:
         return FUSED if s["nnz_blocks"] == 0 else LDS if 6 * s["free_poses"] <= 128 else DENSE
@@ -207,7 +207,7 @@ def window_case_problem(synth, c):
 
 
 def window_expects_device(p):
-    """corb_ba.cpp: ba_staged_window_host takes a window grouped by point with more than BA_SMALL_EDGES edges and 1 .. 64 free keyframes, and declines one
+    """corb_ba_staged.cpp: ba_staged_window_host takes a window grouped by point with more than BA_SMALL_EDGES edges and 1 .. 64 free keyframes, and declines one
     that the fused one-workgroup optimiser takes (at most 16 free keyframes and BA_SMALL_EDGES active edges)"""
     e = p["edges"]
     free = int((p["pose_fixed"] == 0).sum())

@@ -24,7 +24,7 @@ def test_local_bundle_adjustment(corb, pyorc, synth, seed):
                                      (2022, dict(n_local=30, n_fixed=4, pts_per_kf=30))])        # the last: 29 free keyframes -- no one-workgroup solve, no LM chains
 def test_local_window_on_the_device_equals_the_host_route_bit_for_bit(corb, pyorc, synth, seed, kw):
     """A window whose edges come grouped by point (the order Optimizer.cc creates them in) is flattened, optimised and classified on the device
-    (corb_ba.cpp: ba_staged_window_host); the same window with ONE point's edges moved to the end is no longer grouped and takes the host flattening.  The stable sort
+    (corb_ba_staged.cpp: ba_staged_window_host); the same window with ONE point's edges moved to the end is no longer grouped and takes the host flattening.  The stable sort
     of the host flattening puts every landmark's edges back in the same order, so both routes run the same sums: the same bits, the same flags -- and the oracle's."""
     if os.environ.get("CORB_LBA_HOST_FLATTEN") is not None:
         pytest.skip("the library was told to take the host route everywhere (development switch)")

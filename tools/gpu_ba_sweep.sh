@@ -1,6 +1,6 @@
 #!/bin/bash
 # GPU box: device / wall time of the 50 000-keyframe global BA for library variants in variants/*.so (make EXTRA=...; e.g. -DBA_PCG_CHUNK_BIG=n builds) and, with
-# variants/lib_dev.so (corb_ba.cpp built with -DCORB_DEV), for the preconditioner refresh periods given as arguments (default 1 2 3 5)
+# variants/lib_dev.so (ba_lm.cpp built with -DCORB_DEV), for the preconditioner refresh periods given as arguments (default 1 2 3 5)
 set -u
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 cp corb-slam_amd/libcorb_accel.so /tmp/lib_default.so

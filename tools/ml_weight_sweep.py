@@ -1,4 +1,4 @@
-"""Development aid: CG iterations / solve time of the global BA against the weight of the multilevel preconditioner's coarse terms (CORB_BA_ML_W, corb_ba.cpp
+"""Development aid: CG iterations / solve time of the global BA against the weight of the multilevel preconditioner's coarse terms (CORB_BA_ML_W, ba_ml_host.cpp
 ml_level_weight) at several map sizes.  usage: ml_weight_sweep.py [kf_per_client ...]   (8 clients, 100 points per keyframe, 3..8 observations)"""
 import os, sys, time
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
