@@ -237,9 +237,11 @@ typedef struct {
     float fx1, fy1, cx1, cy1, fx2, fy2, cx2, cy2;  /* K1, K2 */
 } OrcSim3Problem;
 /* g2oS12 in/out as (R 3x3 row-major, t, s) in double; removed[i] = 1 when vpMatches1[idx] is nulled; returns nIn (0 and S12 unchanged when
- * fewer than 10 correspondences survive the first round) */
+ * fewer than 10 correspondences survive the first round).  detail (4 ints, may be NULL; for the tests of the case lists): iterations and trials of
+ * the first optimize(), the pairs its classification removed, and whether the last Levenberg trial of the whole call was accepted (the chi2 that
+ * classify are those of the last trial state, which is the returned estimate only then) */
 int orc_optimize_sim3(const OrcSim3Problem* p, double* R12, double* t12, double* s12, float th2, int fix_scale, uint8_t* removed,
-                      int* iters_done, int* trials);
+                      int* iters_done, int* trials, int* detail);
 
 /* ---- Optimizer::OptimizeEssentialGraph (Optimizer.cc:840-1117) ---- */
 int orc_optimize_essential_graph(int K, double* S /* K x 8: quaternion xyzw, t, s */, const uint8_t* fixed, int E, const int32_t* vi, const int32_t* vj,

@@ -183,7 +183,7 @@ static void oplus(Sim3* S, const double* x, int fix_scale)
 }
 
 /* optimizer.initializeOptimization(); optimizer.optimize(iters) on the alive pairs */
-static void optimize7(S3* g, Sim3* S, int iters, int fix_scale, int* iters_done, int* trials)
+static void optimize7(S3* g, Sim3* S, int iters, int fix_scale, int* iters_done, int* trials, int* last_accepted)
 {
     double lambda = -1, ni = 2; int nBad = 0, ok = 1;
     for (int it = 0; it < iters && ok; it++) {
@@ -236,8 +236,8 @@ static void optimize7(S3* g, Sim3* S, int iters, int fix_scale, int* iters_done,
             scale += 1e-3; rho_lm /= scale;
             if (rho_lm > 0 && isfinite(tempChi)) {
                 double alpha = 1. - pow((2 * rho_lm - 1), 3); alpha = fmin(alpha, 2. / 3.);
-                lambda *= fmax(1. / 3., alpha); ni = 2; currentChi = tempChi;
-            } else { lambda *= ni; ni *= 2; *S = bak; }
+                lambda *= fmax(1. / 3., alpha); ni = 2; currentChi = tempChi; *last_accepted = 1;
+            } else { lambda *= ni; ni *= 2; *S = bak; *last_accepted = 0; }
             qmax++; (*trials)++;
         } while (rho_lm < 0 && qmax < 10);
         (*iters_done)++;
@@ -248,7 +248,7 @@ static void optimize7(S3* g, Sim3* S, int iters, int fix_scale, int* iters_done,
 }
 
 int orc_optimize_sim3(const OrcSim3Problem* p, double* R12, double* t12, double* s12, float th2, int fix_scale, uint8_t* removed,
-                      int* iters_done, int* trials)
+                      int* iters_done, int* trials, int* detail)
 {
     const int n = p->n;
     Sim3 S; q_from_R(R12, S.q); S.t[0] = t12[0]; S.t[1] = t12[1]; S.t[2] = t12[2]; S.s = *s12;   /* Sim3(Matrix3d R, t, s) */
@@ -256,14 +256,15 @@ int orc_optimize_sim3(const OrcSim3Problem* p, double* R12, double* t12, double*
     double* l12 = (double*)calloc(n > 0 ? n : 1, sizeof(double)); double* l21 = (double*)calloc(n > 0 ? n : 1, sizeof(double));
     for (int i = 0; i < n; i++) { alive[i] = 1; removed[i] = 0; }
     S3 g; g.p = p; g.n = n; g.alive = alive; g.delta = (double)sqrtf(th2); g.last12 = l12; g.last21 = l21;     /* const float deltaHuber = sqrt(th2) */
-    int it = 0, tr = 0;
-    optimize7(&g, &S, 5, fix_scale, &it, &tr);
+    int it = 0, tr = 0, acc = 0;
+    optimize7(&g, &S, 5, fix_scale, &it, &tr, &acc);
     int nBad = 0;
     for (int i = 0; i < n; i++) if (l12[i] > (double)th2 || l21[i] > (double)th2) { removed[i] = 1; alive[i] = 0; nBad++; }
+    if (detail) { detail[0] = it; detail[1] = tr; detail[2] = nBad; }
     const int nMore = nBad > 0 ? 10 : 5;
     int nIn = 0;
     if (n - nBad >= 10) {
-        optimize7(&g, &S, nMore, fix_scale, &it, &tr);
+        optimize7(&g, &S, nMore, fix_scale, &it, &tr, &acc);
         for (int i = 0; i < n; i++) {
             if (!alive[i]) continue;
             if (l12[i] > (double)th2 || l21[i] > (double)th2) removed[i] = 1; else nIn++;
@@ -272,6 +273,7 @@ int orc_optimize_sim3(const OrcSim3Problem* p, double* R12, double* t12, double*
     }
     if (iters_done) *iters_done = it;
     if (trials) *trials = tr;
+    if (detail) detail[3] = acc;
     free(alive); free(l12); free(l21);
     return nIn;
 }

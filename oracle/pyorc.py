@@ -20,7 +20,7 @@ assert EDGE_DTYPE.itemsize == 24
 
 def build(force=False):
     so = os.path.join(_HERE, "liborc.so")
-    srcs = [os.path.join(_HERE, f) for f in ("orc_orb.c", "orc_match.c", "orc_ba.c", "orc_proj.c", "orc.h", "brief_pattern.h")]
+    srcs = [os.path.join(_HERE, f) for f in ("orc_orb.c", "orc_match.c", "orc_ba.c", "orc_proj.c", "orc_sim3.c", "orc_map.c", "orc.h", "brief_pattern.h")]
     if force or not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs if os.path.exists(s)):
         subprocess.check_call(["make", "-C", _HERE, "-s"])
     return so
@@ -166,7 +166,7 @@ def _proto(L):
     L.orc_essential_graph_apply.restype = None
     L.orc_essential_graph_apply.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
     L.orc_optimize_sim3.restype = C.c_int
-    L.orc_optimize_sim3.argtypes = [C.POINTER(_Sim3Problem), C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_int, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.orc_optimize_sim3.argtypes = [C.POINTER(_Sim3Problem), C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_int, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p]
     L.orc_distinctive_descriptors.restype = None
     L.orc_distinctive_descriptors.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
     L.orc_mappoint_replace.restype = C.c_int
@@ -558,14 +558,16 @@ def rebase_map(To2n, poses, points):
 
 
 def optimize_sim3(q, th2=10.0, fix_scale=False):
-    """q: dict from synth.sim3_problem.  Returns dict(R, t, s, removed, n_in, iters_done, trials)."""
+    """q: dict from synth.sim3_problem.  Returns dict(R, t, s, removed, n_in, iters_done, trials) and, of the first optimize() alone, round1_iters, round1_trials and
+    round1_removed (the pairs its classification took out), and last_accepted (whether the last Levenberg trial of the call was accepted)."""
     a = {k: np.ascontiguousarray(q[k], np.float32) for k in ("p1c", "p2c", "obs1", "obs2", "inv_sigma2_1", "inv_sigma2_2")}
     K = [float(np.float32(q[k])) for k in ("fx1", "fy1", "cx1", "cy1", "fx2", "fy2", "cx2", "cy2")]
     prob = _Sim3Problem(len(a["p1c"]), _ptr(a["p1c"]), _ptr(a["p2c"]), _ptr(a["obs1"]), _ptr(a["obs2"]), _ptr(a["inv_sigma2_1"]), _ptr(a["inv_sigma2_2"]), *K)
     R = np.ascontiguousarray(q["R12"], np.float64).reshape(9).copy(); t = np.ascontiguousarray(q["t12"], np.float64).reshape(3).copy(); s = np.array([q["s12"]], np.float64)
-    removed = np.zeros(max(len(a["p1c"]), 1), np.uint8); it = C.c_int(); tr = C.c_int()
-    n_in = lib().orc_optimize_sim3(C.byref(prob), _ptr(R), _ptr(t), _ptr(s), float(np.float32(th2)), int(fix_scale), _ptr(removed), C.byref(it), C.byref(tr))
-    return dict(R=R.reshape(3, 3), t=t, s=float(s[0]), removed=removed[: len(a["p1c"])].copy(), n_in=n_in, iters_done=it.value, trials=tr.value)
+    removed = np.zeros(max(len(a["p1c"]), 1), np.uint8); it = C.c_int(); tr = C.c_int(); det = np.zeros(4, np.int32)
+    n_in = lib().orc_optimize_sim3(C.byref(prob), _ptr(R), _ptr(t), _ptr(s), float(np.float32(th2)), int(fix_scale), _ptr(removed), C.byref(it), C.byref(tr), _ptr(det))
+    return dict(R=R.reshape(3, 3), t=t, s=float(s[0]), removed=removed[: len(a["p1c"])].copy(), n_in=n_in, iters_done=it.value, trials=tr.value,
+                round1_iters=int(det[0]), round1_trials=int(det[1]), round1_removed=int(det[2]), last_accepted=bool(det[3]))
 
 
 def optimize_essential_graph(g, iters=20, fix_scale=False):
