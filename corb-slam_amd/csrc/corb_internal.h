@@ -48,6 +48,15 @@ struct CorbLevel {
     int patch_size;               // (int)(31*scale)
 };
 
+// Static geometry of one FAST detection cell (orb_fast_kernel), one record per cell of the per-image cell table: everything the kernel's
+// prologue would otherwise derive with divisions from (width, height, nlevels, scale).  Built once at create.
+struct CorbFastCell {
+    uint32_t src_off;             // byte offset inside one image's pyramid arena of the aligned dword that holds tile column 0 (image x = iniX - 1) of row iniY
+    uint32_t org;                 // iniX + 3 - CORB_MIN_BORDER | (iniY + 3 - CORB_MIN_BORDER) << 12 | level << 24 | empty << 31   (empty: cw < 7 || ch < 7)
+    uint32_t dim;                 // cw | ch << 8 | rstep << 16 | ng << 24: cell with its 3-px ring, ng = 4-px groups per interior row, rstep = 64 / ng
+    uint32_t lane;                // ceil(65536 / ng) (lane / ng as a 16.16 multiply) | jlast << 20 (aligned dword of a row that holds the last cell pixel)
+};
+
 #define CORB_BLUR_T 64            // threads per workgroup of the blur kernel (independent wavefronts)
 #define CORB_MAX_PARTS 4          // part-batches of one run (corb_orb.cpp): 1 + side streams
 
@@ -74,6 +83,7 @@ struct CorbOrbParams {
     int* kp_count;                // [n_images][CORB_MAX_LEVELS]
     const short* resize_tab;      // per level: xofs[w], xa0[w], xa1[w], yofs[h], yb0[h], yb1[h]
     const int2* resize_rec;       // per level: xrec[align4(w)] {sx, a0|a1<<16}, yrec[h] {ys0|ys1<<16, b0|b1<<16}
+    const CorbFastCell* fast_cells;   // [cells_per_image]
     CorbKeyPoint* out_kp;         // [n_images][out_cap]
     uint8_t* out_desc;            // [n_images][out_cap][32]
     int* out_count;               // [n_images]

@@ -180,10 +180,33 @@ extern "C" int corb_orb_create(const CorbOrbConfig* cfg, CorbOrb** out)
     DA(d_tab, (size_t)tab_off);
     int2* d_rec = nullptr;
     DA(d_rec, (size_t)rec_off + 4);
+    CorbFastCell* d_cells = nullptr;
+    DA(d_cells, (size_t)cells);
     DA(h->dp, 1);
 #undef DA
     p.resize_tab = d_tab;
     p.resize_rec = d_rec;
+    p.fast_cells = d_cells;
+    {
+        // per-cell geometry of the FAST kernel (ORBextractor.cc:789-805): the same for every image of the handle
+        std::vector<CorbFastCell> fc((size_t)cells);
+        for (int l = 0; l < nl; l++) {
+            const CorbLevel& L = p.lv[l];
+            for (int c = 0; c < L.nCols * L.nRows; c++) {
+                const int ci = c / L.nCols, cj = c - ci * L.nCols;
+                const int iniX = CORB_MIN_BORDER + cj * L.wCell, iniY = CORB_MIN_BORDER + ci * L.hCell;
+                const int cw = std::min(iniX + L.wCell + 6, L.maxBX) - iniX, ch = std::min(iniY + L.hCell + 6, L.maxBY) - iniY;
+                CorbFastCell& f = fc[(size_t)L.cell_base + c];
+                f.org = (uint32_t)(iniX + 3 - CORB_MIN_BORDER) | ((uint32_t)(iniY + 3 - CORB_MIN_BORDER) << 12) | ((uint32_t)l << 24);
+                if (cw < 7 || ch < 7) { f.src_off = 0; f.org |= 0x80000000u; f.dim = 0; f.lane = 0; continue; }
+                const int gx0 = iniX - 1, a = gx0 & 3, ng = (cw - 6 + 3) >> 2;
+                f.src_off = (uint32_t)L.plane_off + (uint32_t)iniY * (uint32_t)L.pitch + (uint32_t)(gx0 - a);
+                f.dim = (uint32_t)cw | ((uint32_t)ch << 8) | ((uint32_t)(64 / ng) << 16) | ((uint32_t)ng << 24);
+                f.lane = (uint32_t)((65536 + ng - 1) / ng) | ((uint32_t)((a + cw) >> 2) << 20);
+            }
+        }
+        if (hipMemcpy(d_cells, fc.data(), fc.size() * sizeof(CorbFastCell), hipMemcpyHostToDevice) != hipSuccess) { corb_set_error("FAST cell table upload failed"); corb_orb_destroy(h); return CORB_ERR_HIP; }
+    }
     {
         std::vector<short> tab(tab_off);
         for (int l = 1; l < nl; l++) build_resize_tables(p.lv[l - 1].w, p.lv[l - 1].h, p.lv[l].w, p.lv[l].h, tab.data() + p.lv[l].resize_tab_off);

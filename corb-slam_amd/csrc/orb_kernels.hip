@@ -269,33 +269,31 @@ template <int K> __device__ __forceinline__ uint32_t pk_pair(const uint32_t (&w)
 }
 typedef short corb_short2 __attribute__((ext_vector_type(2)));
 
-// cornerScore of two pixels at once from their packed ring values v[i] = [ring_i(A), 0 | ring_i(B), 0] and centres c = [A, 0 | B, 0]
-__device__ __forceinline__ uint32_t fast_ring_score(const uint32_t (&v)[16], uint32_t cpk)
+// The 9-of-16 sliding chain of one polarity on packed ring values v[i] = [ring_i(A), 0 | ring_i(B), 0]: 16 3-windows, 16 9-windows, the reduction
+// over the 16 arcs (40 packed ops).  BRIGHT: max over the arcs of the arc's minimum; otherwise min over the arcs of the arc's maximum.
+template <bool BRIGHT> __device__ __forceinline__ uint32_t fast_arc_chain(const uint32_t (&v)[16])
 {
-    uint32_t lo3[16], hi3[16];
+    auto in3 = [](uint32_t a, uint32_t b, uint32_t c) { return BRIGHT ? pk_min3(a, b, c) : pk_max3(a, b, c); };
+    auto out3 = [](uint32_t a, uint32_t b, uint32_t c) { return BRIGHT ? pk_max3(a, b, c) : pk_min3(a, b, c); };
+    uint32_t w3[16], w9[16], r5[5];
 #pragma unroll
-    for (int i = 0; i < 16; i++) {
-        lo3[i] = pk_min3(v[i], v[(i + 1) & 15], v[(i + 2) & 15]);
-        hi3[i] = pk_max3(v[i], v[(i + 1) & 15], v[(i + 2) & 15]);
-    }
-    uint32_t lo9[16], hi9[16];
+    for (int i = 0; i < 16; i++) w3[i] = in3(v[i], v[(i + 1) & 15], v[(i + 2) & 15]);
 #pragma unroll
-    for (int i = 0; i < 16; i++) {
-        lo9[i] = pk_min3(lo3[i], lo3[(i + 3) & 15], lo3[(i + 6) & 15]);
-        hi9[i] = pk_max3(hi3[i], hi3[(i + 3) & 15], hi3[(i + 6) & 15]);
-    }
-    uint32_t b5[5], d5[5];
+    for (int i = 0; i < 16; i++) w9[i] = in3(w3[i], w3[(i + 3) & 15], w3[(i + 6) & 15]);
 #pragma unroll
-    for (int i = 0; i < 5; i++) { b5[i] = pk_max3(lo9[3 * i], lo9[3 * i + 1], lo9[3 * i + 2]); d5[i] = pk_min3(hi9[3 * i], hi9[3 * i + 1], hi9[3 * i + 2]); }
-    const uint32_t B = pk_max3(pk_max3(b5[0], b5[1], b5[2]), pk_max3(b5[3], b5[4], lo9[15]), b5[0]);   // max_arcs min_arc
-    const uint32_t D = pk_min3(pk_min3(d5[0], d5[1], d5[2]), pk_min3(d5[3], d5[4], hi9[15]), d5[0]);   // min_arcs max_arc
-    const corb_short2 c = __builtin_bit_cast(corb_short2, cpk);
-    const corb_short2 s = __builtin_elementwise_max(__builtin_bit_cast(corb_short2, B) - c, c - __builtin_bit_cast(corb_short2, D)) - (short)1;
-    return __builtin_bit_cast(uint32_t, s);
+    for (int i = 0; i < 5; i++) r5[i] = out3(w9[3 * i], w9[3 * i + 1], w9[3 * i + 2]);
+    return out3(out3(r5[0], r5[1], r5[2]), out3(r5[3], r5[4], w9[15]), r5[0]);
 }
 
-// Scores of the two pixels J (= 0: window bytes 4,5; 1: bytes 6,7) of a 4-pixel group; R[dy+3] = window of row y+dy; 0 = below the threshold
-template <int J> __device__ __forceinline__ uint32_t fast_pair_score(const uint32_t (&R)[7][3], uint32_t th2)
+// Scores of the two pixels J (= 0: window bytes 4,5; 1: bytes 6,7) of a 4-pixel group; R[dy+3] = window of row y+dy; 0 = below the threshold t.
+// cornerScore = max(B - c, c - D) - 1 with B = max_arcs min_arc(ring), D = min_arcs max_arc(ring).  Every arc of 9 holds two adjacent compass
+// points, so B <= m and D >= n of fast_compass: a side whose compass test fails at t stays below t and cannot be the score of a pixel that
+// scores >= t.  Nearly every listed pixel passes on one side only (both: 0.3 % of the passing pixels on the synthetic frames), and the dark
+// side is the bright side of the complemented bytes, c - D(v) = B(255 - v) - (255 - c): ring and centre are XOR-ed with 0x00ff in the halves
+// that pass on the dark side only and ONE chain scores both halves.  When a half of any lane passes on both sides the wave also runs the dual
+// chain on the same values (wave-uniform branch) and takes the maximum, which is the two-sided score whatever the halves' masks are.
+// kb = t + 0x200, kd = 0x200 - t - 1 in both halves: the side tests as plain 32-bit adds whose halves stay in 1 .. 0x3fe (no borrow across).
+template <int J> __device__ __forceinline__ uint32_t fast_pair_score(const uint32_t (&R)[7][3], uint32_t th2, uint32_t kb, uint32_t kd)
 {
     constexpr int C = 4 + 2 * J;
     uint32_t v[16];
@@ -303,7 +301,18 @@ template <int J> __device__ __forceinline__ uint32_t fast_pair_score(const uint3
     v[4] = pk_pair<C + 3>(R[3]);  v[5] = pk_pair<C + 3>(R[2]);  v[6] = pk_pair<C + 2>(R[1]);  v[7] = pk_pair<C + 1>(R[0]);
     v[8] = pk_pair<C>(R[0]);      v[9] = pk_pair<C - 1>(R[0]);  v[10] = pk_pair<C - 2>(R[1]); v[11] = pk_pair<C - 3>(R[2]);
     v[12] = pk_pair<C - 3>(R[3]); v[13] = pk_pair<C - 3>(R[4]); v[14] = pk_pair<C - 2>(R[5]); v[15] = pk_pair<C - 1>(R[6]);
-    const corb_short2 s = __builtin_bit_cast(corb_short2, fast_ring_score(v, pk_pair<C>(R[3])));
+    const uint32_t cpk = pk_pair<C>(R[3]);
+    const uint32_t e0 = pk_max3(v[0], v[8], v[8]), e1 = pk_max3(v[4], v[12], v[12]), f0 = pk_min3(v[0], v[8], v[8]), f1 = pk_min3(v[4], v[12], v[12]);
+    const uint32_t m = pk_min3(e0, e1, e1), n = pk_max3(f0, f1, f1);                // as in fast_compass
+    const uint32_t nbright = (cpk + kb) - m;                                       // 0x200 + c + t - m     : bit 9 <=> NOT m - c > t
+    const uint32_t dark = ((cpk + kd) - n) & 0x02000200u;                          // 0x200 + c - n - t - 1 : bit 9 <=> c - n > t
+    const uint32_t donly = dark & nbright, both = dark ^ donly;
+    const uint32_t xm = (donly >> 1) - (donly >> 9);                               // 0x00ff in the dark-only halves
+#pragma unroll
+    for (int i = 0; i < 16; i++) v[i] ^= xm;
+    const corb_short2 c = __builtin_bit_cast(corb_short2, cpk ^ xm) + (short)1;
+    corb_short2 s = __builtin_bit_cast(corb_short2, fast_arc_chain<true>(v)) - c;
+    if (__any(both != 0u)) s = __builtin_elementwise_max(s, c - (short)2 - __builtin_bit_cast(corb_short2, fast_arc_chain<false>(v)));
     const corb_short2 keep = s >= __builtin_bit_cast(corb_short2, th2);            // -1 / 0 per half
     return __builtin_bit_cast(uint32_t, (corb_short2)(s & keep));                  // [s,0 | s',0]
 }
@@ -335,7 +344,7 @@ __device__ __forceinline__ int mbcnt64(unsigned long long m) { return (int)__bui
 //   1. compass test at the pass' threshold for every pixel (a lane owns a group of 4 pixels = two packed pairs, lanes are an ng x (64/ng)
 //      patch sliding down the cell); the pixel PAIRS with a pixel that passes (11 % of the pairs at t = 20 on the synthetic KITTI-size frames) are
 //      appended to a list in LDS (two ballots and lane-prefix counts per sweep, no atomics);
-//   2. the full 9-of-16 arc score only for the listed pairs, one pair per lane (the second pair of a group is the first pair's window two
+//   2. the 9-of-16 arc score only for the listed pairs and only on the side each pixel passed on (fast_pair_score), one pair per lane (the second pair of a group is the first pair's window two
 //      bytes further: one v_alignbyte per window dword); scores >= threshold go to the score bytes (everything else stays 0 -- for
 //      cv::FAST's NMS a non-corner scores 0);
 //   3. strict 8-neighbour NMS on the score bytes, over the listed pairs, survivors as per-row bit masks, compacted in row-major order.
@@ -371,22 +380,21 @@ __global__ __launch_bounds__(64) void orb_fast_kernel(const CorbOrbParams p)
     uint8_t* scb = reinterpret_cast<uint8_t*>(sc);
     int cell, img; corb_xcd_remap(cell, img); img += p.img_base;
     const int lane = threadIdx.x;
-    int level = 0;
-    for (int l = 1; l < p.nlevels; l++) if (cell >= p.lv[l].cell_base) level = l;
-    const CorbLevel& L = p.lv[level];
-    const int c = cell - L.cell_base;
-    const int ci = c / L.nCols, cj = c - ci * L.nCols;
-    const int iniX = CORB_MIN_BORDER + cj * L.wCell, iniY = CORB_MIN_BORDER + ci * L.hCell;
-    const int maxX = min(iniX + L.wCell + 6, L.maxBX), maxY = min(iniY + L.hCell + 6, L.maxBY);
-    const int cw = maxX - iniX, ch = maxY - iniY;
+    // the cell's geometry depends on the handle alone: one record per cell, built at create (CorbFastCell), read through the scalar cache
+    uint4 rec = reinterpret_cast<const uint4*>(p.fast_cells)[cell];
+    asm volatile("" : "+s"(rec.x));                    // keeps the record ONE scalar load: otherwise src_off is sunk to its use as a vector load of its own
     int* out_count = p.cell_count + (size_t)img * p.cells_per_image + cell;
-    if (cw < 7 || ch < 7) { if (lane == 0) *out_count = 0; return; }      // subsumes the skips at :796, :805
+    if (rec.y >> 31) { if (lane == 0) *out_count = 0; return; }           // cw < 7 || ch < 7: subsumes the skips at :796, :805
+    const CorbLevel& L = p.lv[(rec.y >> 24) & 15u];
+    const int c = cell - L.cell_base;
+    const int ox = (int)(rec.y & 0xFFFu), oy = (int)((rec.y >> 12) & 0xFFFu);     // first interior pixel, coordinates - CORB_MIN_BORDER
+    const int cw = (int)(rec.z & 0xFFu), ch = (int)((rec.z >> 8) & 0xFFu);
     const int iw = cw - 6, ih = ch - 6;                  // interior; iw, ih <= 64 (checked at create)
     {
         // tile column k <-> image x = iniX - 1 + k  (column 0 is padding)
-        const int gx0 = iniX - 1, a = gx0 & 3;
-        const uint8_t* src = p.pyr + (size_t)img * p.arena_per_image + L.plane_off + (size_t)iniY * L.pitch + (gx0 - a);
-        const int jlast = (a + cw) >> 2;                 // aligned dword holding the last cell pixel
+        const uint32_t a = (uint32_t)ox & 3u;           // (iniX - 1) & 3: iniX - 1 = ox + 12
+        const uint8_t* src = p.pyr + (size_t)img * p.arena_per_image + rec.x;      // aligned dword holding tile column 0 of the cell's first row
+        const int jlast = (int)(rec.w >> 20);            // aligned dword holding the last cell pixel
         const int r0 = lane / P, wc = lane - r0 * P;
         constexpr int RPI = 64 / P;
         if (r0 < RPI) {
@@ -400,14 +408,13 @@ __global__ __launch_bounds__(64) void orb_fast_kernel(const CorbOrbParams p)
                 }
 #pragma unroll
                 for (int k = 0; k < 4; k++)
-                    if (y + k * RPI < ch) { tile[(y + k * RPI) * P + wc] = __builtin_amdgcn_alignbyte(w1[k], w0[k], (uint32_t)a); sc[(y + k * RPI) * P + wc] = 0u; }
+                    if (y + k * RPI < ch) { tile[(y + k * RPI) * P + wc] = __builtin_amdgcn_alignbyte(w1[k], w0[k], a); sc[(y + k * RPI) * P + wc] = 0u; }
             }
         }
     }
     __syncthreads();
-    const int ng = (iw + 3) >> 2;                        // 4-pixel groups per interior row (<= 16)
-    const int rstep = 64 / ng;
-    const int r = (lane * ((65536 + ng - 1) / ng)) >> 16, g = lane - r * ng;      // lane / ng for lane < 64, ng <= 16 (exact; the reciprocal is wave-uniform)
+    const int rstep = (int)((rec.z >> 16) & 0xFFu), ng = (int)(rec.z >> 24);      // 4-pixel groups per interior row (<= 16), 64 / ng
+    const int r = (int)(((uint32_t)lane * (rec.w & 0xFFFFFu)) >> 16), g = lane - r * ng;      // lane / ng for lane < 64, ng <= 16 (exact 16.16 reciprocal)
     const bool active = r < rstep;
     const int nvalid = min(4, iw - 4 * g);               // pixels of this group inside the interior
     const uint32_t smask0 = nvalid >= 2 ? 0x80008000u : nvalid == 1 ? 0x00008000u : 0u, smask1 = nvalid >= 4 ? 0x80008000u : nvalid == 3 ? 0x00008000u : 0u;
@@ -415,6 +422,7 @@ __global__ __launch_bounds__(64) void orb_fast_kernel(const CorbOrbParams p)
     for (int pass = 0; pass < 2; pass++) {
         const int th = pass == 0 ? p.ini_th : p.min_th;
         const uint32_t th2 = (uint32_t)th * 0x00010001u;
+        const uint32_t kb = th2 + 0x02000200u, kd = 0x02000200u - th2 - 0x00010001u;      // side tests of phase 2 (fast_pair_score)
         if (lane < nrowm) { rowm[lane][0] = 0u; rowm[lane][1] = 0u; }
         int y0 = 3, nbatch = 0, base = 0, nscore = 0;
         while (y0 < ch - 3) {
@@ -460,7 +468,7 @@ __global__ __launch_bounds__(64) void orb_fast_kernel(const CorbOrbParams p)
                     const uint32_t w0 = t[(dy - 3) * P], w1 = t[(dy - 3) * P + 1], w2 = t[(dy - 3) * P + 2];
                     R[dy][0] = __builtin_amdgcn_alignbyte(w1, w0, sh); R[dy][1] = __builtin_amdgcn_alignbyte(w2, w1, sh); R[dy][2] = __builtin_amdgcn_alignbyte(0u, w2, sh);
                 }
-                const uint32_t s0 = fast_pair_score<0>(R, th2);                    // [s,0 | s',0]
+                const uint32_t s0 = fast_pair_score<0>(R, th2, kb, kd);                    // [s,0 | s',0]
                 const int px = 4 * ge + (int)sh;                                  // interior column of the pair's first pixel (< iw: it passed the mask)
                 uint32_t v = __builtin_amdgcn_perm(0u, s0, 0x0c0c0200u);          // s | s' << 8
                 if (px + 1 >= iw) v &= 0xFFu;
@@ -542,7 +550,7 @@ __global__ __launch_bounds__(64) void orb_fast_kernel(const CorbOrbParams p)
         const int x = __ffsll((long long)mask) - 1;
         mask &= mask - 1;
         if (off < L.cell_cap)
-            out[off] = (uint32_t)(iniX + x + 3 - CORB_MIN_BORDER) | ((uint32_t)(iniY + lane + 3 - CORB_MIN_BORDER) << 12) |
+            out[off] = (uint32_t)(ox + x) | ((uint32_t)(oy + lane) << 12) |
                        ((uint32_t)scb[(lane + 3) * TP + x + 4] << 24);
         off++;
     }
