@@ -121,28 +121,63 @@ template <int K> __device__ __forceinline__ void pyr_px(uint32_t& packed, uint32
 // A workgroup = one strip x one column tile, PYR_T threads.  (One workgroup of 1 024 threads per strip over the full width was as fast alone, but a
 // 16-wavefront workgroup needs 16 free wave slots on ONE CU at once: beside the other part-batch's kernels, whose one-wavefront workgroups keep
 // refilling the slots, the pyramid launches were stretched 2.8x.)
+//
+// Work mapping inside the workgroup, per level (rows [r0, r1) x 4-px column groups [g0, g1) of the tile):
+//   * each of the 4 wavefronts takes a quarter of the rows and walks the tile's column groups in chunks of W <= 64 groups (pyr_chunk_width);
+//   * a chunk of W groups holds R = 64 / W row runs side by side: lane = (run, group), and a lane builds CONSECUTIVE output rows of its run.
+//     Output row y reads source rows ys0[y] and ys1[y]; whenever ys0[y] == ys1[y - 1] (5 rows of 6 at scale 1.2) the horizontal pass of the upper
+//     source row is the one the previous output row kept (four 32-bit sums), so only the lower row is loaded, gathered and multiplied: 1.2 horizontal
+//     passes and 3.6 dword loads per output row instead of 2 and 6.  The decision is taken from the row indices of the y records (first row of a run,
+//     a source step of 2 and anything else that does not line up recompute) and is wave-uniform: with R > 1 all lanes recompute when any lane must;
+//   * with R == 1 (every chunk of 48..64 groups: the bulk of KITTI levels 1 and 2, half of level 3) everything indexed by y is wave-uniform: the y records
+//     are read through the scalar cache, b0 | b1, the source / destination row bases and the loop control live in SGPRs (PyrUni; checked in the ISA: the
+//     trip's records are s_load_dwordx2, the keep-or-recompute decisions s_cmp + s_cbranch, a row's address one VALU add of a scalar row offset);
+//   * the records travel one trip ahead of the rows.  PyrUni: the loads of FOUR output rows (12 .. 24 dwords) are issued before the first is consumed;
+//     per-lane runs: two rows (their runs are a few rows long, and four more rows' records per lane do not fit into 64 VGPRs).
+// Busy lanes per KITTI level (1241 x 376, scale 1.2, 4 x 4 tiles with their overlap rows and groups; lane-trips with a row to build out of all lane-trips of the
+// wavefronts' row loops) and horizontal passes per output row (2 without the kept row; 1.2 is the floor at this scale, every run's first row costs one more):
+//   level   groups / tile   rows / strip   chunks (W x R)                  busy lanes   passes / row
+//     1       69 .. 74        83 .. 85     64x1 + 5x12 | 10x6                98 %         1.26
+//     2       57 .. 61        69 .. 70     57x1 | 61x1                       92 %         1.25
+//     3       47 .. 50        57 .. 58     32x2 + 15x4 | 50x1                84 %         1.29
+//     4       39 .. 41        47 .. 48     32x2 + 7x9 | 9x7                  93 %         1.39
+//     5       32 .. 34        39 .. 40     32x2 (+ 1x64 | 2x32)              91 %         1.32
+//     6       26 .. 28        32 .. 33     26x2 | 27x2 | 28x2                82 %         1.38
+//     7       21 .. 22        26 .. 27     21x3 | 16x4 + 6x10                76 %         1.71
+// 64 VGPRs, no scratch, 8 wavefronts per SIMD.
 #define PYR_T 256
+typedef const uint64_t __attribute__((address_space(4)))* pyr_yrec_ptr;      // constant address space: uniform reads become scalar loads although the kernel stores between them
+struct PyrUni { static constexpr bool value = true; };                        // one row run per wavefront: y is wave-uniform
+struct PyrLane { static constexpr bool value = false; };                      // several runs per wavefront: y per lane
+// width of the next chunk when `rem` column groups are left: all of them when the R = 64 / rem runs that fit fill >= 3/4 of the wavefront, else the
+// largest power of two (which divides 64: all lanes busy) with the remainder left to the next chunk
+__device__ __forceinline__ int pyr_chunk_width(int rem)
+{
+    if (rem >= 64) return 64;
+    return (64 / rem) * rem * 4 >= 3 * 64 ? rem : 1 << (31 - __clz(rem));
+}
 __global__ __launch_bounds__(PYR_T, 8) void orb_pyramid_kernel(const CorbOrbParams p)
 {
     const int strip = blockIdx.x / p.pyr_ctiles, ctile = blockIdx.x - strip * p.pyr_ctiles, img = p.img_base + blockIdx.y;
     uint8_t* base = p.pyr + (size_t)img * p.arena_per_image;
     const uint32_t two = 2u;
+    const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6), lane = (int)threadIdx.x & 63;
     for (int level = 1; level < p.nlevels; level++) {
         const CorbLevel& D = p.lv[level];
         const CorbLevel& S = p.lv[level - 1];
         const int2* xrec = p.resize_rec + D.resize_rec_off;          // per x: {sx, a0 | a1 << 16}
-        const int2* yrec = xrec + ((D.w + 3) & ~3);                   // per y: {ys0 | ys1 << 16, b0 | b1 << 16}
+        const pyr_yrec_ptr yrec = (pyr_yrec_ptr)(uintptr_t)(xrec + ((D.w + 3) & ~3));   // per y: {ys0 | ys1 << 16, b0 | b1 << 16}
         const uint8_t* src = base + S.plane_off;
         uint8_t* dstp = base + D.plane_off;
         const int r0 = p.pyr_r0[strip][level], r1 = p.pyr_r1[strip][level];
-        // lanes of the workgroup = (row, 4-px column group) in row-major order: XW column groups x RY rows per step, so the idle
-        // lanes are the < XW left over out of PYR_T instead of the unused part of a fixed 64 x 16 tile (68 % -> 93 % busy on the
-        // smallest KITTI level); a thread keeps its column group for all rows, so the per-column setup is still done once
-        const int gfirst = p.pyr_g0[ctile][level], ngroups = p.pyr_g1[ctile][level];      // this tile's 4-px column groups [gfirst, ngroups)
-        for (int gbase = gfirst; gbase < ngroups; gbase += PYR_T) {
-            const int XW = min(ngroups - gbase, PYR_T), RY = PYR_T / XW;
-            const int ty = (int)threadIdx.x / XW, tx = (int)threadIdx.x - ty * XW;
-            if (ty >= RY) continue;
+        const int gfirst = p.pyr_g0[ctile][level], gend = p.pyr_g1[ctile][level];         // this tile's 4-px column groups [gfirst, gend)
+        const int wq = (r1 - r0 + 3) >> 2, wr0 = r0 + wave * wq, wr1 = min(wr0 + wq, r1); // this wavefront's rows [wr0, wr1)
+        for (int gbase = gfirst, W = 0; gbase < gend && wr0 < wr1; gbase += W) {
+            W = pyr_chunk_width(gend - gbase);
+            const int R = 64 / W, len = (wr1 - wr0 + R - 1) / R;                          // R runs of len rows side by side
+            const int run = lane / W, tx = lane - run * W;
+            const int y0 = wr0 + run * len, y1 = min(y0 + len, wr1);
+            if (run >= R || y0 >= y1) continue;
             const int x4 = (gbase + tx) * 4;
             int sx[4], sx1[4];
             uint32_t A0[4], A1[4];
@@ -159,7 +194,7 @@ __global__ __launch_bounds__(PYR_T, 8) void orb_pyramid_kernel(const CorbOrbPara
             const int bx = sx[0] & ~3;
             const bool wide = (sx1[3] - bx) < 12;           // false only for scale factors > 2
             // v_perm selectors gathering the 4 left / 4 right taps of the group out of the 12 bytes: first from {w1,w0}
-            // (offsets 0..7, others zero), then patched from w2 (offsets 8..11) when any lane needs it
+            // (offsets 0..7, others zero), then patched from w2 (offsets 8..11; the identity for a lane that needs no patch)
             uint32_t s1a = 0, s2a = 0, s1b = 0, s2b = 0;
 #pragma unroll
             for (int k = 0; k < 4; k++) {
@@ -167,58 +202,99 @@ __global__ __launch_bounds__(PYR_T, 8) void orb_pyramid_kernel(const CorbOrbPara
                 s1a |= (uint32_t)(oa < 8 ? oa : 0x0c) << (8 * k); s2a |= (uint32_t)(oa < 8 ? k : oa - 4) << (8 * k);
                 s1b |= (uint32_t)(ob < 8 ? ob : 0x0c) << (8 * k); s2b |= (uint32_t)(ob < 8 ? k : ob - 4) << (8 * k);
             }
-            const bool patch_a = __any(wide && sx[3] - bx >= 8), patch_b = __any(wide && sx1[3] - bx >= 8);
             if (wide) {
-                // two rows per iteration: both rows' 12 dword loads are issued before the first is consumed
-                auto fetch = [&](const int2 yr, uint32_t (&w)[6], uint32_t& bb) {
-                    const uint32_t* q0 = reinterpret_cast<const uint32_t*>(src + (uint32_t)(__mul24(yr.x & 0xFFFF, S.pitch) + bx));
-                    const uint32_t* q1 = reinterpret_cast<const uint32_t*>(src + (uint32_t)(__mul24(yr.x >> 16, S.pitch) + bx));
-                    w[0] = q0[0]; w[1] = q0[1]; w[2] = q0[2]; w[3] = q1[0]; w[4] = q1[1]; w[5] = q1[2];
-                    bb = (uint32_t)yr.y;
+                // horizontal pass of one source row: d[k] = (p * a0 + p' * a1) << 12 of the group's 4 pixels
+                auto hpass = [&](const uint32_t (&w)[3], uint32_t (&d)[4]) {
+                    const uint32_t P0 = __builtin_amdgcn_perm(w[2], __builtin_amdgcn_perm(w[1], w[0], s1a), s2a), P1 = __builtin_amdgcn_perm(w[2], __builtin_amdgcn_perm(w[1], w[0], s1b), s2b);
+                    d[0] = mul24_byte<0>(P0, A0[0]) + mul24_byte<0>(P1, A1[0]); d[1] = mul24_byte<1>(P0, A0[1]) + mul24_byte<1>(P1, A1[1]);
+                    d[2] = mul24_byte<2>(P0, A0[2]) + mul24_byte<2>(P1, A1[2]); d[3] = mul24_byte<3>(P0, A0[3]) + mul24_byte<3>(P1, A1[3]);
                 };
-                auto emit = [&](int y, const uint32_t (&w)[6], uint32_t bb) {
-                    const uint32_t b0 = bb & 0xFFFFu, b1 = bb >> 16;
-                    uint32_t P0 = __builtin_amdgcn_perm(w[1], w[0], s1a), P1 = __builtin_amdgcn_perm(w[1], w[0], s1b);
-                    uint32_t Q0 = __builtin_amdgcn_perm(w[4], w[3], s1a), Q1 = __builtin_amdgcn_perm(w[4], w[3], s1b);
-                    if (patch_a) { P0 = __builtin_amdgcn_perm(w[2], P0, s2a); Q0 = __builtin_amdgcn_perm(w[5], Q0, s2a); }
-                    if (patch_b) { P1 = __builtin_amdgcn_perm(w[2], P1, s2b); Q1 = __builtin_amdgcn_perm(w[5], Q1, s2b); }
-                    uint32_t packed = 0;
-                    pyr_px<0>(packed, P0, P1, Q0, Q1, A0[0], A1[0], b0, b1, two);
-                    pyr_px<1>(packed, P0, P1, Q0, Q1, A0[1], A1[1], b0, b1, two);
-                    pyr_px<2>(packed, P0, P1, Q0, Q1, A0[2], A1[2], b0, b1, two);
-                    pyr_px<3>(packed, P0, P1, Q0, Q1, A0[3], A1[3], b0, b1, two);
-                    uint8_t* dst = dstp + (uint32_t)(__mul24(y, D.pitch) + x4);
-                    if (nvalid == 4) *reinterpret_cast<uint32_t*>(dst) = packed;
-                    else for (int k = 0; k < nvalid; k++) dst[k] = (uint8_t)(packed >> (8 * k));
-                };
-                // the rows' records travel one iteration ahead of the rows: the row loads of an iteration depend on addresses from yrec, and with both fetched in
-                // the iteration that uses them every output row pair paid two dependent trips to memory
-                int y = r0 + ty;
-                const int ylast = max(r1 - 1, 0);
-                int2 ya = yrec[min(y, ylast)], yb = yrec[min(y + RY, ylast)];
-                // FOUR rows per iteration: 24 dword loads in flight per thread (round 5; VERDICT r4 item 7: the kernel waits on its loads -- SQ_WAIT_ANY 74 % of wave cycles --, so
-                // more of them per wavefront, not fewer instructions).  Still 64 VGPRs, 8 wavefronts per SIMD.  Against two rows per iteration, same box, alternating:
-                // 103.4 / 104.0 k -> 104.8 / 104.9 k stereo fps on the 512-frame step, 43.7 -> 41.0 us alone on two images (profiles/r05_ab_pyr_rows4.txt)
-                int2 yc = yrec[min(y + 2 * RY, ylast)], yd = yrec[min(y + 3 * RY, ylast)];
+                auto rows = [&](auto mode) {
+                    constexpr bool UNI = decltype(mode)::value;
+                    auto uni = [](int v) { if constexpr (UNI) return __builtin_amdgcn_readfirstlane(v); else return v; };
+                    auto rec = [&](int yy) { const uint64_t v = yrec[yy]; return make_uint2((uint32_t)v, (uint32_t)(v >> 32)); };
+                    // the upper source row of an output row is recomputed unless it is the row whose horizontal pass the previous output row kept
+                    auto fresh = [](uint32_t s0, uint32_t kept) -> bool { if constexpr (UNI) return s0 != kept; else return __any(s0 != kept) != 0; };
+                    auto load_row = [&](uint32_t s, uint32_t (&w)[3]) {
+                        const uint32_t* q;
+                        if constexpr (UNI) q = reinterpret_cast<const uint32_t*>(src + s * (uint32_t)S.pitch + (uint32_t)bx);     // scalar row base + the lane's column offset
+                        else q = reinterpret_cast<const uint32_t*>(src + (uint32_t)(__mul24((int)s, S.pitch) + bx));
+                        w[0] = q[0]; w[1] = q[1]; w[2] = q[2];
+                    };
+                    uint32_t dk[4] = {0u, 0u, 0u, 0u};                   // horizontal pass of source row `kept`
+                    uint32_t kept = 0xFFFFu;                               // no level has that many rows: the first row of a run recomputes
+                    // vertical pass and store of output row yy; the lower row's horizontal pass becomes the kept one
+                    auto emit = [&](int yy, bool fr, const uint32_t (&t)[3], const uint32_t (&b)[3], uint32_t bb) {
+                        const uint32_t b0 = bb & 0xFFFFu, b1 = bb >> 16;
+                        uint32_t dt[4];
+                        if (fr) hpass(t, dt);
+                        else { dt[0] = dk[0]; dt[1] = dk[1]; dt[2] = dk[2]; dt[3] = dk[3]; }
+                        hpass(b, dk);
+                        uint32_t packed = 0;
+                        shr_into_byte<0>(packed, two, add_hiwords(mul24_hiword(dt[0], b0), mul24_hiword(dk[0], b1)) + 2u);    // ((b0 * (d0 >> 4) >> 16) + (b1 * (d1 >> 4) >> 16) + 2) >> 2  (<= 255)
+                        shr_into_byte<1>(packed, two, add_hiwords(mul24_hiword(dt[1], b0), mul24_hiword(dk[1], b1)) + 2u);
+                        shr_into_byte<2>(packed, two, add_hiwords(mul24_hiword(dt[2], b0), mul24_hiword(dk[2], b1)) + 2u);
+                        shr_into_byte<3>(packed, two, add_hiwords(mul24_hiword(dt[3], b0), mul24_hiword(dk[3], b1)) + 2u);
+                        uint8_t* dst;
+                        if constexpr (UNI) dst = dstp + (uint32_t)yy * (uint32_t)D.pitch + (uint32_t)x4;
+                        else dst = dstp + (uint32_t)(__mul24(yy, D.pitch) + x4);
+                        if (nvalid == 4) *reinterpret_cast<uint32_t*>(dst) = packed;
+                        else for (int k = 0; k < nvalid; k++) dst[k] = (uint8_t)(packed >> (8 * k));
+                    };
+                    int y = uni(y0);
+                    const int yend = uni(y1), ylast = r1 - 1;
+                    // the rows' records travel one trip ahead of the rows: the row loads depend on addresses from the records
+                    uint2 ra = rec(min(y, ylast)), rb = rec(min(y + 1, ylast));
+                    if constexpr (UNI) {
+                        // FOUR output rows per trip: their 12 .. 24 dword loads are issued before the first is consumed (the kernel waits on its loads)
+                        uint2 rc = rec(min(y + 2, ylast)), rd = rec(min(y + 3, ylast));
 #pragma unroll 1
-                for (; y + 3 * RY < r1; y += 4 * RY) {
-                    uint32_t wa[6], wb[6], wc[6], wd[6], ba, bb, bc, bd;
-                    fetch(ya, wa, ba); fetch(yb, wb, bb); fetch(yc, wc, bc); fetch(yd, wd, bd);
-                    const int2 na = yrec[min(y + 4 * RY, ylast)], nb = yrec[min(y + 5 * RY, ylast)], nc = yrec[min(y + 6 * RY, ylast)], nd = yrec[min(y + 7 * RY, ylast)];
-                    emit(y, wa, ba); emit(y + RY, wb, bb); emit(y + 2 * RY, wc, bc); emit(y + 3 * RY, wd, bd);
-                    ya = na; yb = nb; yc = nc; yd = nd;
-                }
-                if (y + RY < r1) {
-                    uint32_t wa[6], wb[6], ba, bb;
-                    fetch(ya, wa, ba); fetch(yb, wb, bb);
-                    emit(y, wa, ba); emit(y + RY, wb, bb);
-                    y += 2 * RY; ya = yc; yb = yd;
-                }
-                if (y < r1) { uint32_t wa[6], ba; fetch(ya, wa, ba); emit(y, wa, ba); }
+                        for (; y + 3 < yend; y += 4) {
+                            uint32_t ta[3], tb[3], tc[3], td[3], ba[3], bb[3], bc[3], bd[3];
+                            const bool fa = fresh(ra.x & 0xFFFFu, kept), fb = fresh(rb.x & 0xFFFFu, ra.x >> 16), fc = fresh(rc.x & 0xFFFFu, rb.x >> 16), fd = fresh(rd.x & 0xFFFFu, rc.x >> 16);
+                            if (fa) load_row(ra.x & 0xFFFFu, ta);
+                            load_row(ra.x >> 16, ba);
+                            if (fb) load_row(rb.x & 0xFFFFu, tb);
+                            load_row(rb.x >> 16, bb);
+                            if (fc) load_row(rc.x & 0xFFFFu, tc);
+                            load_row(rc.x >> 16, bc);
+                            if (fd) load_row(rd.x & 0xFFFFu, td);
+                            load_row(rd.x >> 16, bd);
+                            const uint2 na = rec(min(y + 4, ylast)), nb = rec(min(y + 5, ylast)), nc = rec(min(y + 6, ylast)), nd = rec(min(y + 7, ylast));
+                            emit(y, fa, ta, ba, ra.y); emit(y + 1, fb, tb, bb, rb.y); emit(y + 2, fc, tc, bc, rc.y); emit(y + 3, fd, td, bd, rd.y);
+                            kept = rd.x >> 16;
+                            ra = na; rb = nb; rc = nc; rd = nd;
+                        }
+                    }
+                    // two rows per trip: the rest of a wave-uniform run, and all of the per-lane runs (at most a quarter of the tile's rows / R long: short, and the
+                    // records of four more rows per lane do not fit into 64 VGPRs beside 24 row dwords)
+#pragma unroll 1
+                    for (; y + 1 < yend; y += 2) {
+                        uint32_t ta[3], tb[3], ba[3], bb[3];
+                        const bool fa = fresh(ra.x & 0xFFFFu, kept), fb = fresh(rb.x & 0xFFFFu, ra.x >> 16);
+                        if (fa) load_row(ra.x & 0xFFFFu, ta);
+                        load_row(ra.x >> 16, ba);
+                        if (fb) load_row(rb.x & 0xFFFFu, tb);
+                        load_row(rb.x >> 16, bb);
+                        const uint2 na = rec(min(y + 2, ylast)), nb = rec(min(y + 3, ylast));
+                        emit(y, fa, ta, ba, ra.y); emit(y + 1, fb, tb, bb, rb.y);
+                        kept = rb.x >> 16;
+                        ra = na; rb = nb;
+                    }
+                    if (y < yend) {
+                        uint32_t ta[3], ba[3];
+                        const bool fa = fresh(ra.x & 0xFFFFu, kept);
+                        if (fa) load_row(ra.x & 0xFFFFu, ta);
+                        load_row(ra.x >> 16, ba);
+                        emit(y, fa, ta, ba, ra.y);
+                    }
+                };
+                if (R == 1) rows(PyrUni{}); else rows(PyrLane{});
             } else {
 #pragma unroll 1
-                for (int y = r0 + ty; y < r1; y += RY) {
-                    const int2 yr = yrec[y];
+                for (int y = y0; y < y1; y++) {
+                    const uint64_t yv = yrec[y];
+                    const int2 yr = make_int2((int)(uint32_t)yv, (int)(uint32_t)(yv >> 32));
                     const uint8_t* S0 = src + (uint32_t)__mul24(yr.x & 0xFFFF, S.pitch);
                     const uint8_t* S1 = src + (uint32_t)__mul24(yr.x >> 16, S.pitch);
                     const uint32_t b0 = yr.y & 0xFFFF, b1 = (uint32_t)yr.y >> 16;
