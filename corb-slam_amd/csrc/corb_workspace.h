@@ -106,10 +106,10 @@ struct CorbScratch {                         // one BA call's view of the worksp
         char* st = static_cast<char*>(ws->host_take(total));
         const bool staged = st != nullptr;
         if (!staged) { blob.resize(total + 1); st = blob.data(); }
-        size_t off = 0;
-        for (size_t i = 0; i < n; i++) { const Piece& pc = pieces[i]; if (pc.bytes) memcpy(st + off, pc.src, pc.bytes); *pc.dst = base + off; off += (pc.bytes + 255) & ~(size_t)255; }
-        if (!total) return hipSuccess;
-        return staged ? hipMemcpyAsync(base, st, total, hipMemcpyHostToDevice, stream) : hipMemcpy(base, st, total, hipMemcpyHostToDevice);
+        size_t off = 0, end = 0;                       // (the copy stops where the last piece ends: its padding does not travel)
+        for (size_t i = 0; i < n; i++) { const Piece& pc = pieces[i]; if (pc.bytes) { memcpy(st + off, pc.src, pc.bytes); end = off + pc.bytes; } *pc.dst = base + off; off += (pc.bytes + 255) & ~(size_t)255; }
+        if (!end) return hipSuccess;
+        return staged ? hipMemcpyAsync(base, st, end, hipMemcpyHostToDevice, stream) : hipMemcpy(base, st, end, hipMemcpyHostToDevice);
     }
     template <class T> hipError_t upload(T** out, const std::vector<T>& v) { hipError_t e = alloc(out, v.size()); if (e == hipSuccess && !v.empty()) e = h2d(*out, v.data(), v.size() * sizeof(T)); return e; }
 };

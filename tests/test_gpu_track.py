@@ -17,7 +17,7 @@ def _put_points(mp, rec):
     mp.put(0, rec, off, np.ones(off[-1], np.uint64), np.zeros(off[-1], np.uint32))
 
 
-def _scene(corb, seed=77, t_last=5, t_cur=6, bad_every=17, unobserved_every=23, outlier_every=29, drop_every=5):
+def _scene(corb, seed=77, t_last=5, t_cur=6, bad_every=17, unobserved_every=23, outlier_every=29, drop_every=5, shift_last_octaves=False):
     import replay_client as rc
     w = rc.World(seed, 12)
     CAM = rc.CAM
@@ -38,6 +38,8 @@ def _scene(corb, seed=77, t_last=5, t_cur=6, bad_every=17, unobserved_every=23, 
     frames = {}
     for slot, t in ((0, t_last), (1, t_cur)):
         keys, ur, desc, lm = w.observe(t)
+        if slot == 0 and shift_last_octaves:          # the world sees a landmark at one octave in every frame: here the last frame saw a third of them a level higher, a third a level lower
+            keys["octave"] = np.clip(keys["octave"] + np.array([0, 1, -1])[np.arange(len(keys)) % 3], 0, 7)
         kf.put(slot, keys, desc, ur, None, keyframe_id=slot + 1)
         kf.set_meta(slot, id=slot + 1, fx=cam.fx, fy=cam.fy, cx=cam.cx, cy=cam.cy, bf=cam.bf, nlevels=8, inv_level_sigma2=inv_s2, Tcw=w.pose(t).astype(np.float32))
         frames[slot] = dict(keys=keys, ur=ur, desc=desc, lm=lm, T=w.pose(t).astype(np.float32))
@@ -208,4 +210,77 @@ def test_search_local_points_on_records(corb, pyorc):
     before = np.where(held & (rec["flags"][lm] == 0), ids[lm], NONE)                        # the bad points left the frame
     want = np.where(m_ref >= 0, local_ids[np.maximum(m_ref, 0)], before)
     assert np.array_equal(got, want)
+    kf.close(); mp.close()
+
+
+def _tlc_z(Tcw, Tlw, double):
+    """z of tlc = Rlw * twc + tlw with twc = -Rcw^T tcw (ORBmatcher.cc:1480-1484) in the two arithmetics a host can choose: float accumulation, or cv::gemm's
+    double accumulation with one rounding per product matrix"""
+    if not double:
+        twc = [-(Tcw[0, i] * Tcw[0, 3] + Tcw[1, i] * Tcw[1, 3] + Tcw[2, i] * Tcw[2, 3]) for i in range(3)]
+        return Tlw[2, 0] * twc[0] + Tlw[2, 1] * twc[1] + Tlw[2, 2] * twc[2] + Tlw[2, 3]
+    A, B = Tcw.astype(np.float64), Tlw.astype(np.float64)
+    twc = [np.float64(np.float32((-A[0, i]) * A[0, 3] + (-A[1, i]) * A[1, 3] + (-A[2, i]) * A[2, 3])) for i in range(3)]
+    return np.float32(B[2, 0] * twc[0] + B[2, 1] * twc[1] + B[2, 2] * twc[2] + B[2, 3])
+
+
+def _step(x, k):
+    for _ in range(abs(k)):
+        x = np.nextafter(x, np.float32(np.inf if k > 0 else -np.inf))
+    return x
+
+
+def _threshold_Tlw(Tcw, Tlw0, mb, sign):
+    """a last-frame pose whose sign * tlc.z lies on mb so closely that the two arithmetics of _tlc_z decide `sign * tlc.z > mb` differently: tlw.z is set so that
+    tlc.z lands on sign * mb and stepped by ulps across it; when the two sums keep the same side at every step (they move in lock step), an entry of the
+    rotation is stepped by one ulp, which shifts one sum against the other, and tlw.z is stepped again"""
+    for j in range(400):
+        T = Tlw0.copy(); T[2, 0] = _step(T[2, 0], j); T[2, 3] = 0
+        T[2, 3] = _step(np.float32(sign * np.float64(mb) - np.float64(_tlc_z(Tcw, T, True))), -3)
+        for _ in range(7):
+            if (sign * _tlc_z(Tcw, T, False) > mb) != (sign * _tlc_z(Tcw, T, True) > mb):
+                return T
+            T[2, 3] = _step(T[2, 3], 1)
+    raise AssertionError("no pose found at which the two arithmetics disagree")
+
+
+def test_search_last_frame_motion_test_at_its_threshold(corb, pyorc):
+    """The forward / backward test of SearchByProjection(CurrentFrame, LastFrame) (ORBmatcher.cc:1480-1491) selects the octave window of every point.  With a
+    last-frame pose for which float accumulation and cv::gemm's double accumulation put tlc.z on different sides of +mb (then of -mb), the record route, the
+    host-pointer route and the oracle return the same matches; a few ulps either side of the threshold the matches differ, so the case can tell.  (The octave
+    window decides a match only where the two frames saw a landmark at different octaves, which the synthetic world never does by itself: the last frame's
+    octaves are shifted by one level for two thirds of its features.  Forward motion then drops the points seen a level higher before, backward motion those
+    seen a level lower, and the undirected window [octave - 1, octave + 1] keeps both.)"""
+    import replay_client as rc
+    w, cam, ids, rec, mp, kf, fr = _scene(corb, shift_last_octaves=True)
+    last, cur = fr[0], fr[1]
+    lm = last["lm"]
+    lastp = np.zeros(len(lm), corb.LAST_DTYPE)
+    lastp["world"] = w.Xest[lm]; lastp["angle"] = last["keys"]["angle"]; lastp["octave"] = last["keys"]["octave"]
+    usable = last["has"] & ~last["outl"] & (rec["flags"][lm] == 0)
+    lastp["valid"] = usable; lastp["claims"] = rec["n_obs"][lm] > 0
+    ldesc = np.where(usable[:, None], w.desc[lm], 0).astype(np.uint8)
+    fv = rc._frame_view(w, cur["keys"], cur["ur"], cur["desc"])
+    T_pred = cur["T"].copy(); T_pred[0, 3] += np.float32(0.02)
+    mb = np.float32(cam.mb)
+    matcher = corb.ORBmatcher(0.9, True)
+    host = lambda Tlw: matcher.SearchByProjection_Frame(fv, T_pred, Tlw, cam.fx, cam.fy, cam.cx, cam.cy, cam.bf, cam.mb, lastp, ldesc, 7.0, False)
+    # the last frame's pose turned about an oblique axis: every entry of the rotation takes part in the sums (only the motion test reads Tlw)
+    a = np.array([0.3, -0.5, 0.2]); ang = np.linalg.norm(a); k = a / ang
+    K = np.array([[0, -k[2], k[1]], [k[2], 0, -k[0]], [-k[1], k[0], 0]])
+    Tlw0 = last["T"].astype(np.float64); Tlw0[:3, :3] = (np.eye(3) + np.sin(ang) * K + (1 - np.cos(ang)) * K @ K) @ Tlw0[:3, :3]
+    Tlw0 = Tlw0.astype(np.float32)
+    empty = np.full(len(cur["keys"]), NONE, np.uint64)
+    for sign in (1, -1):                                                             # forward at +mb, backward at -mb
+        Tlw = _threshold_Tlw(T_pred, Tlw0, mb, sign)
+        m_ref, n_ref = host(Tlw)
+        m_orc, n_orc = pyorc.search_by_projection_frame(fv, T_pred, Tlw, cam.fx, cam.fy, cam.cx, cam.cy, cam.bf, cam.mb, lastp, ldesc, 7.0, 0, 1)
+        kf.set_map_points(1, empty)                                                  # (the call before left its matches in the record)
+        m, n = kf.TrackSearchLastFrame(1, 0, mp, T_pred, Tlw, cam, 7.0, mono=False)
+        print("sign %+d: matches host-pointer %d, oracle %d, records %d; differing entries records / host-pointer %d" % (sign, n_ref, n_orc, n, int((m != m_ref).sum())))
+        assert n_ref > 500 and n_orc == n_ref and np.array_equal(m_orc, m_ref)
+        assert n == n_ref and np.array_equal(m, m_ref)
+        below, above = Tlw.copy(), Tlw.copy()
+        below[2, 3] = _step(Tlw[2, 3], -8); above[2, 3] = _step(Tlw[2, 3], 8)
+        assert not np.array_equal(host(below)[0], host(above)[0])
     kf.close(); mp.close()
