@@ -37,6 +37,7 @@ EXPORTS = [
     "corb_mp_store_build_index", "corb_kf_store_count", "corb_track_search_last_frame", "corb_track_pose_optimization", "corb_track_search_local_points", "corb_kf_store_put_frame",
     "corb_rgbd_create", "corb_rgbd_destroy", "corb_rgbd_orb", "corb_rgbd_upload_batch", "corb_rgbd_run", "corb_rgbd_sync", "corb_rgbd_fetch_batch",
     "corb_rgbd_frame_layout", "corb_rgbd_frames", "corb_rgbd_image_bounds", "corb_kf_store_put_from_rgbd",
+    "corb_triangulate_pairs", "corb_create_new_map_points_store",
 ]
 
 
@@ -304,6 +305,9 @@ def load():
     L.corb_rgbd_frames.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     L.corb_rgbd_image_bounds.argtypes = [C.c_void_p, C.c_void_p]
     L.corb_kf_store_put_from_rgbd.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_uint64]
+    L.corb_triangulate_pairs.argtypes = [C.POINTER(_NewPointSide), C.POINTER(_NewPointSide), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.c_int]
+    L.corb_create_new_map_points_store.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(TrackCamera), C.c_int, C.c_int, C.c_void_p, C.c_int,
+                                                   C.c_uint64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
     _lib = L
     return L
 
@@ -792,6 +796,37 @@ class ORBmatcher:
         return pairs[: n.value].copy(), n.value
 
 
+# status of a pair in CreateNewMapPoints (include/corb_accel.h: CORB_NP_*)
+NP_OK, NP_NO_PARALLAX, NP_W_ZERO, NP_BEHIND_1, NP_BEHIND_2, NP_REPROJ_1, NP_REPROJ_2, NP_SCALE = range(8)
+
+
+class _NewPointSide(C.Structure):
+    _fields_ = [("keys_un", C.c_void_p), ("u_right", C.c_void_p), ("depth", C.c_void_p), ("n", C.c_int32), ("Tcw", C.c_float * 16)] + \
+               [(k, C.c_float) for k in ("fx", "fy", "cx", "cy", "bf", "mb")] + [("scale", C.c_void_p), ("nlevels", C.c_int32)]
+
+
+def TriangulatePairs(kf1, kf2, pairs, device=0):
+    """The triangulation loop of LocalMapping::CreateNewMapPoints (LocalMapping.cc:268-398) for the pairs of one SearchForTriangulation call (corb_triangulate_pairs).
+    kf1 / kf2: dict(kp (mvKeysUn), u_right, depth, Tcw, fx, fy, cx, cy, bf, mb, scale).  Returns (x3D [n, 3], status, source, n_new)."""
+    keep = []
+    def side(k):
+        kp = np.ascontiguousarray(k["kp"], KP_DTYPE); ur = np.ascontiguousarray(k["u_right"], np.float32); dp = np.ascontiguousarray(k["depth"], np.float32)
+        sc = np.ascontiguousarray(k["scale"], np.float32); keep.extend([kp, ur, dp, sc])
+        s = _NewPointSide(); s.keys_un, s.u_right, s.depth, s.n = _p(kp), _p(ur), _p(dp), len(kp)
+        T = np.ascontiguousarray(k["Tcw"], np.float32).reshape(16)
+        for i in range(16):
+            s.Tcw[i] = float(T[i])
+        for f in ("fx", "fy", "cx", "cy", "bf", "mb"):
+            setattr(s, f, float(np.float32(k[f])))
+        s.scale, s.nlevels = _p(sc), len(sc)
+        return s
+    A, B = side(kf1), side(kf2)
+    pr = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2); n = len(pr)
+    x3d = np.zeros((max(n, 1), 3), np.float32); st = np.zeros(max(n, 1), np.uint8); src = np.zeros(max(n, 1), np.uint8); nn = C.c_int(0)
+    _chk(load().corb_triangulate_pairs(C.byref(A), C.byref(B), _p(pr), n, _p(x3d), _p(st), _p(src), C.byref(nn), device), "corb_triangulate_pairs")
+    return x3d[:n], st[:n], src[:n], nn.value
+
+
 def spd_solve(A, b, device=0):
     """corb_spd_solve: x with A x = b for a symmetric positive definite A (hand-written blocked Cholesky, csrc/dense_chol.hip); returns (x, info)"""
     A = np.ascontiguousarray(A, np.float64); b = np.ascontiguousarray(b, np.float64); x = np.zeros(len(b), np.float64); info = C.c_int(0)
@@ -1072,6 +1107,22 @@ class KeyFrameStore:
         _chk(load().corb_fuse_store(self.h, int(slot), mp_store.h, _p(ms), len(ms), C.byref(cam), _p(T), C.c_float(log_scale_factor), C.c_float(th), int(bool(apply)),
                                     _p(bi), _p(bd), _p(act), C.byref(n)), "corb_fuse_store")
         return bi[: len(ms)], bd[: len(ms)], n.value, act[: len(ms)]
+
+    def CreateNewMapPoints(self, cur_slot, nb_slots, F12, epipoles, cam, mp_store=None, first_mp_slot=0, first_mp_id=0, client_id=0, only_stereo=False, apply=False):
+        """The neighbour loop of LocalMapping::CreateNewMapPoints on records (corb_create_new_map_points_store): matching per neighbour against the evolving flags of
+        cur_slot, triangulation, and (apply) the new MapPoint records of mp_store from first_mp_slot on.  F12 [n_nb, 3, 3], epipoles [n_nb, 2].
+        Returns dict(pair_offset, pairs, x3d, status, source, n_new)."""
+        nb = np.ascontiguousarray(nb_slots, np.int32).reshape(-1); n_nb = len(nb); n1 = self._n_features(cur_slot)
+        F = np.ascontiguousarray(F12, np.float32).reshape(-1); ep = np.ascontiguousarray(epipoles, np.float32).reshape(-1)
+        assert len(F) == 9 * n_nb and len(ep) == 2 * n_nb
+        cap = max(n_nb * n1, 1)
+        off = np.zeros(n_nb + 1, np.int32); pr = np.zeros((cap, 2), np.int32); x3d = np.zeros((cap, 3), np.float32); st = np.zeros(cap, np.uint8); src = np.zeros(cap, np.uint8)
+        nn = C.c_int(0)
+        _chk(load().corb_create_new_map_points_store(self.h, int(cur_slot), _p(nb), n_nb, _p(F), _p(ep), C.byref(cam), int(bool(only_stereo)), int(bool(apply)),
+                                                     mp_store.h if mp_store is not None else None, int(first_mp_slot), int(first_mp_id), int(client_id),
+                                                     _p(off), _p(pr), _p(x3d), _p(st), _p(src), C.byref(nn)), "corb_create_new_map_points_store")
+        m = int(off[n_nb])
+        return dict(pair_offset=off, pairs=pr[:m].copy(), x3d=x3d[:m].copy(), status=st[:m].copy(), source=src[:m].copy(), n_new=nn.value)
 
     def TrackSearchReloc(self, cur_slot, kf_store, kf_slot, mp_store, cam, Tcw, log_scale_factor, th=10.0, orb_dist=100, check_orientation=True):
         """ORBmatcher::SearchByProjection(Frame&, KeyFrame*, sAlreadyFound, th, ORBdist) on records (corb_track_search_reloc): the frame = this store's cur_slot,

@@ -200,11 +200,6 @@ extern "C" int corb_kf_store_get(CorbKfStore* s, int slot, CorbKeyPoint* kp, uin
 }
 
 // ---- matchers on slots: the kernels of corb_match.cpp on the records' device arrays ----
-static void common_nodes(const std::vector<uint32_t>& a, const std::vector<uint32_t>& b, std::vector<int>& pa, std::vector<int>& pb)
-{
-    size_t i = 0, j = 0;
-    while (i < a.size() && j < b.size()) { if (a[i] == b[j]) { pa.push_back((int)i++); pb.push_back((int)j++); } else if (a[i] < b[j]) i++; else j++; }
-}
 static int two_slots(CorbKfStore* a, int sa, CorbKfStore* b, int sb, const char* who)
 {
     int rc = slot_ok(a, sa, who); if (rc) return rc;

@@ -33,3 +33,10 @@ struct CorbMpStore {
     hipEvent_t lba_event = nullptr;                // the window's graph is complete (corb_local_ba_store: this store's stream -> the optimiser's)
     char* rec(int slot) const { return base + (size_t)slot * L.bytes; }
 };
+
+// the vocabulary nodes two FeatureVectors share (both ascend in the node id): positions in a and in b -- what the BoW-guided matchers on slots walk
+inline void common_nodes(const std::vector<uint32_t>& a, const std::vector<uint32_t>& b, std::vector<int>& pa, std::vector<int>& pb)
+{
+    size_t i = 0, j = 0;
+    while (i < a.size() && j < b.size()) { if (a[i] == b[j]) { pa.push_back((int)i++); pb.push_back((int)j++); } else if (a[i] < b[j]) i++; else j++; }
+}

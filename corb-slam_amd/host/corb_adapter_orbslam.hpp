@@ -136,6 +136,36 @@ public:
         return m_.SearchForTriangulation(flatten_keyframe(pKF1, false), flatten_keyframe(pKF2, false), F, ex, ey, pKF2->mvScaleFactors, pKF2->mvLevelSigma2,
                                          vMatchedPairs, bOnlyStereo);
     }
+    // LocalMapping::CreateNewMapPoints' "Triangulate each match" loop (C/src/LocalMapping.cc:262-398) for the pairs SearchForTriangulation returned for ONE neighbour:
+    // both keyframes are flattened (mvKeysUn, mvuRight, mvDepth, GetPose(), fx .. mbf, mb, mvScaleFactors), the pairs go through corb_triangulate_pairs, and the accepted
+    // ones come back as (idx1, idx2, x3D) for the caller's `new MapPoint(x3D, mpCurrentKeyFrame, mpCacher)` + AddObservation / AddMapPoint (:401-415) -- which it does
+    // before matching the next neighbour, as the reference does.  Returns their number.
+    struct NewPoint { size_t idx1, idx2; float x3D[3]; };
+    static int CreateNewMapPoints(KeyFrame* pKF1, KeyFrame* pKF2, const std::vector<std::pair<size_t, size_t>>& vMatchedIndices, std::vector<NewPoint>& vNew, int device = 0)
+    {
+        vNew.clear();
+        const int n = (int)vMatchedIndices.size();
+        if (n == 0) return 0;
+        std::vector<CorbKeyPoint> kp[2]; CorbNewPointSide side[2]; KeyFrame* kfs[2] = {pKF1, pKF2};
+        for (int s = 0; s < 2; s++) {
+            KeyFrame* pKF = kfs[s];
+            kp[s].reserve(pKF->mvKeysUn.size());
+            for (const auto& k : pKF->mvKeysUn) kp[s].push_back(to_kp(k));
+            const Mat T = pKF->GetPose();
+            CorbNewPointSide& d = side[s];
+            d.keys_un = kp[s].data(); d.u_right = pKF->mvuRight.data(); d.depth = pKF->mvDepth.data(); d.n = (int)kp[s].size();
+            for (int i = 0; i < 4; i++) for (int j = 0; j < 4; j++) d.Tcw[4 * i + j] = matf(T, i, j);
+            d.fx = pKF->fx; d.fy = pKF->fy; d.cx = pKF->cx; d.cy = pKF->cy; d.bf = pKF->mbf; d.mb = pKF->mb;
+            d.scale = pKF->mvScaleFactors.data(); d.nlevels = (int)pKF->mvScaleFactors.size();
+        }
+        std::vector<int32_t> pairs(2 * (size_t)n); std::vector<float> x3d(3 * (size_t)n); std::vector<uint8_t> status((size_t)n), source((size_t)n);
+        for (int i = 0; i < n; i++) { pairs[2 * (size_t)i] = (int32_t)vMatchedIndices[i].first; pairs[2 * (size_t)i + 1] = (int32_t)vMatchedIndices[i].second; }
+        int nnew = 0;
+        check(corb_triangulate_pairs(&side[0], &side[1], pairs.data(), n, x3d.data(), status.data(), source.data(), &nnew, device), "corb_triangulate_pairs");
+        for (int i = 0; i < n; i++)
+            if (status[i] == CORB_NP_OK) vNew.push_back(NewPoint{vMatchedIndices[i].first, vMatchedIndices[i].second, {x3d[3 * (size_t)i], x3d[3 * (size_t)i + 1], x3d[3 * (size_t)i + 2]}});
+        return nnew;
+    }
     // ORBmatcher.cc:425-538 -- LoopClosing::ComputeSim3 (C/src/LoopClosing.cc:377) and the server's map fusion (S/src/GlobalOptimize.cpp:199) call it with the loop
     // keyframe's covisible points right before CorrectLoop / the global BA.  What the reference reads: pKF->fx.., mnMinX.., mvScaleFactors, mfLogScaleFactor, mvKeysUn,
     // mDescriptors (GetFeaturesInArea + the loop body); pMP->isBad / GetWorldPos / GetNormal / Get{Min,Max}DistanceInvariance / PredictScale / GetDescriptor.  The two

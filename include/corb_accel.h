@@ -834,6 +834,48 @@ int corb_search_by_sim3_store(CorbKfStore* kf, int slot1, int slot2, CorbMpStore
                               const float* T1w /* 16 */, const float* T2w /* 16 */, const uint64_t* matched12_ids, float s12, const float* R12 /* 9 */, const float* t12 /* 3 */, float th,
                               int32_t* match12, uint64_t* match12_ids, int* n_found);
 
+/* ============================ CreateNewMapPoints (LocalMapping thread) =====================
+ * The triangulation loop of LocalMapping::CreateNewMapPoints (C/src/LocalMapping.cc:262-418): what turns the pairs of SearchForTriangulation into MapPoints.
+ * Per pair (:268-398): the parallax test, linear triangulation or KeyFrame::UnprojectStereo, the two depth tests, the two reprojection tests, the scale test.
+ * Numerics: the reference's float expressions as non-fused IEEE operations; the stereo parallax cos(2 atan2(mb / 2, depth)) is evaluated as
+ * (d^2 - h^2) / (d^2 + h^2) in double and rounded once; the null vector of the float 4x4 system A comes from a one-sided Jacobi SVD of A in FP64, rounded to float.
+ * status of a pair (x3d is written whenever a point was computed, also where a later test rejects it; else 0): */
+#define CORB_NP_OK           0
+#define CORB_NP_NO_PARALLAX  1   /* :320-321 no stereo and very low parallax */
+#define CORB_NP_W_ZERO       2   /* :310 */
+#define CORB_NP_BEHIND_1     3   /* :327 */
+#define CORB_NP_BEHIND_2     4   /* :331 */
+#define CORB_NP_REPROJ_1     5   /* :345 / :354 */
+#define CORB_NP_REPROJ_2     6   /* :368 / :377 */
+#define CORB_NP_SCALE        7   /* :388, :397 */
+/* source of x3d: 0 the SVD, 1 UnprojectStereo of keyframe 1, 2 UnprojectStereo of keyframe 2.  Two quirks of the reference are kept: with both sides stereo only
+ * side 1's stereo parallax is evaluated (`else if`, :290), and the second keyframe's stereo reprojection uses the CURRENT keyframe's mbf (:372). */
+typedef struct CorbNewPointSide {     /* one keyframe as CreateNewMapPoints reads it */
+    const CorbKeyPoint* keys_un; const float* u_right; const float* depth; int32_t n;      /* mvKeysUn, mvuRight, mvDepth */
+    float Tcw[16]; float fx, fy, cx, cy, bf, mb;
+    const float* scale; int32_t nlevels;          /* mvScaleFactors; mvLevelSigma2 = scale^2 in float */
+} CorbNewPointSide;
+/* the pairs of ONE corb_search_for_triangulation call (kf1 = mpCurrentKeyFrame, kf2 = the neighbour): x3d n_pairs x 3, status / source n_pairs,
+ * *n_new = pairs with CORB_NP_OK.  Host pointers; synchronous. */
+int corb_triangulate_pairs(const CorbNewPointSide* kf1, const CorbNewPointSide* kf2, const int32_t* pairs, int n_pairs,
+                           float* x3d /* n_pairs x 3 */, uint8_t* status, uint8_t* source, int* n_new, int device);
+/* The whole neighbour loop (:219-419) on records: mpCurrentKeyFrame = record cur_slot of `kf`, vpNeighKFs = the records nb_slots (distinct, not cur_slot; the caller
+ * has applied the baseline test :225-239) with F12 / epipole per neighbour as corb_search_for_triangulation_slots takes them (ComputeF12 stays with the adapter).
+ * Poses and intrinsics come from the records' meta, mb and mvScaleFactors from cam.  Neighbour j is matched by the kernels of corb_search_for_triangulation_slots
+ * with check_orientation = 0 (CreateNewMapPoints builds ORBmatcher(0.6, false)) against the current keyframe's has-a-map-point flags as they stand after
+ * neighbours 0 .. j-1: a feature whose pair reached CORB_NP_OK is flagged from then on.  The pairs of neighbour j, ascending in idx1, are entries
+ * pair_offset[j] .. pair_offset[j+1] of pairs (x 2) / x3d (x 3) / status / source; room for n_nb x n(cur_slot) entries.  *n_new = pairs with CORB_NP_OK.
+ * apply == 0: no record changes (map may be NULL).  apply != 0: for the k-th OK pair in (neighbour, idx1) order record first_mp_slot + k of `map` becomes the new
+ * MapPoint (:401-415): id = first_mp_id + k, ref_kf_id = the current keyframe's id, client_id, world_pos = x3d, the two observations in ascending keyframe id,
+ * descriptor by the rule of corb_distinctive_descriptors (two observations: the first one's), normal / min_distance / max_distance as MapPoint::UpdateNormalAndDepth
+ * computes them for the two observations, counters and scratch zero; the id and the has-a-map-point flag enter both keyframe records' features (two pairs of one
+ * neighbour that share idx2 leave the later id there, as AddMapPoint does).  Fewer than *n_new records from first_mp_slot on: CORB_ERR_CAPACITY, no record written
+ * (the outputs are complete).  corb_mp_store_build_index again afterwards.  One synchronisation and one read-back per call; locks as corb_fuse_store. */
+int corb_create_new_map_points_store(CorbKfStore* kf, int cur_slot, const int32_t* nb_slots, int n_nb,
+        const float* F12 /* n_nb x 9 */, const float* epipole /* n_nb x 2 */, const CorbTrackCamera* cam,
+        int only_stereo, int apply, CorbMpStore* map, int first_mp_slot, uint64_t first_mp_id, int32_t client_id,
+        int32_t* pair_offset /* n_nb + 1 */, int32_t* pairs, float* x3d, uint8_t* status, uint8_t* source, int* n_new);
+
 #ifdef __cplusplus
 }
 #endif
