@@ -159,17 +159,18 @@ extern "C" int corb_track_pose_optimization(CorbKfStore* frames, int slot, CorbM
     struct Res { double pose[7]; int cnt[4]; int E[2]; };           // (the finish kernel packs it: one copy instead of three)
     static_assert(sizeof(Res) == 80, "pose | counters | edge counts");
     double* dres; HIPCHK(pool.alloc(&dres, 10)); t.result = dres;
+    if (outlier) HIPCHK(pool.alloc(&t.rejected, (size_t)n));
     track_launch_pose_finish(t, pool.stream);
     HIPCHK(hipGetLastError());
     Res* r = static_cast<Res*>(pool.pinned());
     HIPCHK(hipMemcpyAsync(r, dres, sizeof(Res), hipMemcpyDeviceToHost, pool.stream));
     std::vector<unsigned char> fl;
-    if (outlier) { fl.resize((size_t)n); const RecLayout L(frames->F); HIPCHK(pool.d2h(fl.data(), t.cur + L.flags, (size_t)n)); }
+    if (outlier) { fl.resize((size_t)n); HIPCHK(pool.d2h(fl.data(), t.rejected, (size_t)n)); }
     HIPCHK(pool.fetch_finish());
     if (r->cnt[2]) corb_pose_to_T(r->pose, Tcw_out);
     if (n_inliers) *n_inliers = r->E[1] < 3 ? 0 : r->cnt[3];          // `if(nInitialCorrespondences<3) return 0;`
-    // (flags as they were BEFORE a discard would clear mvbOutlier: the caller sees which features the optimisation rejected)
-    if (outlier) for (int i = 0; i < n; i++) outlier[i] = (fl[i] & (discard_outliers ? CORB_FEATURE_DISCARDED : CORB_FEATURE_OUTLIER)) ? 1 : 0;
+    // (the features THIS call rejected, whether or not a discard then clears their mvbOutlier; a feature that an earlier call discarded carries no edge and is not one)
+    if (outlier) memcpy(outlier, fl.data(), (size_t)n);
     return CORB_OK;
 }
 

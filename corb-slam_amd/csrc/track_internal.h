@@ -33,6 +33,7 @@ struct TrackPoseDev {
     int* efeat;                                          // [E] feature of edge e
     const unsigned char* active; const double* pose; const int* counters;     // results of the optimisation
     int discard;                                         // outliers lose their MapPoint (TrackWithMotionModel / TrackLocalMap's "Discard outliers")
+    unsigned char* rejected;                             // [n_cur] or NULL: 1 for the features whose edge this call rejected (a feature discarded by an earlier call is not one)
     double* result;                                      // [10] what the host reads, as one block (one copy): pose[7] | counters[4] and edge_off[2] as six ints
 };
 // one edge per feature that holds a usable MapPoint, in feature order (Optimizer.cc:300-366); edge_off[1] = their number

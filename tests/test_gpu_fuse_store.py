@@ -1,7 +1,14 @@
 """GPU parity: ORBmatcher::Fuse on records (corb_fuse_store) against the host-pointer form / the oracle on the same scene, and the reference's map update
-(AddObservation / AddMapPoint for features without a MapPoint, Replace cases reported) against a sequential restatement of ORBmatcher.cc:1083-1104."""
+(AddObservation / AddMapPoint for features without a MapPoint, Replace cases reported) against a sequential restatement of ORBmatcher.cc:1083-1104
+(tests/records_reference.py fuse_writes)."""
+import os
+import sys
+
 import numpy as np
 import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from records_reference import fuse_writes  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 NONE = np.uint64(0xFFFFFFFFFFFFFFFF)
@@ -55,15 +62,7 @@ def test_fuse_on_records(corb, pyorc, synth, seed, n, span):
         assert r1.tobytes() == rec.tobytes() and np.array_equal(KF.get_map_points(1), held)         # apply = False: the records are as they were
     assert g[2] > 50
     # the map update, sequentially (ORBmatcher.cc:1083-1104)
-    mp = held.copy(); act = np.zeros(n, np.uint8); lists = [list(zip(okf[off[i]: off[i + 1]], oidx[off[i]: off[i + 1]])) for i in range(n)]
-    for i in range(n):
-        f = int(g[0][i])
-        if f < 0:
-            continue
-        if mp[f] != NONE:
-            act[i] = 2
-        else:
-            act[i] = 1; mp[f] = np.uint64(rec["id"][i]); lists[i] = sorted(lists[i] + [(KF2_ID, f)])
+    mp, act, lists = fuse_writes(g[0], held, rec["id"], [list(zip(okf[off[i]: off[i + 1]], oidx[off[i]: off[i + 1]])) for i in range(n)], KF2_ID)
     assert np.array_equal(g[3], act) and (act == 1).sum() > 20 and (act == 2).sum() > 20
     a = KF.Fuse(1, MP, np.arange(n), cam, T, k2["log_scale_factor"], 4.0, apply=True)
     assert np.array_equal(a[0], g[0]) and np.array_equal(a[3], act)

@@ -370,3 +370,217 @@ def test_sim3_log_sweep_reaches_all_four_branches_and_measures_the_oracle(pyorc)
         R1 = pyorc.optimize_essential_graph(g1, 1, False)
         assert np.isfinite(R1["S"]).all()
         RL._check_apply(R1, g["S"], R1["S"], pt["p"])
+
+
+# ---- the calls on device-resident records: tests/test_gpu_random_records.py, tests/records_reference.py ----
+import records_reference as R  # noqa: E402
+import test_gpu_random_records as RC  # noqa: E402
+
+RC_LISTS = ("TRACK_POSE_CASES", "TRACK_LAST_CASES", "TRACK_LOCAL_CASES", "REC_RELOC_CASES", "REC_SCW_CASES", "REC_SIM3_CASES", "REC_FUSE_CASES", "REPLACE_CASES",
+            "DISTINCTIVE_SIZES")
+
+
+def test_record_case_lists_are_deterministic_and_reach_every_size_and_setting():
+    global RC
+    before = {k: _fingerprint(getattr(RC, k)) for k in RC_LISTS}
+    RC = importlib.reload(RC)
+    for k in RC_LISTS:
+        assert _fingerprint(getattr(RC, k)) == before[k], k
+    for k in RC_LISTS[:-1]:
+        cs = getattr(RC, k)
+        ids = [RC._id("x", c, sorted(set(c) - {"i", "seed"})) for c in cs]
+        assert len(set(ids)) == len(ids) and [c["i"] for c in cs] == list(range(len(cs))), k
+    P = RC.TRACK_POSE_CASES
+    assert {0, 2, 3, 9, 10, 11} <= {c["edges"] for c in P} and {63, 64, 65, 1023, 1024, 1025, 2049, 3000} <= {c["n"] for c in P}
+    assert all(0.4 * c["n"] <= c["edges"] <= 0.7 * c["n"] for c in P if c["n"] >= 1023 or c["i"] in (6, 7, 8))
+    assert {0, 1, 37} == {c["F"] - c["n"] for c in P} and {True, False} == {c["discard"] for c in P} and sum(c["collide"] for c in P) == 1
+    assert any(c["F"] % 64 for c in P)
+    sizes = {40, 63, 64, 65, 700, 2100, 2900}
+    for cs, other in ((RC.TRACK_LAST_CASES, "n_last"), (RC.TRACK_LOCAL_CASES, "n_local")):
+        assert sizes <= {c["n_cur"] for c in cs} and sizes <= {c[other] for c in cs} and {c[other] for c in cs} <= sizes and all(c["n_cur"] != c[other] for c in cs)
+        assert sum(c["collide"] for c in cs) == 1 and len({c["th"] for c in cs}) == 2 and len({c["nnratio"] for c in cs}) == 2
+    assert {True, False} == {c["mono"] for c in RC.TRACK_LAST_CASES} == {c["ori"] for c in RC.TRACK_LAST_CASES}
+    assert sum(c["only_bad"] for c in RC.TRACK_LOCAL_CASES) == 1
+    assert {50, 64, 600, 2100} == {c["n"] for c in RC.REC_RELOC_CASES} and sum(c["cur_smaller"] for c in RC.REC_RELOC_CASES) * 2 == len(RC.REC_RELOC_CASES)
+    for cs in (RC.REC_SCW_CASES, RC.REC_SIM3_CASES, RC.REC_FUSE_CASES):
+        assert {40, 63, 65, 600, 2100} <= {c["n"] for c in cs} and {1.0, 0.3} == {c["span"] for c in cs}
+    assert {True, False} == {c["apply"] for c in RC.REC_FUSE_CASES} and {2, 8} == {c["max_obs"] for c in RC.REC_FUSE_CASES}
+    assert {True, False} == {c["later"] for c in RC.REC_FUSE_CASES if c["apply"] and c["max_obs"] == 2}
+    assert [c["merged"] for c in RC.REPLACE_CASES] == [1, 2, 63, 64, 65, 80] and RC.REPLACE_O == 80 and RC.REPLACE_NKF == 96 and RC.REPLACE_F == 8
+    D = RC.DISTINCTIVE_SIZES
+    assert {1, 2, 3, 4, 63, 64, 65, 128, 1023, 1024} <= set(D) and any(D[k] == 0 and D[k - 1] > 0 and D[k + 1] > 0 for k in range(1, len(D) - 1))
+
+
+def test_record_pose_cases_have_the_edges_they_name_and_outliers_in_the_oracle(synth, pyorc):
+    for c in RC.TRACK_POSE_CASES:
+        p = RC.track_pose_problem(synth, c)
+        e, r = RC.track_pose_reference(pyorc, p)
+        E = len(e["feat"])
+        assert E == c["edges"] and e["klass"] == (0 if E < 3 else 1 if E < 10 else 4) and np.all(np.diff(e["feat"]) > 0), c
+        fl = p["fr"]["flags"]
+        assert (fl == 2).any() or E < 3
+        assert E == 0 or c["n"] < 100 or ((fl == 4).any() and (fl == 6).any() and (p["fr"]["mp_id"] == R.NONE).any() and (p["rec"]["flags"] & 1).any())
+        if E >= 3:
+            assert e["mono"].any() and not e["mono"].all()
+        if E >= 10:
+            assert 0 < r["outlier"].sum() < E, c
+        if c["n"] >= 1023:                           # every 1024-chunk and every wave of 64 features has edges and gaps
+            has = np.zeros(-(-c["n"] // 64) * 64, bool); has[e["feat"]] = True
+            per = has.reshape(-1, 64).sum(1)
+            assert per[:-1].min() > 0 and per.max() < 64
+        if c["collide"]:
+            assert R.probe_chain(p["rec"]["id"], R.id_table_cells(c["n"]))[0] >= 8
+
+
+def test_record_tracking_cases_match_and_see_something_in_the_oracle(synth, pyorc):
+    for c in RC.TRACK_LAST_CASES:
+        p = RC.track_last_problem(synth, c)
+        m, n, lastp, claimed = RC.track_last_reference(pyorc, c, p)
+        assert n > 0 and 0 < lastp["valid"].sum() < c["n_last"], c
+        assert claimed.any() or c["n_cur"] < 100, c
+    for c in RC.TRACK_LOCAL_CASES:
+        p = RC.track_local_problem(synth, c)
+        m, n, exp, after = RC.track_local_reference(pyorc, c, p)
+        assert n > 0 and 0 < int(exp["valid"].sum()) < c["n_local"], c
+        assert (after != p["cur"]["mp_id"]).any(), c                                          # a bad point left the frame
+        if c["only_bad"]:
+            assert (after == R.NONE).all()
+        if c["collide"]:
+            seen = sorted(R.seen_in_frame(p["cur"]["mp_id"], p["cur"]["flags"], p["rec"], p["slot_of"]))      # what the call's in-frame table holds
+            for ids in (p["rec"]["id"], seen):
+                longest, wrapped = R.probe_chain(ids, R.id_table_cells(c["n_cur"]))
+                assert longest >= 8 and wrapped > 0
+
+
+def test_record_keyframe_matcher_cases_match_in_the_oracle(synth, pyorc):
+    for c in RC.REC_RELOC_CASES:
+        p = RC.rec_reloc_problem(synth, c)
+        m, n, v, claimed = RC.rec_reloc_reference(pyorc, c, p)
+        assert n > 0 and 0 < v["valid"].sum() < c["n"] and claimed.any(), c
+        assert (R.slots_of(p["cur"]["mp_id"][claimed != 0], p["slot_of"]) < 0).any()           # held ids the store does not know
+    for c in RC.REC_SCW_CASES:
+        assert RC.rec_scw_reference(pyorc, c, RC.rec_scw_problem(synth, c))[1] > 0, c
+    for c in RC.REC_SIM3_CASES:
+        p = RC.rec_sim3_problem(synth, c)
+        m0, n0, _, _ = RC.rec_sim3_reference(pyorc, c, p, None)
+        m1, n1, v1, v2 = RC.rec_sim3_reference(pyorc, c, p, p["matched"])
+        assert n0 > 0 and n1 > 0 and not v1["valid"][p["pre"]].any() and not v2["valid"][p["at"][2:]].any(), c
+        pos = {R.index_in_keyframe(p["lists"][s], RC.KF2_ID) >= 0 and [k for k, _ in p["lists"][s]].index(RC.KF2_ID) for s in R.slots_of(p["matched"][p["pre"]], p["slot_of"]) if s >= 0}
+        assert {0, c["max_obs"] // 2, c["max_obs"] - 1} <= pos
+    for c in RC.REC_FUSE_CASES:
+        p = RC.rec_fuse_problem(synth, c)
+        bi, bd, nf = RC.rec_fuse_reference(pyorc, c, p)
+        mp, act, lists = R.fuse_writes(bi, p["held"], p["rec"]["id"], p["lists"], RC.KF2_ID)
+        assert nf > 0 and (act == 1).any() and ((act == 2).any() or c["n"] < 100), c
+        if c["max_obs"] == 2 and c["apply"]:                                                  # with a later observer the full-list error path is taken, without it never
+            assert any(act[i] == 1 and len(p["lists"][i]) >= 2 for i in range(c["n"])) == c["later"]
+
+
+def test_replace_and_distinctive_cases_tie_on_the_least_median(pyorc):
+    bests = []
+    for c in RC.REPLACE_CASES:
+        p = RC.replace_problem(c)
+        st, into, act, _ = pyorc.mappoint_replace(100, 200, p["this"], p["into"], RC.REPLACE_O)
+        rows = RC.replace_rows(p, into)
+        assert st == 0 and len(rows) == c["merged"] and len(into) <= RC.REPLACE_O and {1, 2} <= set(act.tolist()) | ({1, 2} if c["merged"] <= 2 else set()), c
+        assert any(k == 0 for k, _ in into) or c["merged"] < 2
+        if len(rows) >= 3:
+            med = R.row_medians(np.stack(rows))
+            assert (med == med.min()).sum() >= 2
+            bests.append(int(pyorc.distinctive_descriptors(np.stack(rows), np.array([0, len(rows)], np.int32))[0]))
+            assert bests[-1] == int(np.argmin(med))
+    desc, offset = RC.distinctive_problem()
+    r = pyorc.distinctive_descriptors(desc, offset)
+    for k, N in enumerate(RC.DISTINCTIVE_SIZES):
+        if N == 0:
+            assert r[k] == -1
+            continue
+        med = R.row_medians(desc[offset[k]: offset[k + 1]])
+        assert r[k] == int(np.argmin(med))                                                      # the first row with the least median
+        if N >= 3:
+            assert (med == med.min()).sum() >= 2
+            bests.append(int(r[k]))
+    assert any(b > 0 for b in bests) and any(b >= 64 for b in bests)                            # not always row 0, and past the first wave
+
+
+def test_colliding_ids_collide_under_the_restated_hash():
+    for cells in (256, 2048, 8192):
+        ids = R.colliding_ids(cells // 2 - 3, cells, np.random.default_rng(cells))
+        assert len(set(ids.tolist())) == len(ids) and 0 in ids.tolist() and (1 << 64) - 2 in ids.tolist() and R.NO_MAP_POINT not in ids.tolist()
+        assert sum((R.id_hash(int(k)) & (cells - 1)) >= cells - 4 for k in ids) >= 16
+        longest, wrapped = R.probe_chain(ids, cells)
+        assert longest >= 8 and wrapped >= 8
+        assert R.id_table_cells(len(ids)) == cells
+    assert [R.id_table_cells(n) for n in (0, 1, 32, 33, 1024, 1025)] == [64, 64, 64, 128, 2048, 4096]
+
+
+def test_records_reference_agrees_with_the_hand_built_views_of_the_record_tests(synth):
+    """the scene of tests/test_gpu_kfproj_store.py::test_reloc_projection_on_records with its ids, bad flags and claimed array built by hand as that test builds them"""
+    seed, n = 5312, 500
+    rng = np.random.default_rng(seed)
+    sc = synth.keyframe_scene(seed, n=n, span=1.0)
+    pts = sc["pts1"]; has = pts["valid"] != 0
+    cause = rng.integers(0, 3, n)
+    ids1 = np.where(has | (cause != 0), np.uint64(1000) + np.arange(n, dtype=np.uint64), R.NONE)
+    bad1 = ~has & (cause == 1); found = np.nonzero(~has & (cause == 2))[0]
+    claimed = sc["claimed2"] != 0
+    ids2 = np.where(claimed, np.uint64(700000) + np.arange(n, dtype=np.uint64), R.NONE)
+    ci = np.nonzero(claimed)[0]; ids2[ci[: len(found)]] = np.uint64(1000) + found.astype(np.uint64)
+    rec = np.zeros(n, R.MP_RECORD_DTYPE); rec["id"] = 1000 + np.arange(n); rec["descriptor"] = sc["desc1"]; rec["world_pos"] = pts["world"]; rec["normal"] = pts["normal"]
+    rec["min_distance"] = pts["min_distance"]; rec["max_distance"] = pts["max_distance"]; rec["flags"] = np.where(bad1, R.MP_BAD, 0); rec["n_obs"] = 1
+    v, d, cl = R.reloc_view(sc["kf1"]["keys_un"], ids1, ids2, np.zeros(n, np.uint8), rec, R.slot_dict(rec))
+    assert np.array_equal(cl, sc["claimed2"]) and np.array_equal(v["valid"], pts["valid"])
+    ok = has
+    for k in ("world", "normal", "min_distance", "max_distance", "angle"):
+        assert np.array_equal(v[k][ok], pts[k][ok]), k
+    assert np.array_equal(d[ok], sc["desc1"][ok])
+    # test_search_by_sim3_on_records' second round: a third of some pairs enter as matched, KF2's side through the observation (22, i) of KF2's point i
+    lists = [[(11, i)] for i in range(n)] + [[(22, i)] for i in range(n)]
+    rec2 = np.concatenate([rec, rec]); rec2["id"][n:] = 500000 + np.arange(n); rec2["flags"] = 0
+    i1 = np.uint64(1000) + np.arange(n, dtype=np.uint64); i2 = np.uint64(500000) + np.arange(n, dtype=np.uint64)
+    pre = np.arange(0, n, 7); to = (pre * 3) % n
+    matched = np.full(n, R.NONE, np.uint64); matched[pre] = i2[to]
+    (v1, _), (v2, _) = R.sim3_views(i1, i2, matched, rec2, R.slot_dict(rec2), lists, 22)
+    w1 = np.ones(n, bool); w1[pre] = False; w2 = np.ones(n, bool); w2[to] = False
+    assert np.array_equal(v1["valid"].astype(bool), w1) and np.array_equal(v2["valid"].astype(bool), w2)
+
+
+def test_pointer_level_rules_on_hand_checked_examples():
+    rec = np.zeros(4, R.MP_RECORD_DTYPE); rec["id"] = [10, 20, 30, 40]; rec["n_obs"] = [1, 0, 1, 1]; rec["flags"] = [0, 0, R.MP_BAD, 0]
+    rec["world_pos"] = np.arange(12).reshape(4, 3); rec["descriptor"] = np.arange(4)[:, None] + 1
+    so = R.slot_dict(rec)
+    keys = np.zeros(4, R.KP_DTYPE); keys["angle"] = [1, 2, 3, 4]; keys["octave"] = [0, 1, 2, 3]; keys["x"] = [5, 6, 7, 8]
+    U = np.uint64
+    # last frame: a good point; an outlier; a bad point; an id nobody knows.  Current frame: holds the unobserved point 20 (not claimed), 10 discarded, 40, nothing
+    lastp, ld, cl = R.last_frame_view(keys, [U(10), U(40), U(30), U(99)], [0, R.OUTLIER, 0, 0], [U(20), U(10), U(40), R.NONE], [0, R.DISCARDED, R.OUTLIER, 0], rec, so)
+    assert lastp["valid"].tolist() == [1, 0, 0, 0] and lastp["claims"].tolist() == [1, 0, 0, 0] and lastp["world"][0].tolist() == [0, 1, 2] and not lastp["world"][1:].any()
+    assert ld[0, 0] == 1 and not ld[1:].any() and cl.tolist() == [0, 0, 1, 0] and lastp["octave"].tolist() == [0, 1, 2, 3]
+    ids, fl = R.matched_writes([U(20), U(10), U(40), R.NONE], [0, R.DISCARDED, R.OUTLIER, 0], [-1, 0, -1, 3], [U(10), U(40), U(30), U(99)])
+    assert ids.tolist() == [20, 10, 40, 99] and fl.tolist() == [0, 0, R.OUTLIER, 0]
+    # pose edges: held and outlier-marked points carry an edge, in index order; discarded, bad and unknown ones do not
+    e = R.pose_edges(keys, np.array([-1, 3, -1, 2], np.float32), [U(40), U(10), U(30), U(10)], [R.OUTLIER, 0, 0, R.DISCARDED], rec, so, np.array([1, .5, .25, .125], np.float32))
+    assert e["feat"].tolist() == [0, 1] and e["mono"].tolist() == [True, False] and e["w"].tolist() == [1, .5] and e["points"].tolist() == [[9, 10, 11], [0, 1, 2]] and e["klass"] == 0
+    assert e["obs"].tolist() == [[5, 0, -1], [6, 0, 3]]
+    assert R.pose_writes([R.OUTLIER, 0, R.OUTLIER | R.DISCARDED, 1], [0, 1], [False, True], False).tolist() == [0, R.OUTLIER, R.DISCARDED, 1]
+    assert R.pose_writes([R.OUTLIER, 0, R.OUTLIER | R.DISCARDED, 1], [0, 1], [False, True], True).tolist() == [0, R.DISCARDED, R.DISCARDED, 1]
+    # SearchLocalPoints: the bad point 30 leaves the frame; 10 (held) and 40 (discarded) are seen; candidates: 20 only (30 bad, 99 unknown)
+    after, cand, cl = R.local_points_view([U(10), U(30), U(40), R.NONE], [0, 0, R.DISCARDED, 0], [U(40), U(20), U(30), U(99), U(10)], rec, so)
+    assert after.tolist() == [10, R.NO_MAP_POINT, 40, R.NO_MAP_POINT] and cand.tolist() == [False, True, False, False, False] and cl.tolist() == [1, 0, 0, 0]
+    # relocalisation: the frame holds 20 and the unknown 99 (both claimed), 10 only discarded; pKF's points 10 (candidate), 20 (already found), 30 (bad), none
+    v, d, cl = R.reloc_view(keys, [U(10), U(20), U(30), R.NONE], [U(20), U(99), U(10), R.NONE], [0, 0, R.DISCARDED, 0], rec, so)
+    assert v["valid"].tolist() == [1, 0, 0, 0] and v["angle"].tolist() == [1, 0, 0, 0] and cl.tolist() == [1, 1, 0, 0] and d[0, 0] == 1
+    # Scw: vpMatched holds 20 and an unknown id; vpPoints in the order 40, 30, 20, 10
+    v, d, cl = R.scw_view([R.NONE, U(20), U(99)], [3, 2, 1, 0], rec)
+    assert v["valid"].tolist() == [1, 0, 0, 1] and cl.tolist() == [0, 1, 1] and d[:, 0].tolist() == [4, 0, 0, 1]
+    # Sim3: feature 0 of KF1 enters matched to point 40, which KF2 (id 7) sees at feature 2; feature 1 to point 10, seen at feature 9 >= N2; GetIndexInKeyFrame
+    lists = [[(3, 0), (7, 9)], [(7, 1)], [(7, 0)], [(3, 1), (5, 0), (7, 2)]]
+    assert [R.index_in_keyframe(l, 7) for l in lists] == [9, 1, 0, 2] and R.index_in_keyframe(lists[1], 3) == -1
+    (v1, _), (v2, _) = R.sim3_views([U(10), U(20), U(30)], [U(30), U(20), U(40)], [U(40), U(10), R.NONE], rec, so, lists, 7)
+    assert v1["valid"].tolist() == [0, 0, 0] and v2["valid"].tolist() == [0, 1, 0]
+    (v1, _), (v2, _) = R.sim3_views([U(10), U(20), U(30)], [U(30), U(20), U(40)], None, rec, so, lists, 7)
+    assert v1["valid"].tolist() == [1, 1, 0] and v2["valid"].tolist() == [0, 1, 1]
+    # Fuse: 10 is seen by keyframe 7 already, 30 is bad; the fused points 20 and 40 meet an empty feature and a held one
+    v, d = R.fuse_view([0, 1, 2, 3], rec, [[(3, 0), (7, 9)], [(9, 1)], [], [(3, 1)]], 7)
+    assert v["valid"].tolist() == [0, 1, 0, 1]
+    mp, act, out = R.fuse_writes([-1, 2, -1, 2], [R.NONE, U(5), R.NONE], [10, 20, 30, 40], [[(3, 0), (7, 9)], [(9, 1)], [], [(3, 1)]], 7)
+    assert mp.tolist() == [R.NO_MAP_POINT, 5, 20] and act.tolist() == [0, 1, 0, 2] and out[1] == [(7, 2), (9, 1)] and out[3] == [(3, 1)]
