@@ -38,6 +38,7 @@ EXPORTS = [
     "corb_rgbd_create", "corb_rgbd_destroy", "corb_rgbd_orb", "corb_rgbd_upload_batch", "corb_rgbd_run", "corb_rgbd_sync", "corb_rgbd_fetch_batch",
     "corb_rgbd_frame_layout", "corb_rgbd_frames", "corb_rgbd_image_bounds", "corb_kf_store_put_from_rgbd",
     "corb_triangulate_pairs", "corb_create_new_map_points_store",
+    "corb_sim3_ransac", "corb_sim3_ransac_store",
 ]
 
 
@@ -308,6 +309,9 @@ def load():
     L.corb_triangulate_pairs.argtypes = [C.POINTER(_NewPointSide), C.POINTER(_NewPointSide), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.c_int]
     L.corb_create_new_map_points_store.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(TrackCamera), C.c_int, C.c_int, C.c_void_p, C.c_int,
                                                    C.c_uint64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
+    L.corb_sim3_ransac.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 6 + [C.c_int]
+    L.corb_sim3_ransac_store.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(TrackCamera), C.c_void_p, C.c_void_p, C.c_double, C.c_int, C.c_int, C.c_int,
+                                         C.c_void_p, C.c_int] + [C.c_void_p] * 8
     _lib = L
     return L
 
@@ -827,6 +831,106 @@ def TriangulatePairs(kf1, kf2, pairs, device=0):
     return x3d[:n], st[:n], src[:n], nn.value
 
 
+class _Sim3RansacProblem(C.Structure):
+    _fields_ = [("n", C.c_int32), ("p1c", C.c_void_p), ("p2c", C.c_void_p), ("sigma2_1", C.c_void_p), ("sigma2_2", C.c_void_p)] + \
+               [(k, C.c_float) for k in ("fx1", "fy1", "cx1", "cy1", "fx2", "fy2", "cx2", "cy2")]
+
+
+SIM3_EVENT_DTYPE = np.dtype([("iteration", "<i4"), ("n_inliers", "<i4"), ("R12", "<f4", 9), ("t12", "<f4", 3), ("s12", "<f4")])      # CorbSim3RansacEvent
+
+
+def _sim3_ransac_result(c, n_ev, max_events, cap, events, flags, counts, q):
+    k = min(int(n_ev[c]), max_events)
+    return dict(ransac_max_its=int(cap[c]), n_events=int(n_ev[c]), events=events[c, :k].copy(), inliers=flags[c, :k].astype(bool),
+                counts=counts[c].copy(), q=q[c].copy())
+
+
+def Sim3Ransac(problems, rand_values, probability=0.99, min_inliers=20, max_iterations=300, fix_scale=False, max_events=None, device=0):
+    """Sim3Solver's RANSAC for a list of candidates in one call (corb_sim3_ransac).  problems: dicts(p1c [n, 3], p2c [n, 3], sigma2_1 [n], sigma2_2 [n], K1, K2 =
+    (fx, fy, cx, cy)); rand_values [n_problems, max_iterations, 3] results of rand().  Returns per problem dict(ransac_max_its, n_events, events (SIM3_EVENT_DTYPE, the
+    first max_events), inliers [events, n] bool, counts [max_iterations], q [max_iterations, 4])."""
+    n = len(problems); max_events = max_iterations if max_events is None else int(max_events)
+    arr = (_Sim3RansacProblem * max(n, 1))(); keep = []
+    for c, q in enumerate(problems):
+        a = [np.ascontiguousarray(q[k], np.float32) for k in ("p1c", "p2c", "sigma2_1", "sigma2_2")]
+        keep.append(a)
+        K = [float(np.float32(v)) for v in tuple(q["K1"]) + tuple(q["K2"])]
+        arr[c] = _Sim3RansacProblem(len(a[2]), *[_p(x) for x in a], *K)
+    stride = max([len(a[2]) for a in keep] + [1])
+    rv = np.ascontiguousarray(rand_values, np.int32).reshape(-1)
+    assert len(rv) == n * max_iterations * 3
+    cap = np.zeros(max(n, 1), np.int32); n_ev = np.zeros(max(n, 1), np.int32); ev = np.zeros((max(n, 1), max(max_events, 1)), SIM3_EVENT_DTYPE)
+    fl = np.zeros((max(n, 1), max(max_events, 1), stride), np.uint8); cnt = np.zeros((max(n, 1), max_iterations), np.int32); qo = np.zeros((max(n, 1), max_iterations, 4), np.float32)
+    _chk(load().corb_sim3_ransac(C.cast(arr, C.c_void_p), n, float(probability), int(min_inliers), int(max_iterations), int(bool(fix_scale)), _p(rv), max_events, stride,
+                                 _p(cap), _p(n_ev), _p(ev), _p(fl), _p(cnt), _p(qo), device), "corb_sim3_ransac")
+    out = [_sim3_ransac_result(c, n_ev, max_events, cap, ev, fl, cnt, qo) for c in range(n)]
+    for c, r in enumerate(out):
+        r["inliers"] = r["inliers"][:, : len(keep[c][2])]
+    return out
+
+
+class Sim3Solver:
+    """Sim3Solver (C/include/Sim3Solver.h) over corb_sim3_ransac: one library call evaluates every hypothesis, then iterate() is replayed from the events.  The
+    constructor takes what the reference's leaves (:37-112): mvX3Dc1 / mvX3Dc2, mvLevelSigma2 of the two octaves, both intrinsics (fx, fy, cx, cy); indices1 / n1 =
+    mvnIndices1 / mN1 scatter vbInliers as :195-197 do (default: the correspondences themselves).  The draws are an argument: rand_values [maxIterations, 3] results of
+    rand() in [0, 2^31), or a seeded numpy.random.RandomState."""
+
+    def __init__(self, p1c, p2c, sigma2_1, sigma2_2, K1, K2, bFixScale=False, indices1=None, n1=None, rand_values=None, seed=0, device=0):
+        self.problem = dict(p1c=np.ascontiguousarray(p1c, np.float32).reshape(-1, 3), p2c=np.ascontiguousarray(p2c, np.float32).reshape(-1, 3),
+                            sigma2_1=np.ascontiguousarray(sigma2_1, np.float32), sigma2_2=np.ascontiguousarray(sigma2_2, np.float32), K1=tuple(K1), K2=tuple(K2))
+        self.N = len(self.problem["sigma2_1"]); self.mbFixScale = bool(bFixScale); self.device = device
+        self.mvnIndices1 = np.arange(self.N) if indices1 is None else np.asarray(indices1, np.int64)
+        self.mN1 = int(n1) if n1 is not None else (self.N if indices1 is None else int(self.mvnIndices1.max(initial=-1)) + 1)
+        self._rand = rand_values; self._seed = seed
+        self.SetRansacParameters()
+
+    def SetRansacParameters(self, probability=0.99, minInliers=6, maxIterations=300):
+        self.mRansacProb, self.mRansacMinInliers, self._max_its = float(probability), int(minInliers), int(maxIterations)
+        self.mnIterations = 0; self._res = None; self._last = None
+
+    def _run(self):
+        if self._res is None:
+            rv = self._rand if self._rand is not None else np.random.RandomState(self._seed).randint(0, 2 ** 31, (self._max_its, 3))
+            rv = np.ascontiguousarray(rv, np.int32).reshape(-1, 3)[: self._max_its]
+            self._res = Sim3Ransac([self.problem], rv[None], self.mRansacProb, self.mRansacMinInliers, self._max_its, self.mbFixScale, device=self.device)[0]
+            self.mRansacMaxIts = self._res["ransac_max_its"]
+        return self._res
+
+    def iterate(self, nIterations):
+        """-> (T12 4x4 float32 or None, bNoMore, vbInliers [mN1] bool, nInliers)"""
+        vbInliers = np.zeros(self.mN1, bool)
+        if self.N < self.mRansacMinInliers:
+            return None, True, vbInliers, 0
+        r = self._run(); cap = r["ransac_max_its"]
+        end = min(self.mnIterations + int(nIterations), cap)
+        for k, e in enumerate(r["events"]):
+            if self.mnIterations < e["iteration"] <= end:
+                self.mnIterations = int(e["iteration"]); self._last = e
+                vbInliers[self.mvnIndices1[r["inliers"][k]]] = True
+                T = np.eye(4, dtype=np.float32)
+                T[:3, :3] = e["s12"] * e["R12"].reshape(3, 3); T[:3, 3] = e["t12"]
+                return T, False, vbInliers, int(e["n_inliers"])
+        self.mnIterations = end
+        return None, self.mnIterations >= cap, vbInliers, 0
+
+    def find(self):
+        """-> (T12 or None, vbInliers12, nInliers)"""
+        if self.N < self.mRansacMinInliers:
+            return None, np.zeros(self.mN1, bool), 0
+        T, _, vb, n = self.iterate(self._run()["ransac_max_its"])
+        return T, vb, n
+
+    # the best model so far; as every caller reads them after iterate() returned a transformation, they are that return's
+    def GetEstimatedRotation(self):
+        return None if self._last is None else self._last["R12"].reshape(3, 3).copy()
+
+    def GetEstimatedTranslation(self):
+        return None if self._last is None else self._last["t12"].copy()
+
+    def GetEstimatedScale(self):
+        return None if self._last is None else float(self._last["s12"])
+
+
 def spd_solve(A, b, device=0):
     """corb_spd_solve: x with A x = b for a symmetric positive definite A (hand-written blocked Cholesky, csrc/dense_chol.hip); returns (x, info)"""
     A = np.ascontiguousarray(A, np.float64); b = np.ascontiguousarray(b, np.float64); x = np.zeros(len(b), np.float64); info = C.c_int(0)
@@ -1147,6 +1251,29 @@ class KeyFrameStore:
         _chk(L.corb_search_by_sim3_store(self.h, int(slot1), int(slot2), mp_store.h, C.byref(cam), C.c_float(log_scale_factor), _p(a), _p(b), _p(mi) if mi is not None else None,
                                          C.c_float(s12), _p(R), _p(t), C.c_float(th), _p(m), _p(ids), C.byref(cnt)), "corb_search_by_sim3_store")
         return m, ids, cnt.value
+
+    def Sim3Ransac(self, slot1, slots2, mp_store, cam1, cams2, matched12_ids, rand_values, probability=0.99, min_inliers=20, max_iterations=300, fix_scale=False, max_events=None):
+        """Sim3Solver's constructor and RANSAC on records for the candidates slots2 of keyframe slot1 (corb_sim3_ransac_store).  matched12_ids [n_candidates, n(slot1)] =
+        vpMatched12 as MapPoint ids; cams2 = one TrackCamera per candidate.  Returns per candidate what Sim3Ransac returns (inliers per feature of slot1 = vbInliers),
+        plus n_corr and index1 (mvnIndices1)."""
+        sl = np.ascontiguousarray(slots2, np.int32).reshape(-1); n = len(sl); n1 = self._n_features(slot1)
+        max_events = max_iterations if max_events is None else int(max_events)
+        ids = np.ascontiguousarray(matched12_ids, np.uint64).reshape(-1); rv = np.ascontiguousarray(rand_values, np.int32).reshape(-1)
+        assert len(ids) == n * n1 and len(rv) == n * max_iterations * 3 and len(cams2) == n
+        cams = (TrackCamera * max(n, 1))(*cams2)
+        m = max(n, 1)
+        cap = np.zeros(m, np.int32); n_ev = np.zeros(m, np.int32); ev = np.zeros((m, max(max_events, 1)), SIM3_EVENT_DTYPE)
+        fl = np.zeros((m, max(max_events, 1), max(n1, 1)), np.uint8); cnt = np.zeros((m, max_iterations), np.int32); qo = np.zeros((m, max_iterations, 4), np.float32)
+        nc = np.zeros(m, np.int32); ix = np.full((m, max(n1, 1)), -1, np.int32)
+        _chk(load().corb_sim3_ransac_store(self.h, int(slot1), _p(sl), n, mp_store.h, C.byref(cam1), C.cast(cams, C.c_void_p), _p(ids), float(probability), int(min_inliers),
+                                           int(max_iterations), int(bool(fix_scale)), _p(rv), max_events, _p(cap), _p(n_ev), _p(ev), _p(fl), _p(nc), _p(ix), _p(cnt), _p(qo)),
+             "corb_sim3_ransac_store")
+        out = []
+        for c in range(n):
+            r = _sim3_ransac_result(c, n_ev, max_events, cap, ev, fl, cnt, qo)
+            r["inliers"] = r["inliers"][:, :n1]; r["n_corr"] = int(nc[c]); r["index1"] = ix[c, : nc[c]].copy()
+            out.append(r)
+        return out
 
     def _n_features(self, slot):
         n = load().corb_kf_store_count(self.h, int(slot))

@@ -9,6 +9,7 @@
 //   void Optimizer::BundleAdjustment(const vector<KeyFrame*>&, const vector<MapPoint*>&, int, bool*, unsigned long, bool)   include/Optimizer.h:42-44
 //   void Optimizer::GlobalBundleAdjustemnt(Cache*, int, bool*, unsigned long, bool)            :45-46
 //   int  Optimizer::PoseOptimization(Frame*)                                                   :51
+//   Sim3Solver(KeyFrame*, KeyFrame*, const vector<MapPoint*>&, bool) / SetRansacParameters / iterate / find / GetEstimated*   include/Sim3Solver.h:39-49
 //
 // The adapters FLATTEN the reference's pointer graph into the arrays of the C-ABI (KeyFrame* / Frame& -> descriptors, keypoints, mvuRight,
 // "has a good MapPoint" flags, DBoW2::FeatureVector; Cache* -> poses, per-keyframe intrinsics, points, observations), call the accelerator,
@@ -25,7 +26,9 @@
 #include <algorithm>
 #include <atomic>
 #include <chrono>
+#include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <map>
 #include <set>
 #include <thread>
@@ -633,6 +636,107 @@ template <class Frame, class MapPoint, class Mat> struct FrameStoreT {
 }  // namespace corb
 
 // ---- on a tree with the reference's headers: the reference's own class names ----
+// ---- Sim3Solver (corbslam_client/include/Sim3Solver.h) over corb_sim3_ransac ----
+// The reference's constructor and method signatures.  The constructor flattens as C/src/Sim3Solver.cc:43-109 do (GetMapPointMatches, isBad, GetIndexInKeyFrame,
+// mvKeysUn[index].octave -> mvLevelSigma2, Rcw * Xw + tcw as cv::gemm computes it: double accumulation, one rounding; mK); the first iterate() pre-draws
+// maxIterations x 3 values from the random source (a callable returning rand()'s range [0, 2^31); DUtils::Random::RandomInt consumes exactly one rand() per draw),
+// makes ONE library call that evaluates every hypothesis, and iterate() is then replayed from the events: the position advances by nIterations, an event inside
+// the window is returned, bNoMore is set when mRansacMaxIts is reached without a return.  Mat = the type KeyFrame::GetRotation() returns.
+namespace corb {
+template <class KeyFrame, class MapPoint>
+class Sim3Solver {
+public:
+    using Mat = decltype(std::declval<KeyFrame&>().GetRotation());
+    using RandomSource = std::function<int()>;
+    Sim3Solver(KeyFrame* pKF1, KeyFrame* pKF2, const std::vector<MapPoint*>& vpMatched12, const bool bFixScale = true, RandomSource rnd = [] { return std::rand(); }, int device = 0)
+        : mbFixScale(bFixScale), rnd_(std::move(rnd)), device_(device)
+    {
+        check_abi();
+        std::vector<MapPoint*> vpKeyFrameMP1 = pKF1->GetMapPointMatches();
+        mN1 = (int)vpMatched12.size();
+        const Mat Rcw1 = pKF1->GetRotation(), tcw1 = pKF1->GetTranslation(), Rcw2 = pKF2->GetRotation(), tcw2 = pKF2->GetTranslation();
+        auto to_camera = [](const Mat& R, const Mat& t, const Mat& X, std::vector<float>& out) {
+            for (int r = 0; r < 3; r++) {
+                double s = (double)adapt::matf(R, r, 0) * (double)adapt::matf(X, 0);
+                s = s + (double)adapt::matf(R, r, 1) * (double)adapt::matf(X, 1);
+                s = s + (double)adapt::matf(R, r, 2) * (double)adapt::matf(X, 2);
+                out.push_back((float)(s + (double)adapt::matf(t, r)));
+            }
+        };
+        for (int i1 = 0; i1 < mN1; i1++) {
+            if (!vpMatched12[i1]) continue;
+            MapPoint* pMP1 = vpKeyFrameMP1[i1]; MapPoint* pMP2 = vpMatched12[i1];
+            if (!pMP1) continue;
+            if (pMP1->isBad() || pMP2->isBad()) continue;
+            const int indexKF1 = pMP1->GetIndexInKeyFrame(pKF1), indexKF2 = pMP2->GetIndexInKeyFrame(pKF2);
+            if (indexKF1 < 0 || indexKF2 < 0) continue;
+            sigma2_1_.push_back(pKF1->mvLevelSigma2[pKF1->mvKeysUn[indexKF1].octave]);
+            sigma2_2_.push_back(pKF2->mvLevelSigma2[pKF2->mvKeysUn[indexKF2].octave]);
+            mvnIndices1.push_back((size_t)i1);
+            to_camera(Rcw1, tcw1, pMP1->GetWorldPos(), p1c_); to_camera(Rcw2, tcw2, pMP2->GetWorldPos(), p2c_);
+        }
+        N = (int)mvnIndices1.size();
+        const Mat K1 = pKF1->mK, K2 = pKF2->mK;
+        problem_.fx1 = adapt::matf(K1, 0, 0); problem_.fy1 = adapt::matf(K1, 1, 1); problem_.cx1 = adapt::matf(K1, 0, 2); problem_.cy1 = adapt::matf(K1, 1, 2);
+        problem_.fx2 = adapt::matf(K2, 0, 0); problem_.fy2 = adapt::matf(K2, 1, 1); problem_.cx2 = adapt::matf(K2, 0, 2); problem_.cy2 = adapt::matf(K2, 1, 2);
+        SetRansacParameters();
+    }
+    void SetRansacParameters(double probability = 0.99, int minInliers = 6, int maxIterations = 300)
+    {
+        mRansacProb = probability; mRansacMinInliers = minInliers; maxIterations_ = maxIterations;
+        mnIterations = 0; ready_ = false; last_ = -1;
+    }
+    Mat iterate(int nIterations, bool& bNoMore, std::vector<bool>& vbInliers, int& nInliers)
+    {
+        bNoMore = false; vbInliers = std::vector<bool>(mN1, false); nInliers = 0;
+        if (N < mRansacMinInliers) { bNoMore = true; return Mat(); }
+        run();
+        const int end = std::min(mnIterations + std::max(nIterations, 0), mRansacMaxIts);
+        for (int k = 0; k < (int)events_.size(); k++) {
+            const CorbSim3RansacEvent& e = events_[k];
+            if (e.iteration <= mnIterations || e.iteration > end) continue;
+            mnIterations = e.iteration; last_ = k; nInliers = e.n_inliers;
+            for (int i = 0; i < N; i++) if (flags_[(size_t)k * N + i]) vbInliers[mvnIndices1[i]] = true;
+            float T[16] = {e.s12 * e.R12[0], e.s12 * e.R12[1], e.s12 * e.R12[2], e.t12[0], e.s12 * e.R12[3], e.s12 * e.R12[4], e.s12 * e.R12[5], e.t12[1],
+                           e.s12 * e.R12[6], e.s12 * e.R12[7], e.s12 * e.R12[8], e.t12[2], 0.f, 0.f, 0.f, 1.f};
+            return adapt::MatFactory<Mat>::from_floats(4, 4, T);
+        }
+        mnIterations = end;
+        if (mnIterations >= mRansacMaxIts) bNoMore = true;
+        return Mat();
+    }
+    Mat find(std::vector<bool>& vbInliers12, int& nInliers)
+    {
+        bool bFlag;
+        if (N >= mRansacMinInliers) run();
+        return iterate(mRansacMaxIts, bFlag, vbInliers12, nInliers);
+    }
+    // the best model so far; every caller reads them after iterate() returned a transformation, and they are that return's
+    Mat GetEstimatedRotation() { return last_ < 0 ? Mat() : adapt::MatFactory<Mat>::from_floats(3, 3, events_[last_].R12); }
+    Mat GetEstimatedTranslation() { return last_ < 0 ? Mat() : adapt::MatFactory<Mat>::from_floats(3, 1, events_[last_].t12); }
+    float GetEstimatedScale() { return last_ < 0 ? 1.0f : events_[last_].s12; }
+
+private:
+    void run()
+    {
+        if (ready_) return;
+        std::vector<int32_t> rv((size_t)std::max(maxIterations_, 0) * 3);
+        for (auto& v : rv) v = (int32_t)rnd_();
+        problem_.n = N; problem_.p1c = p1c_.data(); problem_.p2c = p2c_.data(); problem_.sigma2_1 = sigma2_1_.data(); problem_.sigma2_2 = sigma2_2_.data();
+        const int me = std::max(maxIterations_, 1); int32_t cap = 0, n_ev = 0;
+        events_.assign((size_t)me, CorbSim3RansacEvent()); flags_.assign((size_t)me * std::max(N, 1), 0);
+        check(corb_sim3_ransac(&problem_, 1, mRansacProb, mRansacMinInliers, maxIterations_, mbFixScale ? 1 : 0, rv.data(), me, std::max(N, 1), &cap, &n_ev, events_.data(),
+                               flags_.data(), nullptr, nullptr, device_), "corb_sim3_ransac");
+        mRansacMaxIts = cap; events_.resize((size_t)std::min<int>(n_ev, me)); ready_ = true;
+    }
+    int N = 0, mN1 = 0, mnIterations = 0, mRansacMinInliers = 6, mRansacMaxIts = 0, maxIterations_ = 300, last_ = -1;
+    double mRansacProb = 0.99; bool mbFixScale, ready_ = false;
+    std::vector<size_t> mvnIndices1; std::vector<float> p1c_, p2c_, sigma2_1_, sigma2_2_;
+    CorbSim3RansacProblem problem_{}; std::vector<CorbSim3RansacEvent> events_; std::vector<uint8_t> flags_;
+    RandomSource rnd_; int device_;
+};
+}  // namespace corb
+
 #if defined(__has_include)
 #if __has_include(<opencv2/core/core.hpp>) && __has_include("KeyFrame.h") && __has_include("Frame.h") && __has_include("MapPoint.h") && __has_include("Cache.h")
 #include <opencv2/core/core.hpp>
@@ -649,6 +753,7 @@ using ORBmatcher = corb::adapt::ORBmatcherT<KeyFrame, Frame, MapPoint, cv::Mat>;
 using Optimizer = corb::adapt::OptimizerT<KeyFrame, Frame, MapPoint, Cache, cv::Mat>;
 using MapStore = corb::adapt::MapStoreT<KeyFrame, MapPoint, cv::Mat>;
 using FrameStore = corb::adapt::FrameStoreT<Frame, MapPoint, cv::Mat>;
+using Sim3Solver = corb::Sim3Solver<KeyFrame, MapPoint>;
 }  // namespace accel
 }  // namespace ORB_SLAM2
 #endif

@@ -876,6 +876,47 @@ int corb_create_new_map_points_store(CorbKfStore* kf, int cur_slot, const int32_
         int only_stereo, int apply, CorbMpStore* map, int first_mp_slot, uint64_t first_mp_id, int32_t client_id,
         int32_t* pair_offset /* n_nb + 1 */, int32_t* pairs, float* x3d, uint8_t* status, uint8_t* source, int* n_new);
 
+/* ============================ Sim3Solver RANSAC (LoopClosing::ComputeSim3) =====================
+ * C/src/Sim3Solver.cc for all candidates of a loop / map-fusion event in one call: up to max_iterations hypotheses per candidate, one wavefront each -- the three
+ * draws (:163-177), ComputeSim3 (Horn on 3 points, :226-337), CheckInliers (:340-364) -- and iterate()'s stateful loop (:158-201) as a rule over the per-hypothesis
+ * inlier counts c_i: iteration i returns (an *event*) iff c_i > min_inliers and c_i >= max_{j<i} c_j.  The reference seeds rand() from the clock, so the draws are an
+ * input: rand_values = n x max_iterations x 3 results of rand() in [0, 2^31) (RAND_MAX + 1 = 2^31), consumed as DUtils::Random::RandomInt does
+ * (Thirdparty/DBoW2/DUtils/Random.cpp:47-50) with the swap-with-back removal of :175-176.
+ * Numerics: the reference's expressions as non-fused IEEE operations with the C++ types of the source; cv::eigen of the float 4x4 N = a cyclic
+ * Jacobi iteration on N in FP64 (column of the largest diagonal entry, rounded to float); atan2 + cv::Rodrigues = R = I + (2 q0 [v]x + 2 [v]x^2) / |q|^2 in double,
+ * each entry rounded once.  A hypothesis whose quaternion has a zero vector part (the reference divides 0 by 0, :280) or any non-finite R, t, s has no inliers. */
+typedef struct CorbSim3RansacProblem {          /* what the constructor (:37-112) leaves, flattened by the adapter */
+    int32_t n;                                  /* N = mvpMapPoints1.size() */
+    const float* p1c; const float* p2c;         /* n x 3: mvX3Dc1, mvX3Dc2 (:94-98) */
+    const float* sigma2_1; const float* sigma2_2;      /* n: mvLevelSigma2[kp.octave] of both sides (:84-85); the library applies 9.210 * sigma2, truncated (:87-88) */
+    float fx1, fy1, cx1, cy1, fx2, fy2, cx2, cy2;      /* mK1, mK2 (:105-106) */
+} CorbSim3RansacProblem;
+typedef struct CorbSim3RansacEvent {            /* one return of iterate() with a transformation (:192-199) */
+    int32_t iteration;                          /* mnIterations at the return, 1-based */
+    int32_t n_inliers;                          /* nInliers */
+    float R12[9], t12[3], s12;                  /* mBestRotation, mBestTranslation, mBestScale; T12 = [s12 R12 | t12] */
+} CorbSim3RansacEvent;
+/* SetRansacParameters(probability, min_inliers, max_iterations) (:114-138) + every iterate() a caller could make, per problem: ransac_max_its = mRansacMaxIts (0 with no
+ * events when n < min_inliers: bNoMore at once, :146-150); n_events = all events (may exceed max_events); events / inlier_flags = the first max_events of them, flags one
+ * byte per correspondence (mvbInliersi) in rows of flags_stride >= every n.  counts (optional, n_problems x max_iterations) = c_i, q_out (optional, x 4) = the
+ * quaternion of hypothesis i; entries from ransac_max_its on are 0.  min_inliers < 3, probability outside (0, 1), max_iterations outside [1, 65535] or a rand_values
+ * entry outside [0, 2^31): CORB_ERR_ARG, nothing written.  Host pointers; one synchronisation and one read-back per call. */
+int corb_sim3_ransac(const CorbSim3RansacProblem* problems, int n_problems, double probability, int min_inliers, int max_iterations, int fix_scale,
+                     const int32_t* rand_values /* n_problems x max_iterations x 3 */, int max_events, int flags_stride,
+                     int32_t* ransac_max_its /* n_problems */, int32_t* n_events /* n_problems */, CorbSim3RansacEvent* events /* n_problems x max_events */,
+                     uint8_t* inlier_flags /* n_problems x max_events x flags_stride */, int32_t* counts, float* q_out, int device);
+/* The same on records, constructor included (:37-112): pKF1 = record slot1 of `kf`, candidate c = record slots2[c] (not slot1), vpMatched12 of candidate c =
+ * matched12_ids[c x n(slot1) ..] as MapPoint ids (CORB_NO_MAP_POINT = NULL) -- what corb_search_by_bow_slots + the records' map-point ids give.  Feature i1 is kept when
+ * KF1 holds a MapPoint there, both ids resolve through the map's index (corb_mp_store_build_index) to records that are not bad, and GetIndexInKeyFrame finds both
+ * keyframes in the points' observation lists (:64-79); the keypoints are those at the observation indices (:81-82).  Poses and intrinsics come from the records' meta,
+ * sigma2 = scale[octave]^2 in float from cam1 / cam2[c] as CorbNewPointSide reads it.  n_corr[c] = N, index1 (optional, n_candidates x n(slot1)) = mvnIndices1 (-1 behind
+ * N); inlier_flags rows have n(slot1) bytes and are scattered through mvnIndices1: the vbInliers of iterate() (:195-197).  No record changes.  Locks as corb_fuse_store. */
+int corb_sim3_ransac_store(CorbKfStore* kf, int slot1, const int32_t* slots2, int n_candidates, CorbMpStore* map, const CorbTrackCamera* cam1,
+                           const CorbTrackCamera* cam2 /* n_candidates */, const uint64_t* matched12_ids /* n_candidates x n(slot1) */,
+                           double probability, int min_inliers, int max_iterations, int fix_scale, const int32_t* rand_values, int max_events,
+                           int32_t* ransac_max_its, int32_t* n_events, CorbSim3RansacEvent* events, uint8_t* inlier_flags /* n_candidates x max_events x n(slot1) */,
+                           int32_t* n_corr /* n_candidates */, int32_t* index1, int32_t* counts, float* q_out);
+
 #ifdef __cplusplus
 }
 #endif
