@@ -39,6 +39,7 @@ EXPORTS = [
     "corb_rgbd_frame_layout", "corb_rgbd_frames", "corb_rgbd_image_bounds", "corb_kf_store_put_from_rgbd",
     "corb_triangulate_pairs", "corb_create_new_map_points_store",
     "corb_sim3_ransac", "corb_sim3_ransac_store",
+    "corb_pnp_ransac", "corb_pnp_ransac_store",
 ]
 
 
@@ -310,6 +311,9 @@ def load():
     L.corb_create_new_map_points_store.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(TrackCamera), C.c_int, C.c_int, C.c_void_p, C.c_int,
                                                    C.c_uint64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
     L.corb_sim3_ransac.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 6 + [C.c_int]
+    L.corb_pnp_ransac.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 9 + [C.c_int]
+    L.corb_pnp_ransac_store.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(TrackCamera), C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int,
+                                        C.c_void_p, C.c_int] + [C.c_void_p] * 11
     L.corb_sim3_ransac_store.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(TrackCamera), C.c_void_p, C.c_void_p, C.c_double, C.c_int, C.c_int, C.c_int,
                                          C.c_void_p, C.c_int] + [C.c_void_p] * 8
     _lib = L
@@ -929,6 +933,140 @@ class Sim3Solver:
 
     def GetEstimatedScale(self):
         return None if self._last is None else float(self._last["s12"])
+
+
+class _PnPRansacProblem(C.Structure):
+    _fields_ = [("n", C.c_int32), ("p3dw", C.c_void_p), ("p2d", C.c_void_p), ("sigma2", C.c_void_p)] + [(k, C.c_float) for k in ("fx", "fy", "cx", "cy")]
+
+
+PNP_RECORD_DTYPE = np.dtype([("iteration", "<i4"), ("n_inliers", "<i4"), ("Tcw_best", "<f4", 12), ("n_refined", "<i4"), ("refine_ok", "<i4"),
+                             ("Tcw_refined", "<f4", 12)])                                                              # CorbPnPRansacRecord
+
+
+def PnPRansac(problems, rand_values, probability=0.99, min_inliers=8, max_iterations=300, min_set=4, epsilon=0.4, th2=5.991, tail_iterations=0, max_records=None, device=0):
+    """PnPsolver's RANSAC, Refine() included, for a list of candidates in one call (corb_pnp_ransac).  problems: dicts(p3dw [n, 3], p2d [n, 2], sigma2 [n], K = (fx, fy,
+    cx, cy)); rand_values [n_problems, max_iterations + tail_iterations, min_set] results of rand().  Returns per problem dict(ransac_max_its, ransac_min_inliers,
+    n_records, records (PNP_RECORD_DTYPE, the first max_records), best_inliers / refined_inliers [records, n] bool, counts [max_iterations + tail_iterations], pose
+    [.., 16] float64 = R[9], t[3], rep_errors[3], chosen N of every hypothesis, refine_pose [records, 16])."""
+    n = len(problems); stride_its = int(max_iterations) + int(tail_iterations)
+    max_records = stride_its if max_records is None else int(max_records)
+    arr = (_PnPRansacProblem * max(n, 1))(); keep = []
+    for c, q in enumerate(problems):
+        a = [np.ascontiguousarray(q[k], np.float32) for k in ("p3dw", "p2d", "sigma2")]
+        keep.append(a)
+        arr[c] = _PnPRansacProblem(len(a[2]), *[_p(x) for x in a], *[float(np.float32(v)) for v in q["K"]])
+    stride = max([len(a[2]) for a in keep] + [1])
+    rv = np.ascontiguousarray(rand_values, np.int32).reshape(-1)
+    assert len(rv) == n * stride_its * min_set
+    n1, r1 = max(n, 1), max(max_records, 1)
+    cap = np.zeros(n1, np.int32); mi = np.zeros(n1, np.int32); n_rec = np.zeros(n1, np.int32); rec = np.zeros((n1, r1), PNP_RECORD_DTYPE)
+    bf = np.zeros((n1, r1, stride), np.uint8); rf = np.zeros((n1, r1, stride), np.uint8); cnt = np.zeros((n1, max(stride_its, 1)), np.int32)
+    po = np.zeros((n1, max(stride_its, 1), 16), np.float64); rpo = np.zeros((n1, r1, 16), np.float64)
+    _chk(load().corb_pnp_ransac(C.cast(arr, C.c_void_p), n, float(probability), int(min_inliers), int(max_iterations), int(min_set), float(epsilon), float(th2),
+                                int(tail_iterations), _p(rv), max_records, stride, _p(cap), _p(mi), _p(n_rec), _p(rec), _p(bf), _p(rf), _p(cnt), _p(po), _p(rpo), device),
+         "corb_pnp_ransac")
+    out = []
+    for c in range(n):
+        k = min(int(n_rec[c]), max_records); nc = len(keep[c][2])
+        out.append(_pnp_ransac_result(c, k, nc, cap, mi, n_rec, rec, bf, rf, cnt, po, rpo))
+    return out
+
+
+def _pnp_ransac_result(c, k, nc, cap, mi, n_rec, rec, bf, rf, cnt, po, rpo):
+    return dict(ransac_max_its=int(cap[c]), ransac_min_inliers=int(mi[c]), n_records=int(n_rec[c]), records=rec[c, :k].copy(), best_inliers=bf[c, :k, :nc].astype(bool),
+                refined_inliers=rf[c, :k, :nc].astype(bool), counts=cnt[c].copy(), pose=po[c].copy(), refine_pose=rpo[c, :k].copy())
+
+
+def PnPRansacStore(frames, slot, mp_store, cam, matched_ids, rand_values, probability=0.99, min_inliers=8, max_iterations=300, min_set=4, epsilon=0.4, th2=5.991,
+                   tail_iterations=0, max_records=None):
+    """PnPsolver's constructor, RANSAC and Refine() on records (corb_pnp_ransac_store): the frame = record `slot` of the KeyFrameStore `frames`, matched_ids [n_candidates,
+    n(slot)] = one row of vvpMapPointMatches per candidate as MapPoint ids.  Returns per candidate what PnPRansac returns (both inlier sets per feature of the frame =
+    vbInliers) plus n_corr and index = mvKeyPointIndices."""
+    n1 = load().corb_kf_store_count(frames.h, int(slot))          # the host-known count: an empty slot (-1) is the library's error to report
+    ids = np.ascontiguousarray(matched_ids, np.uint64); ids = ids.reshape(len(ids), -1); n = len(ids)
+    assert n == 0 or n1 <= 0 or ids.shape[1] == n1
+    stride_its = int(max_iterations) + int(tail_iterations); max_records = stride_its if max_records is None else int(max_records)
+    rv = np.ascontiguousarray(rand_values, np.int32).reshape(-1)
+    assert len(rv) == n * stride_its * min_set
+    nn, r1, s1 = max(n, 1), max(max_records, 1), max(n1, 1)
+    cap = np.zeros(nn, np.int32); mi = np.zeros(nn, np.int32); n_rec = np.zeros(nn, np.int32); rec = np.zeros((nn, r1), PNP_RECORD_DTYPE)
+    bf = np.zeros((nn, r1, s1), np.uint8); rf = np.zeros((nn, r1, s1), np.uint8); cnt = np.zeros((nn, max(stride_its, 1)), np.int32)
+    po = np.zeros((nn, max(stride_its, 1), 16), np.float64); rpo = np.zeros((nn, r1, 16), np.float64); ncorr = np.zeros(nn, np.int32); index = np.full((nn, s1), -1, np.int32)
+    _chk(load().corb_pnp_ransac_store(frames.h, int(slot), mp_store.h, C.byref(cam), _p(ids), n, float(probability), int(min_inliers), int(max_iterations), int(min_set),
+                                      float(epsilon), float(th2), int(tail_iterations), _p(rv), max_records, _p(cap), _p(mi), _p(n_rec), _p(rec), _p(bf), _p(rf), _p(ncorr),
+                                      _p(index), _p(cnt), _p(po), _p(rpo)), "corb_pnp_ransac_store")
+    out = []
+    for c in range(n):
+        r = _pnp_ransac_result(c, min(int(n_rec[c]), max_records), n1, cap, mi, n_rec, rec, bf, rf, cnt, po, rpo)
+        r["n_corr"] = int(ncorr[c]); r["index"] = index[c, : ncorr[c]].copy()
+        out.append(r)
+    return out
+
+
+def pnp_replay(counts, records, m, cap, s, n_iterations):
+    """iterate()'s loop (C/src/PnPsolver.cc:227-300) as a function of what corb_pnp_ransac returns: counts = c_i of the evaluated hypotheses, records = the call's records,
+    m = ransac_min_inliers, cap = ransac_max_its, s = mnIterations before the call.  Returns (kind, record index or None, mnIterations after): kind 'refined' = the
+    refined pose of that record, 'best' = bNoMore with its unrefined pose, None = bNoMore with an empty Mat.  The call returns at the first i >= s with c_i >= m whose
+    last record at or before i is ok, else at max(cap, s + n_iterations) -- or where the evaluated hypotheses end."""
+    end = min(max(cap, s + int(n_iterations)), len(counts))
+    its = [int(r["iteration"]) - 1 for r in records]
+    b = -1
+    for i in range(end):
+        if b + 1 < len(its) and its[b + 1] == i:
+            b += 1
+        if i >= s and counts[i] >= m and b >= 0 and records[b]["refine_ok"]:
+            return "refined", b, i + 1
+    return ("best" if b >= 0 else None), (b if b >= 0 else None), max(end, s)
+
+
+class PnPsolver:
+    """PnPsolver (C/include/PnPsolver.h) over corb_pnp_ransac: one library call evaluates every hypothesis and every Refine(), then iterate() is replayed by pnp_replay.  The
+    constructor takes what the reference's leaves (:67-110): mvP3Dw, mvP2D, mvSigma2 and (fx, fy, cx, cy); indices / n_matches = mvKeyPointIndices /
+    mvpMapPointMatches.size() scatter vbInliers as :274-279 do (default: the correspondences themselves).  The draws are an argument: rand_values [>= maxIterations +
+    tail, minSet] results of rand() in [0, 2^31), or a seeded numpy.random.RandomState.  mRansacMaxIts + tail_iterations hypotheses are evaluated: the reference's loop
+    runs on behind the cap for as long as it is called (:227), here iterate() reports bNoMore once the evaluated hypotheses run out."""
+
+    def __init__(self, p3dw, p2d, sigma2, K, indices=None, n_matches=None, rand_values=None, seed=0, tail_iterations=0, device=0):
+        self.problem = dict(p3dw=np.ascontiguousarray(p3dw, np.float32).reshape(-1, 3), p2d=np.ascontiguousarray(p2d, np.float32).reshape(-1, 2),
+                            sigma2=np.ascontiguousarray(sigma2, np.float32).reshape(-1), K=tuple(K))
+        self.N = len(self.problem["sigma2"]); self.device = device; self._tail = int(tail_iterations)
+        self.mvKeyPointIndices = np.arange(self.N) if indices is None else np.asarray(indices, np.int64)
+        self._n_matches = int(n_matches) if n_matches is not None else (self.N if indices is None else int(self.mvKeyPointIndices.max(initial=-1)) + 1)
+        self._rand = rand_values; self._seed = seed
+        self.SetRansacParameters()
+
+    def SetRansacParameters(self, probability=0.99, minInliers=8, maxIterations=300, minSet=4, epsilon=0.4, th2=5.991):
+        self._par = (float(probability), int(minInliers), int(maxIterations), int(minSet), float(epsilon), float(th2))
+        self.mnIterations = 0; self._res = None
+
+    def _run(self):
+        if self._res is None:
+            pr, mi, its, ms, eps, th2 = self._par; total = its + self._tail
+            rv = self._rand if self._rand is not None else np.random.RandomState(self._seed).randint(0, 2 ** 31, (total, ms))
+            rv = np.ascontiguousarray(rv, np.int32).reshape(-1, ms)[:total]
+            self._res = PnPRansac([self.problem], rv[None], pr, mi, its, ms, eps, th2, self._tail, device=self.device)[0]
+            self.mRansacMaxIts = self._res["ransac_max_its"]; self.mRansacMinInliers = self._res["ransac_min_inliers"]
+        return self._res
+
+    def iterate(self, nIterations):
+        """-> (Tcw 4x4 float32 or None, bNoMore, vbInliers [mvpMapPointMatches.size()] bool, nInliers)"""
+        vbInliers = np.zeros(self._n_matches, bool)
+        r = self._run()
+        if r["ransac_max_its"] == 0:                                    # N < mRansacMinInliers (:218-222)
+            return None, True, vbInliers, 0
+        evaluated = r["ransac_max_its"] + self._tail
+        kind, b, self.mnIterations = pnp_replay(r["counts"][:evaluated], r["records"], r["ransac_min_inliers"], r["ransac_max_its"], self.mnIterations, nIterations)
+        if kind is None:
+            return None, True, vbInliers, 0
+        e = r["records"][b]; refined = kind == "refined"
+        vbInliers[self.mvKeyPointIndices[r["refined_inliers" if refined else "best_inliers"][b]]] = True
+        T = np.eye(4, dtype=np.float32); T[:3] = e["Tcw_refined" if refined else "Tcw_best"].reshape(3, 4)
+        return T, not refined, vbInliers, int(e["n_refined" if refined else "n_inliers"])
+
+    def find(self):
+        """-> (Tcw or None, vbInliers, nInliers)"""
+        T, _, vb, n = self.iterate(self._run()["ransac_max_its"])
+        return T, vb, n
 
 
 def spd_solve(A, b, device=0):

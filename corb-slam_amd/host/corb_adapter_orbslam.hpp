@@ -737,6 +737,119 @@ private:
 };
 }  // namespace corb
 
+// ---- PnPsolver (corbslam_client/include/PnPsolver.h) over corb_pnp_ransac ----
+// The reference's constructors (over a Frame, C/src/PnPsolver.cc:67-110, and over a KeyFrame, :112-155) and method signatures.  The constructor flattens as the
+// reference's does (vpMapPointMatches[i] non-NULL and not bad; mvKeysUn[i].pt, mvLevelSigma2[octave], GetWorldPos(), fx / fy / cx / cy).  The first iterate() pre-draws
+// (maxIterations + tail_iterations) x minSet values from the random source (a callable returning rand()'s range [0, 2^31)), makes ONE library call that evaluates
+// every hypothesis and every Refine(), and iterate() is then replayed by corb::pnp_replay.  The reference's loop runs on behind mRansacMaxIts for as long as it is
+// called (:227); here mRansacMaxIts + tail_iterations hypotheses exist and iterate() reports bNoMore once they run out.  PnPsolver::RunBatch evaluates all candidates
+// of a relocalisation in one call.  Mat = the type MapPoint::GetWorldPos() returns.
+namespace corb {
+template <class Frame, class KeyFrame, class MapPoint>
+class PnPsolver {
+public:
+    using Mat = decltype(std::declval<MapPoint&>().GetWorldPos());
+    using RandomSource = std::function<int()>;
+    PnPsolver(const Frame& F, const std::vector<MapPoint*>& vpMapPointMatches, RandomSource rnd = [] { return std::rand(); }, int tail_iterations = 0, int device = 0)
+        : rnd_(std::move(rnd)), tail_(tail_iterations), device_(device) { init(F, vpMapPointMatches); }
+    PnPsolver(const KeyFrame& F, const std::vector<MapPoint*>& vpMapPointMatches, RandomSource rnd = [] { return std::rand(); }, int tail_iterations = 0, int device = 0)
+        : rnd_(std::move(rnd)), tail_(tail_iterations), device_(device) { init(F, vpMapPointMatches); }
+    void SetRansacParameters(double probability = 0.99, int minInliers = 8, int maxIterations = 300, int minSet = 4, float epsilon = 0.4, float th2 = 5.991)
+    {
+        mRansacProb = probability; minInliers_ = minInliers; maxIterations_ = maxIterations; mRansacMinSet = minSet; epsilon_ = epsilon; th2_ = th2;
+        mnIterations = 0; ready_ = false;
+    }
+    Mat iterate(int nIterations, bool& bNoMore, std::vector<bool>& vbInliers, int& nInliers)
+    {
+        RunBatch({this});
+        bNoMore = false; vbInliers.clear(); nInliers = 0;
+        if (mRansacMaxIts == 0) { bNoMore = true; return Mat(); }                 // N < mRansacMinInliers (:218-222)
+        const PnPReplay r = pnp_replay(counts_.data(), mRansacMaxIts + tail_, records_.data(), (int)records_.size(), mRansacMinInliers, mRansacMaxIts, mnIterations, nIterations);
+        mnIterations = r.iterations;
+        if (r.kind == PnPReplay::None) { bNoMore = true; return Mat(); }
+        const bool refined = r.kind == PnPReplay::Refined;
+        const CorbPnPRansacRecord& e = records_[r.record];
+        bNoMore = !refined; nInliers = refined ? e.n_refined : e.n_inliers;
+        vbInliers = std::vector<bool>(n_matches_, false);
+        const uint8_t* fl = (refined ? refined_flags_ : best_flags_).data() + (size_t)r.record * std::max(N, 1);
+        for (int i = 0; i < N; i++) if (fl[i]) vbInliers[mvKeyPointIndices[i]] = true;
+        const float* T = refined ? e.Tcw_refined : e.Tcw_best;
+        const float T16[16] = {T[0], T[1], T[2], T[3], T[4], T[5], T[6], T[7], T[8], T[9], T[10], T[11], 0.f, 0.f, 0.f, 1.f};
+        return adapt::MatFactory<Mat>::from_floats(4, 4, T16);
+    }
+    Mat find(std::vector<bool>& vbInliers, int& nInliers)
+    {
+        bool bFlag;
+        RunBatch({this});
+        return iterate(mRansacMaxIts, bFlag, vbInliers, nInliers);
+    }
+    // every solver of `solvers` that has not run yet, in ONE corb_pnp_ransac call per set of equal parameters (Tracking::Relocalization: all candidate keyframes)
+    static void RunBatch(const std::vector<PnPsolver*>& solvers)
+    {
+        std::vector<PnPsolver*> todo;
+        for (PnPsolver* s : solvers) if (s && !s->ready_) todo.push_back(s);
+        while (!todo.empty()) {
+            PnPsolver* h = todo.front(); std::vector<PnPsolver*> grp, rest;
+            for (PnPsolver* s : todo)
+                (s->mRansacProb == h->mRansacProb && s->minInliers_ == h->minInliers_ && s->maxIterations_ == h->maxIterations_ && s->mRansacMinSet == h->mRansacMinSet &&
+                 s->epsilon_ == h->epsilon_ && s->th2_ == h->th2_ && s->tail_ == h->tail_ && s->device_ == h->device_ ? grp : rest).push_back(s);
+            const int n = (int)grp.size(), stride_its = std::max(h->maxIterations_, 0) + std::max(h->tail_, 0), me = std::max(stride_its, 1);
+            std::vector<CorbPnPRansacProblem> pr((size_t)n); std::vector<int32_t> rv((size_t)n * stride_its * std::max(h->mRansacMinSet, 0));
+            int stride = 1;
+            for (int c = 0; c < n; c++) {
+                PnPsolver* s = grp[c];
+                for (size_t k = 0; k < (size_t)stride_its * std::max(h->mRansacMinSet, 0); k++) rv[(size_t)c * stride_its * h->mRansacMinSet + k] = (int32_t)s->rnd_();
+                pr[c].n = s->N; pr[c].p3dw = s->p3dw_.data(); pr[c].p2d = s->p2d_.data(); pr[c].sigma2 = s->sigma2_.data();
+                pr[c].fx = s->fx_; pr[c].fy = s->fy_; pr[c].cx = s->cx_; pr[c].cy = s->cy_;
+                stride = std::max(stride, s->N);
+            }
+            std::vector<int32_t> cap((size_t)n), mi((size_t)n), n_rec((size_t)n), counts((size_t)n * me);
+            std::vector<CorbPnPRansacRecord> rec((size_t)n * me); std::vector<uint8_t> bf((size_t)n * me * stride), rf((size_t)n * me * stride);
+            check(corb_pnp_ransac(pr.data(), n, h->mRansacProb, h->minInliers_, h->maxIterations_, h->mRansacMinSet, h->epsilon_, h->th2_, h->tail_, rv.data(), me, stride,
+                                  cap.data(), mi.data(), n_rec.data(), rec.data(), bf.data(), rf.data(), counts.data(), nullptr, nullptr, h->device_), "corb_pnp_ransac");
+            for (int c = 0; c < n; c++) {
+                PnPsolver* s = grp[c]; const int k = std::min<int>(n_rec[c], me), w = std::max(s->N, 1);
+                s->mRansacMaxIts = cap[c]; s->mRansacMinInliers = mi[c];
+                s->counts_.assign(counts.begin() + (size_t)c * me, counts.begin() + (size_t)(c + 1) * me);
+                s->records_.assign(rec.begin() + (size_t)c * me, rec.begin() + (size_t)c * me + k);
+                s->best_flags_.assign((size_t)k * w, 0); s->refined_flags_.assign((size_t)k * w, 0);
+                for (int r = 0; r < k; r++)
+                    for (int i = 0; i < s->N; i++) {
+                        s->best_flags_[(size_t)r * w + i] = bf[((size_t)c * me + r) * stride + i]; s->refined_flags_[(size_t)r * w + i] = rf[((size_t)c * me + r) * stride + i];
+                    }
+                s->ready_ = true;
+            }
+            todo.swap(rest);
+        }
+    }
+
+private:
+    template <class F> void init(const F& frame, const std::vector<MapPoint*>& vpMapPointMatches)
+    {
+        check_abi();
+        n_matches_ = vpMapPointMatches.size();
+        for (size_t i = 0, iend = vpMapPointMatches.size(); i < iend; i++) {
+            MapPoint* pMP = vpMapPointMatches[i];
+            if (!pMP || pMP->isBad()) continue;
+            const auto& kp = frame.mvKeysUn[i];
+            p2d_.push_back(kp.pt.x); p2d_.push_back(kp.pt.y);
+            sigma2_.push_back(frame.mvLevelSigma2[kp.octave]);
+            const Mat Pos = pMP->GetWorldPos();
+            for (int k = 0; k < 3; k++) p3dw_.push_back(adapt::matf(Pos, k));
+            mvKeyPointIndices.push_back(i);
+        }
+        N = (int)mvKeyPointIndices.size();
+        fx_ = frame.fx; fy_ = frame.fy; cx_ = frame.cx; cy_ = frame.cy;
+        SetRansacParameters();
+    }
+    int N = 0, mnIterations = 0, mRansacMinInliers = 0, mRansacMaxIts = 0, mRansacMinSet = 4, minInliers_ = 8, maxIterations_ = 300;
+    double mRansacProb = 0.99; float epsilon_ = 0.4f, th2_ = 5.991f, fx_ = 0, fy_ = 0, cx_ = 0, cy_ = 0; bool ready_ = false; size_t n_matches_ = 0;
+    std::vector<size_t> mvKeyPointIndices; std::vector<float> p3dw_, p2d_, sigma2_;
+    std::vector<int32_t> counts_; std::vector<CorbPnPRansacRecord> records_; std::vector<uint8_t> best_flags_, refined_flags_;
+    RandomSource rnd_; int tail_, device_;
+};
+}  // namespace corb
+
 #if defined(__has_include)
 #if __has_include(<opencv2/core/core.hpp>) && __has_include("KeyFrame.h") && __has_include("Frame.h") && __has_include("MapPoint.h") && __has_include("Cache.h")
 #include <opencv2/core/core.hpp>
@@ -754,6 +867,7 @@ using Optimizer = corb::adapt::OptimizerT<KeyFrame, Frame, MapPoint, Cache, cv::
 using MapStore = corb::adapt::MapStoreT<KeyFrame, MapPoint, cv::Mat>;
 using FrameStore = corb::adapt::FrameStoreT<Frame, MapPoint, cv::Mat>;
 using Sim3Solver = corb::Sim3Solver<KeyFrame, MapPoint>;
+using PnPsolver = corb::PnPsolver<Frame, KeyFrame, MapPoint>;
 }  // namespace accel
 }  // namespace ORB_SLAM2
 #endif

@@ -12,6 +12,7 @@
 // corb_adapter_opencv.hpp layers the exact cv::/KeyFrame signatures on top of this where OpenCV exists.
 #pragma once
 #include <corb_accel.h>
+#include <algorithm>
 #include <cstdint>
 #include <stdexcept>
 #include <string>
@@ -447,4 +448,19 @@ inline std::vector<int32_t> ComputeDistinctiveDescriptors(const std::vector<uint
 inline void RebaseMap(const float To2n[16], std::vector<float>& Tcw, std::vector<float>& worldPos, int device = 0)
 { check(corb_rebase_map(To2n, Tcw.data(), (int)(Tcw.size() / 16), worldPos.data(), (int)(worldPos.size() / 3), device), "corb_rebase_map"); }
 
+// iterate()'s loop (C/src/PnPsolver.cc:227-300) as a function of what corb_pnp_ransac returns for one problem -- the one C++ statement of the replay rule (Python:
+// pnp_replay).  counts = c_i of the n_counts evaluated hypotheses, records = the call's records (all n_records of them), m = ransac_min_inliers, cap = ransac_max_its,
+// s = mnIterations before the call.  The call returns at the first i >= s with c_i >= m whose last record at or before i has refine_ok, else at
+// max(cap, s + nIterations) -- or where the evaluated hypotheses end -- with bNoMore and the last record's unrefined pose, if there is one.
+struct PnPReplay { enum Kind { None, Best, Refined } kind; int record; int iterations; };
+inline PnPReplay pnp_replay(const int32_t* counts, int n_counts, const CorbPnPRansacRecord* records, int n_records, int m, int cap, int s, int nIterations)
+{
+    const int end = std::min(std::max(cap, s + std::max(nIterations, 0)), n_counts);
+    int b = -1;
+    for (int i = 0; i < end; i++) {
+        if (b + 1 < n_records && records[b + 1].iteration - 1 == i) b++;
+        if (i >= s && counts[i] >= m && b >= 0 && records[b].refine_ok) return {PnPReplay::Refined, b, i + 1};
+    }
+    return {b >= 0 ? PnPReplay::Best : PnPReplay::None, b, std::max(end, s)};
+}
 }  // namespace corb

@@ -917,6 +917,60 @@ int corb_sim3_ransac_store(CorbKfStore* kf, int slot1, const int32_t* slots2, in
                            int32_t* ransac_max_its, int32_t* n_events, CorbSim3RansacEvent* events, uint8_t* inlier_flags /* n_candidates x max_events x n(slot1) */,
                            int32_t* n_corr /* n_candidates */, int32_t* index1, int32_t* counts, float* q_out);
 
+/* ============================ PnPsolver RANSAC (Tracking::Relocalization, MapFusion) ============
+ * C/src/PnPsolver.cc for all candidates of a relocalisation / map-fusion step in one call: per candidate mRansacMaxIts + tail_iterations hypotheses, one wavefront each
+ * -- the min_set draws (:233-246), EPnP's compute_pose (:522-570) and CheckInliers (:353-384) -- then Refine() (:305-350) for every hypothesis that changes the running
+ * best, and iterate()'s state (:210-303) as a rule over the per-hypothesis inlier counts c_i, with m = mRansacMinInliers after SetRansacParameters' adjustment:
+ * iteration i is a *record* iff c_i >= m and c_i > every earlier c_j >= m; b(i) = the last record at or before i; Refine() depends only on the record and is ok iff its
+ * own count is > m; iteration i returns the refined pose of b(i) iff c_i >= m and b(i) is ok (a later non-record i returns the same pose again).  The loop condition of
+ * :227 is an OR: a call from mnIterations = s runs to an event or to max(mRansacMaxIts, s + nIterations), where it sets bNoMore and returns the last record's unrefined
+ * pose if there is one (:286-300) -- hence tail_iterations, the hypotheses evaluated behind the cap.  corb::pnp_replay (host/corb_host.hpp) states that rule.
+ * The reference seeds rand() from the clock, so the draws are an input: rand_values = per problem (max_iterations + tail_iterations) x min_set results of rand() in
+ * [0, 2^31), consumed as DUtils::Random::RandomInt does, with the swap-with-back removal of :244-245.
+ * Numerics (csrc/pnp_math.h is the text, tests/pnpsolver_reference.py the definition): the source's double expressions, unfused, sums over
+ * correspondences in ascending order; cvSVD of the symmetric PW0tPW0 and MtM = a cyclic Jacobi eigen-iteration in FP64; cvInvert / cvSolve(CV_SVD) / cvSVD(ABt) = a
+ * one-sided Jacobi SVD in FP64 whose terms with w_k <= 2 DBL_EPSILON sum_j w_j are dropped.  NaN and infinity flow through as in the source: such a hypothesis has no
+ * inliers because error2 < mvMaxError is false. */
+typedef struct CorbPnPRansacProblem {           /* what the constructor (:67-110) leaves */
+    int32_t n;                                  /* N = mvP2D.size() */
+    const float* p3dw;                          /* n x 3: mvP3Dw */
+    const float* p2d;                           /* n x 2: mvP2D (mvKeysUn[i].pt) */
+    const float* sigma2;                        /* n: mvSigma2; the library applies mvMaxError = sigma2 * th2 (:199-201) */
+    float fx, fy, cx, cy;                       /* fu, fv, uc, vc (:104-107) */
+} CorbPnPRansacProblem;
+typedef struct CorbPnPRansacRecord {            /* one change of the running best (:257-269) and its Refine() (:305-350) */
+    int32_t iteration;                          /* mnIterations at the change, 1-based */
+    int32_t n_inliers;                          /* mnBestInliers */
+    float Tcw_best[12];                         /* rows 0-2 of mBestTcw: the convertTo(CV_32F) of :262-268 */
+    int32_t n_refined;                          /* mnRefinedInliers */
+    int32_t refine_ok;                          /* Refine()'s return: n_refined > mRansacMinInliers */
+    float Tcw_refined[12];                      /* rows 0-2 of mRefinedTcw (written whatever refine_ok is) */
+} CorbPnPRansacRecord;
+/* SetRansacParameters(probability, min_inliers, max_iterations, min_set, epsilon, th2) (:166-202) + everything iterate() could return, per problem: ransac_max_its =
+ * mRansacMaxIts (0 with no records when n < ransac_min_inliers: bNoMore at once, :218-222), ransac_min_inliers = the adjusted mRansacMinInliers; hypotheses
+ * 0 .. ransac_max_its + tail_iterations - 1 are evaluated.  n_records = all records (may exceed max_records); records / best_flags / refined_flags = the first
+ * max_records of them, flags one byte per correspondence (mvbBestInliers, mvbRefinedInliers) in rows of flags_stride >= every n.  counts (optional, n_problems x
+ * (max_iterations + tail_iterations)) = c_i; pose_out (optional, x 16 doubles) = R[9], t[3], rep_errors[1..3] and the chosen N of hypothesis i; refine_pose_out
+ * (optional, n_problems x max_records x 16) = the same of each record's Refine(); entries behind the evaluated hypotheses / records are 0.  min_set outside 4..8,
+ * min_inliers < min_set, probability outside (0, 1), epsilon outside (0, 1], max_iterations outside [1, 65535], tail_iterations outside [0, 65535] or a rand_values entry
+ * outside [0, 2^31): CORB_ERR_ARG, nothing written.  Host pointers; three launches, one synchronisation and one read-back per call. */
+int corb_pnp_ransac(const CorbPnPRansacProblem* problems, int n_problems, double probability, int min_inliers, int max_iterations, int min_set, float epsilon, float th2,
+                    int tail_iterations, const int32_t* rand_values /* n_problems x (max_iterations + tail_iterations) x min_set */, int max_records, int flags_stride,
+                    int32_t* ransac_max_its /* n_problems */, int32_t* ransac_min_inliers /* n_problems */, int32_t* n_records /* n_problems */,
+                    CorbPnPRansacRecord* records /* n_problems x max_records */, uint8_t* best_flags /* n_problems x max_records x flags_stride */,
+                    uint8_t* refined_flags /* the same */, int32_t* counts, double* pose_out, double* refine_pose_out, int device);
+/* The same on records, constructor included (:67-110 over a Frame, :112-155 over a KeyFrame): the frame = record `slot` of `frames`, one candidate per row of
+ * vvpMapPointMatches: matched_ids[c x n(slot) ..] as MapPoint ids (CORB_NO_MAP_POINT = NULL) -- what corb_search_by_bow_slots + the candidate records' map-point ids give.
+ * Feature i is kept when its id resolves through the map's index (corb_mp_store_build_index) to a record that is not bad; mvP2D = mvKeysUn[i].pt of the frame record,
+ * mvSigma2 = scale[octave]^2 in float from cam, mvP3Dw = the map-point record's world position, fu, fv, uc, vc = the frame record's meta.  n_corr[c] = N, index (optional,
+ * n_candidates x n(slot)) = mvKeyPointIndices (-1 behind N); both flag sets have rows of n(slot) bytes and are scattered through mvKeyPointIndices: the vbInliers of
+ * iterate() (:274-279, :292-297).  Five launches (prepare, scan, compaction, hypotheses, Refine).  No record changes.  Locks as corb_sim3_ransac_store. */
+int corb_pnp_ransac_store(CorbKfStore* frames, int slot, CorbMpStore* map, const CorbTrackCamera* cam, const uint64_t* matched_ids /* n_candidates x n(slot) */,
+                          int n_candidates, double probability, int min_inliers, int max_iterations, int min_set, float epsilon, float th2, int tail_iterations,
+                          const int32_t* rand_values, int max_records, int32_t* ransac_max_its, int32_t* ransac_min_inliers, int32_t* n_records,
+                          CorbPnPRansacRecord* records, uint8_t* best_flags /* n_candidates x max_records x n(slot) */, uint8_t* refined_flags,
+                          int32_t* n_corr /* n_candidates */, int32_t* index, int32_t* counts, double* pose_out, double* refine_pose_out);
+
 #ifdef __cplusplus
 }
 #endif
