@@ -40,6 +40,7 @@ EXPORTS = [
     "corb_triangulate_pairs", "corb_create_new_map_points_store",
     "corb_sim3_ransac", "corb_sim3_ransac_store",
     "corb_pnp_ransac", "corb_pnp_ransac_store",
+    "corb_mono_initialize",
 ]
 
 
@@ -316,6 +317,7 @@ def load():
                                         C.c_void_p, C.c_int] + [C.c_void_p] * 11
     L.corb_sim3_ransac_store.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(TrackCamera), C.c_void_p, C.c_void_p, C.c_double, C.c_int, C.c_int, C.c_int,
                                          C.c_void_p, C.c_int] + [C.c_void_p] * 8
+    L.corb_mono_initialize.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 6 + [C.c_int]
     _lib = L
     return L
 
@@ -1067,6 +1069,66 @@ class PnPsolver:
         """-> (Tcw or None, vbInliers, nInliers)"""
         T, _, vb, n = self.iterate(self._run()["ransac_max_its"])
         return T, vb, n
+
+
+class _InitProblem(C.Structure):
+    _fields_ = [("keys1", C.c_void_p), ("n1", C.c_int32), ("keys2", C.c_void_p), ("n2", C.c_int32), ("matches12", C.c_void_p)] + [(k, C.c_float) for k in ("fx", "fy", "cx", "cy")]
+
+
+INIT_RESULT_DTYPE = np.dtype([("status", "<i4"), ("model", "<i4"), ("n_matches", "<i4"), ("score_h", "<f4"), ("score_f", "<f4"), ("rh", "<f4"), ("best_it_h", "<i4"),
+                              ("best_it_f", "<i4"), ("H21", "<f4", 9), ("F21", "<f4", 9), ("n_inliers", "<i4"), ("n_good", "<i4", 8), ("cos_parallax", "<f4", 8),
+                              ("parallax", "<f4", 8), ("best_hypothesis", "<i4"), ("second_best_good", "<i4"), ("R21", "<f4", 9), ("t21", "<f4", 3),
+                              ("n_triangulated", "<i4")])                                                             # CorbInitResult
+INIT_OK, INIT_NO_MODEL, INIT_H_DEGENERATE, INIT_AMBIGUOUS, INIT_FEW_POINTS, INIT_LOW_PARALLAX = range(6)                # CORB_INIT_*
+
+
+def _keys(k):
+    """keypoints as KP_DTYPE records: a KP_DTYPE array, or [n, 2] coordinates"""
+    k = np.asarray(k)
+    if k.dtype == KP_DTYPE:
+        return np.ascontiguousarray(k)
+    out = np.zeros(len(k), KP_DTYPE); xy = np.asarray(k, np.float32).reshape(-1, 2)
+    out["x"] = xy[:, 0]; out["y"] = xy[:, 1]
+    return out
+
+
+def MonoInitialize(problems, rand_values, sigma=1.0, max_iterations=200, min_parallax=1.0, min_triangulated=50, p3d_stride=None, flags_stride=None, device=0):
+    """Initializer::Initialize for a list of (reference, current) pairs in one call (corb_mono_initialize).  problems: dicts(keys1, keys2 (KP_DTYPE or [n, 2]), matches12
+    [n1], K = (fx, fy, cx, cy)); rand_values [n_problems, max_iterations, 8] results of rand().  Returns per problem dict(result (INIT_RESULT_DTYPE record), p3d [n1, 3],
+    triangulated [n1] bool, inliers_h / inliers_f [N] bool, scores [max_iterations, 2], raw = the call's rows of p3d_stride / flags_stride entries before that slicing)."""
+    n = len(problems); arr = (_InitProblem * max(n, 1))(); keep = []
+    for c, q in enumerate(problems):
+        a = (_keys(q["keys1"]), _keys(q["keys2"]), np.ascontiguousarray(q["matches12"], np.int32))
+        keep.append(a)
+        arr[c] = _InitProblem(_p(a[0]), len(a[0]), _p(a[1]), len(a[1]), _p(a[2]), *[float(np.float32(v)) for v in q["K"]])
+    Ns = [int((a[2] >= 0).sum()) for a in keep]
+    ps = max([len(a[0]) for a in keep] + [1]) if p3d_stride is None else int(p3d_stride)
+    fs = max(Ns + [1]) if flags_stride is None else int(flags_stride)
+    rv = np.ascontiguousarray(rand_values, np.int32).reshape(-1)
+    assert len(rv) == n * int(max_iterations) * 8
+    n1 = max(n, 1)
+    res = np.zeros(n1, INIT_RESULT_DTYPE); p3d = np.zeros((n1, ps, 3), np.float32); tri = np.zeros((n1, ps), np.uint8)
+    ih = np.zeros((n1, fs), np.uint8); i_f = np.zeros((n1, fs), np.uint8); sc = np.zeros((n1, int(max_iterations), 2), np.float32)
+    _chk(load().corb_mono_initialize(C.cast(arr, C.c_void_p), n, float(sigma), int(max_iterations), float(min_parallax), int(min_triangulated), _p(rv), ps, fs, _p(res), _p(p3d),
+                                     _p(tri), _p(ih), _p(i_f), _p(sc), device), "corb_mono_initialize")
+    return [dict(result=res[c].copy(), p3d=p3d[c, :len(keep[c][0])].copy(), triangulated=tri[c, :len(keep[c][0])].astype(bool), inliers_h=ih[c, :Ns[c]].astype(bool),
+                 inliers_f=i_f[c, :Ns[c]].astype(bool), scores=sc[c].copy(), raw=dict(p3d=p3d[c], triangulated=tri[c], inliers_h=ih[c], inliers_f=i_f[c])) for c in range(n)]
+
+
+class Initializer:
+    """Initializer (C/include/Initializer.h) over corb_mono_initialize.  keys1 = ReferenceFrame.mvKeysUn, K = (fx, fy, cx, cy).  The draws are an argument of Initialize:
+    rand_values [iterations, 8] results of rand() in [0, 2^31) (the reference's stream is shared with every other RANSAC of the process)."""
+
+    def __init__(self, keys1, K, sigma=1.0, iterations=200, device=0):
+        self.mvKeys1 = _keys(keys1); self.mK = tuple(K); self.mSigma = float(sigma); self.mMaxIterations = int(iterations); self.device = device
+        self.last = None
+
+    def Initialize(self, keys2, matches12, rand_values):
+        """-> (ok, R21 [3, 3], t21 [3], vP3D [n1, 3], vbTriangulated [n1] bool); self.last = everything MonoInitialize returns"""
+        r = MonoInitialize([dict(keys1=self.mvKeys1, keys2=keys2, matches12=matches12, K=self.mK)], np.asarray(rand_values)[None], self.mSigma, self.mMaxIterations, 1.0, 50,
+                           device=self.device)[0]
+        self.last = r; e = r["result"]
+        return bool(e["status"] == INIT_OK), e["R21"].reshape(3, 3).copy(), e["t21"].copy(), r["p3d"], r["triangulated"]
 
 
 def spd_solve(A, b, device=0):

@@ -10,6 +10,7 @@
 //   void Optimizer::GlobalBundleAdjustemnt(Cache*, int, bool*, unsigned long, bool)            :45-46
 //   int  Optimizer::PoseOptimization(Frame*)                                                   :51
 //   Sim3Solver(KeyFrame*, KeyFrame*, const vector<MapPoint*>&, bool) / SetRansacParameters / iterate / find / GetEstimated*   include/Sim3Solver.h:39-49
+//   Initializer(const Frame&, float sigma, int iterations) / Initialize(const Frame&, const vector<int>&, cv::Mat&, cv::Mat&, vector<cv::Point3f>&, vector<bool>&)   include/Initializer.h:38-43
 //
 // The adapters FLATTEN the reference's pointer graph into the arrays of the C-ABI (KeyFrame* / Frame& -> descriptors, keypoints, mvuRight,
 // "has a good MapPoint" flags, DBoW2::FeatureVector; Cache* -> poses, per-keyframe intrinsics, points, observations), call the accelerator,
@@ -850,6 +851,83 @@ private:
 };
 }  // namespace corb
 
+// ---- Initializer (corbslam_client/include/Initializer.h) over corb_mono_initialize ----
+// The reference's constructor (C/src/Initializer.cc:33-42: mK and mvKeysUn of the reference frame, sigma, iterations) and Initialize signature (:44-45).  Each
+// Initialize draws iterations x 8 values from the random source (a callable returning rand()'s range [0, 2^31)) in the order the source consumes rand() at :82-97 and
+// makes ONE library call; Initializer::RunBatch evaluates the (reference, current) pairs of several clients in one call and Result() then hands each its answer.
+// Mat = the type of Frame::mK; the points go into any vector of a type with float x, y, z.
+namespace corb {
+template <class Frame>
+class Initializer {
+public:
+    using Mat = typename std::decay<decltype(std::declval<const Frame&>().mK)>::type;
+    using RandomSource = std::function<int()>;
+    struct Job { Initializer* init; const Frame* current; const std::vector<int>* vMatches12; };
+    Initializer(const Frame& ReferenceFrame, float sigma = 1.0, int iterations = 200, RandomSource rnd = [] { return std::rand(); }, int device = 0)
+        : mSigma(sigma), mMaxIterations(iterations), rnd_(std::move(rnd)), device_(device)
+    {
+        check_abi();
+        fx_ = adapt::matf(ReferenceFrame.mK, 0, 0); fy_ = adapt::matf(ReferenceFrame.mK, 1, 1); cx_ = adapt::matf(ReferenceFrame.mK, 0, 2); cy_ = adapt::matf(ReferenceFrame.mK, 1, 2);
+        for (const auto& k : ReferenceFrame.mvKeysUn) { CorbKeyPoint o{}; o.x = k.pt.x; o.y = k.pt.y; mvKeys1.push_back(o); }
+    }
+    template <class Point3f>
+    bool Initialize(const Frame& CurrentFrame, const std::vector<int>& vMatches12, Mat& R21, Mat& t21, std::vector<Point3f>& vP3D, std::vector<bool>& vbTriangulated)
+    {
+        RunBatch({Job{this, &CurrentFrame, &vMatches12}});
+        return Result(R21, t21, vP3D, vbTriangulated);
+    }
+    // what the last Initialize / RunBatch left for this initializer; R21, t21, vP3D and vbTriangulated are written on success only, as in the source
+    template <class Point3f>
+    bool Result(Mat& R21, Mat& t21, std::vector<Point3f>& vP3D, std::vector<bool>& vbTriangulated) const
+    {
+        if (result.status != CORB_INIT_OK) return false;
+        R21 = adapt::MatFactory<Mat>::from_floats(3, 3, result.R21); t21 = adapt::MatFactory<Mat>::from_floats(3, 1, result.t21);
+        vP3D.resize(mvKeys1.size()); vbTriangulated.assign(mvKeys1.size(), false);
+        for (size_t i = 0; i < mvKeys1.size(); i++) { vP3D[i].x = p3d_[3 * i]; vP3D[i].y = p3d_[3 * i + 1]; vP3D[i].z = p3d_[3 * i + 2]; vbTriangulated[i] = tri_[i] != 0; }
+        return true;
+    }
+    // every job in ONE corb_mono_initialize call per set of equal parameters (the server runs one client per robot)
+    static void RunBatch(const std::vector<Job>& jobs)
+    {
+        std::vector<Job> todo(jobs);
+        while (!todo.empty()) {
+            const Initializer* h = todo.front().init; std::vector<Job> grp, rest;
+            for (const Job& j : todo) (j.init->mSigma == h->mSigma && j.init->mMaxIterations == h->mMaxIterations && j.init->device_ == h->device_ ? grp : rest).push_back(j);
+            const int n = (int)grp.size(), its = std::max(h->mMaxIterations, 0);
+            std::vector<CorbInitProblem> pr((size_t)n); std::vector<std::vector<CorbKeyPoint>> keys2((size_t)n); std::vector<std::vector<int32_t>> m12((size_t)n);
+            std::vector<int32_t> rv((size_t)n * its * 8);
+            int stride = 1;
+            for (int c = 0; c < n; c++) {
+                Initializer* s = grp[c].init;
+                for (const auto& k : grp[c].current->mvKeysUn) { CorbKeyPoint o{}; o.x = k.pt.x; o.y = k.pt.y; keys2[c].push_back(o); }
+                m12[c].assign(s->mvKeys1.size(), -1);                  // vMatches12 is indexed by the reference frame's keys (:54-63)
+                for (size_t i = 0; i < grp[c].vMatches12->size() && i < m12[c].size(); i++) m12[c][i] = (*grp[c].vMatches12)[i];
+                for (int k = 0; k < its * 8; k++) rv[(size_t)c * its * 8 + k] = (int32_t)s->rnd_();
+                pr[c].keys1 = s->mvKeys1.data(); pr[c].n1 = (int32_t)s->mvKeys1.size(); pr[c].keys2 = keys2[c].data(); pr[c].n2 = (int32_t)keys2[c].size();
+                pr[c].matches12 = m12[c].data(); pr[c].fx = s->fx_; pr[c].fy = s->fy_; pr[c].cx = s->cx_; pr[c].cy = s->cy_;
+                stride = std::max(stride, (int)s->mvKeys1.size());
+            }
+            std::vector<CorbInitResult> res((size_t)n); std::vector<float> p3d((size_t)n * stride * 3); std::vector<uint8_t> tri((size_t)n * stride);
+            check(corb_mono_initialize(pr.data(), n, h->mSigma, h->mMaxIterations, 1.0f, 50, rv.data(), stride, 0, res.data(), p3d.data(), tri.data(), nullptr, nullptr, nullptr,
+                                       h->device_), "corb_mono_initialize");                    // minParallax 1.0, minTriangulated 50 (:116-118)
+            for (int c = 0; c < n; c++) {
+                Initializer* s = grp[c].init; const size_t n1 = s->mvKeys1.size();
+                s->result = res[c];
+                s->p3d_.assign(p3d.begin() + (size_t)c * stride * 3, p3d.begin() + (size_t)c * stride * 3 + n1 * 3);
+                s->tri_.assign(tri.begin() + (size_t)c * stride, tri.begin() + (size_t)c * stride + n1);
+            }
+            todo.swap(rest);
+        }
+    }
+    CorbInitResult result{};                                           // every diagnostic of the last call
+
+private:
+    std::vector<CorbKeyPoint> mvKeys1; float mSigma; int mMaxIterations; float fx_ = 0, fy_ = 0, cx_ = 0, cy_ = 0;
+    std::vector<float> p3d_; std::vector<uint8_t> tri_;
+    RandomSource rnd_; int device_;
+};
+}  // namespace corb
+
 #if defined(__has_include)
 #if __has_include(<opencv2/core/core.hpp>) && __has_include("KeyFrame.h") && __has_include("Frame.h") && __has_include("MapPoint.h") && __has_include("Cache.h")
 #include <opencv2/core/core.hpp>
@@ -868,6 +946,7 @@ using MapStore = corb::adapt::MapStoreT<KeyFrame, MapPoint, cv::Mat>;
 using FrameStore = corb::adapt::FrameStoreT<Frame, MapPoint, cv::Mat>;
 using Sim3Solver = corb::Sim3Solver<KeyFrame, MapPoint>;
 using PnPsolver = corb::PnPsolver<Frame, KeyFrame, MapPoint>;
+using Initializer = corb::Initializer<Frame>;
 }  // namespace accel
 }  // namespace ORB_SLAM2
 #endif

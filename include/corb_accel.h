@@ -971,6 +971,61 @@ int corb_pnp_ransac_store(CorbKfStore* frames, int slot, CorbMpStore* map, const
                           CorbPnPRansacRecord* records, uint8_t* best_flags /* n_candidates x max_records x n(slot) */, uint8_t* refined_flags,
                           int32_t* n_corr /* n_candidates */, int32_t* index, int32_t* counts, double* pose_out, double* refine_pose_out);
 
+/* ============================ Initializer (Tracking::MonocularInitialization) ============
+ * C/src/Initializer.cc for the (reference, current) frame pairs of several clients in one call: Initialize (:44-121) -- the 8-point sets of every iteration (:77-97),
+ * FindHomography (:124-172) and FindFundamental (:175-223) as 2 x max_iterations independent hypotheses per problem, one wavefront each, over the same sets -- then RH
+ * and the model (:112-118), the 4 motion hypotheses of DecomposeE (:909-929) or the 8 of :584-686, a CheckRT (:798-907) per hypothesis, and the decision of ReconstructF
+ * (:499-569) or ReconstructH (:689-731).  Tracking.cc:620 calls it once per frame until it succeeds.
+ * DUtils::Random::SeedRandOnce(0) seeds only the first call of a process and the stream is shared with every other RANSAC, so the draws are an input: rand_values = per
+ * problem max_iterations x 8 results of rand() in [0, 2^31), each consumed as RandomInt(0, size - 1) with the swap-with-back removal of :94-95; H and F share the sets.
+ * Numerics (csrc/init_math.h is the text, tests/initializer_reference.py the definition): the source's float expressions, unfused, in the types C++
+ * gives them; Normalize (:749-795) over all keys of a frame and the scores (:363, :379, :441, :459) are float sums in ascending index order -- the score decides which
+ * hypothesis wins, so its order is part of the definition; cv::SVDecomp / cv::SVD::compute = a one-sided Jacobi SVD in FP64 rounded to float once (the sign of a null
+ * vector is whatever the iteration leaves: H is homogeneous, F enters squared, s = det U det Vt and the +-t of DecomposeE absorb it); Mat::inv() of a 3 x 3 = adjugate
+ * times 1 / det in double; float products accumulate in double.  The parallax tests (:525 >, :721 >=) are made on the cosine against thresholds the host finds with its
+ * own acos; the reported parallax is float(acos((double)c) * 180 / pi) of the returned cosine.  vCosParallax[min(50, size - 1)] is the order statistic by (value,
+ * position), a NaN last.  Where the reference would crash -- an empty H21 / F21, RH = NaN -- the call reports a status. */
+typedef struct CorbInitProblem {
+    const CorbKeyPoint* keys1; int32_t n1;      /* mvKeys1 = ReferenceFrame.mvKeysUn (x, y read) */
+    const CorbKeyPoint* keys2; int32_t n2;      /* CurrentFrame.mvKeysUn */
+    const int32_t* matches12;                   /* n1: vMatches12, -1 = none */
+    float fx, fy, cx, cy;                       /* mK */
+} CorbInitProblem;
+#define CORB_INIT_OK           0                /* Initialize returned true */
+#define CORB_INIT_NO_MODEL     1                /* no positive finite score for the model the ratio selects, or RH is NaN */
+#define CORB_INIT_H_DEGENERATE 2                /* :597: d1 / d2 or d2 / d3 below 1.00001 */
+#define CORB_INIT_AMBIGUOUS    3                /* :517 nsimilar > 1, or :721 secondBestGood >= 0.75 bestGood */
+#define CORB_INIT_FEW_POINTS   4                /* :517 maxGood < nMinGood, or :721 bestGood <= minTriangulated or <= 0.9 N */
+#define CORB_INIT_LOW_PARALLAX 5                /* :525-565 parallax <= minParallax, or :721 bestParallax < minParallax */
+typedef struct CorbInitResult {
+    int32_t status;                             /* CORB_INIT_*.  Several failing tests at once: F in the order of :517-525 (few points, ambiguous, parallax), H of :721 as
+                                                   parallax, ambiguous, few points */
+    int32_t model;                              /* 0 = H (RH > 0.40), 1 = F */
+    int32_t n_matches;                          /* N = mvMatches12.size() */
+    float score_h, score_f, rh;                 /* SH, SF (0 if no hypothesis scored above 0), RH = SH / (SH + SF) */
+    int32_t best_it_h, best_it_f;               /* the iteration that won, 0-based: the first maximum (the source's strict >); -1 if none */
+    float H21[9], F21[9];                       /* row-major; zero if none */
+    int32_t n_inliers;                          /* N of :473-476 / :575-578: the inliers of the chosen model */
+    int32_t n_good[8];                          /* nGood of CheckRT per motion hypothesis in the source's order: F (R1,t) (R2,t) (R1,-t) (R2,-t); entries 4..7 unused for F */
+    float cos_parallax[8];                      /* vCosParallax[min(50, size - 1)] after the sort; 1 where nGood = 0 (parallax 0, :904) */
+    float parallax[8];                          /* :901, computed on the host from cos_parallax */
+    int32_t best_hypothesis;                    /* F: the first hypothesis that equals maxGood (the else-if chain of :523-567 tries no other); H: bestSolutionIdx (-1 if every nGood is 0) */
+    int32_t second_best_good;                   /* H: secondBestGood; F: the same rule over its four */
+    float R21[9], t21[3];                       /* zero unless status = CORB_INIT_OK */
+    int32_t n_triangulated;                     /* number of set entries of vbTriangulated */
+} CorbInitResult;
+/* Initializer(ReferenceFrame, sigma, max_iterations).Initialize(...) with ReconstructH / ReconstructF's minParallax and minTriangulated (1.0 and 50 at :116-118), per
+ * problem.  rand_values: n_problems x max_iterations x 8.  p3d (n_problems x p3d_stride x 3) = vP3D and triangulated (n_problems x p3d_stride) = vbTriangulated, both by
+ * key-1 index, p3d_stride >= every n1; vP3D is written even where cosParallax >= 0.99998 leaves vbTriangulated false (:889-893).  inliers_h / inliers_f (optional,
+ * n_problems x flags_stride bytes, flags_stride >= every N) = vbMatchesInliersH / F, one byte per entry of mvMatches12.  scores (optional, n_problems x max_iterations x
+ * 2) = currentScore of every H and F hypothesis.  On a failed status the diagnostics (scores, H21, F21, inliers, n_good, cos_parallax) stay filled and R21, t21, p3d and
+ * triangulated are zero.  N < 8 (the source indexes an empty vector; Tracking never calls it below 100), a match index outside [-1, n2), max_iterations outside
+ * [1, 65535], sigma <= 0 or a rand_values entry outside [0, 2^31): CORB_ERR_ARG, nothing written.  Host pointers; four launches, one synchronisation and one read-back
+ * per call.  (A form on records is not built: SearchForInitialization has no slots form to chain it to.) */
+int corb_mono_initialize(const CorbInitProblem* problems, int n_problems, float sigma, int max_iterations, float min_parallax, int min_triangulated,
+                         const int32_t* rand_values /* n_problems x max_iterations x 8 */, int p3d_stride, int flags_stride, CorbInitResult* results /* n_problems */,
+                         float* p3d, uint8_t* triangulated, uint8_t* inliers_h, uint8_t* inliers_f, float* scores, int device);
+
 #ifdef __cplusplus
 }
 #endif
