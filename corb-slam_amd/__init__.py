@@ -41,6 +41,9 @@ EXPORTS = [
     "corb_sim3_ransac", "corb_sim3_ransac_store",
     "corb_pnp_ransac", "corb_pnp_ransac_store",
     "corb_mono_initialize",
+    "corb_voc_create", "corb_voc_load_text", "corb_voc_destroy", "corb_voc_info", "corb_voc_transform", "corb_kf_store_compute_bow",
+    "corb_kfdb_create", "corb_kfdb_destroy", "corb_kfdb_set_bow", "corb_kfdb_get_bow", "corb_kfdb_add", "corb_kfdb_erase", "corb_kfdb_clear", "corb_kfdb_set_neighbours",
+    "corb_kfdb_get_state", "corb_kfdb_score", "corb_kfdb_detect", "corb_bow_profile", "corb_bow_profile_read",
 ]
 
 
@@ -77,6 +80,11 @@ class KernelTime(C.Structure):
 
 class _FeatVec(C.Structure):
     _fields_ = [("n_nodes", C.c_int32), ("node_id", C.c_void_p), ("offset", C.c_void_p), ("idx", C.c_void_p)]
+
+
+class _VocDesc(C.Structure):
+    _fields_ = [("k", C.c_int32), ("L", C.c_int32), ("scoring", C.c_int32), ("weighting", C.c_int32), ("n_nodes", C.c_int32),
+                ("parent", C.c_void_p), ("is_leaf", C.c_void_p), ("descriptor", C.c_void_p), ("weight", C.c_void_p)]
 
 
 class _BowSide(C.Structure):
@@ -318,6 +326,27 @@ def load():
     L.corb_sim3_ransac_store.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(TrackCamera), C.c_void_p, C.c_void_p, C.c_double, C.c_int, C.c_int, C.c_int,
                                          C.c_void_p, C.c_int] + [C.c_void_p] * 8
     L.corb_mono_initialize.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 6 + [C.c_int]
+    L.corb_voc_create.argtypes = [C.POINTER(_VocDesc), C.c_int, C.POINTER(C.c_void_p)]
+    L.corb_voc_load_text.argtypes = [C.c_char_p, C.c_int, C.POINTER(C.c_void_p)]
+    L.corb_voc_destroy.argtypes = [C.c_void_p]
+    L.corb_voc_destroy.restype = None
+    L.corb_voc_info.argtypes = [C.c_void_p] + [C.POINTER(C.c_int32)] * 4
+    L.corb_voc_transform.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 9
+    L.corb_kfdb_create.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
+    L.corb_kfdb_destroy.argtypes = [C.c_void_p]
+    L.corb_kfdb_destroy.restype = None
+    L.corb_kfdb_set_bow.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
+    L.corb_kfdb_get_bow.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+    L.corb_kfdb_add.argtypes = [C.c_void_p, C.c_int]
+    L.corb_kfdb_erase.argtypes = [C.c_void_p, C.c_int]
+    L.corb_kfdb_clear.argtypes = [C.c_void_p]
+    L.corb_kfdb_set_neighbours.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    L.corb_kfdb_get_state.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+    L.corb_kfdb_score.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+    L.corb_kfdb_detect.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_uint64, C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+    L.corb_bow_profile.argtypes = [C.c_int, C.c_int]
+    L.corb_bow_profile_read.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+    L.corb_kf_store_compute_bow.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
     _lib = L
     return L
 
@@ -1281,6 +1310,148 @@ class Optimizer:
 
 
 
+BOW_MAX_FEATURES = 8192                          # CORB_BOW_MAX_FEATURES
+KFDB_STATE_DTYPE = np.dtype([("loop_query", "<u8"), ("loop_words", "<i4"), ("loop_score", "<f4"), ("reloc_query", "<u8"), ("reloc_words", "<i4"), ("reloc_score", "<f4")])
+
+
+def bow_profile(enable, device=0):
+    _chk(load().corb_bow_profile(int(enable), device), "corb_bow_profile")
+
+
+def bow_profile_read():
+    """{name: (total_ms, launches)} since the last read (corb_bow_profile_read)"""
+    out = (KernelTime * 32)(); n = C.c_int(0)
+    _chk(load().corb_bow_profile_read(C.cast(out, C.c_void_p), 32, C.byref(n)), "corb_bow_profile_read")
+    return dict((out[i].name.decode(), (out[i].total_ms, out[i].launches)) for i in range(min(n.value, 32)))
+
+
+class Vocabulary:
+    """ORBVocabulary (DBoW2::TemplatedVocabulary, L1_NORM / TF_IDF) on the device (corb_voc_*): flat arrays in -- node ids 1 .. n in array order, the root is node 0 -- or
+    the text format of loadFromTextFile."""
+
+    def __init__(self, k, L, parent, is_leaf, descriptor, weight, scoring=0, weighting=0, device=0):
+        p = np.ascontiguousarray(parent, np.int32); lf = np.ascontiguousarray(is_leaf, np.int32); d = np.ascontiguousarray(descriptor, np.uint8).reshape(-1, 32)
+        w = np.ascontiguousarray(weight, np.float64)
+        if not (len(p) == len(lf) == len(d) == len(w)):
+            raise CorbError("Vocabulary: the node arrays differ in length")
+        self.h = C.c_void_p(); self.device = device
+        c = _VocDesc(int(k), int(L), int(scoring), int(weighting), len(p), _p(p), _p(lf), _p(d), _p(w))
+        _chk(load().corb_voc_create(C.byref(c), device, C.byref(self.h)), "corb_voc_create")
+
+    @classmethod
+    def from_text(cls, path, device=0):
+        self = cls.__new__(cls); self.h = C.c_void_p(); self.device = device
+        _chk(load().corb_voc_load_text(os.fsencode(path), device, C.byref(self.h)), "corb_voc_load_text")
+        return self
+
+    def close(self):
+        if self.h:
+            load().corb_voc_destroy(self.h); self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def info(self):
+        v = [C.c_int32(0) for _ in range(4)]
+        _chk(load().corb_voc_info(self.h, *[C.byref(x) for x in v]), "corb_voc_info")
+        return dict(k=v[0].value, L=v[1].value, n_nodes=v[2].value, n_words=v[3].value)
+
+    def transform_sets(self, sets, levelsup, per_feature=False):
+        """corb_voc_transform: a list of [n, 32] descriptor arrays in one call -> per set (word, value, fv_node, fv_off, fv_idx[, feat_word, feat_node])"""
+        sets = [np.ascontiguousarray(d, np.uint8).reshape(-1, 32) for d in sets]
+        off = np.zeros(len(sets) + 1, np.int32); off[1:] = np.cumsum([len(d) for d in sets])
+        t = int(off[-1]); ns = len(sets)
+        desc = np.concatenate(sets) if sets else np.zeros((0, 32), np.uint8)
+        word = np.zeros(t, np.uint32); val = np.zeros(t, np.float64); bc = np.zeros(ns, np.int32); node = np.zeros(t, np.uint32); fo = np.zeros(t + ns, np.int32)
+        idx = np.zeros(t, np.uint32); nn = np.zeros(ns, np.int32); fw = np.zeros(t, np.int32) if per_feature else None; fn = np.zeros(t, np.uint32) if per_feature else None
+        _chk(load().corb_voc_transform(self.h, _p(np.ascontiguousarray(desc)), _p(off), ns, int(levelsup), _p(word), _p(val), _p(bc), _p(node), _p(fo), _p(idx), _p(nn), _p(fw), _p(fn)),
+             "corb_voc_transform")
+        out = []
+        for s in range(ns):
+            o = int(off[s]); k = int(nn[s]); o2 = fo[o + s:o + s + k + 1].copy()
+            r = (word[o:o + bc[s]].copy(), val[o:o + bc[s]].copy(), node[o:o + k].copy(), o2, idx[o:o + int(o2[k])].copy())
+            out.append(r + (fw[o:off[s + 1]].copy(), fn[o:off[s + 1]].copy()) if per_feature else r)
+        return out
+
+    def transform(self, desc, levelsup, per_feature=False):
+        """TemplatedVocabulary::transform(features, BowVector, FeatureVector, levelsup)"""
+        return self.transform_sets([desc], levelsup, per_feature)[0]
+
+
+class KeyFrameDatabase:
+    """KeyFrameDatabase (C/src/KeyFrameDatabase.cc) over entries of a device-resident table (corb_kfdb_*).  The detect functions take (query entry, query id); the loop
+    variant also the connected keyframes as entries and minScore.  They return the candidates as entries, in the reference's order."""
+
+    def __init__(self, voc, capacity, max_words):
+        self.h = C.c_void_p(); self.voc = voc; self.capacity = capacity; self.max_words = max_words
+        _chk(load().corb_kfdb_create(voc.h, capacity, max_words, C.byref(self.h)), "corb_kfdb_create")
+
+    def close(self):
+        if self.h:
+            load().corb_kfdb_destroy(self.h); self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_bow(self, entry, word, value):
+        w = np.ascontiguousarray(word, np.uint32); v = np.ascontiguousarray(value, np.float64)
+        if len(w) != len(v):
+            raise CorbError("KeyFrameDatabase.set_bow: words and values differ in length")
+        _chk(load().corb_kfdb_set_bow(self.h, int(entry), _p(w), _p(v), len(w)), "corb_kfdb_set_bow")
+
+    def get_bow(self, entry):
+        w = np.zeros(self.max_words, np.uint32); v = np.zeros(self.max_words, np.float64); n = C.c_int(0)
+        _chk(load().corb_kfdb_get_bow(self.h, int(entry), _p(w), _p(v), self.max_words, C.byref(n)), "corb_kfdb_get_bow")
+        return w[:n.value].copy(), v[:n.value].copy()
+
+    def add(self, entry):
+        _chk(load().corb_kfdb_add(self.h, int(entry)), "corb_kfdb_add")
+
+    def erase(self, entry):
+        _chk(load().corb_kfdb_erase(self.h, int(entry)), "corb_kfdb_erase")
+
+    def clear(self):
+        _chk(load().corb_kfdb_clear(self.h), "corb_kfdb_clear")
+
+    def set_neighbours(self, entries, nb):
+        e = np.ascontiguousarray(np.atleast_1d(entries), np.int32); b = np.ascontiguousarray(nb, np.int32).reshape(len(e), 10)
+        _chk(load().corb_kfdb_set_neighbours(self.h, _p(e), len(e), _p(b)), "corb_kfdb_set_neighbours")
+
+    def state(self, first=0, n=None):
+        n = self.capacity - first if n is None else n
+        out = np.zeros(n, KFDB_STATE_DTYPE)
+        _chk(load().corb_kfdb_get_state(self.h, int(first), int(n), _p(out)), "corb_kfdb_get_state")
+        return out
+
+    def score(self, entry_a, entries_b):
+        b = np.ascontiguousarray(entries_b, np.int32); out = np.zeros(len(b), np.float64)
+        _chk(load().corb_kfdb_score(self.h, int(entry_a), _p(b), len(b), _p(out)), "corb_kfdb_score")
+        return out
+
+    def detect(self, kind, query_entry, query_id, connected=(), min_score=0.0, cap=None):
+        cap = self.capacity if cap is None else cap
+        c = np.ascontiguousarray(list(connected), np.int32); out = np.zeros(max(cap, 1), np.int32); n = C.c_int(0)
+        rc = load().corb_kfdb_detect(self.h, int(kind), int(query_entry), int(query_id), _p(c), len(c), C.c_float(min_score), _p(out), int(cap), C.byref(n))
+        self.last_count = n.value
+        _chk(rc, "corb_kfdb_detect")
+        return out[:n.value].copy()
+
+    def DetectLoopCandidates(self, query_entry, query_id, connected, min_score):
+        return self.detect(0, query_entry, query_id, connected, min_score)
+
+    def DetectRelocalizationCandidates(self, query_entry, query_id):
+        return self.detect(1, query_entry, query_id)
+
+    def DetectMapFusionCandidatesFromDB(self, query_entry, query_id):
+        return self.detect(2, query_entry, query_id)
+
+
 class TrackCamera(C.Structure):
     """CorbTrackCamera: Frame intrinsics, image bounds and mvScaleFactors"""
     _fields_ = [("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("bf", C.c_float), ("mb", C.c_float),
@@ -1340,6 +1511,13 @@ class KeyFrameStore:
         node, off, idx = (np.ascontiguousarray(fv[0], np.uint32), np.ascontiguousarray(fv[1], np.int32), np.ascontiguousarray(fv[2], np.uint32))
         c = _FeatVec(len(node), _p(node), _p(off), _p(idx))
         _chk(load().corb_kf_store_set_bow(self.h, slot, C.byref(c)), "corb_kf_store_set_bow")
+
+    def compute_bow(self, slots, voc, levelsup=4, db=None, entries=None):
+        """Frame::ComputeBoW / KeyFrame::ComputeBoW on records (corb_kf_store_compute_bow): the FeatureVector into the slots, the BowVector into `entries` of `db`"""
+        sl = np.ascontiguousarray(np.atleast_1d(slots), np.int32); en = None if entries is None else np.ascontiguousarray(np.atleast_1d(entries), np.int32)
+        if db is not None and (en is None or len(en) != len(sl)):
+            raise CorbError("compute_bow: one database entry per slot")
+        _chk(load().corb_kf_store_compute_bow(self.h, _p(sl), len(sl), voc.h, int(levelsup), db.h if db is not None else None, _p(en)), "corb_kf_store_compute_bow")
 
     def set_flags(self, slot, flags):
         f = None if flags is None else np.ascontiguousarray(flags, np.uint8)

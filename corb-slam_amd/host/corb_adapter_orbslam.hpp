@@ -928,6 +928,128 @@ private:
 };
 }  // namespace corb
 
+// ---- place recognition: ORBVocabulary (DBoW2::TemplatedVocabulary<FORB::TDescriptor, FORB>) and KeyFrameDatabase (include/KeyFrameDatabase.h:46-68) ----
+//   void ORBVocabulary::transform(const vector<cv::Mat>&, DBoW2::BowVector&, DBoW2::FeatureVector&, int levelsup)   TemplatedVocabulary.h:1127
+//   double ORBVocabulary::score(const BowVector&, const BowVector&)                                               :1199
+//   void add(KeyFrame*) / erase(KeyFrame*) / clear()                                                               KeyFrameDatabase.cc:38-70
+//   vector<KeyFrame*> DetectLoopCandidates(KeyFrame*, float minScore) / DetectRelocalizationCandidates(Frame*) / DetectMapFusionCandidatesFromDB(KeyFrame*)   :73-401
+// The database maps KeyFrame* to entries of a CorbKfDb as it meets them: a keyframe's mBowVec is uploaded once (ComputeBoW computes it once), the six per-keyframe fields
+// live in the device table (State() reads them), and GetBestCovisibilityKeyFrames(10) is read at add() and whenever the caller reports UpdateConnections().  The Frame of a
+// relocalisation uses the table's last entry.  Two limits: an entry is given to a KeyFrame* once and kept after erase() (the reference's erased keyframes keep their
+// fields, and neighbours may still name them), so capacity_keyframes bounds the keyframes ever met, not the live ones; and mBowVec is read at first sight only, so a
+// keyframe must have its BoW computed before the database meets it (as KeyFrame's constructor guarantees in the reference).
+namespace corb {
+class ORBVocabulary {
+public:
+    ORBVocabulary() {}
+    explicit ORBVocabulary(const std::string& text_file, int device = 0) { if (!loadFromTextFile(text_file, device)) throw Error(CORB_ERR_ARG, "ORBVocabulary"); }
+    ORBVocabulary(const ORBVocabulary&) = delete; ORBVocabulary& operator=(const ORBVocabulary&) = delete;
+    ~ORBVocabulary() { if (h_) corb_voc_destroy(h_); }
+    bool loadFromTextFile(const std::string& path, int device = 0) { if (h_) { corb_voc_destroy(h_); h_ = nullptr; } return corb_voc_load_text(path.c_str(), device, &h_) == CORB_OK; }
+    void create(const CorbVocDesc& d, int device = 0) { if (h_) { corb_voc_destroy(h_); h_ = nullptr; } check(corb_voc_create(&d, device, &h_), "corb_voc_create"); }
+    unsigned size() const { int32_t w = 0; if (h_) corb_voc_info(h_, nullptr, nullptr, nullptr, &w); return (unsigned)w; }
+    bool empty() const { return size() == 0; }
+    template <class Desc, class BowVec, class FeatVec> void transform(const std::vector<Desc>& features, BowVec& v, FeatVec& fv, int levelsup) const
+    {
+        v.clear(); fv.clear();
+        const int n = (int)features.size();
+        std::vector<uint8_t> d((size_t)n * 32 + 32);
+        for (int i = 0; i < n; i++) std::memcpy(&d[(size_t)i * 32], adapt::desc_row(features[i], 0), 32);
+        const int32_t off[2] = {0, n}; int32_t nw = 0, nn = 0;
+        std::vector<uint32_t> w(n + 1), node(n + 1), idx(n + 1); std::vector<double> val(n + 1); std::vector<int32_t> fo(n + 2);
+        check(corb_voc_transform(h_, d.data(), off, 1, levelsup, w.data(), val.data(), &nw, node.data(), fo.data(), idx.data(), &nn, nullptr, nullptr), "corb_voc_transform");
+        for (int i = 0; i < nw; i++) v.insert(v.end(), std::make_pair(w[i], val[i]));
+        for (int j = 0; j < nn; j++) { auto& g = fv[node[j]]; g.assign(idx.begin() + fo[j], idx.begin() + fo[j + 1]); }
+    }
+    // L1Scoring::score (ScoringObject.cpp:23-68) on two host vectors, as the source states it
+    template <class BowVec> double score(const BowVec& v1, const BowVec& v2) const
+    {
+        auto i = v1.begin(), j = v2.begin(); double s = 0;
+        while (i != v1.end() && j != v2.end()) {
+            if (i->first == j->first) { s += std::fabs(i->second - j->second) - std::fabs(i->second) - std::fabs(j->second); ++i; ++j; }
+            else if (i->first < j->first) i = v1.lower_bound(j->first);
+            else j = v2.lower_bound(i->first);
+        }
+        return -s / 2.0;
+    }
+    CorbVoc* handle() const { return h_; }
+private:
+    CorbVoc* h_ = nullptr;
+};
+
+template <class KeyFrame, class Frame = KeyFrame>
+class KeyFrameDatabase {
+public:
+    KeyFrameDatabase(const ORBVocabulary& voc, int capacity_keyframes, int max_words) : cap_(capacity_keyframes + 1), kf_((size_t)capacity_keyframes + 1, nullptr)
+    { check(corb_kfdb_create(voc.handle(), cap_, max_words, &h_), "corb_kfdb_create"); }
+    KeyFrameDatabase(const KeyFrameDatabase&) = delete; KeyFrameDatabase& operator=(const KeyFrameDatabase&) = delete;
+    ~KeyFrameDatabase() { if (h_) corb_kfdb_destroy(h_); }
+
+    void add(KeyFrame* pKF) { const int e = entry(pKF); check(corb_kfdb_add(h_, e), "corb_kfdb_add"); UpdateConnections(pKF); }
+    void erase(KeyFrame* pKF) { auto it = entry_.find(pKF); if (it != entry_.end()) check(corb_kfdb_erase(h_, it->second), "corb_kfdb_erase"); }
+    void clear() { check(corb_kfdb_clear(h_), "corb_kfdb_clear"); }
+    // to be called where the reference's covisibility graph changes (KeyFrame::UpdateConnections / UpdateBestCovisibles): re-reads GetBestCovisibilityKeyFrames(10)
+    void UpdateConnections(KeyFrame* pKF)
+    {
+        const int32_t e = entry(pKF); int32_t row[10]; int m = 0;
+        for (KeyFrame* p : pKF->GetBestCovisibilityKeyFrames(10)) if (m < 10) row[m++] = entry(p);
+        for (; m < 10; m++) row[m] = -1;
+        check(corb_kfdb_set_neighbours(h_, &e, 1, row), "corb_kfdb_set_neighbours");
+    }
+    std::vector<KeyFrame*> DetectLoopCandidates(KeyFrame* pKF, float minScore)
+    {
+        std::vector<int32_t> conn;
+        for (KeyFrame* p : pKF->GetConnectedKeyFrames()) { auto it = entry_.find(p); if (it != entry_.end()) conn.push_back(it->second); }
+        return detect(0, entry(pKF), (uint64_t)pKF->mnId, conn, minScore);
+    }
+    std::vector<KeyFrame*> DetectMapFusionCandidatesFromDB(KeyFrame* pKF) { return detect(2, entry(pKF), (uint64_t)pKF->mnId, {}, 0.f); }
+    std::vector<KeyFrame*> DetectRelocalizationCandidates(Frame* F)
+    {
+        set_bow(cap_ - 1, F->mBowVec);
+        return detect(1, cap_ - 1, (uint64_t)F->mnId, {}, 0.f);
+    }
+    // the minScore loop of LoopClosing::DetectLoop (C/src/LoopClosing.cc:122-137): mpVoc->score(pKF->mBowVec, other->mBowVec) for each of `others`
+    std::vector<double> Scores(KeyFrame* pKF, const std::vector<KeyFrame*>& others)
+    {
+        std::vector<int32_t> b; for (KeyFrame* p : others) b.push_back(entry(p));
+        std::vector<double> s(b.size());
+        check(corb_kfdb_score(h_, entry(pKF), b.data(), (int)b.size(), s.data()), "corb_kfdb_score");
+        return s;
+    }
+    CorbKfDbState State(KeyFrame* pKF) const
+    {
+        CorbKfDbState s; std::memset(&s, 0, sizeof(s));
+        auto it = entry_.find(pKF); if (it != entry_.end()) check(corb_kfdb_get_state(h_, it->second, 1, &s), "corb_kfdb_get_state");
+        return s;
+    }
+    CorbKfDb* handle() const { return h_; }
+private:
+    template <class BowVec> void set_bow(int e, const BowVec& v)
+    {
+        std::vector<uint32_t> w; std::vector<double> val;
+        for (auto it = v.begin(); it != v.end(); ++it) { w.push_back((uint32_t)it->first); val.push_back(it->second); }
+        check(corb_kfdb_set_bow(h_, e, w.data(), val.data(), (int)w.size()), "corb_kfdb_set_bow");
+    }
+    int entry(KeyFrame* pKF)
+    {
+        auto it = entry_.find(pKF); if (it != entry_.end()) return it->second;
+        if (next_ >= cap_ - 1) throw Error(CORB_ERR_CAPACITY, "KeyFrameDatabase: more keyframes than capacity_keyframes");
+        const int e = next_++;
+        set_bow(e, pKF->mBowVec); entry_[pKF] = e; kf_[e] = pKF;
+        return e;
+    }
+    std::vector<KeyFrame*> detect(int kind, int q, uint64_t id, const std::vector<int32_t>& conn, float minScore)
+    {
+        std::vector<int32_t> out((size_t)cap_); int n = 0;
+        check(corb_kfdb_detect(h_, kind, q, id, conn.data(), (int)conn.size(), minScore, out.data(), cap_, &n), "corb_kfdb_detect");
+        std::vector<KeyFrame*> r; for (int i = 0; i < n; i++) r.push_back(kf_[out[i]]);
+        return r;
+    }
+    CorbKfDb* h_ = nullptr; int cap_, next_ = 0;
+    std::map<KeyFrame*, int> entry_; std::vector<KeyFrame*> kf_;
+};
+}  // namespace corb
+
 #if defined(__has_include)
 #if __has_include(<opencv2/core/core.hpp>) && __has_include("KeyFrame.h") && __has_include("Frame.h") && __has_include("MapPoint.h") && __has_include("Cache.h")
 #include <opencv2/core/core.hpp>
@@ -947,6 +1069,8 @@ using FrameStore = corb::adapt::FrameStoreT<Frame, MapPoint, cv::Mat>;
 using Sim3Solver = corb::Sim3Solver<KeyFrame, MapPoint>;
 using PnPsolver = corb::PnPsolver<Frame, KeyFrame, MapPoint>;
 using Initializer = corb::Initializer<Frame>;
+using ORBVocabulary = corb::ORBVocabulary;
+using KeyFrameDatabase = corb::KeyFrameDatabase<KeyFrame, Frame>;
 }  // namespace accel
 }  // namespace ORB_SLAM2
 #endif

@@ -546,7 +546,8 @@ int corb_kf_store_put_from_stereo(CorbKfStore* s, int slot, CorbStereo* sf, int 
 int corb_kf_store_put_from_rgbd(CorbKfStore* s, int slot, CorbRgbd* h, int frame, uint64_t keyframe_id);
 /* slot <- host arrays (adapters / tests); any pointer except kp / desc may be NULL (u_right, depth default to -1) */
 int corb_kf_store_put_host(CorbKfStore* s, int slot, const CorbKeyPoint* kp, const uint8_t* desc, const float* u_right, const float* depth, int n, uint64_t keyframe_id);
-/* the parts the host computes: DBoW2 FeatureVector (Frame::ComputeBoW, C/src/Frame.cc:397-406) and the per-feature "vpMapPoints[i] && !isBad()" flags */
+/* the parts the host computes: DBoW2 FeatureVector (Frame::ComputeBoW, C/src/Frame.cc:397-406) and the per-feature "vpMapPoints[i] && !isBad()" flags
+ * (corb_kf_store_compute_bow, last section, computes the FeatureVector on the device from the record's descriptors instead) */
 int corb_kf_store_set_bow(CorbKfStore* s, int slot, const CorbFeatVec* fv);
 int corb_kf_store_set_flags(CorbKfStore* s, int slot, const uint8_t* has_good_mappoint /* n entries, NULL = all 0 */);
 /* slot -> host (any output may be NULL; *n = feature count); fv arrays need max_features (+1 for the offsets) entries */
@@ -1025,6 +1026,77 @@ typedef struct CorbInitResult {
 int corb_mono_initialize(const CorbInitProblem* problems, int n_problems, float sigma, int max_iterations, float min_parallax, int min_triangulated,
                          const int32_t* rand_values /* n_problems x max_iterations x 8 */, int p3d_stride, int flags_stride, CorbInitResult* results /* n_problems */,
                          float* p3d, uint8_t* triangulated, uint8_t* inliers_h, uint8_t* inliers_f, float* scores, int device);
+
+/* ============================ place recognition: DBoW2 vocabulary transform and keyframe database =============================
+ * Frame::ComputeBoW / KeyFrame::ComputeBoW (C/src/Frame.cc:397-406) and C/src/KeyFrameDatabase.cc on the device.  The arithmetic is csrc/bow_math.h, the definition
+ * tests/dbow_reference.py (DESIGN.md section 2 lists the readings); BowVector values, scores and the six per-keyframe fields are bit-equal to it.  Only L1_NORM scoring
+ * (0) with TF_IDF weighting (0) exists -- what ORB-SLAM's vocabulary carries; anything else is CORB_ERR_ARG. */
+typedef struct CorbVoc CorbVoc;
+typedef struct CorbVocDesc {
+    int32_t k, L, scoring, weighting;           /* the first line of the text format; k <= 20, 1 <= L <= 10 (the loader's bounds, TemplatedVocabulary.h:1359) */
+    int32_t n_nodes;                            /* nodes below the root: ids 1 .. n_nodes in array order (the root is node 0) */
+    const int32_t* parent;                      /* [n_nodes] id of the parent, smaller than the node's own */
+    const int32_t* is_leaf;                     /* [n_nodes] > 0: a word; word ids are given in array order of the leaves */
+    const uint8_t* descriptor;                  /* [n_nodes][32] */
+    const double* weight;                       /* [n_nodes] read for the leaves */
+} CorbVocDesc;
+/* TemplatedVocabulary from flat arrays, or from the text format of loadFromTextFile (TemplatedVocabulary.h:1338-1424: `k L scoring weighting`, then one line
+ * `parent isLeaf d0 .. d31 weight` per node; children keep line order; blank lines make no node).  A parent at or after its child, a leaf with children, a node that is
+ * neither leaf nor parent, more than k children, k > 20 or an unsupported scoring / weighting: CORB_ERR_ARG with a message. */
+int corb_voc_create(const CorbVocDesc* desc, int device, CorbVoc** out);
+int corb_voc_load_text(const char* path, int device, CorbVoc** out);
+void corb_voc_destroy(CorbVoc* v);
+int corb_voc_info(const CorbVoc* v, int32_t* k, int32_t* L, int32_t* n_nodes /* with the root, like m_nodes.size() */, int32_t* n_words);
+#define CORB_BOW_MAX_FEATURES 8192              /* features per descriptor set: one set is sorted in the LDS of one workgroup */
+/* TemplatedVocabulary::transform(features, BowVector, FeatureVector, levelsup) (TemplatedVocabulary.h:1127-1194, :1218-1259; BowVector.cpp:34-84; FeatureVector.cpp:31)
+ * for n_sets descriptor sets in one call: set s is desc[offset[s] .. offset[s + 1]) x 32 bytes, at most CORB_BOW_MAX_FEATURES features, at most 65535 sets per call.  Outputs of set s start at
+ * offset[s]: bow_word / bow_value (ascending words, L1-normalised) with bow_count[s] entries; fv_node_id and fv_idx in CorbFeatVec form with fv_n_nodes[s] nodes, their
+ * offsets at fv_offset[offset[s] + s ..] (n_nodes + 1 entries; the array has offset[n_sets] + n_sets entries).  feat_word / feat_node (optional, per feature) are the
+ * descent's word and recorded node, stopped words included.  The node recorded is the one at depth L - levelsup, the root if that is <= 0, and the leaf itself if the
+ * descent ends above that depth.  Host pointers; two launches, one synchronisation, one read-back. */
+int corb_voc_transform(CorbVoc* v, const uint8_t* desc, const int32_t* offset, int n_sets, int levelsup, uint32_t* bow_word, double* bow_value, int32_t* bow_count,
+                       uint32_t* fv_node_id, int32_t* fv_offset, uint32_t* fv_idx, int32_t* fv_n_nodes, int32_t* feat_word, uint32_t* feat_node);
+
+/* KeyFrameDatabase (C/src/KeyFrameDatabase.cc:38-401) over entries 0 .. capacity_entries - 1.  An entry holds a BowVector of up to max_words words, the six fields the
+ * detect functions keep per keyframe, and its GetBestCovisibilityKeyFrames(10).  These live in this object, not in the keyframe record.  The inverted file is not kept:
+ * an entry's place in lKFsSharingWords is (its first word in common with the query, the sequence number of its add), which is the order the walk over
+ * mvInvertedFile[word] meets it in. */
+typedef struct CorbKfDb CorbKfDb;
+typedef struct CorbKfDbState {                  /* mnLoopQuery, mnLoopWords, mLoopScore, mnRelocQuery, mnRelocWords, mRelocScore; all 0 for a new keyframe */
+    uint64_t loop_query; int32_t loop_words; float loop_score; uint64_t reloc_query; int32_t reloc_words; float reloc_score;
+} CorbKfDbState;
+/* The database keeps a pointer to its vocabulary: destroy the databases of a vocabulary before the vocabulary. */
+int corb_kfdb_create(CorbVoc* voc, int capacity_entries, int max_words, CorbKfDb** out);
+void corb_kfdb_destroy(CorbKfDb* db);
+/* mBowVec of an entry (ascending words below the vocabulary's size, every value above 0 -- what the transform produces; a value that is not is CORB_ERR_ARG, because
+ * the kernels mark a word's presence in the query by its value).  Setting it makes the entry a new keyframe: its six fields are zeroed.  A live entry: CORB_ERR_ARG. */
+int corb_kfdb_set_bow(CorbKfDb* db, int entry, const uint32_t* word, const double* value, int n);
+int corb_kfdb_get_bow(CorbKfDb* db, int entry, uint32_t* word, double* value, int cap, int* n);
+/* add (:38-46), erase (:48-65), clear (:67-70; the per-keyframe fields stay).  Adding a live entry or one without a BowVector, erasing one that is not live: CORB_ERR_ARG. */
+int corb_kfdb_add(CorbKfDb* db, int entry);
+int corb_kfdb_erase(CorbKfDb* db, int entry);
+int corb_kfdb_clear(CorbKfDb* db);
+/* GetBestCovisibilityKeyFrames(10) of n entries as entry indices in that order, -1 padded: nb[n][10] */
+int corb_kfdb_set_neighbours(CorbKfDb* db, const int32_t* entries, int n, const int32_t* nb);
+int corb_kfdb_get_state(CorbKfDb* db, int first_entry, int n, CorbKfDbState* out);
+/* mpVoc->score(entry_a, entries_b[i]) (ScoringObject.cpp:23-68): the minScore loop of LoopClosing::DetectLoop (C/src/LoopClosing.cc:122-137) */
+int corb_kfdb_score(CorbKfDb* db, int entry_a, const int32_t* entries_b, int n, double* score);
+/* kind 0: DetectLoopCandidates (:73-187), 1: DetectRelocalizationCandidates (:297-401), 2: DetectMapFusionCandidatesFromDB (:189-295).  The query is any entry with a
+ * BowVector, live or not (a caller keeps one entry as the current Frame's); query_id is its mnId.  connected (GetConnectedKeyFrames as entries) and min_score are read
+ * for kind 0 only.  out = the candidates as entries in the reference's order, *n their number; more than cap: CORB_ERR_OVERFLOW with *n the size needed (the fields are
+ * updated all the same).  One call, one synchronisation, one read-back. */
+int corb_kfdb_detect(CorbKfDb* db, int kind, int query_entry, uint64_t query_id, const int32_t* connected, int n_connected, float min_score, int32_t* out, int cap, int* n);
+/* Frame::ComputeBoW / KeyFrame::ComputeBoW on records: the transform of the slots' descriptors, without a host trip of descriptors or vectors.  Writes each slot's
+ * FeatureVector into the record fields corb_kf_store_set_bow writes (and the host mirror of its node ids, from one small read-back), so every slots matcher works
+ * unchanged, and its BowVector into entries[i] of db as corb_kfdb_set_bow would (db may be NULL: the BowVector is dropped).  The store must hold at most
+ * CORB_BOW_MAX_FEATURES features per keyframe (CORB_ERR_ARG otherwise); a BowVector of more than the database's max_words words: CORB_ERR_CAPACITY, that entry is
+ * left without a BowVector. */
+int corb_kf_store_compute_bow(CorbKfStore* s, const int32_t* slots, int n_slots, CorbVoc* voc, int levelsup, CorbKfDb* db, const int32_t* entries);
+/* Event timing of this section's launches, process-wide (corb_orb_profile's form): per kernel the summed duration and the launch count since the last read, and four
+ * counters of the in-order sums taken with the device's wall clock inside the kernels -- "build: norm sum, one lane" beside "build: lane 0 in all" (bow_build_kernel), and
+ * "score: ordered sum, waves" beside "score: waves in all" (kfdb_score_kernel, summed over its wavefronts); for these `launches` holds the raw ticks.  Off by default. */
+int corb_bow_profile(int enable, int device);
+int corb_bow_profile_read(CorbKernelTime* out, int cap, int* n);   /* resets the accumulators */
 
 #ifdef __cplusplus
 }
