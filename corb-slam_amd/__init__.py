@@ -44,6 +44,8 @@ EXPORTS = [
     "corb_voc_create", "corb_voc_load_text", "corb_voc_destroy", "corb_voc_info", "corb_voc_transform", "corb_kf_store_compute_bow",
     "corb_kfdb_create", "corb_kfdb_destroy", "corb_kfdb_set_bow", "corb_kfdb_get_bow", "corb_kfdb_add", "corb_kfdb_erase", "corb_kfdb_clear", "corb_kfdb_set_neighbours",
     "corb_kfdb_get_state", "corb_kfdb_score", "corb_kfdb_detect", "corb_bow_profile", "corb_bow_profile_read",
+    "corb_covis_create", "corb_covis_destroy", "corb_covis_update", "corb_covis_erase", "corb_covis_get", "corb_covis_query", "corb_covis_weight",
+    "corb_covis_keyframe_culling", "corb_covis_local_window",
 ]
 
 
@@ -344,6 +346,16 @@ def load():
     L.corb_kfdb_get_state.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
     L.corb_kfdb_score.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
     L.corb_kfdb_detect.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_uint64, C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+    L.corb_covis_create.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]
+    L.corb_covis_destroy.argtypes = [C.c_void_p]
+    L.corb_covis_destroy.restype = None
+    L.corb_covis_update.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+    L.corb_covis_erase.argtypes = [C.c_void_p, C.c_int]
+    L.corb_covis_get.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.c_int]
+    L.corb_covis_query.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+    L.corb_covis_weight.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int)]
+    L.corb_covis_keyframe_culling.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+    L.corb_covis_local_window.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p, C.c_int, C.POINTER(C.c_int)]
     L.corb_bow_profile.argtypes = [C.c_int, C.c_int]
     L.corb_bow_profile_read.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int)]
     L.corb_kf_store_compute_bow.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
@@ -1450,6 +1462,78 @@ class KeyFrameDatabase:
 
     def DetectMapFusionCandidatesFromDB(self, query_entry, query_id):
         return self.detect(2, query_entry, query_id)
+
+
+NO_ID = 0xFFFFFFFFFFFFFFFF       # CORB_NO_MAP_POINT: "none"
+
+
+class Covisibility:
+    """The covisibility graph over a KeyFrameStore and a MapPointStore (corb_covis_*): KeyFrame::UpdateConnections, the covisibility queries, LocalMapping::KeyFrameCulling
+    and the window of Optimizer::LocalBundleAdjustment on records.  Keyframes are named by their slots; the queries answer slots."""
+
+    def __init__(self, kf_store, mp_store, max_connections=0):
+        self.h = C.c_void_p(); self.kf = kf_store; self.mp = mp_store; self.M = max_connections if max_connections > 0 else 512
+        _chk(load().corb_covis_create(kf_store.h, mp_store.h, int(max_connections), C.byref(self.h)), "corb_covis_create")
+
+    def close(self):
+        if self.h:
+            load().corb_covis_destroy(self.h); self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def UpdateConnections(self, slots, th=15):
+        """corb_covis_update for the slots in list order; returns the front of each keyframe's ordered list (its id, NO_ID if none)"""
+        s = np.ascontiguousarray(np.atleast_1d(slots), np.int32); fp = np.full(max(len(s), 1), NO_ID, np.uint64)
+        _chk(load().corb_covis_update(self.h, _p(s), len(s), int(th), _p(fp)), "corb_covis_update")
+        return fp[:len(s)].copy()
+
+    def EraseConnections(self, slot):
+        _chk(load().corb_covis_erase(self.h, int(slot)), "corb_covis_erase")
+
+    def get(self, slot):
+        """the row of a slot: (ids, weights) of the weight map in descending (weight, id), and (ids, weights) of the ordered list"""
+        M = self.M; ai = np.zeros(M, np.uint64); aw = np.zeros(M, np.int32); oi = np.zeros(M, np.uint64); ow = np.zeros(M, np.int32); na = C.c_int(0); no = C.c_int(0)
+        _chk(load().corb_covis_get(self.h, int(slot), _p(ai), _p(aw), C.byref(na), _p(oi), _p(ow), C.byref(no), M), "corb_covis_get")
+        return (ai[:na.value].copy(), aw[:na.value].copy()), (oi[:no.value].copy(), ow[:no.value].copy())
+
+    def query(self, slot, N=0, min_weight=0, cap=None):
+        cap = self.M if cap is None else cap
+        out = np.zeros(max(cap, 1), np.int32); w = np.zeros(max(cap, 1), np.int32); n = C.c_int(0)
+        _chk(load().corb_covis_query(self.h, int(slot), int(N), int(min_weight), _p(out), _p(w), int(cap), C.byref(n)), "corb_covis_query")
+        return out[:n.value].copy(), w[:n.value].copy()
+
+    def GetVectorCovisibleKeyFrames(self, slot):
+        return self.query(slot)[0]
+
+    def GetBestCovisibilityKeyFrames(self, slot, N):
+        return self.query(slot, N=N)[0]
+
+    def GetCovisiblesByWeight(self, slot, w):
+        return self.query(slot, min_weight=w)[0]
+
+    def GetWeight(self, slot_a, slot_b):
+        w = C.c_int(0)
+        _chk(load().corb_covis_weight(self.h, int(slot_a), int(slot_b), C.byref(w)), "corb_covis_weight")
+        return w.value
+
+    def KeyFrameCulling(self, cur_slot, monocular, th_depth, cap=None):
+        """per covisible keyframe of cur_slot: (slots, nMPs, nRedundantObservations, cull)"""
+        cap = self.M if cap is None else cap; m = max(cap, 1)
+        ks = np.zeros(m, np.int32); nm = np.zeros(m, np.int32); nr = np.zeros(m, np.int32); cu = np.zeros(m, np.uint8); n = C.c_int(0)
+        _chk(load().corb_covis_keyframe_culling(self.h, int(cur_slot), int(bool(monocular)), C.c_float(th_depth), _p(ks), _p(nm), _p(nr), _p(cu), int(cap), C.byref(n)),
+             "corb_covis_keyframe_culling")
+        k = n.value
+        return ks[:k].copy(), nm[:k].copy(), nr[:k].copy(), cu[:k].copy()
+
+    def LocalWindow(self, slot, kf_cap, mp_cap):
+        """(kf_slots, n_local, mp_slots): lLocalKeyFrames + lFixedCameras and lLocalMapPoints as corb_local_ba_store takes them"""
+        ks = np.zeros(max(kf_cap, 1), np.int32); ms = np.zeros(max(mp_cap, 1), np.int32); nl = C.c_int(0); nk = C.c_int(0); nm = C.c_int(0)
+        _chk(load().corb_covis_local_window(self.h, int(slot), _p(ks), int(kf_cap), C.byref(nl), C.byref(nk), _p(ms), int(mp_cap), C.byref(nm)), "corb_covis_local_window")
+        return ks[:nk.value].copy(), nl.value, ms[:nm.value].copy()
 
 
 class TrackCamera(C.Structure):

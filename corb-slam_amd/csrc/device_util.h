@@ -49,3 +49,6 @@ __device__ __forceinline__ bool corb_idtab_insert(const CorbIdTable& t, unsigned
         h = (h + 1) & t.mask;
     }
 }
+// mnId -> slot of the keyframe records [first, first + n) into a table prepared for corb_idtab_insert_min (map_kernels.hip: a slot without features is not a keyframe,
+// of two slots with one id the lower is the keyframe)
+void corb_launch_kf_index(const char* kf_base, size_t kf_bytes, int first, int n, CorbIdTable idt, hipStream_t s);

@@ -292,6 +292,10 @@ __global__ __launch_bounds__(256) void kf_index_kernel(const char* kf_base, size
     if (h->n <= 0) return;
     corb_idtab_insert_min(idt, h->m.id, first + i);
 }
+void corb_launch_kf_index(const char* kf_base, size_t kf_bytes, int first, int n, CorbIdTable idt, hipStream_t s)
+{
+    if (n > 0) hipLaunchKernelGGL(kf_index_kernel, dim3((n + 255) / 256), dim3(256), 0, s, kf_base, kf_bytes, first, n, idt);
+}
 __global__ __launch_bounds__(64) void mp_replace_kernel(MpReplaceDev t)
 {
     __shared__ unsigned short dist[DD_MAX_OBS];
@@ -356,7 +360,7 @@ __global__ __launch_bounds__(64) void mp_replace_kernel(MpReplaceDev t)
 void corb_launch_mp_replace(char* mp_base, size_t mp_bytes, int max_obs, int slot_this, int slot_into, char* kf_base, size_t kf_bytes, int F, int kf_first, int kf_n,
                             CorbIdTable kfid, unsigned long long* desc, int* status, hipStream_t s)
 {
-    if (kf_n > 0) hipLaunchKernelGGL(kf_index_kernel, dim3((kf_n + 255) / 256), dim3(256), 0, s, kf_base, kf_bytes, kf_first, kf_n, kfid);
+    corb_launch_kf_index(kf_base, kf_bytes, kf_first, kf_n, kfid, s);
     MpReplaceDev t; t.mp_base = mp_base; t.mp_bytes = mp_bytes; t.max_obs = max_obs; t.slot_this = slot_this; t.slot_into = slot_into;
     t.kf_base = kf_base; t.kf_bytes = kf_bytes; t.F = F; t.kfid = kfid; t.desc = desc; t.status = status;
     hipLaunchKernelGGL(mp_replace_kernel, dim3(1), dim3(64), 0, s, t);

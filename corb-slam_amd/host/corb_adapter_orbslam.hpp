@@ -1050,6 +1050,70 @@ private:
 };
 }  // namespace corb
 
+// ---- covisibility graph: what KeyFrame::UpdateConnections and its readers do, on the records (corb_covis_*) ----
+//   void KeyFrame::UpdateConnections()                                            KeyFrame.cc:404-502
+//   vector<KeyFrame*> GetVectorCovisibleKeyFrames() / GetBestCovisibilityKeyFrames(N) / GetCovisiblesByWeight(w); int GetWeight(KeyFrame*)   :199-269
+//   void LocalMapping::KeyFrameCulling()                                          LocalMapping.cc:590-648 (the decisions; SetBadFlag stays with the caller)
+//   the window of Optimizer::LocalBundleAdjustment                                Optimizer.cc:493-544 (as the slot lists MapStoreT::LocalBundleAdjustment takes)
+// The keyframes are named by the slots MapStoreT::PutKeyFrame filed them in (Bind).  The spanning tree stays with the objects: UpdateConnections returns the front of
+// the ordered list, which is mpParent on a keyframe's first connection (:493-499).  Db (optional) is the place-recognition database of this header: its
+// UpdateConnections(KeyFrame*) is called for the keyframe and for every keyframe on its ordered list -- the rows an update can change the best ten of.
+namespace corb {
+template <class KeyFrame, class Db>
+class Covisibility {
+public:
+    struct Culling { KeyFrame* pKF; int nMPs, nRedundantObservations; bool bCull; };
+    Covisibility(CorbKfStore* kf, CorbMpStore* mp, int max_connections = 0, Db* db = nullptr) : db_(db) { check(corb_covis_create(kf, mp, max_connections, &h_), "corb_covis_create"); }
+    Covisibility(const Covisibility&) = delete; Covisibility& operator=(const Covisibility&) = delete;
+    ~Covisibility() { if (h_) corb_covis_destroy(h_); }
+    void Bind(KeyFrame* pKF, int slot) { slot_[pKF] = slot; if ((int)kf_.size() <= slot) kf_.resize((size_t)slot + 1, nullptr); kf_[slot] = pKF; }
+    int Slot(KeyFrame* pKF) const { auto it = slot_.find(pKF); if (it == slot_.end()) throw Error(CORB_ERR_ARG, "Covisibility: keyframe without a slot (Bind)"); return it->second; }
+
+    KeyFrame* UpdateConnections(KeyFrame* pKF, int th = 15)
+    {
+        const int32_t s = Slot(pKF); uint64_t first = CORB_NO_MAP_POINT;
+        check(corb_covis_update(h_, &s, 1, th, &first), "corb_covis_update");
+        const std::vector<KeyFrame*> listed = GetVectorCovisibleKeyFrames(pKF);
+        if (db_) { db_->UpdateConnections(pKF); for (KeyFrame* p : listed) db_->UpdateConnections(p); }
+        return first == CORB_NO_MAP_POINT || listed.empty() ? nullptr : listed.front();
+    }
+    // the connection part of KeyFrame::SetBadFlag (KeyFrame.cc:592-595, :604-605)
+    void EraseConnections(KeyFrame* pKF) { check(corb_covis_erase(h_, Slot(pKF)), "corb_covis_erase"); }
+    std::vector<KeyFrame*> GetVectorCovisibleKeyFrames(KeyFrame* pKF) { return query(pKF, 0, 0); }
+    std::vector<KeyFrame*> GetBestCovisibilityKeyFrames(KeyFrame* pKF, int N) { return N > 0 ? query(pKF, N, 0) : std::vector<KeyFrame*>(); }
+    std::vector<KeyFrame*> GetCovisiblesByWeight(KeyFrame* pKF, int w) { return w > 0 ? query(pKF, 0, w) : query(pKF, 0, 1); }       // (every counted weight is at least 1)
+    int GetWeight(KeyFrame* pKF, KeyFrame* pOther) { int w = 0; check(corb_covis_weight(h_, Slot(pKF), Slot(pOther), &w), "corb_covis_weight"); return w; }
+    std::vector<Culling> KeyFrameCulling(KeyFrame* pCurrent, bool bMonocular, float thDepth)
+    {
+        std::vector<int32_t> s(cap()), nm(cap()), nr(cap()); std::vector<uint8_t> c(cap()); int n = 0;
+        check(corb_covis_keyframe_culling(h_, Slot(pCurrent), bMonocular ? 1 : 0, thDepth, s.data(), nm.data(), nr.data(), c.data(), (int)cap(), &n), "corb_covis_keyframe_culling");
+        std::vector<Culling> out;
+        for (int i = 0; i < n; i++) out.push_back(Culling{at(s[i]), nm[i], nr[i], c[i] != 0});
+        return out;
+    }
+    // lLocalKeyFrames, lFixedCameras, lLocalMapPoints as slots; maxKeyFrames / maxMapPoints bound the window (CORB_ERR_CAPACITY beyond)
+    void LocalWindow(KeyFrame* pKF, std::vector<int32_t>& localKfSlots, std::vector<int32_t>& fixedKfSlots, std::vector<int32_t>& mpSlots, int maxKeyFrames, int maxMapPoints)
+    {
+        std::vector<int32_t> ks((size_t)std::max(maxKeyFrames, 1)), ms((size_t)std::max(maxMapPoints, 1)); int nl = 0, nk = 0, nm = 0;
+        check(corb_covis_local_window(h_, Slot(pKF), ks.data(), maxKeyFrames, &nl, &nk, ms.data(), maxMapPoints, &nm), "corb_covis_local_window");
+        localKfSlots.assign(ks.begin(), ks.begin() + nl); fixedKfSlots.assign(ks.begin() + nl, ks.begin() + nk); mpSlots.assign(ms.begin(), ms.begin() + nm);
+    }
+    KeyFrame* at(int slot) const { return slot >= 0 && slot < (int)kf_.size() ? kf_[slot] : nullptr; }
+    CorbCovis* handle() const { return h_; }
+private:
+    size_t cap() const { return 1024; }                           // (COVIS_MAX_CONNECTIONS: no row is longer)
+    std::vector<KeyFrame*> query(KeyFrame* pKF, int N, int w)
+    {
+        std::vector<int32_t> s(cap()); int n = 0;
+        check(corb_covis_query(h_, Slot(pKF), N, w, s.data(), nullptr, (int)cap(), &n), "corb_covis_query");
+        std::vector<KeyFrame*> out; for (int i = 0; i < n; i++) out.push_back(at(s[i]));
+        return out;
+    }
+    CorbCovis* h_ = nullptr; Db* db_;
+    std::map<KeyFrame*, int> slot_; std::vector<KeyFrame*> kf_;
+};
+}  // namespace corb
+
 #if defined(__has_include)
 #if __has_include(<opencv2/core/core.hpp>) && __has_include("KeyFrame.h") && __has_include("Frame.h") && __has_include("MapPoint.h") && __has_include("Cache.h")
 #include <opencv2/core/core.hpp>
@@ -1071,6 +1135,7 @@ using PnPsolver = corb::PnPsolver<Frame, KeyFrame, MapPoint>;
 using Initializer = corb::Initializer<Frame>;
 using ORBVocabulary = corb::ORBVocabulary;
 using KeyFrameDatabase = corb::KeyFrameDatabase<KeyFrame, Frame>;
+using Covisibility = corb::Covisibility<KeyFrame, corb::KeyFrameDatabase<KeyFrame, Frame>>;
 }  // namespace accel
 }  // namespace ORB_SLAM2
 #endif

@@ -1098,6 +1098,50 @@ int corb_kf_store_compute_bow(CorbKfStore* s, const int32_t* slots, int n_slots,
 int corb_bow_profile(int enable, int device);
 int corb_bow_profile_read(CorbKernelTime* out, int cap, int* n);   /* resets the accumulators */
 
+/* ============================ covisibility graph on the stores ==============================
+ * KeyFrame::UpdateConnections / AddConnection / UpdateBestCovisibles / EraseConnection (C/src/KeyFrame.cc:133-168, :404-502, :685-698), the covisibility queries
+ * (:199-269), LocalMapping::KeyFrameCulling (C/src/LocalMapping.cc:590-648) and the window selection of Optimizer::LocalBundleAdjustment (C/src/Optimizer.cc:493-544),
+ * computed on the device from the records of a keyframe store and a map-point store.  The graph object holds, per slot of `kf`, mConnectedKeyFrameWeights (every
+ * counted id with its weight) and mvpOrderedConnectedKeyFrames / mvOrderedWeights (C/include/KeyFrame.h:291-293) in device memory; nothing is written into the records.
+ * What the reference's words mean here:
+ *   "in the cache" (Cache::KeyFrameInCache)  the id is the mnId of a slot of `kf` that holds features (of two such slots with one id: the lower); looked up per call
+ *   a non-bad MapPoint                       the id resolves through the map-point store's index (corb_mp_store_build_index; none: CORB_ERR_ARG) to a record without CORB_MP_BAD
+ *   MapPoint::Observations()                 derived from the observation list by corb_local_ba_store's rule: 2 for an observation whose keyframe is held and has
+ *                                            u_right[idx] >= 0, else 1 (the scratch field is not read)
+ * Every output is integer work and does not depend on the order the device's atomics land in.  max_connections (<= 0: 512; at most 1024) bounds the distinct ids of a
+ * row: a row is sorted in the local memory of one workgroup.  Locks: the graph, then the stores as corb_fuse_store does. */
+typedef struct CorbCovis CorbCovis;
+int corb_covis_create(CorbKfStore* kf, CorbMpStore* mp, int max_connections, CorbCovis** out);   /* the stores outlive the graph */
+void corb_covis_destroy(CorbCovis* g);
+/* KeyFrame::UpdateConnections (KeyFrame.cc:404-502) for slots[0 .. n) (distinct), AS IF called one after the other in list order, AddConnection (:133-148) on the rows of
+ * the listed keyframes included: the unchanged-weight early return leaves such a row's ordered list as it was, any other AddConnection rebuilds it from the row's WHOLE
+ * weight map (UpdateBestCovisibles, :150-168).  th = 15 in the reference (:445).  A keyframe whose counter is empty changes nothing (:438-439).  A counter without a
+ * single held keyframe (the reference dereferences NULL at :468) replaces the weight map and leaves the ordered list empty.
+ * first_parent[i] (optional) = id of the front of keyframe i's ordered list after its own update -- mpParent of :493-495 if this is its first connection and its id
+ * is not 0 -- or CORB_NO_MAP_POINT ("none") when there is none; the spanning tree itself stays with the caller.
+ * CORB_ERR_CAPACITY: a counter holds more than max_connections distinct ids; detected before anything is committed, the graph is unchanged.
+ * CORB_ERR_OVERFLOW: an AddConnection met a full row of ANOTHER keyframe; that connection is missing, the rest of the batch is applied. */
+int corb_covis_update(CorbCovis* g, const int32_t* slots, int n, int th, uint64_t* first_parent);
+/* the connection part of KeyFrame::SetBadFlag (KeyFrame.cc:592-595, :604-605): EraseConnection(this) (:685-698) on every keyframe of the row that the store holds, then the row cleared */
+int corb_covis_erase(CorbCovis* g, int slot);
+/* row -> host: the weight map in descending (weight, id) and the ordered list as it stands; more than cap entries in either: CORB_ERR_CAPACITY with the counts set */
+int corb_covis_get(CorbCovis* g, int slot, uint64_t* all_id, int32_t* all_w, int* n_all, uint64_t* ord_id, int32_t* ord_w, int* n_ord, int cap);
+/* GetVectorCovisibleKeyFrames (:199-211; N <= 0, min_weight <= 0), GetBestCovisibilityKeyFrames(N) (:213-230; min_weight <= 0) and GetCovisiblesByWeight(w) (:232-260;
+ * min_weight = w > 0, N <= 0) as SLOTS of kf, directly usable as nb_slots / kf_slots / corb_kfdb_set_neighbours input.  The first two drop the ids the store does not hold;
+ * the third keeps them as -1 and, like the reference's upper_bound followed by `it == end()`, answers an EMPTY list when every weight of the list reaches w.
+ * out_w (optional) = the weights.  More than cap: CORB_ERR_CAPACITY with *n the size needed. */
+int corb_covis_query(CorbCovis* g, int slot, int N, int min_weight, int32_t* out_slots, int32_t* out_w, int cap, int* n);
+int corb_covis_weight(CorbCovis* g, int slot_a, int slot_b, int* w);    /* GetWeight (:262-269): weight of keyframe slot_b in the map of slot_a, 0 if none */
+/* LocalMapping::KeyFrameCulling (LocalMapping.cc:590-648) for mpCurrentKeyFrame = cur_slot: per covisible keyframe, in GetVectorCovisibleKeyFrames order, its slot, nMPs,
+ * nRedundantObservations and the decision `nRedundantObservations > 0.9 * nMPs` (a keyframe with mnId 0 is skipped: 0, 0, 0).  th_depth = mThDepth, read unless monocular.
+ * An observation counts towards the three of :630-633 when its keyframe is held, is not this one and its feature index is below that keyframe's feature count.
+ * Nothing is written: SetBadFlag stays with the caller, who then calls corb_covis_erase. */
+int corb_covis_keyframe_culling(CorbCovis* g, int cur_slot, int monocular, float th_depth, int32_t* kf_slots, int32_t* n_mps, int32_t* n_redundant, uint8_t* cull, int cap, int* n);
+/* the window of Optimizer::LocalBundleAdjustment (Optimizer.cc:493-544): kf_slots[0 .. n_local) lLocalKeyFrames, [n_local .. n_kf) lFixedCameras, mp_slots lLocalMapPoints,
+ * in the reference's list orders (observations in ascending keyframe id) -- exactly the arguments corb_local_ba_store takes.  mnBALocalForKF / mnBAFixedForKF are
+ * per-call marks; no record changes.  A window larger than kf_cap / mp_cap: CORB_ERR_CAPACITY, nothing written. */
+int corb_covis_local_window(CorbCovis* g, int slot, int32_t* kf_slots, int kf_cap, int* n_local, int* n_kf, int32_t* mp_slots, int mp_cap, int* n_mp);
+
 #ifdef __cplusplus
 }
 #endif
