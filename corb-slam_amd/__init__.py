@@ -46,11 +46,18 @@ EXPORTS = [
     "corb_kfdb_get_state", "corb_kfdb_score", "corb_kfdb_detect", "corb_bow_profile", "corb_bow_profile_read",
     "corb_covis_create", "corb_covis_destroy", "corb_covis_update", "corb_covis_erase", "corb_covis_get", "corb_covis_query", "corb_covis_weight",
     "corb_covis_keyframe_culling", "corb_covis_local_window",
+    "corb_covis_set_tree", "corb_covis_get_tree", "corb_covis_add_child", "corb_covis_erase_child", "corb_covis_change_parent", "corb_covis_reparent_children",
+    "corb_track_update_local_map",
 ]
 
 
 class CorbError(RuntimeError):
     pass
+
+
+class LocalMap(C.Structure):
+    """CorbLocalMap: what corb_track_update_local_map reports beside its lists"""
+    _fields_ = [("n_kf", C.c_int32), ("n_voted", C.c_int32), ("n_mp", C.c_int32), ("ref_slot", C.c_int32), ("ref_id", C.c_uint64), ("counter_empty", C.c_int32), ("n_cleared", C.c_int32)]
 
 
 class OrbConfig(C.Structure):
@@ -356,6 +363,13 @@ def load():
     L.corb_covis_weight.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int)]
     L.corb_covis_keyframe_culling.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
     L.corb_covis_local_window.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+    L.corb_covis_set_tree.argtypes = [C.c_void_p, C.c_int, C.c_uint64, C.c_int, C.c_void_p, C.c_int]
+    L.corb_covis_get_tree.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_int), C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+    L.corb_covis_add_child.argtypes = [C.c_void_p, C.c_int, C.c_int]
+    L.corb_covis_erase_child.argtypes = [C.c_void_p, C.c_int, C.c_int]
+    L.corb_covis_change_parent.argtypes = [C.c_void_p, C.c_int, C.c_int]
+    L.corb_covis_reparent_children.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.corb_track_update_local_map.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(LocalMap)]
     L.corb_bow_profile.argtypes = [C.c_int, C.c_int]
     L.corb_bow_profile_read.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int)]
     L.corb_kf_store_compute_bow.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
@@ -1535,6 +1549,32 @@ class Covisibility:
         _chk(load().corb_covis_local_window(self.h, int(slot), _p(ks), int(kf_cap), C.byref(nl), C.byref(nk), _p(ms), int(mp_cap), C.byref(nm)), "corb_covis_local_window")
         return ks[:nk.value].copy(), nl.value, ms[:nm.value].copy()
 
+    # ---- the spanning tree (mpParent, mbFirstConnection, mspChildrens per slot) ----
+    def SetTree(self, slot, parent_id=NO_ID, first_connection=True, children=()):
+        ch = np.ascontiguousarray(children, np.uint64)
+        _chk(load().corb_covis_set_tree(self.h, int(slot), C.c_uint64(int(parent_id)), int(bool(first_connection)), _p(ch) if len(ch) else None, len(ch)), "corb_covis_set_tree")
+
+    def GetTree(self, slot):
+        """(parent id or NO_ID, mbFirstConnection, children ids ascending)"""
+        ch = np.zeros(self.M, np.uint64); p = C.c_uint64(0); f = C.c_int(0); n = C.c_int(0)
+        _chk(load().corb_covis_get_tree(self.h, int(slot), C.byref(p), C.byref(f), _p(ch), self.M, C.byref(n)), "corb_covis_get_tree")
+        return int(p.value), bool(f.value), ch[:n.value].copy()
+
+    def AddChild(self, slot, child_slot):
+        _chk(load().corb_covis_add_child(self.h, int(slot), int(child_slot)), "corb_covis_add_child")
+
+    def EraseChild(self, slot, child_slot):
+        _chk(load().corb_covis_erase_child(self.h, int(slot), int(child_slot)), "corb_covis_erase_child")
+
+    def ChangeParent(self, slot, other_slot):
+        _chk(load().corb_covis_change_parent(self.h, int(slot), int(other_slot)), "corb_covis_change_parent")
+
+    def ReparentChildren(self, slot):
+        """the tree part of KeyFrame::SetBadFlag, after EraseConnections(slot): (ChangeParent calls, whether the reference sets mbBad)"""
+        n = C.c_int(0); b = C.c_int(0)
+        _chk(load().corb_covis_reparent_children(self.h, int(slot), C.byref(n), C.byref(b)), "corb_covis_reparent_children")
+        return n.value, bool(b.value)
+
 
 class TrackCamera(C.Structure):
     """CorbTrackCamera: Frame intrinsics, image bounds and mvScaleFactors"""
@@ -1651,6 +1691,21 @@ class KeyFrameStore:
         _chk(load().corb_track_search_local_points(self.h, int(slot), mp_store.h, _p(ids), len(ids), C.byref(cam), _p(a), C.c_float(log_scale_factor), C.c_float(th),
                                                    C.c_float(nnratio), _p(m), _p(tr), C.byref(cnt), C.byref(inv)), "corb_track_search_local_points")
         return (m, cnt.value, inv.value, tr) if want_tracked else (m, cnt.value, inv.value)
+
+    def TrackUpdateLocalMap(self, slot, covis, prev_kf_slots=(), kf_cap=None, mp_cap=None):
+        """Tracking::UpdateLocalMap (Tracking.cc:1218-1366) for the frame in `slot` of this store against the graph `covis` (corb_track_update_local_map): returns
+        (kf_slots, mp_slots, mp_ids, info) -- mvpLocalKeyFrames and mvpLocalMapPoints as slots of the graph's stores, the points' ids as TrackSearchLocalPoints takes
+        them, and the LocalMap record (n_kf, n_voted, n_mp, ref_slot, ref_id, counter_empty, n_cleared).  kf_cap / mp_cap default to 128 keyframes and 16384 points;
+        a longer list answers CORB_ERR_CAPACITY with nothing written."""
+        prev = np.ascontiguousarray(prev_kf_slots, np.int32)
+        # the caps size the points pass's launch and the read-back (4 bytes per keyframe, 12 per point of the caps), so the defaults fit a local map, not the store:
+        # 128 keyframes (the walk stops beyond 80; only more voters than that give more) and 16384 points.  Larger maps: pass the caps.
+        kf_cap = max(min(covis.M, 128), 83, len(prev)) if kf_cap is None else int(kf_cap)
+        mp_cap = min(covis.mp.capacity, kf_cap * covis.kf.F, 16384) if mp_cap is None else int(mp_cap)
+        ks = np.zeros(max(kf_cap, 1), np.int32); ms = np.zeros(max(mp_cap, 1), np.int32); ids = np.zeros(max(mp_cap, 1), np.uint64); info = LocalMap()
+        _chk(load().corb_track_update_local_map(covis.h, self.h, int(slot), _p(prev) if len(prev) else None, len(prev), _p(ks), kf_cap, _p(ms), _p(ids), mp_cap, C.byref(info)),
+             "corb_track_update_local_map")
+        return ks[:info.n_kf].copy(), ms[:info.n_mp].copy(), ids[:info.n_mp].copy(), info
 
     def SearchByProjectionScw(self, slot, mp_store, mp_slots, cam, Scw, log_scale_factor, matched_ids, th=10):
         """ORBmatcher::SearchByProjection(pKF, Scw, vpPoints, vpMatched, th) (ORBmatcher.cc:425-538) on records (corb_search_by_projection_scw_store): pKF = this store's `slot`,

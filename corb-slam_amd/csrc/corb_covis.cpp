@@ -2,24 +2,11 @@
 // The graph keeps one row per slot of the keyframe store (the weight map and the ordered list of C/include/KeyFrame.h:291-293) in device memory.  Every call locks the
 // graph and the two stores (keyframes, then map points: the stores' documented order), waits for the stores' pending fills, rebuilds the keyframe id -> slot table
 // (the records' headers may have changed since the last call) and runs on the short-call lane of the per-device workspace, whose arena holds the call's scratch.
-#include "covis_internal.h"
-#include "store_host.h"
-#include "corb_workspace.h"
-#include <memory>
-#include <mutex>
+#include "covis_host.h"
 #include <vector>
 #include <algorithm>
 
-void corb_set_error(const char* fmt, ...);
-int corb_select_device(int device);
-#define HIPCHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { corb_set_error("%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); return CORB_ERR_HIP; } } while (0)
-
-struct CorbCovis {
-    CorbKfStore* kf = nullptr; CorbMpStore* mp = nullptr;
-    CovisRows R{};
-    char* mem = nullptr;
-    std::mutex mu;
-};
+#define HIPCHK COVIS_HIPCHK
 
 extern "C" int corb_covis_create(CorbKfStore* kf, CorbMpStore* mp, int max_connections, CorbCovis** out)
 {
@@ -38,6 +25,14 @@ extern "C" int corb_covis_create(CorbKfStore* kf, CorbMpStore* mp, int max_conne
     g->R.all_w = reinterpret_cast<int*>(g->R.ord_id + cells); g->R.ord_w = g->R.all_w + cells;
     g->R.n_all = reinterpret_cast<int*>(g->mem + cells * 24); g->R.n_ord = reinterpret_cast<int*>(g->mem + cells * 24 + heads);
     if (hipMemset(g->mem, 0, bytes) != hipSuccess) { corb_set_error("corb_covis_create: hipMemset failed"); (void)hipFree(g->mem); delete g; return CORB_ERR_HIP; }
+    // the spanning tree beside the rows: parent ids, child sets, then the two per-slot ints
+    const size_t tree_bytes = (((size_t)kf->capacity * 8 + 255) & ~(size_t)255) + cells * 8 + 2 * heads;
+    if (hipMalloc((void**)&g->tree_mem, tree_bytes) != hipSuccess) { corb_set_error("corb_covis_create: %d child sets x %d ids: allocation failed", kf->capacity, M); (void)hipFree(g->mem); delete g; return CORB_ERR_HIP; }
+    g->T.parent = reinterpret_cast<unsigned long long*>(g->tree_mem); g->T.child_id = reinterpret_cast<unsigned long long*>(g->tree_mem + (((size_t)kf->capacity * 8 + 255) & ~(size_t)255));
+    g->T.first = reinterpret_cast<int*>(g->T.child_id + cells); g->T.n_child = reinterpret_cast<int*>(reinterpret_cast<char*>(g->T.first) + heads);
+    covis_launch_tree_init(g->T, kf->capacity, nullptr);                                          // none / first connection / no children
+    // (a wait for the stream of the launch alone: the device's other streams, other clients' stores among them, are not waited for)
+    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(nullptr) != hipSuccess) { corb_set_error("corb_covis_create: the tree's initialisation failed"); (void)hipFree(g->tree_mem); (void)hipFree(g->mem); delete g; return CORB_ERR_HIP; }
     *out = g;
     return CORB_OK;
 }
@@ -46,40 +41,12 @@ extern "C" void corb_covis_destroy(CorbCovis* g)
     if (!g) return;
     (void)hipSetDevice(g->kf->device);
     if (g->mem) (void)hipFree(g->mem);
+    if (g->tree_mem) (void)hipFree(g->tree_mem);
     delete g;
 }
 
 namespace {
-// one call's hold on the graph and the stores, and the stores as the kernels read them
-struct CovisCall {
-    std::unique_lock<std::mutex> lk_g, lk_kf, lk_mp;
-    std::unique_ptr<CorbScratch> scratch;            // taken after the stores' locks, as every store call does
-    CovisStores S{};
-    int begin(CorbCovis* g, const char* who, bool need_points)
-    {
-        CorbKfStore* kf = g->kf; CorbMpStore* mp = g->mp;
-        lk_g = std::unique_lock<std::mutex>(g->mu); lk_kf = std::unique_lock<std::mutex>(kf->mu); lk_mp = std::unique_lock<std::mutex>(mp->mu);
-        scratch.reset(new CorbScratch(0));
-        CorbScratch& pool = *scratch;
-        if (!pool.stream) { corb_set_error("%s: no workspace stream", who); return CORB_ERR_HIP; }
-        if (need_points && (!mp->idt.keys || !mp->idt_valid)) { corb_set_error("%s: the map-point store has no current id index (corb_mp_store_build_index after the last put / push)", who); return CORB_ERR_ARG; }
-        HIPCHK(hipStreamSynchronize(kf->stream)); HIPCHK(hipStreamSynchronize(mp->stream));
-        S.kf_base = kf->base; S.kf_bytes = kf->L.bytes; S.F = kf->F; S.kf_capacity = kf->capacity;
-        S.mp_base = mp->base; S.mp_bytes = mp->L.bytes; S.O = mp->O; S.mp_capacity = mp->capacity; S.mpid = mp->idt;
-        unsigned int cap = 64; while (cap < 2u * (unsigned int)kf->capacity) cap <<= 1;
-        HIPCHK(pool.alloc(&S.kfid.keys, (size_t)cap)); HIPCHK(pool.alloc(&S.kfid.vals, (size_t)cap)); S.kfid.mask = cap - 1;
-        HIPCHK(hipMemsetAsync(S.kfid.keys, 0xFF, (size_t)cap * 8, pool.stream));
-        HIPCHK(hipMemsetAsync(S.kfid.vals, 0x7F, (size_t)cap * 4, pool.stream));              // (corb_idtab_insert_min)
-        corb_launch_kf_index(S.kf_base, S.kf_bytes, 0, S.kf_capacity, S.kfid, pool.stream);        // "in the cache" (Cache::KeyFrameInCache) means: found in this table
-        HIPCHK(hipGetLastError());
-        return CORB_OK;
-    }
-};
-int slot_ok(CorbCovis* g, int slot, const char* who)
-{
-    if (!g || slot < 0 || slot >= g->kf->capacity) { corb_set_error("%s: bad graph / slot", who); return CORB_ERR_ARG; }
-    return CORB_OK;
-}
+int slot_ok(CorbCovis* g, int slot, const char* who) { return covis_slot_ok(g, slot, who); }
 }
 
 extern "C" int corb_covis_update(CorbCovis* g, const int32_t* slots, int n, int th, uint64_t* first_parent)
@@ -110,13 +77,13 @@ extern "C" int corb_covis_update(CorbCovis* g, const int32_t* slots, int n, int 
         return CORB_ERR_CAPACITY;
     }
     // commit after: the members in list order, a launch each, nothing between them but the stream's order
-    for (int i = 0; i < n; i++) if (head[i].n_all > 0) covis_launch_apply(g->R, c.S, st, i, slots[i], head[i].n_ord, dover, pool.stream);
+    for (int i = 0; i < n; i++) if (head[i].n_all > 0) covis_launch_apply(g->R, g->T, c.S, st, i, slots[i], head[i].n_ord, dover, pool.stream);
     HIPCHK(hipGetLastError());
     int over = 0;
     HIPCHK(pool.d2h(&over, dover, 4));
     HIPCHK(pool.fetch_finish());
     if (first_parent) for (int i = 0; i < n; i++) first_parent[i] = head[i].first;
-    if (over) { corb_set_error("corb_covis_update: AddConnection found the row of a neighbour full (max_connections = %d); that connection is missing", M); return CORB_ERR_OVERFLOW; }
+    if (over) { corb_set_error("corb_covis_update: AddConnection / AddChild found the row or the child set of a neighbour full (max_connections = %d); that entry is missing", M); return CORB_ERR_OVERFLOW; }
     return CORB_OK;
 }
 
@@ -246,5 +213,89 @@ extern "C" int corb_covis_local_window(CorbCovis* g, int slot, int32_t* kf_slots
     if (cnt[1] > 0) HIPCHK(hipMemcpyAsync(mp_slots, w.mp_out, (size_t)cnt[1] * 4, hipMemcpyDeviceToHost, pool.stream));
     HIPCHK(hipStreamSynchronize(pool.stream));
     *n_local = cnt[0]; *n_kf = cnt[0] + cnt[2]; *n_mp = cnt[1];
+    return CORB_OK;
+}
+
+// ---- the spanning tree ----
+extern "C" int corb_covis_set_tree(CorbCovis* g, int slot, uint64_t parent_id, int first_connection, const uint64_t* children, int n)
+{
+    int rc = slot_ok(g, slot, "corb_covis_set_tree"); if (rc) return rc;
+    if (n < 0 || (n > 0 && !children)) { corb_set_error("corb_covis_set_tree: bad argument"); return CORB_ERR_ARG; }
+    if (n > g->R.M) { corb_set_error("corb_covis_set_tree: %d children, max_connections = %d", n, g->R.M); return CORB_ERR_OVERFLOW; }
+    std::vector<unsigned long long> ids(children, children + n);
+    std::sort(ids.begin(), ids.end());
+    if (std::adjacent_find(ids.begin(), ids.end()) != ids.end()) { corb_set_error("corb_covis_set_tree: a child is listed twice"); return CORB_ERR_ARG; }
+    rc = corb_select_device(g->kf->device); if (rc) return rc;
+    std::lock_guard<std::mutex> lk(g->mu);
+    CorbScratch pool(0);                                                                        // the short-call lane: staged copies on its stream, one synchronisation
+    if (!pool.stream) { corb_set_error("corb_covis_set_tree: no workspace stream"); return CORB_ERR_HIP; }
+    const unsigned long long p = parent_id; const int f = first_connection ? 1 : 0;
+    HIPCHK(pool.h2d(g->T.parent + slot, &p, 8)); HIPCHK(pool.h2d(g->T.first + slot, &f, 4)); HIPCHK(pool.h2d(g->T.n_child + slot, &n, 4));
+    if (n) HIPCHK(pool.h2d(g->T.child_id + (size_t)slot * g->R.M, ids.data(), (size_t)n * 8));
+    HIPCHK(hipStreamSynchronize(pool.stream));
+    return CORB_OK;
+}
+
+extern "C" int corb_covis_get_tree(CorbCovis* g, int slot, uint64_t* parent_id, int* first_connection, uint64_t* children, int cap, int* n)
+{
+    int rc = slot_ok(g, slot, "corb_covis_get_tree"); if (rc) return rc;
+    if (!n || cap < 0) { corb_set_error("corb_covis_get_tree: bad argument"); return CORB_ERR_ARG; }
+    rc = corb_select_device(g->kf->device); if (rc) return rc;
+    std::lock_guard<std::mutex> lk(g->mu);
+    CorbScratch pool(0);
+    if (!pool.stream) { corb_set_error("corb_covis_get_tree: no workspace stream"); return CORB_ERR_HIP; }
+    unsigned long long p = 0; int f = 0, nc = 0;
+    std::vector<unsigned long long> ch((size_t)g->R.M);                                         // the whole set's room (at most 8 KiB): the count comes back with it
+    HIPCHK(pool.d2h(&p, g->T.parent + slot, 8)); HIPCHK(pool.d2h(&f, g->T.first + slot, 4)); HIPCHK(pool.d2h(&nc, g->T.n_child + slot, 4));
+    if (children) HIPCHK(pool.d2h(ch.data(), g->T.child_id + (size_t)slot * g->R.M, ch.size() * 8));
+    HIPCHK(pool.fetch_finish());
+    if (parent_id) *parent_id = p;
+    if (first_connection) *first_connection = f;
+    nc = std::min(std::max(nc, 0), g->R.M);
+    *n = nc;
+    if (nc > cap) { corb_set_error("corb_covis_get_tree: the set holds %d children, cap = %d", nc, cap); return CORB_ERR_CAPACITY; }
+    if (children && nc) memcpy(children, ch.data(), (size_t)nc * 8);
+    return CORB_OK;
+}
+
+namespace {
+int tree_op(CorbCovis* g, int op, int slot, int other, const char* who)
+{
+    int rc = slot_ok(g, slot, who); if (rc) return rc;
+    rc = slot_ok(g, other, who); if (rc) return rc;
+    rc = corb_select_device(g->kf->device); if (rc) return rc;
+    CovisCall c; rc = c.begin(g, who, false); if (rc) return rc;
+    int* dover = nullptr;
+    HIPCHK(c.scratch->alloc(&dover, 1));
+    HIPCHK(hipMemsetAsync(dover, 0, 4, c.scratch->stream));
+    covis_launch_tree_op(g->R, g->T, c.S, op, slot, other, dover, c.scratch->stream);
+    HIPCHK(hipGetLastError());
+    int over = 0;
+    HIPCHK(c.scratch->d2h(&over, dover, 4));
+    HIPCHK(c.scratch->fetch_finish());
+    if (over) { corb_set_error("%s: the child set is full (max_connections = %d); the child is missing", who, g->R.M); return CORB_ERR_OVERFLOW; }
+    return CORB_OK;
+}
+}
+extern "C" int corb_covis_add_child(CorbCovis* g, int slot, int child_slot) { return tree_op(g, 0, slot, child_slot, "corb_covis_add_child"); }
+extern "C" int corb_covis_erase_child(CorbCovis* g, int slot, int child_slot) { return tree_op(g, 1, slot, child_slot, "corb_covis_erase_child"); }
+extern "C" int corb_covis_change_parent(CorbCovis* g, int slot, int other_slot) { return tree_op(g, 2, slot, other_slot, "corb_covis_change_parent"); }
+
+extern "C" int corb_covis_reparent_children(CorbCovis* g, int slot, int* n_changed, int* reference_sets_bad)
+{
+    int rc = slot_ok(g, slot, "corb_covis_reparent_children"); if (rc) return rc;
+    rc = corb_select_device(g->kf->device); if (rc) return rc;
+    CovisCall c; rc = c.begin(g, "corb_covis_reparent_children", false); if (rc) return rc;
+    int* d = nullptr;
+    HIPCHK(c.scratch->alloc(&d, 4));
+    HIPCHK(hipMemsetAsync(d, 0, 16, c.scratch->stream));
+    covis_launch_reparent(g->R, g->T, c.S, slot, d, c.scratch->stream);
+    HIPCHK(hipGetLastError());
+    int h[4] = {0, 0, 0, 0};
+    HIPCHK(c.scratch->d2h(h, d, 16));
+    HIPCHK(c.scratch->fetch_finish());
+    if (n_changed) *n_changed = h[0];
+    if (reference_sets_bad) *reference_sets_bad = h[1];
+    if (h[2]) { corb_set_error("corb_covis_reparent_children: the child set of a new parent is full (max_connections = %d); that child is missing from it", g->R.M); return CORB_ERR_OVERFLOW; }
     return CORB_OK;
 }

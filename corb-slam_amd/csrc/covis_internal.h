@@ -18,6 +18,12 @@ struct CovisRows {
     int *n_all, *n_ord;                      // [capacity]
     int M;
 };
+// The spanning tree beside the rows: mpParent / mbFirstConnection / mspChildrens of slot r (C/include/KeyFrame.h).  The set is kept in ascending id.
+struct CovisTree {
+    unsigned long long* parent;              // [capacity] an id, COVIS_NO_ID = none
+    unsigned long long* child_id;            // [capacity][M]
+    int *first, *n_child;                    // [capacity]
+};
 // the two stores as the kernels read them, with the per-call id -> slot table of the keyframes and the map-point store's index
 struct CovisStores {
     const char* kf_base; size_t kf_bytes; int F, kf_capacity; CorbIdTable kfid;
@@ -43,10 +49,19 @@ struct CovisWindow {                         // device scratch of one corb_covis
 
 size_t covis_lds_bytes(int M);
 void covis_launch_count(const CovisStores& S, const int* slots, int n, int th, int M, const CovisStage& st, hipStream_t s);
-void covis_launch_apply(const CovisRows& R, const CovisStores& S, const CovisStage& st, int member, int slot, int n_ord, int* overflow, hipStream_t s);
+void covis_launch_apply(const CovisRows& R, const CovisTree& T, const CovisStores& S, const CovisStage& st, int member, int slot, int n_ord, int* overflow, hipStream_t s);
 void covis_launch_erase(const CovisRows& R, const CovisStores& S, int slot, hipStream_t s);
 // mode 0: the in-store entries of the ordered list, the first N of them if N > 0; mode 1: GetCovisiblesByWeight(min_weight).  out_n[0] = entries written to out_slots / out_w ([M])
 void covis_launch_query(const CovisRows& R, const CovisStores& S, int slot, int N, int min_weight, int mode, int* out_slots, int* out_w, int* out_n, hipStream_t s);
 void covis_launch_weight(const CovisRows& R, const CovisStores& S, int slot_a, int slot_b, int* out_w, hipStream_t s);
 void covis_launch_culling(const CovisStores& S, const int* list, const int* n_list, int max_list, int monocular, float th_depth, int* n_mps, int* n_red, unsigned char* cull, hipStream_t s);
 void covis_launch_window(const CovisRows& R, const CovisStores& S, int slot, const CovisWindow& w, hipStream_t s);
+// the compaction of the window's points alone (pass 0, 1, scan, 2) over w.kf_out[0 .. counts[0]): corb_track_update_local_map's UpdateLocalPoints has this structure
+void covis_launch_window_points(const CovisStores& S, const CovisWindow& w, hipStream_t s);
+// ---- the spanning tree (one workgroup each) ----
+void covis_launch_tree_init(const CovisTree& T, int capacity, hipStream_t s);
+// op 0: AddChild(other), 1: EraseChild(other), 2: ChangeParent(other) on `slot`; overflow[0] is set when a full set refuses an id
+void covis_launch_tree_op(const CovisRows& R, const CovisTree& T, const CovisStores& S, int op, int slot, int other, int* overflow, hipStream_t s);
+// the tree part of SetBadFlag: out[0] = ChangeParent calls, out[1] = the `if` of :658 was entered, out[2] = a full set refused an id
+size_t covis_reparent_lds_bytes(int M);
+void covis_launch_reparent(const CovisRows& R, const CovisTree& T, const CovisStores& S, int slot, int* out, hipStream_t s);

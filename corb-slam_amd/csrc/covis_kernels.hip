@@ -4,48 +4,13 @@
 // is a sum, a row is a set of distinct ids put into the total (weight, id) order of covis_math.h, and the window lists take the FIRST position of the reference's walk
 // (atomicMin) and are placed by an exclusive scan.
 #include "covis_internal.h"
-#include "lane_exchange.h"
+#include "covis_device.h"
 
 extern __shared__ unsigned long long covis_lds[];
 
-// entries a row is sorted as: the power of two at or above max_connections, at least a wavefront
-__host__ __device__ static inline int covis_pow2(int M) { int p = 64; while (p < M) p <<= 1; return p; }
 // sort arrays of P entries (8 + 4 bytes), the vote table of 4 P slots (8 + 4 bytes), P scan entries
 size_t covis_lds_bytes(int M) { const size_t P = (size_t)covis_pow2(M); return P * 8 + 4 * P * 8 + P * 4 + 4 * P * 4 + P * 4; }
 
-__device__ __forceinline__ const KfHeader* covis_kf(const CovisStores& S, int slot) { return reinterpret_cast<const KfHeader*>(S.kf_base + (size_t)slot * S.kf_bytes); }
-__device__ __forceinline__ int covis_kf_n(const CovisStores& S, int slot) { return min(max(covis_kf(S, slot)->n, 0), S.F); }
-// the record of a non-bad map point by id, or nullptr (getMapPoint() is NULL, or isBad())
-__device__ __forceinline__ const char* covis_good_point(const CovisStores& S, unsigned long long id, int* slot_out)
-{
-    if (id == CORB_NO_MAP_POINT) return nullptr;
-    const int ms = corb_idtab_find(S.mpid, id);
-    if (ms < 0 || ms >= S.mp_capacity) return nullptr;
-    const char* r = S.mp_base + (size_t)ms * S.mp_bytes;
-    if (reinterpret_cast<const CorbMapPointRecord*>(r)->flags & CORB_MP_BAD) return nullptr;
-    *slot_out = ms;
-    return r;
-}
-__device__ __forceinline__ int covis_n_obs(const CovisStores& S, const char* mrec) { return min(max(reinterpret_cast<const CorbMapPointRecord*>(mrec)->n_obs, 0), S.O); }
-
-// a[0 .. n) -> exclusive prefix sums in place, the total returned to every thread; a thread owns ceil(n / COVIS_T) consecutive entries
-__device__ __forceinline__ int covis_block_scan(int* a, int n, int* sh)
-{
-    const int per = (n + COVIS_T - 1) / COVIS_T;
-    const int b = min((int)threadIdx.x * per, n), e = min(b + per, n);
-    int sum = 0;
-    for (int i = b; i < e; i++) sum += a[i];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int inc = lx_wave_incl_scan_i(sum);
-    if (lane == 63) sh[w] = inc;
-    __syncthreads();
-    int base = 0, total = 0;
-    for (int i = 0; i < COVIS_T / 64; i++) { if (i < w) base += sh[i]; total += sh[i]; }
-    int run = base + inc - sum;
-    for (int i = b; i < e; i++) { const int v = a[i]; a[i] = run; run += v; }
-    __syncthreads();
-    return total;
-}
 // P entries (w, id) in LDS -> descending (weight, id) (covis_before); pads carry w = -1 and sort behind every counted entry
 __device__ __forceinline__ void covis_sort(unsigned long long* sid, int* sw, int P)
 {
@@ -168,9 +133,67 @@ __device__ __forceinline__ int covis_row_find(const CovisRows& R, int x, int nx,
     return *sh_found;
 }
 
-// ---- the commit of one batch member (:461, :468, :489-491): workgroup 0 replaces the member's row, workgroup 1 + e runs AddConnection(this, weight) on the
-// e-th keyframe of its ordered list.  The rows are distinct, so the workgroups of one launch do not meet; the members of a batch are launches in list order. ----
-__global__ __launch_bounds__(COVIS_T) void covis_apply_kernel(CovisRows R, CovisStores S, CovisStage st, int member, int slot, int* overflow)
+// ---- the spanning tree: mspChildrens is a set of ids in ascending order (std::set<LightKeyFrame>), at most M of them ----
+// mspChildrens.insert(id) on slot x by the whole workgroup (sh: two ints of LDS); a full set refuses the id and sets *overflow
+__device__ __forceinline__ void covis_child_insert(const CovisTree& T, int M, int x, unsigned long long id, int* overflow, int* sh)
+{
+    const int tid = threadIdx.x;
+    if (tid == 0) { sh[0] = 0; sh[1] = 0; }
+    __syncthreads();
+    const int n = min(max(T.n_child[x], 0), M);
+    unsigned long long* c = T.child_id + (size_t)x * M;
+    unsigned long long keep[COVIS_MAX_CONNECTIONS / COVIS_T];
+    int below = 0; bool found = false;
+#pragma unroll
+    for (int r = 0; r < COVIS_MAX_CONNECTIONS / COVIS_T; r++) {
+        const int i = tid + r * COVIS_T;
+        keep[r] = i < n ? c[i] : COVIS_NO_ID;
+        if (i < n) { below += keep[r] < id ? 1 : 0; found = found || keep[r] == id; }
+    }
+    if (below) atomicAdd(&sh[0], below);
+    if (found) sh[1] = 1;
+    __syncthreads();
+    const int pos = sh[0], present = sh[1];
+    __syncthreads();
+    if (present) return;
+    if (n >= M) { if (tid == 0) *overflow = 1; return; }
+#pragma unroll
+    for (int r = 0; r < COVIS_MAX_CONNECTIONS / COVIS_T; r++) { const int i = tid + r * COVIS_T; if (i < n && keep[r] > id) c[i + 1] = keep[r]; }
+    if (tid == 0) { c[pos] = id; T.n_child[x] = n + 1; }
+    __threadfence_block();
+    __syncthreads();
+}
+// mspChildrens.erase(id) on slot x
+__device__ __forceinline__ void covis_child_erase(const CovisTree& T, int M, int x, unsigned long long id, int* sh)
+{
+    const int tid = threadIdx.x;
+    if (tid == 0) sh[1] = 0;
+    __syncthreads();
+    const int n = min(max(T.n_child[x], 0), M);
+    unsigned long long* c = T.child_id + (size_t)x * M;
+    unsigned long long keep[COVIS_MAX_CONNECTIONS / COVIS_T];
+    bool found = false;
+#pragma unroll
+    for (int r = 0; r < COVIS_MAX_CONNECTIONS / COVIS_T; r++) {
+        const int i = tid + r * COVIS_T;
+        keep[r] = i < n ? c[i] : COVIS_NO_ID;
+        if (i < n) found = found || keep[r] == id;
+    }
+    if (found) sh[1] = 1;
+    __syncthreads();
+    const int present = sh[1];
+    __syncthreads();
+    if (!present) return;
+#pragma unroll
+    for (int r = 0; r < COVIS_MAX_CONNECTIONS / COVIS_T; r++) { const int i = tid + r * COVIS_T; if (i < n && keep[r] > id) c[i - 1] = keep[r]; }
+    if (tid == 0) T.n_child[x] = n - 1;
+    __threadfence_block();
+    __syncthreads();
+}
+
+// ---- the commit of one batch member (:461, :468, :489-491, :493-499): a launch of 2 + (length of its ordered list) workgroups.  Workgroup 0 replaces the member's
+// row, workgroup 1 + e runs AddConnection(this, weight) on the e-th keyframe of its ordered list, the last workgroup keeps the spanning tree.  The rows are distinct, so the workgroups of one launch do not meet; the members of a batch are launches in list order. ----
+__global__ __launch_bounds__(COVIS_T) void covis_apply_kernel(CovisRows R, CovisTree T, CovisStores S, CovisStage st, int member, int slot, int* overflow)
 {
     const int M = R.M, P = covis_pow2(M), tid = threadIdx.x;
     unsigned long long* sid = covis_lds;
@@ -186,7 +209,21 @@ __global__ __launch_bounds__(COVIS_T) void covis_apply_kernel(CovisRows R, Covis
         return;
     }
     const int e = blockIdx.x - 1;
-    if (e >= hd.n_ord) return;
+    if (e == hd.n_ord) {                                                                     // the last workgroup: the spanning tree (:493-499); it touches no row
+        __shared__ int sh_ins[2];
+        const unsigned long long own = covis_kf(S, slot)->m.id;
+        if (hd.n_ord <= 0 || !T.first[slot] || own == 0ull) return;                           // if (mbFirstConnection && mnId != 0)
+        // (the front and its slot were staged before the earlier members of the batch were committed; they are still "as if one after the other" because a member's
+        // ordered list comes from its own counter over the records alone -- no commit of another member changes it)
+        const int px = st.ord_slot[srow];
+        if (tid == 0) T.parent[slot] = st.ord_id[srow];                                      // mpParent = mvpOrderedConnectedKeyFrames.front();
+        if (px >= 0 && px < S.kf_capacity) {                                                 // if (mpParent.getKeyFrame())
+            covis_child_insert(T, M, px, own, overflow, sh_ins);
+            if (tid == 0) T.first[slot] = 0;
+        }
+        return;
+    }
+    if (e > hd.n_ord) return;
     const int x = st.ord_slot[srow + e], w = st.ord_w[srow + e];
     if (x < 0 || x >= S.kf_capacity || x == slot) return;
     const unsigned long long key = covis_kf(S, slot)->m.id;
@@ -203,10 +240,10 @@ __global__ __launch_bounds__(COVIS_T) void covis_apply_kernel(CovisRows R, Covis
     covis_sort(sid, sw, P);
     covis_store_everything(R, x, sid, sw, nx);
 }
-void covis_launch_apply(const CovisRows& R, const CovisStores& S, const CovisStage& st, int member, int slot, int n_ord, int* overflow, hipStream_t s)
+void covis_launch_apply(const CovisRows& R, const CovisTree& T, const CovisStores& S, const CovisStage& st, int member, int slot, int n_ord, int* overflow, hipStream_t s)
 {
     const size_t lds = (size_t)covis_pow2(R.M) * 12;
-    hipLaunchKernelGGL(covis_apply_kernel, dim3(1 + n_ord), dim3(COVIS_T), lds, s, R, S, st, member, slot, overflow);
+    hipLaunchKernelGGL(covis_apply_kernel, dim3(2 + n_ord), dim3(COVIS_T), lds, s, R, T, S, st, member, slot, overflow);
 }
 
 // ---- the connection part of KeyFrame::SetBadFlag (:592-595): EraseConnection(this) on the e-th keyframe of the row's weight map (:685-698) ----
@@ -403,12 +440,7 @@ __global__ __launch_bounds__(COVIS_T) void covis_window_fixed_kernel(CovisStores
 void covis_launch_window(const CovisRows& R, const CovisStores& S, int slot, const CovisWindow& w, hipStream_t s)
 {
     hipLaunchKernelGGL(covis_window_local_kernel, dim3(1), dim3(COVIS_T), (size_t)covis_pow2(R.M) * 8, s, R, S, slot, w);
-    const long long n1 = (long long)w.local_bound * S.F;
-    const unsigned g1 = (unsigned)((n1 + COVIS_T - 1) / COVIS_T);
-    hipLaunchKernelGGL(covis_window_points_kernel, dim3(g1), dim3(COVIS_T), 0, s, S, w, n1, 0);
-    hipLaunchKernelGGL(covis_window_points_kernel, dim3(g1), dim3(COVIS_T), 0, s, S, w, n1, 1);
-    corb_launch_exclusive_scan(w.flag, w.pos, (size_t)n1, w.scan_scratch, s);
-    hipLaunchKernelGGL(covis_window_points_kernel, dim3(g1), dim3(COVIS_T), 0, s, S, w, n1, 2);
+    covis_launch_window_points(S, w, s);
     const long long n2 = (long long)w.mp_bound * S.O;
     if (n2 > 0) {
         const unsigned g2 = (unsigned)((n2 + COVIS_T - 1) / COVIS_T);
@@ -417,4 +449,130 @@ void covis_launch_window(const CovisRows& R, const CovisStores& S, int slot, con
         corb_launch_exclusive_scan(w.flag, w.pos, (size_t)n2, w.scan_scratch, s);
         hipLaunchKernelGGL(covis_window_fixed_kernel, dim3(g2), dim3(COVIS_T), 0, s, S, w, n2, 2);
     }
+}
+
+void covis_launch_window_points(const CovisStores& S, const CovisWindow& w, hipStream_t s)
+{
+    const long long n1 = (long long)w.local_bound * S.F;
+    if (n1 <= 0) return;
+    const unsigned g1 = (unsigned)((n1 + COVIS_T - 1) / COVIS_T);
+    hipLaunchKernelGGL(covis_window_points_kernel, dim3(g1), dim3(COVIS_T), 0, s, S, w, n1, 0);
+    hipLaunchKernelGGL(covis_window_points_kernel, dim3(g1), dim3(COVIS_T), 0, s, S, w, n1, 1);
+    corb_launch_exclusive_scan(w.flag, w.pos, (size_t)n1, w.scan_scratch, s);
+    hipLaunchKernelGGL(covis_window_points_kernel, dim3(g1), dim3(COVIS_T), 0, s, S, w, n1, 2);
+}
+
+// ---- the spanning tree's calls: one workgroup each ----
+__global__ __launch_bounds__(COVIS_T) void covis_tree_init_kernel(CovisTree T, int capacity)
+{
+    const int i = blockIdx.x * COVIS_T + threadIdx.x;
+    if (i < capacity) { T.parent[i] = COVIS_NO_ID; T.first[i] = 1; T.n_child[i] = 0; }
+}
+void covis_launch_tree_init(const CovisTree& T, int capacity, hipStream_t s)
+{
+    hipLaunchKernelGGL(covis_tree_init_kernel, dim3((capacity + COVIS_T - 1) / COVIS_T), dim3(COVIS_T), 0, s, T, capacity);
+}
+// AddChild / EraseChild / ChangeParent (KeyFrame.cc:504-521)
+__global__ __launch_bounds__(COVIS_T) void covis_tree_op_kernel(CovisRows R, CovisTree T, CovisStores S, int op, int slot, int other, int* overflow)
+{
+    __shared__ int sh_ins[2];
+    const unsigned long long oid = covis_kf(S, other)->m.id;
+    if (op == 0) covis_child_insert(T, R.M, slot, oid, overflow, sh_ins);                    // mspChildrens.insert(tLKF)
+    else if (op == 1) covis_child_erase(T, R.M, slot, oid, sh_ins);                          // mspChildrens.erase(tLKF)
+    else {
+        if (threadIdx.x == 0) T.parent[slot] = oid;                                          // mpParent = tLKF;
+        covis_child_insert(T, R.M, other, covis_kf(S, slot)->m.id, overflow, sh_ins);        // pKF->AddChild(this);
+    }
+}
+void covis_launch_tree_op(const CovisRows& R, const CovisTree& T, const CovisStores& S, int op, int slot, int other, int* overflow, hipStream_t s)
+{
+    hipLaunchKernelGGL(covis_tree_op_kernel, dim3(1), dim3(COVIS_T), 0, s, R, T, S, op, slot, other, overflow);
+}
+
+// ---- the tree part of KeyFrame::SetBadFlag (:607-668): one workgroup; the rounds are sequential, the (child, connected keyframe) pairs of a round are not ----
+size_t covis_reparent_lds_bytes(int M) { const size_t P = (size_t)covis_pow2(M); return P * 8 + (P + 2) * 8 + P * 4 + P * 4; }
+__global__ __launch_bounds__(COVIS_T) void covis_reparent_kernel(CovisRows R, CovisTree T, CovisStores S, int slot, int* out)
+{
+    const int M = R.M, P = covis_pow2(M), tid = threadIdx.x;
+    unsigned long long* cid = covis_lds;                       // [P]     mspChildrens of this keyframe
+    unsigned long long* cand = cid + P;                        // [P + 2] sParentCandidates, the non-NULL ones
+    int* cslot = reinterpret_cast<int*>(cand + P + 2);         // [P]     slot of the child, -1: getKeyFrame() is NULL
+    int* remain = cslot + P;                                   // [P]     still in the set
+    __shared__ unsigned long long sh_best;
+    __shared__ int sh_ins[2], sh_ncand, sh_changed;
+    const unsigned long long own = covis_kf(S, slot)->m.id;
+    const int nc = min(max(T.n_child[slot], 0), M);
+    const unsigned long long par = T.parent[slot];
+    int px = par == COVIS_NO_ID ? -1 : corb_idtab_find(S.kfid, par);                         // mpParent.getKeyFrame()
+    if (px >= S.kf_capacity) px = -1;
+    for (int i = tid; i < nc; i += COVIS_T) {
+        const unsigned long long id = T.child_id[(size_t)slot * M + i];
+        const int x = corb_idtab_find(S.kfid, id);
+        cid[i] = id; cslot[i] = x >= 0 && x < S.kf_capacity ? x : -1; remain[i] = 1;
+    }
+    if (tid == 0) { sh_ncand = 0; sh_changed = 0; if (px >= 0) { cand[0] = par; sh_ncand = 1; } }
+    __syncthreads();
+    int left = nc;
+    for (int round = 0; round < nc; round++) {                                               // while (!mspChildrens.empty())
+        if (tid == 0) sh_best = 0ull;
+        __syncthreads();
+        const int ncand = sh_ncand;
+        for (int ci = 0; ci < nc; ci++) {                                                    // uniform over the workgroup
+            if (!remain[ci]) continue;
+            const int x = cslot[ci];
+            if (x < 0 || (covis_kf(S, x)->m.flags & CORB_KF_BAD)) continue;                  // if (!pKF) continue; if (pKF->isBad()) continue;
+            const int no = min(max(R.n_ord[x], 0), M), na = min(max(R.n_all[x], 0), M);
+            const size_t row = (size_t)x * M;
+            for (int i = tid; i < no; i += COVIS_T) {                                        // vpConnected = pKF->GetVectorCovisibleKeyFrames()
+                const unsigned long long id = R.ord_id[row + i];
+                if (corb_idtab_find(S.kfid, id) < 0) continue;
+                bool is_cand = false;
+                for (int k = 0; k < ncand; k++) is_cand = is_cand || cand[k] == id;          // vpConnected[i]->mnId == (*spcit)->mnId
+                if (!is_cand) continue;
+                int w = 0;                                                                   // pKF->GetWeight(vpConnected[i])
+                for (int k = 0; k < na; k++) if (R.all_id[row + k] == id) w = R.all_w[row + k];
+                // `w > max` from max = -1, children in ascending id, the list in its order: the greatest weight, of equals the first met
+                atomicMax(&sh_best, ((unsigned long long)(unsigned int)(w + 1) << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned int)(ci * M + i)));
+            }
+        }
+        __syncthreads();
+        const unsigned long long best = sh_best;
+        if (best == 0ull) break;                                                             // !bContinue
+        const unsigned int code = 0xFFFFFFFFu - (unsigned int)(best & 0xFFFFFFFFull);
+        const int ci = (int)(code / (unsigned int)M), i = (int)(code % (unsigned int)M);
+        const int xc = cslot[ci];
+        const unsigned long long pid = R.ord_id[(size_t)xc * M + i], child = cid[ci];
+        const int xp = corb_idtab_find(S.kfid, pid);
+        __syncthreads();
+        if (tid == 0) { T.parent[xc] = pid; cand[ncand] = child; sh_ncand = ncand + 1; remain[ci] = 0; sh_changed++; }      // pC->ChangeParent(pP); sParentCandidates.insert(pC); mspChildrens.erase(pC)
+        if (xp >= 0 && xp < S.kf_capacity) covis_child_insert(T, M, xp, child, out + 2, sh_ins);
+        left--;
+        __syncthreads();
+    }
+    __syncthreads();
+    // the set without the re-parented children, written BEFORE the fallback: a keyframe can be its own parent (two keyframes that took each other as parents, one of
+    // them culled), and then the fallback's AddChild / EraseChild below work on this very set, as they do in the reference
+    if (tid == 0) {
+        int n = 0;
+        for (int ci = 0; ci < nc; ci++) if (remain[ci]) T.child_id[(size_t)slot * M + n++] = cid[ci];
+        T.n_child[slot] = n;
+    }
+    __threadfence_block();
+    __syncthreads();
+    if (left > 0 && px >= 0) {                                                               // if (!mspChildrens.empty() && mpParent.getKeyFrame())
+        for (int ci = 0; ci < nc; ci++) {
+            if (!remain[ci] || cslot[ci] < 0) continue;                                      // if ((*sit).getKeyFrame())
+            if (tid == 0) { T.parent[cslot[ci]] = par; sh_changed++; }                       // ->ChangeParent(mpParent.getKeyFrame())
+            covis_child_insert(T, M, px, cid[ci], out + 2, sh_ins);
+        }
+        covis_child_erase(T, M, px, own, sh_ins);                                            // mpParent.getKeyFrame()->EraseChild(this);
+        if (tid == 0) out[1] = 1;                                                            // mbBad = true;
+    }
+    __syncthreads();
+    if (tid == 0) out[0] = sh_changed;
+}
+void covis_launch_reparent(const CovisRows& R, const CovisTree& T, const CovisStores& S, int slot, int* out, hipStream_t s)
+{
+    const size_t lds = covis_reparent_lds_bytes(R.M);
+    hipLaunchKernelGGL(covis_reparent_kernel, dim3(1), dim3(COVIS_T), lds, s, R, T, S, slot, out);
 }

@@ -527,7 +527,38 @@ public:
 // ---- the tracking thread on device-resident records (corb_track_*, include/corb_accel.h): a Frame lives in a slot of a keyframe store, the client's map in a
 // map-point store; the calls below are Tracking::TrackWithMotionModel / TrackLocalMap's matcher and optimiser calls with the reference's argument meaning.
 // MapPoint needs two accessors the reference does not have (the raw mfMinDistance / mfMaxDistance next to Get*DistanceInvariance()): GetMinDistance(), GetMaxDistance().
+// what Tracking::UpdateLocalMap leaves (corb_track_update_local_map): mvpLocalKeyFrames / mvpLocalMapPoints as slots of the graph's stores, the points' ids as
+// SearchLocalPoints sends them, and pKFmax (refSlot -1: mpReferenceKF stays)
+struct LocalMapSlots { std::vector<int32_t> kfSlots, mpSlots; std::vector<uint64_t> mpIds; int nVoted = 0, refSlot = -1, nCleared = 0; bool counterEmpty = false; };
+inline LocalMapSlots UpdateLocalMapSlots(CorbCovis* graph, CorbKfStore* frames, int slot, const std::vector<int32_t>& prevKfSlots, int maxKeyFrames, int maxMapPoints)
+{
+    LocalMapSlots r; CorbLocalMap info; std::memset(&info, 0, sizeof(info));
+    r.kfSlots.resize((size_t)std::max(maxKeyFrames, 1)); r.mpSlots.resize((size_t)std::max(maxMapPoints, 1)); r.mpIds.resize((size_t)std::max(maxMapPoints, 1));
+    check(corb_track_update_local_map(graph, frames, slot, prevKfSlots.data(), (int)prevKfSlots.size(), r.kfSlots.data(), maxKeyFrames, r.mpSlots.data(), r.mpIds.data(), maxMapPoints, &info),
+          "corb_track_update_local_map");
+    r.kfSlots.resize((size_t)info.n_kf); r.mpSlots.resize((size_t)info.n_mp); r.mpIds.resize((size_t)info.n_mp);
+    r.nVoted = info.n_voted; r.refSlot = info.ref_slot; r.nCleared = info.n_cleared; r.counterEmpty = info.counter_empty != 0;
+    return r;
+}
+
 template <class Frame, class MapPoint, class Mat> struct FrameStoreT {
+    // void Tracking::UpdateLocalMap() for the Frame in `slot` of `store` (Tracking.cc:1218-1366): the lists as slots and ids; the frame's record loses its bad points
+    // (ReadBackMapPoints brings that into the Frame).  corb::Covisibility::UpdateLocalMap answers KeyFrame pointers.
+    static LocalMapSlots UpdateLocalMap(CorbCovis* graph, CorbKfStore* store, int slot, const std::vector<int32_t>& prevKfSlots, int maxKeyFrames, int maxMapPoints)
+    {
+        return UpdateLocalMapSlots(graph, store, slot, prevKfSlots, maxKeyFrames, maxMapPoints);
+    }
+    // void Tracking::SearchLocalPoints() with mvpLocalMapPoints as the ids UpdateLocalMap returned
+    static int SearchLocalPoints(CorbKfStore* store, int slot, CorbMpStore* map, const Frame& F, const std::vector<uint64_t>& localPointIds, const float th, float nnratio = 0.8f, int* nToMatch = nullptr)
+    {
+        float Tcw[16];
+        for (int r = 0; r < 4; r++) for (int c = 0; c < 4; c++) Tcw[4 * r + c] = matf(F.mTcw, r, c);
+        const CorbTrackCamera cam = Camera(F);
+        int n = 0, nv = 0;
+        check(corb_track_search_local_points(store, slot, map, localPointIds.data(), (int)localPointIds.size(), &cam, Tcw, F.mfLogScaleFactor, th, nnratio, nullptr, nullptr, &n, &nv), "corb_track_search_local_points");
+        if (nToMatch) *nToMatch = nv;
+        return n;
+    }
     static CorbTrackCamera Camera(const Frame& F)
     {
         CorbTrackCamera c; std::memset(&c, 0, sizeof(c));
@@ -1055,8 +1086,10 @@ private:
 //   vector<KeyFrame*> GetVectorCovisibleKeyFrames() / GetBestCovisibilityKeyFrames(N) / GetCovisiblesByWeight(w); int GetWeight(KeyFrame*)   :199-269
 //   void LocalMapping::KeyFrameCulling()                                          LocalMapping.cc:590-648 (the decisions; SetBadFlag stays with the caller)
 //   the window of Optimizer::LocalBundleAdjustment                                Optimizer.cc:493-544 (as the slot lists MapStoreT::LocalBundleAdjustment takes)
-// The keyframes are named by the slots MapStoreT::PutKeyFrame filed them in (Bind).  The spanning tree stays with the objects: UpdateConnections returns the front of
-// the ordered list, which is mpParent on a keyframe's first connection (:493-499).  Db (optional) is the place-recognition database of this header: its
+//   AddChild / EraseChild / ChangeParent / GetChilds / GetParent / hasChild and the tree part of SetBadFlag      KeyFrame.cc:504-543, :607-668
+//   void Tracking::UpdateLocalMap()                                               Tracking.cc:1218-1366
+// The keyframes are named by the slots MapStoreT::PutKeyFrame filed them in (Bind).  The spanning tree lives in the graph (corb_covis_update keeps it as :493-499 do);
+// UpdateConnections still returns the front of the ordered list, which is mpParent on a keyframe's first connection.  Db (optional) is the place-recognition database of this header: its
 // UpdateConnections(KeyFrame*) is called for the keyframe and for every keyframe on its ordered list -- the rows an update can change the best ten of.
 namespace corb {
 template <class KeyFrame, class Db>
@@ -1098,9 +1131,53 @@ public:
         check(corb_covis_local_window(h_, Slot(pKF), ks.data(), maxKeyFrames, &nl, &nk, ms.data(), maxMapPoints, &nm), "corb_covis_local_window");
         localKfSlots.assign(ks.begin(), ks.begin() + nl); fixedKfSlots.assign(ks.begin() + nl, ks.begin() + nk); mpSlots.assign(ms.begin(), ms.begin() + nm);
     }
+    // ---- the spanning tree ----
+    void AddChild(KeyFrame* pKF, KeyFrame* pChild) { check(corb_covis_add_child(h_, Slot(pKF), Slot(pChild)), "corb_covis_add_child"); }
+    void EraseChild(KeyFrame* pKF, KeyFrame* pChild) { check(corb_covis_erase_child(h_, Slot(pKF), Slot(pChild)), "corb_covis_erase_child"); }
+    void ChangeParent(KeyFrame* pKF, KeyFrame* pParent) { check(corb_covis_change_parent(h_, Slot(pKF), Slot(pParent)), "corb_covis_change_parent"); }
+    // mpParent's id (CORB_NO_MAP_POINT: none), mbFirstConnection and mspChildrens' ids in ascending order: what OptimizeEssentialGraph's tree edges are flattened from
+    void GetTree(KeyFrame* pKF, uint64_t* parentId, bool* firstConnection, std::vector<uint64_t>* childIds)
+    {
+        std::vector<uint64_t> c(cap()); uint64_t p = CORB_NO_MAP_POINT; int f = 0, n = 0;
+        check(corb_covis_get_tree(h_, Slot(pKF), &p, &f, c.data(), (int)cap(), &n), "corb_covis_get_tree");
+        if (parentId) *parentId = p;
+        if (firstConnection) *firstConnection = f != 0;
+        if (childIds) childIds->assign(c.begin(), c.begin() + n);
+    }
+    void SetTree(KeyFrame* pKF, uint64_t parentId, bool firstConnection, const std::vector<uint64_t>& childIds)
+    {
+        check(corb_covis_set_tree(h_, Slot(pKF), parentId, firstConnection ? 1 : 0, childIds.data(), (int)childIds.size()), "corb_covis_set_tree");
+    }
+    KeyFrame* GetParent(KeyFrame* pKF) { uint64_t p; GetTree(pKF, &p, nullptr, nullptr); return byId(p); }              // getKeyFrameInCache(): NULL for a keyframe without a slot
+    std::vector<KeyFrame*> GetChilds(KeyFrame* pKF)                                                                       // ascending mnId; the ones without a slot dropped (:523-532)
+    {
+        std::vector<uint64_t> c; GetTree(pKF, nullptr, nullptr, &c);
+        std::vector<KeyFrame*> out; for (uint64_t id : c) if (KeyFrame* p = byId(id)) out.push_back(p);
+        return out;
+    }
+    bool hasChild(KeyFrame* pKF, KeyFrame* pChild) { std::vector<uint64_t> c; GetTree(pKF, nullptr, nullptr, &c); return std::binary_search(c.begin(), c.end(), (uint64_t)pChild->mnId); }
+    // the tree part of KeyFrame::SetBadFlag (:607-668), after EraseConnections(pKF); returns whether the reference sets mbBad (its `if` of :658)
+    bool ReparentChildren(KeyFrame* pKF, int* nChanged = nullptr)
+    {
+        int n = 0, bad = 0;
+        check(corb_covis_reparent_children(h_, Slot(pKF), &n, &bad), "corb_covis_reparent_children");
+        if (nChanged) *nChanged = n;
+        return bad != 0;
+    }
+    // void Tracking::UpdateLocalMap() for the frame in `slot` of `frames`: mvpLocalKeyFrames (in and out), the local points as slots and ids, *ppReferenceKF = pKFmax
+    // when there is one (mpReferenceKF stays otherwise)
+    adapt::LocalMapSlots UpdateLocalMap(CorbKfStore* frames, int slot, std::vector<KeyFrame*>& vpLocalKeyFrames, KeyFrame** ppReferenceKF, int maxMapPoints, int maxKeyFrames = 128)
+    {
+        std::vector<int32_t> prev; for (KeyFrame* p : vpLocalKeyFrames) prev.push_back(Slot(p));
+        adapt::LocalMapSlots r = adapt::UpdateLocalMapSlots(h_, frames, slot, prev, std::max(maxKeyFrames, (int)prev.size()), maxMapPoints);
+        vpLocalKeyFrames.clear(); for (int32_t s : r.kfSlots) vpLocalKeyFrames.push_back(at(s));
+        if (ppReferenceKF && r.refSlot >= 0) *ppReferenceKF = at(r.refSlot);
+        return r;
+    }
     KeyFrame* at(int slot) const { return slot >= 0 && slot < (int)kf_.size() ? kf_[slot] : nullptr; }
     CorbCovis* handle() const { return h_; }
 private:
+    KeyFrame* byId(uint64_t id) const { if (id != CORB_NO_MAP_POINT) for (KeyFrame* p : kf_) if (p && (uint64_t)p->mnId == id) return p; return nullptr; }
     size_t cap() const { return 1024; }                           // (COVIS_MAX_CONNECTIONS: no row is longer)
     std::vector<KeyFrame*> query(KeyFrame* pKF, int N, int w)
     {

@@ -1118,9 +1118,10 @@ void corb_covis_destroy(CorbCovis* g);
  * weight map (UpdateBestCovisibles, :150-168).  th = 15 in the reference (:445).  A keyframe whose counter is empty changes nothing (:438-439).  A counter without a
  * single held keyframe (the reference dereferences NULL at :468) replaces the weight map and leaves the ordered list empty.
  * first_parent[i] (optional) = id of the front of keyframe i's ordered list after its own update -- mpParent of :493-495 if this is its first connection and its id
- * is not 0 -- or CORB_NO_MAP_POINT ("none") when there is none; the spanning tree itself stays with the caller.
+ * is not 0 -- or CORB_NO_MAP_POINT ("none") when there is none.  The spanning tree is kept in the graph and maintained by this call (see the tree section below).
  * CORB_ERR_CAPACITY: a counter holds more than max_connections distinct ids; detected before anything is committed, the graph is unchanged.
- * CORB_ERR_OVERFLOW: an AddConnection met a full row of ANOTHER keyframe; that connection is missing, the rest of the batch is applied. */
+ * CORB_ERR_OVERFLOW: an AddConnection met a full row of ANOTHER keyframe (or the first connection's AddChild a full child set); that entry is missing, the rest of
+ * the batch is applied. */
 int corb_covis_update(CorbCovis* g, const int32_t* slots, int n, int th, uint64_t* first_parent);
 /* the connection part of KeyFrame::SetBadFlag (KeyFrame.cc:592-595, :604-605): EraseConnection(this) (:685-698) on every keyframe of the row that the store holds, then the row cleared */
 int corb_covis_erase(CorbCovis* g, int slot);
@@ -1141,6 +1142,54 @@ int corb_covis_keyframe_culling(CorbCovis* g, int cur_slot, int monocular, float
  * in the reference's list orders (observations in ascending keyframe id) -- exactly the arguments corb_local_ba_store takes.  mnBALocalForKF / mnBAFixedForKF are
  * per-call marks; no record changes.  A window larger than kf_cap / mp_cap: CORB_ERR_CAPACITY, nothing written. */
 int corb_covis_local_window(CorbCovis* g, int slot, int32_t* kf_slots, int kf_cap, int* n_local, int* n_kf, int32_t* mp_slots, int mp_cap, int* n_mp);
+
+/* ---- the spanning tree (mpParent, mbFirstConnection, mspChildrens of C/include/KeyFrame.h) per slot of the graph's keyframe store, in device memory beside the rows ----
+ * mpParent is an id or CORB_NO_MAP_POINT ("none"); a fresh graph holds none / first connection / no children for every slot.  mspChildrens is a set of ids kept in
+ * ascending id (LightKeyFrame::operator<), stored explicitly and NOT derived from the parent pointers: ChangeParent never removes the keyframe from its old parent's set,
+ * as in the reference.  A set holds at most max_connections ids; an insertion into a full set is skipped and answers CORB_ERR_OVERFLOW, as a full row does.
+ * corb_covis_update maintains the tree as KeyFrame.cc:493-499 does, per member in list order: a member with mbFirstConnection and mnId != 0 takes the front of its ordered
+ * list (after its own update) as mpParent; if the store holds that keyframe it gains the member as a child and mbFirstConnection clears.  An empty ordered list (empty
+ * counter, or the no-held-keyframe reading) changes nothing. */
+int corb_covis_set_tree(CorbCovis* g, int slot, uint64_t parent_id, int first_connection, const uint64_t* children, int n);   /* what an archive or a push delivers; children distinct, any order */
+int corb_covis_get_tree(CorbCovis* g, int slot, uint64_t* parent_id, int* first_connection, uint64_t* children, int cap, int* n);   /* children ascending; more than cap: CORB_ERR_CAPACITY with *n set */
+int corb_covis_add_child(CorbCovis* g, int slot, int child_slot);      /* KeyFrame::AddChild (KeyFrame.cc:504-508): mspChildrens.insert(child's mnId) */
+int corb_covis_erase_child(CorbCovis* g, int slot, int child_slot);    /* KeyFrame::EraseChild (:510-514) */
+int corb_covis_change_parent(CorbCovis* g, int slot, int other_slot);  /* KeyFrame::ChangeParent (:516-521): mpParent = other; other->AddChild(this) -- nothing else */
+/* The tree part of KeyFrame::SetBadFlag (:607-668) for the keyframe of `slot`; call it after corb_covis_erase(slot), as the reference orders it.  The greedy loop: per
+ * round every child (ascending id; a child the store does not hold or a bad one is skipped) walks its GetVectorCovisibleKeyFrames() in list order, an entry whose mnId
+ * equals a parent candidate's competes with GetWeight, a strict `>` keeps the first best; the winner gets ChangeParent, joins the candidates (which start as the held
+ * mpParent) and leaves the set.  What is left goes to the original parent ONLY under the reference's condition `!mspChildrens.empty() && mpParent held` (:658), and
+ * `mpParent->EraseChild(this)` and `mbBad = true` sit inside that same `if`: a keyframe whose children were all re-parented, or that had none, is NOT erased from its
+ * parent's set and the reference does not mark it bad.  *reference_sets_bad tells which (1: the `if` was entered).  The leftover children stay in the set (the reference
+ * does not clear it).  *n_changed = ChangeParent calls made.  CORB_KF_BAD itself stays the caller's to set. */
+int corb_covis_reparent_children(CorbCovis* g, int slot, int* n_changed, int* reference_sets_bad);
+
+/* Tracking::UpdateLocalMap (C/src/Tracking.cc:1218-1366): UpdateLocalKeyFrames + UpdateLocalPoints for the current frame = record `slot` of `frames` (the graph's keyframe
+ * store or another one).  prev_kf_slots = mvpLocalKeyFrames before the call; kf_slots / mp_slots / mp_ids = mvpLocalKeyFrames / mvpLocalMapPoints after it, as slots of the
+ * graph's stores; mp_ids is the local_ids argument of corb_track_search_local_points.  What the reference's words mean here:
+ *   walk orders    keyframeCounter, GetChilds() and GetObservations() are pointer-keyed containers in the reference (allocator-dependent order); here every such walk
+ *                  is in ASCENDING KEYFRAME ID.  pKFmax is the non-bad voter with the most votes, the smallest id among equals (strict `>`, :1299)
+ *   a voter        an observer the graph's keyframe store holds (GetObservations, MapPoint.cc:219-231); other observers are dropped before counting
+ *   :1278          a feature whose point resolves to a bad record loses its point IN THE FRAME RECORD; an id that does not resolve is left alone (n_cleared counts)
+ *   :1282          an empty counter returns early: the list is prev_kf_slots unchanged, the reference keyframe untouched (ref_slot -1), counter_empty set;
+ *                  UpdateLocalPoints still runs on that list.  A non-empty counter whose voters are all bad gives an empty list and no points
+ *   :1310-1360     the neighbour walk runs over the voted keyframes only (the end iterator is taken before the pushes), stops when the list holds more than 80 at the
+ *                  top of an iteration, pushes per keyframe the first not-yet-included non-bad member of GetBestCovisibilityKeyFrames(10), then the first such child,
+ *                  then the parent if not yet included -- and the `break` after pushing a parent LEAVES THE WHOLE WALK (:1356)
+ *   marks          mnTrackReferenceForFrame of keyframes and points are per-call; no record but the frame's is written
+ *   :1230-1256     UpdateLocalPoints does not test pKF->isBad(): every feature's point that resolves and is not bad, first occurrence in (list order, feature order)
+ * CORB_ERR_CAPACITY: more than max_connections distinct voters, or a list beyond kf_cap / mp_cap; detected before anything is written, the frame record's cleared points
+ * included.  Without a map-point index, or with an empty slot as the frame or among prev_kf_slots: CORB_ERR_ARG.  One read-back per call: the true counts are not known
+ * before it, so 4 bytes per keyframe of kf_cap and 12 per point of mp_cap cross whatever the lists hold, and kf_cap x (feature capacity) sizes the points pass's launch --
+ * size the caps for a local map (a hundred keyframes, some thousand points), not for the stores.  Locks: the graph, then each store once as corb_fuse_store does. */
+typedef struct CorbLocalMap {
+    int32_t n_kf, n_voted, n_mp;    /* local keyframes, the voted ones among them (the front of the list), local map points */
+    int32_t ref_slot;               /* pKFmax as a slot, -1: mpReferenceKF unchanged */
+    uint64_t ref_id;                /* its mnId, CORB_NO_MAP_POINT if none */
+    int32_t counter_empty, n_cleared;
+} CorbLocalMap;
+int corb_track_update_local_map(CorbCovis* g, CorbKfStore* frames, int slot, const int32_t* prev_kf_slots, int n_prev, int32_t* kf_slots, int kf_cap,
+                                int32_t* mp_slots, uint64_t* mp_ids, int mp_cap, CorbLocalMap* out);
 
 #ifdef __cplusplus
 }
