@@ -48,6 +48,7 @@ EXPORTS = [
     "corb_covis_keyframe_culling", "corb_covis_local_window",
     "corb_covis_set_tree", "corb_covis_get_tree", "corb_covis_add_child", "corb_covis_erase_child", "corb_covis_change_parent", "corb_covis_reparent_children",
     "corb_track_update_local_map",
+    "corb_loop_correct_store", "corb_fuse_sim3_store", "corb_gba_propagate_store", "corb_covis_set_pose_before_gba", "corb_covis_get_pose_before_gba",
 ]
 
 
@@ -58,6 +59,11 @@ class CorbError(RuntimeError):
 class LocalMap(C.Structure):
     """CorbLocalMap: what corb_track_update_local_map reports beside its lists"""
     _fields_ = [("n_kf", C.c_int32), ("n_voted", C.c_int32), ("n_mp", C.c_int32), ("ref_slot", C.c_int32), ("ref_id", C.c_uint64), ("counter_empty", C.c_int32), ("n_cleared", C.c_int32)]
+
+
+class GbaPropagation(C.Structure):
+    """CorbGbaPropagation: the counts of corb_gba_propagate_store"""
+    _fields_ = [(k, C.c_int32) for k in ("n_popped", "n_reached", "n_propagated", "n_revisited", "n_points_set", "n_points_moved", "n_points_skipped")]
 
 
 class OrbConfig(C.Structure):
@@ -1575,6 +1581,33 @@ class Covisibility:
         _chk(load().corb_covis_reparent_children(self.h, int(slot), C.byref(n), C.byref(b)), "corb_covis_reparent_children")
         return n.value, bool(b.value)
 
+    # ---- CorrectLoop's propagation on records ----
+    def CorrectLoop(self, cur_slot, Scw, scale_factor=0.0, cap=None):
+        """corb_loop_correct_store for mpCurrentKF = cur_slot and mg2oScw = Scw (8 doubles: quaternion x y z w, t, s): (kf_slots, CorrectedSim3 [n, 8],
+        NonCorrectedSim3 [n, 8], points corrected), the set in ascending keyframe id.  Follow it with UpdateConnections(kf_slots)."""
+        cap = self.M + 1 if cap is None else int(cap); m = max(cap, 1)
+        S = np.ascontiguousarray(Scw, np.float64).reshape(8)
+        ks = np.zeros(m, np.int32); co = np.zeros((m, 8), np.float64); nc = np.zeros((m, 8), np.float64); n = C.c_int(0); npt = C.c_int(0)
+        _chk(load().corb_loop_correct_store(self.h, int(cur_slot), _p(S), C.c_float(scale_factor), _p(ks), _p(co), _p(nc), cap, C.byref(n), C.byref(npt)), "corb_loop_correct_store")
+        k = n.value
+        return ks[:k].copy(), co[:k].copy(), nc[:k].copy(), npt.value
+
+    # ---- the map update after a global bundle adjustment (RunGlobalBundleAdjustment's spread through the tree) ----
+    def PropagateGlobalBA(self, origin_slots, loop_kf, queue_cap=0):
+        """corb_gba_propagate_store: TcwGBA / pos_gba become Tcw / world_pos, unmarked keyframes are corrected through the child sets; returns the counts"""
+        o = np.ascontiguousarray(np.atleast_1d(origin_slots), np.int32); out = GbaPropagation()
+        _chk(load().corb_gba_propagate_store(self.h, _p(o) if len(o) else None, len(o), C.c_uint64(int(loop_kf)), int(queue_cap), C.byref(out)), "corb_gba_propagate_store")
+        return out
+
+    def SetPoseBeforeGBA(self, slot, T):
+        a = np.ascontiguousarray(T, np.float32).reshape(16)
+        _chk(load().corb_covis_set_pose_before_gba(self.h, int(slot), _p(a)), "corb_covis_set_pose_before_gba")
+
+    def GetPoseBeforeGBA(self, slot):
+        a = np.zeros(16, np.float32)
+        _chk(load().corb_covis_get_pose_before_gba(self.h, int(slot), _p(a)), "corb_covis_get_pose_before_gba")
+        return a.reshape(4, 4)
+
 
 class TrackCamera(C.Structure):
     """CorbTrackCamera: Frame intrinsics, image bounds and mvScaleFactors"""
@@ -1728,6 +1761,15 @@ class KeyFrameStore:
         _chk(load().corb_fuse_store(self.h, int(slot), mp_store.h, _p(ms), len(ms), C.byref(cam), _p(T), C.c_float(log_scale_factor), C.c_float(th), int(bool(apply)),
                                     _p(bi), _p(bd), _p(act), C.byref(n)), "corb_fuse_store")
         return bi[: len(ms)], bd[: len(ms)], n.value, act[: len(ms)]
+
+    def FuseSim3(self, slot, mp_store, mp_slots, cam, Scw, log_scale_factor, th=4.0, apply=False):
+        """ORBmatcher::Fuse(pKF, Scw, vpPoints, th, vpReplacePoint) on records (corb_fuse_sim3_store): Scw = 16 floats.  Returns (best_idx, best_dist, n_fused, action,
+        replace_slot): action 1 = entered an empty feature, 2 = replace_slot holds vpReplacePoint (Replace pending, -1: the id has no record), 4 = the feature's point is bad."""
+        ms = np.ascontiguousarray(mp_slots, np.int32); T = np.ascontiguousarray(Scw, np.float32).reshape(16); k = max(len(ms), 1)
+        bi = np.full(k, -1, np.int32); bd = np.full(k, 256, np.int32); act = np.zeros(k, np.uint8); rs = np.full(k, -1, np.int32); n = C.c_int(0)
+        _chk(load().corb_fuse_sim3_store(self.h, int(slot), mp_store.h, _p(ms), len(ms), C.byref(cam), _p(T), C.c_float(log_scale_factor), C.c_float(th), int(bool(apply)),
+                                         _p(bi), _p(bd), _p(rs), _p(act), C.byref(n)), "corb_fuse_sim3_store")
+        return bi[: len(ms)], bd[: len(ms)], n.value, act[: len(ms)], rs[: len(ms)]
 
     def CreateNewMapPoints(self, cur_slot, nb_slots, F12, epipoles, cam, mp_store=None, first_mp_slot=0, first_mp_id=0, client_id=0, only_stereo=False, apply=False):
         """The neighbour loop of LocalMapping::CreateNewMapPoints on records (corb_create_new_map_points_store): matching per neighbour against the evolving flags of

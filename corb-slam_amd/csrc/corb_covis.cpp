@@ -33,6 +33,14 @@ extern "C" int corb_covis_create(CorbKfStore* kf, CorbMpStore* mp, int max_conne
     covis_launch_tree_init(g->T, kf->capacity, nullptr);                                          // none / first connection / no children
     // (a wait for the stream of the launch alone: the device's other streams, other clients' stores among them, are not waited for)
     if (hipGetLastError() != hipSuccess || hipStreamSynchronize(nullptr) != hipSuccess) { corb_set_error("corb_covis_create: the tree's initialisation failed"); (void)hipFree(g->tree_mem); (void)hipFree(g->mem); delete g; return CORB_ERR_HIP; }
+    // mTcwBefGBA beside the tree (the record's header has no room for it).  The reference leaves the matrix uninitialised (KeyFrame.cc:62); here it starts as the identity
+    std::vector<float> eye((size_t)kf->capacity * 16, 0.f);
+    for (size_t i = 0; i < (size_t)kf->capacity; i++) eye[i * 16] = eye[i * 16 + 5] = eye[i * 16 + 10] = eye[i * 16 + 15] = 1.f;
+    if (hipMalloc((void**)&g->bef, eye.size() * 4 + 256) != hipSuccess || hipMemcpy(g->bef, eye.data(), eye.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
+        corb_set_error("corb_covis_create: %d poses before the global BA: allocation failed", kf->capacity);
+        if (g->bef) (void)hipFree(g->bef);
+        (void)hipFree(g->tree_mem); (void)hipFree(g->mem); delete g; return CORB_ERR_HIP;
+    }
     *out = g;
     return CORB_OK;
 }
@@ -42,6 +50,7 @@ extern "C" void corb_covis_destroy(CorbCovis* g)
     (void)hipSetDevice(g->kf->device);
     if (g->mem) (void)hipFree(g->mem);
     if (g->tree_mem) (void)hipFree(g->tree_mem);
+    if (g->bef) (void)hipFree(g->bef);
     delete g;
 }
 

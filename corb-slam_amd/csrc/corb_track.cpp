@@ -263,6 +263,52 @@ extern "C" int corb_fuse_store(CorbKfStore* kf, int slot, CorbMpStore* map, cons
     return CORB_OK;
 }
 
+// ---- int ORBmatcher::Fuse(KeyFrame* pKF, cv::Mat Scw, const vector<MapPoint*>& vpPoints, float th, vector<MapPoint*>& vpReplacePoint) on records (see include/corb_accel.h) ----
+extern "C" int corb_fuse_sim3_store(CorbKfStore* kf, int slot, CorbMpStore* map, const int32_t* mp_slots, int n_points, const CorbTrackCamera* cam,
+                                    const float* Scw, float log_scale_factor, float th, int apply, int32_t* best_idx, int32_t* best_dist, int32_t* replace_slot, uint8_t* action, int* n_fused)
+{
+    const char* who = "corb_fuse_sim3_store";
+    int rc = check_mp_slots(who, map, mp_slots, n_points); if (rc) return rc;
+    RecordCall call; rc = call.open(who, n_points >= 0 && (n_points == 0 || (mp_slots && best_idx && best_dist && replace_slot)) && Scw && n_fused && log_scale_factor > 0, kf, slot, map, cam, true); if (rc) return rc;
+    const int n = call.n, nq = n_points;
+    *n_fused = 0;
+    for (int i = 0; i < nq; i++) { best_idx[i] = -1; best_dist[i] = 256; replace_slot[i] = -1; if (action) action[i] = 0; }
+    if (n == 0 || nq == 0) return CORB_OK;
+    if (proj_too_large(n, nq)) { corb_set_error("%s: too large (%d features, %d points)", who, n, nq); return CORB_ERR_ARG; }
+    rc = call.sync(); if (rc) return rc;
+    CorbScratch pool(0);
+    FuseStoreDev t; memset(&t, 0, sizeof(t));
+    t.kf_rec = kf->rec(slot); t.F = kf->F; t.n_feat = n; t.mp_base = map->base; t.mp_bytes = map->L.bytes; t.max_obs = map->O; t.n_points = nq; t.apply = apply ? 1 : 0; t.mpid = map->idt;
+    int* dslots = nullptr;
+    HIPCHK(pool.upload_block({{(void**)&dslots, mp_slots, (size_t)nq * 4}}));
+    t.mp_slots = dslots;
+    unsigned char* claimed;
+    HIPCHK(pool.alloc(&t.pts, (size_t)nq)); HIPCHK(pool.alloc(&t.qdesc, (size_t)nq * 4)); HIPCHK(pool.alloc(&t.claim, (size_t)n)); HIPCHK(pool.alloc(&t.action, (size_t)nq));
+    HIPCHK(pool.alloc(&t.replace_slot, (size_t)nq));
+    HIPCHK(pool.alloc(&claimed, (size_t)n)); HIPCHK(hipMemsetAsync(claimed, 0, (size_t)n, pool.stream));
+    ProjBuffers pb; rc = pb.alloc(pool, n, nq, false, 0); if (rc) return rc;
+    t.best_idx = pb.res;
+    fuse_sim3_launch_prepare(t, pool.stream);
+    // the search itself: the kernels of corb_fuse with sim3 = 1 on the record's arrays (Scw decomposed as ORBmatcher.cc:1127-1131 does)
+    CorbProjDev d{}; CorbProjTf tf = tf_of(cam, log_scale_factor, th);
+    decompose_scw(Scw, tf);
+    record_target(d, cam, t.kf_rec, RecLayout(kf->F), n, nq);
+    preset_fuse_sim3(d, tf); pb.bind(d);
+    d.claimed = claimed; d.qdesc = t.qdesc;
+    corb_launch_projection_points(d, t.pts, tf, 0, pool.stream);
+    fuse_sim3_launch_apply(t, pool.stream);
+    HIPCHK(hipGetLastError());
+    static thread_local std::vector<uint8_t> h_act; static thread_local std::vector<int32_t> h_rs;
+    h_act.resize((size_t)nq); h_rs.resize((size_t)nq);
+    HIPCHK(pool.d2h(h_act.data(), t.action, (size_t)nq)); HIPCHK(pool.d2h(h_rs.data(), t.replace_slot, (size_t)nq * 4));
+    rc = proj_finish_best(pool, pb, best_idx, best_dist); if (rc) return rc;
+    int nf = 0, full = 0;
+    for (int i = 0; i < nq; i++) { if (action) action[i] = h_act[i]; replace_slot[i] = h_rs[i]; nf += best_idx[i] >= 0; full += h_act[i] == 3; }
+    *n_fused = nf;
+    if (full) { corb_set_error("%s: %d map points have no room for another observation (max_observations = %d); they were not added", who, full, map->O); return CORB_ERR_CAPACITY; }
+    return CORB_OK;
+}
+
 // ---- int ORBmatcher::SearchByProjection(Frame&, KeyFrame*, const set<MapPoint*>& sAlreadyFound, th, ORBdist) on records (see include/corb_accel.h) ----
 extern "C" int corb_track_search_reloc(CorbKfStore* frames, int cur_slot, CorbKfStore* kfs, int kf_slot, CorbMpStore* map, const CorbTrackCamera* cam,
                                        const float* Tcw, float log_scale_factor, float th, int orb_dist, int check_orientation, int32_t* match, int* n_matches)

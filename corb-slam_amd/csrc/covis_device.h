@@ -38,3 +38,20 @@ __device__ __forceinline__ int covis_block_scan(int* a, int n, int* sh)
     __syncthreads();
     return total;
 }
+// P entries (id, slot) in LDS -> ascending id (LightKeyFrame::operator<); pads carry COVIS_NO_ID and sort behind every entry
+__device__ __forceinline__ void covis_sort_by_id(unsigned long long* sid, int* sslot, int P)
+{
+    for (int k = 2; k <= P; k <<= 1) {
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int i = threadIdx.x; i < P; i += COVIS_T) {
+                const int x = i ^ j;
+                if (x > i) {
+                    const bool up = (i & k) == 0;
+                    const unsigned long long a = sid[i], b = sid[x];
+                    if (up ? a > b : a < b) { const int sa = sslot[i]; sid[i] = b; sid[x] = a; sslot[i] = sslot[x]; sslot[x] = sa; }
+                }
+            }
+            __syncthreads();
+        }
+    }
+}

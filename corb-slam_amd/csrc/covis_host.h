@@ -17,6 +17,7 @@ struct CorbCovis {
     CovisTree T{};
     char* mem = nullptr;
     char* tree_mem = nullptr;
+    float* bef = nullptr;                    // [capacity][16] mTcwBefGBA of slot r (C/include/KeyFrame.h:63); a fresh graph holds the identity
     std::mutex mu;
 };
 

@@ -17,23 +17,6 @@ __device__ __forceinline__ int localmap_held(const CovisStores& S, unsigned long
     const int x = corb_idtab_find(S.kfid, id);
     return x >= 0 && x < S.kf_capacity ? x : -1;
 }
-// P entries (id, slot) in LDS -> ascending id (LightKeyFrame::operator<); pads carry COVIS_NO_ID and sort behind every voter
-__device__ __forceinline__ void localmap_sort(unsigned long long* sid, int* sslot, int P)
-{
-    for (int k = 2; k <= P; k <<= 1) {
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int i = threadIdx.x; i < P; i += COVIS_T) {
-                const int x = i ^ j;
-                if (x > i) {
-                    const bool up = (i & k) == 0;
-                    const unsigned long long a = sid[i], b = sid[x];
-                    if (up ? a > b : a < b) { const int sa = sslot[i]; sid[i] = b; sid[x] = a; sslot[i] = sslot[x]; sslot[x] = sa; }
-                }
-            }
-            __syncthreads();
-        }
-    }
-}
 // the first lane of the wavefront whose candidate is set: its value to every lane, or -1
 __device__ __forceinline__ int localmap_first(bool cand, int value)
 {
@@ -97,7 +80,7 @@ __global__ __launch_bounds__(COVIS_T) void localmap_vote_walk_kernel(CovisRows R
     }
     for (int i = nd + tid; i < P; i += COVIS_T) { sid[i] = COVIS_NO_ID; sslot[i] = -1; }
     __syncthreads();
-    localmap_sort(sid, sslot, P);
+    covis_sort_by_id(sid, sslot, P);
     // ---- the voters in ascending id (:1292-1307): a bad one is passed over, the rest are listed and marked; pKFmax on a strict `>` ----
     for (int i = tid; i < P; i += COVIS_T) { good[i] = i < nd && !localmap_kf_bad(S, sslot[i]) ? 1 : 0; pos[i] = good[i]; }
     __syncthreads();

@@ -5,6 +5,7 @@
 #include "lane_exchange.h"
 #include "device_util.h"
 #include "ba_store_internal.h"
+#include "normal_depth.h"
 
 // per keyframe of the problem: pose, intrinsics, fixed / bad flags; id -> vertex index into the table
 __global__ __launch_bounds__(256) void bas_kf_kernel(BAStoreDev d)
@@ -68,44 +69,16 @@ __global__ __launch_bounds__(256) void bas_mp_kernel(BAStoreDev d)
     if (!FILL) d.edge_cnt[j] = cnt;
 }
 
-// camera centre of vertex p from the solver's output pose (KeyFrame::SetPose: Ow = -Rwc * tcw in float, KeyFrame.cc:120-135)
-__device__ __forceinline__ void bas_camera_center(const float* T, float* Ow)
-{
-#pragma unroll
-    for (int a = 0; a < 3; a++) Ow[a] = -(T[0 * 4 + a] * T[3] + T[1 * 4 + a] * T[7] + T[2 * 4 + a] * T[11]);
-}
-// MapPoint::UpdateNormalAndDepth (C/src/MapPoint.cc:424-472) on a record: the observations whose keyframes are vertices of the problem, with the poses the solve
-// left; mvScaleFactors rebuilt from scale_factor as ORBextractor.cc:418-424 does
+// MapPoint::UpdateNormalAndDepth on a record (normal_depth.h) with the observations whose keyframes are vertices of the problem and the poses the solve left
+struct BasPoseLookup {
+    const BAStoreDev& d;
+    __device__ __forceinline__ int find(unsigned long long id) const { return corb_idtab_find(d.tab, id); }
+    __device__ __forceinline__ const float* pose(int p) const { return d.poses + 16 * (size_t)p; }
+    __device__ __forceinline__ const char* record(int p) const { return d.kf_base + (size_t)d.kf_slots[p] * d.kf_bytes; }
+};
 __device__ __forceinline__ void bas_update_normal_depth(const BAStoreDev& d, CorbMapPointRecord* h, const unsigned long long* okf, const uint32_t* oidx, int kept, const RecLayout& KL, float scale_factor)
 {
-    const int pr = corb_idtab_find(d.tab, h->ref_kf_id);
-    if (pr < 0) return;                                                       // pRefKF == nullptr (:438)
-    int ref_f = -1;
-    float nx = 0.f, ny = 0.f, nz = 0.f; int n = 0;
-    const float px = h->world_pos[0], py = h->world_pos[1], pz = h->world_pos[2];
-    for (int k = 0; k < kept; k++) {
-        if (okf[k] == h->ref_kf_id) ref_f = (int)oidx[k];
-        const int p = corb_idtab_find(d.tab, okf[k]);
-        if (p < 0) continue;                                                  // if (pKF) (:452): a keyframe that is not at hand
-        float Ow[3]; bas_camera_center(d.poses + 16 * (size_t)p, Ow);
-        const float vx = px - Ow[0], vy = py - Ow[1], vz = pz - Ow[2];
-        const double inv = 1.0 / sqrt((double)vx * vx + (double)vy * vy + (double)vz * vz);     // cv::norm accumulates in double; Mat / double scales by its reciprocal
-        nx += (float)(vx * inv); ny += (float)(vy * inv); nz += (float)(vz * inv); n++;
-    }
-    const char* rrec = d.kf_base + (size_t)d.kf_slots[pr] * d.kf_bytes;
-    const KfHeader* rh = reinterpret_cast<const KfHeader*>(rrec);
-    if (ref_f < 0 || ref_f >= rh->n || n == 0) return;                        // (:441-444)
-    float Or[3]; bas_camera_center(d.poses + 16 * (size_t)pr, Or);
-    const float cx = px - Or[0], cy = py - Or[1], cz = pz - Or[2];
-    const float dist = (float)sqrt((double)cx * cx + (double)cy * cy + (double)cz * cz);
-    const int nl = min(max(rh->m.nlevels, 1), CORB_MAX_LEVELS);
-    const int level = min(max(reinterpret_cast<const CorbKeyPoint*>(rrec + KL.kp)[ref_f].octave, 0), nl - 1);
-    float sc = 1.f, sc_level = 1.f;                                           // mvScaleFactor[i] = mvScaleFactor[i-1] * scaleFactor (ORBextractor.cc:418-424)
-    for (int l = 1; l < nl; l++) { sc *= scale_factor; if (l == level) sc_level = sc; }
-    h->max_distance = dist * sc_level;
-    h->min_distance = h->max_distance / sc;
-    const double rn = 1.0 / (double)n;
-    h->normal[0] = (float)(nx * rn); h->normal[1] = (float)(ny * rn); h->normal[2] = (float)(nz * rn);
+    corb_update_normal_depth(BasPoseLookup{d}, h, okf, oidx, kept, KL, scale_factor);
 }
 // estimates -> records (Optimizer.cc:216-262).  poses / points hold the solver's outputs (inputs copied through for fixed / untouched vertices).
 // scale_factor > 0 and loop_kf == 0: SetWorldPos is followed by UpdateNormalAndDepth (:254-256) over the point's observers in the solve.

@@ -67,11 +67,16 @@ struct FuseStoreDev {
     int* claim;                                                  // [n_feat] lowest point index that was fused into the feature
     unsigned char* action;                                       // [n_points] 0 none, 1 added, 2 the feature holds a MapPoint (Replace pending), 3 added but the observation list is full
     int apply;
+    CorbIdTable mpid; int* replace_slot;                         // the Sim3 form only: the map's index, [n_points] vpReplacePoint as slots (-1 = none)
 };
 // pts / qdesc <- the records: a point takes part unless it is bad or already observed by the keyframe (ORBmatcher.cc:987-993)
 void fuse_launch_prepare(const FuseStoreDev& t, hipStream_t s);
 // the map update of the fused points (ORBmatcher.cc:1083-1104), see corb_accel.h
 void fuse_launch_apply(const FuseStoreDev& t, hipStream_t s);
+// the Sim3 form, Fuse(pKF, Scw, vpPoints, th, vpReplacePoint) (ORBmatcher.cc:1118-1241, corb_fuse_sim3_store): a point takes part unless it is bad or the keyframe
+// RECORD holds its id (spAlreadyFound = pKF->GetMapPoints(), :1131, :1143); actions and vpReplacePoint decided from the record as it was, then the additions
+void fuse_sim3_launch_prepare(const FuseStoreDev& t, hipStream_t s);
+void fuse_sim3_launch_apply(const FuseStoreDev& t, hipStream_t s);
 
 // ---- relocalisation's SearchByProjection(Frame&, KeyFrame*, sAlreadyFound, th, ORBdist) on records (corb_track_search_reloc) ----
 struct RelocStoreDev {

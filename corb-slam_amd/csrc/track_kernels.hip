@@ -293,6 +293,85 @@ __global__ __launch_bounds__(256) void fuse_apply_kernel(FuseStoreDev t)
     }
     t.action[i] = act;
 }
+// ---- ORBmatcher::Fuse(KeyFrame*, cv::Mat Scw, vpPoints, th, vpReplacePoint) on records (C/src/ORBmatcher.cc:1118-1241) ----
+__global__ __launch_bounds__(256) void fuse_sim3_prepare_kernel(FuseStoreDev t)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < t.n_feat) t.claim[i] = 0x7FFFFFFF;
+    if (i >= t.n_points) return;
+    const char* rec = t.mp_base + (size_t)t.mp_slots[i] * t.mp_bytes;
+    const CorbMapPointRecord* h = reinterpret_cast<const CorbMapPointRecord*>(rec);
+    bool ok = (h->flags & CORB_MP_BAD) == 0;                     // if(pMP->isBad() || spAlreadyFound.count(pMP)) continue; (:1143)
+    if (ok) {                                                    // spAlreadyFound = pKF->GetMapPoints() (:1131): the record's per-feature ids, not the observation list
+        const RecLayout KL(t.F);
+        const unsigned long long* mp_id = reinterpret_cast<const unsigned long long*>(t.kf_rec + KL.mp_id);
+        for (int f = 0; f < t.n_feat; f++) if (mp_id[f] == h->id) { ok = false; break; }
+    }
+    CorbMapPointView v;
+    v.world[0] = h->world_pos[0]; v.world[1] = h->world_pos[1]; v.world[2] = h->world_pos[2];
+    v.normal[0] = h->normal[0]; v.normal[1] = h->normal[1]; v.normal[2] = h->normal[2];
+    v.min_distance = h->min_distance; v.max_distance = h->max_distance; v.angle = 0.f; v.valid = ok ? 1 : 0; v.pad[0] = v.pad[1] = v.pad[2] = 0;
+    t.pts[i] = v;
+    const unsigned long long* dsc = reinterpret_cast<const unsigned long long*>(h->descriptor);
+#pragma unroll
+    for (int k = 0; k < 4; k++) t.qdesc[4 * (size_t)i + k] = dsc[k];
+}
+// :1206-1237 as the reference's walk over the points leaves it, decided from the record as it stands before the call (nothing is written here): a feature that held a
+// point gives vpReplacePoint = that point (action 2; bad: action 4, nothing done; an id without a record: action 2 without a slot, as corb_fuse_store reports it);
+// an empty feature takes the first point of the list fused into it (action 1), which every later point then meets there (action 2, vpReplacePoint = that point)
+__global__ __launch_bounds__(256) void fuse_sim3_decide_kernel(FuseStoreDev t)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= t.n_points) return;
+    const int f = t.best_idx[i];
+    unsigned char act = 0; int rs = -1;
+    if (f >= 0) {
+        const RecLayout KL(t.F);
+        const unsigned long long id0 = reinterpret_cast<const unsigned long long*>(t.kf_rec + KL.mp_id)[f];
+        if (id0 != CORB_NO_MAP_POINT) {
+            const int ms = corb_idtab_find(t.mpid, id0);
+            if (ms < 0) act = 2;
+            else if (reinterpret_cast<const CorbMapPointRecord*>(t.mp_base + (size_t)ms * t.mp_bytes)->flags & CORB_MP_BAD) act = 4;
+            else { act = 2; rs = ms; }
+        } else if (t.claim[f] != i) { act = 2; rs = t.mp_slots[t.claim[f]]; }
+        else act = 1;
+    }
+    t.action[i] = act; t.replace_slot[i] = rs;
+}
+// pMP->AddObservation(pKF, bestIdx); pKF->AddMapPoint(pMP, bestIdx) (:1233-1234) for the points of action 1
+__global__ __launch_bounds__(256) void fuse_sim3_commit_kernel(FuseStoreDev t)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= t.n_points || t.action[i] != 1) return;
+    char* rec = t.mp_base + (size_t)t.mp_slots[i] * t.mp_bytes;
+    CorbMapPointRecord* h = reinterpret_cast<CorbMapPointRecord*>(rec);
+    const MpLayout L(t.max_obs); const RecLayout KL(t.F);
+    unsigned long long* okf = reinterpret_cast<unsigned long long*>(rec + L.obs_kf);
+    uint32_t* oidx = reinterpret_cast<uint32_t*>(rec + L.obs_idx);
+    const unsigned long long kf_id = reinterpret_cast<const KfHeader*>(t.kf_rec)->m.id;
+    const int n = min(max(h->n_obs, 0), t.max_obs), f = t.best_idx[i];
+    bool listed = false;                                         // AddObservation returns at once for a keyframe the list holds already (MapPoint.cc:146-148): a point
+    for (int k = 0; k < n; k++) if (okf[k] == kf_id) listed = true;      // the keyframe observes but no longer holds takes part here, unlike in the SE3 form
+    if (!listed) {
+        if (n >= t.max_obs) { t.action[i] = 3; return; }
+        int k = n;                                               // mObservations[pKF] = idx: the list ascends in the keyframe id (MapPoint.h:182)
+        while (k > 0 && okf[k - 1] > kf_id) { okf[k] = okf[k - 1]; oidx[k] = oidx[k - 1]; k--; }
+        okf[k] = kf_id; oidx[k] = (uint32_t)f; h->n_obs = n + 1;
+    }
+    reinterpret_cast<unsigned long long*>(t.kf_rec + KL.mp_id)[f] = h->id;
+}
+void fuse_sim3_launch_prepare(const FuseStoreDev& t, hipStream_t s)
+{
+    const int n = t.n_points > t.n_feat ? t.n_points : t.n_feat;
+    if (n > 0) hipLaunchKernelGGL(fuse_sim3_prepare_kernel, dim3((n + 255) / 256), dim3(256), 0, s, t);
+}
+void fuse_sim3_launch_apply(const FuseStoreDev& t, hipStream_t s)
+{
+    if (t.n_points <= 0) return;
+    hipLaunchKernelGGL(fuse_claim_kernel, dim3((t.n_points + 255) / 256), dim3(256), 0, s, t);
+    hipLaunchKernelGGL(fuse_sim3_decide_kernel, dim3((t.n_points + 255) / 256), dim3(256), 0, s, t);
+    if (t.apply) hipLaunchKernelGGL(fuse_sim3_commit_kernel, dim3((t.n_points + 255) / 256), dim3(256), 0, s, t);
+}
 void fuse_launch_prepare(const FuseStoreDev& t, hipStream_t s)
 {
     const int n = t.n_points > t.n_feat ? t.n_points : t.n_feat;

@@ -1088,6 +1088,7 @@ private:
 //   the window of Optimizer::LocalBundleAdjustment                                Optimizer.cc:493-544 (as the slot lists MapStoreT::LocalBundleAdjustment takes)
 //   AddChild / EraseChild / ChangeParent / GetChilds / GetParent / hasChild and the tree part of SetBadFlag      KeyFrame.cc:504-543, :607-668
 //   void Tracking::UpdateLocalMap()                                               Tracking.cc:1218-1366
+//   CorrectLoop's propagation and the map update of RunGlobalBundleAdjustment      GlobalOptimize.cpp:253-338, :463-532 (LoopClosing.cc:436-522, :684-753)
 // The keyframes are named by the slots MapStoreT::PutKeyFrame filed them in (Bind).  The spanning tree lives in the graph (corb_covis_update keeps it as :493-499 do);
 // UpdateConnections still returns the front of the ordered list, which is mpParent on a keyframe's first connection.  Db (optional) is the place-recognition database of this header: its
 // UpdateConnections(KeyFrame*) is called for the keyframe and for every keyframe on its ordered list -- the rows an update can change the best ten of.
@@ -1172,6 +1173,79 @@ public:
         adapt::LocalMapSlots r = adapt::UpdateLocalMapSlots(h_, frames, slot, prev, std::max(maxKeyFrames, (int)prev.size()), maxMapPoints);
         vpLocalKeyFrames.clear(); for (int32_t s : r.kfSlots) vpLocalKeyFrames.push_back(at(s));
         if (ppReferenceKF && r.refSlot >= 0) *ppReferenceKF = at(r.refSlot);
+        return r;
+    }
+    // ---- a loop event on records (corb_loop_correct_store, corb_gba_propagate_store) ----
+    // vpMP[m] is the object of map-point slot first + m of the graph's map-point store; every keyframe involved is bound.  MapPoint needs one setter the reference
+    // does not have, next to the two getters the tracking calls ask for: SetNormalAndDistances(normal, mfMinDistance, mfMaxDistance); KeyFrame::mTcwBefGBA is public.
+    //
+    // CorrectLoop's propagation (GlobalOptimize.cpp:253-338 = LoopClosing.cc:436-522) for mpCurrentKF and mg2oScw (8 doubles: quaternion x y z w, t, s); scaleFactor =
+    // mpCurrentKF->mfScaleFactor (0: no UpdateNormalAndDepth).  Returns mvpCurrentConnectedKFs in the walk's order (ascending mnId), fills CorrectedSim3 /
+    // NonCorrectedSim3 through makeSim3(const double* v8) and leaves in the objects what the reference leaves: SetPose + addUpdateKeyframe for every member,
+    // SetWorldPos + addUpdateMapPoint + mnCorrectedByKF + mnCorrectedReference (+ normal and distances) for every corrected point, then UpdateConnections per member (:337)
+    template <class MapPoint, class Mat, class Cache, class PoseMap, class MakeSim3>
+    std::vector<KeyFrame*> CorrectLoop(KeyFrame* pCurrentKF, const double* Scw, float scaleFactor, CorbKfStore* kfs, CorbMpStore* mps, int first, const std::vector<MapPoint*>& vpMP,
+                                       Cache* pCacher, PoseMap& CorrectedSim3, PoseMap& NonCorrectedSim3, MakeSim3 makeSim3, int* pnPointsCorrected = nullptr)
+    {
+        const int c = (int)cap() + 1;
+        std::vector<int32_t> s((size_t)c); std::vector<double> co((size_t)c * 8), nc((size_t)c * 8); int n = 0, np = 0;
+        check(corb_loop_correct_store(h_, Slot(pCurrentKF), Scw, scaleFactor, s.data(), co.data(), nc.data(), c, &n, &np), "corb_loop_correct_store");
+        std::vector<KeyFrame*> connected;
+        for (int i = 0; i < n; i++) {
+            KeyFrame* pKFi = at(s[i]); connected.push_back(pKFi);
+            CorrectedSim3[pKFi] = makeSim3(&co[(size_t)i * 8]); NonCorrectedSim3[pKFi] = makeSim3(&nc[(size_t)i * 8]);
+            CorbKeyFrameMeta m; check(corb_kf_store_get_meta(kfs, s[i], &m), "corb_kf_store_get_meta");
+            pKFi->SetPose(adapt::MatFactory<Mat>::from_floats(4, 4, m.Tcw)); pCacher->addUpdateKeyframe(pKFi);                                     // :332-334
+        }
+        std::vector<CorbMapPointRecord> rec(vpMP.size()); std::vector<CorbMapPointScratch> sc(vpMP.size());
+        if (!vpMP.empty()) {
+            check(corb_mp_store_get(mps, first, (int)vpMP.size(), rec.data(), nullptr, nullptr), "corb_mp_store_get");
+            check(corb_mp_store_get_scratch(mps, first, (int)sc.size(), sc.data()), "corb_mp_store_get_scratch");
+        }
+        for (size_t m = 0; m < vpMP.size(); m++) {
+            MapPoint* pMP = vpMP[m];
+            if (!pMP || sc[m].corrected_by_kf != (uint64_t)pCurrentKF->mnId || pMP->mnCorrectedByKF == pCurrentKF->mnId) continue;               // corrected by THIS call
+            pMP->SetWorldPos(adapt::MatFactory<Mat>::from_floats(3, 1, rec[m].world_pos)); pCacher->addUpdateMapPoint(pMP);                       // :315-316
+            pMP->mnCorrectedByKF = (long unsigned int)sc[m].corrected_by_kf; pMP->mnCorrectedReference = (long unsigned int)sc[m].corrected_reference;
+            if (scaleFactor > 0.f) pMP->SetNormalAndDistances(adapt::MatFactory<Mat>::from_floats(3, 1, rec[m].normal), rec[m].min_distance, rec[m].max_distance);   // :320
+        }
+        for (KeyFrame* pKFi : connected) UpdateConnections(pKFi);                                                                               // :337
+        if (pnPointsCorrected) *pnPointsCorrected = np;
+        return connected;
+    }
+    // the map update of RunGlobalBundleAdjustment (GlobalOptimize.cpp:463-532 = LoopClosing.cc:684-753) for mvpKeyFrameOrigins and nLoopKF.  The objects receive what
+    // the reference leaves: mTcwBefGBA, SetPose, mTcwGBA and mnBAGlobalForKF + addUpdateKeyframe for every keyframe the walk reaches (the closure of the origins over
+    // GetChilds(), one small read per keyframe), SetWorldPos + addUpdateMapPoint for every point it sets or moves
+    template <class MapPoint, class Mat, class Cache>
+    CorbGbaPropagation PropagateGlobalBA(const std::vector<KeyFrame*>& vpKeyFrameOrigins, unsigned long nLoopKF, CorbKfStore* kfs, CorbMpStore* mps, int first,
+                                         const std::vector<MapPoint*>& vpMP, Cache* pCacher, int queueCap = 0)
+    {
+        std::vector<int32_t> origins; for (KeyFrame* p : vpKeyFrameOrigins) origins.push_back(Slot(p));
+        CorbGbaPropagation r{};
+        check(corb_gba_propagate_store(h_, origins.data(), (int)origins.size(), (uint64_t)nLoopKF, queueCap, &r), "corb_gba_propagate_store");
+        std::vector<KeyFrame*> reached(vpKeyFrameOrigins); std::map<KeyFrame*, bool> seen;
+        for (KeyFrame* p : reached) seen[p] = true;
+        for (size_t i = 0; i < reached.size(); i++) for (KeyFrame* ch : GetChilds(reached[i])) if (!seen[ch]) { seen[ch] = true; reached.push_back(ch); }
+        for (KeyFrame* pKF : reached) {
+            const int slot = Slot(pKF); float bef[16];
+            CorbKeyFrameMeta m; check(corb_kf_store_get_meta(kfs, slot, &m), "corb_kf_store_get_meta");
+            check(corb_covis_get_pose_before_gba(h_, slot, bef), "corb_covis_get_pose_before_gba");
+            pKF->mTcwGBA = adapt::MatFactory<Mat>::from_floats(4, 4, m.TcwGBA);                                                                    // :477
+            if (m.ba_global_for_kf == (uint64_t)nLoopKF) pKF->mnBAGlobalForKF = nLoopKF;                                                         // :478
+            pKF->mTcwBefGBA = adapt::MatFactory<Mat>::from_floats(4, 4, bef); pKF->SetPose(adapt::MatFactory<Mat>::from_floats(4, 4, m.Tcw));     // :484-485
+            pCacher->addUpdateKeyframe(pKF);
+        }
+        std::vector<CorbMapPointRecord> rec(vpMP.size());
+        if (!vpMP.empty()) check(corb_mp_store_get(mps, first, (int)vpMP.size(), rec.data(), nullptr, nullptr), "corb_mp_store_get");
+        for (size_t m = 0; m < vpMP.size(); m++) {
+            MapPoint* pMP = vpMP[m];
+            if (!pMP || pMP->isBad()) continue;                                                                                                  // :498
+            if (pMP->mnBAGlobalForKF != nLoopKF) {                                                                                               // :507-515
+                KeyFrame* pRefKF = pMP->GetReferenceKeyFrame();
+                if (!pRefKF || slot_.find(pRefKF) == slot_.end() || pRefKF->mnBAGlobalForKF != nLoopKF) continue;
+            }
+            pMP->SetWorldPos(adapt::MatFactory<Mat>::from_floats(3, 1, rec[m].world_pos)); pCacher->addUpdateMapPoint(pMP);                       // :504-505, :527-528
+        }
         return r;
     }
     KeyFrame* at(int slot) const { return slot >= 0 && slot < (int)kf_.size() ? kf_[slot] : nullptr; }

@@ -786,9 +786,27 @@ int corb_fuse_store(CorbKfStore* kf, int slot, CorbMpStore* map, const int32_t* 
 typedef struct CorbMapPointCounters { int32_t n_visible, n_found; uint64_t replaced_by; } CorbMapPointCounters;
 int corb_mp_store_set_counters(CorbMpStore* s, int first, int n, const CorbMapPointCounters* counters);
 int corb_mp_store_get_counters(CorbMpStore* s, int first, int n, CorbMapPointCounters* counters);
+/* int ORBmatcher::Fuse(KeyFrame* pKF, cv::Mat Scw, const vector<MapPoint*>& vpPoints, float th, vector<MapPoint*>& vpReplacePoint) (C/src/ORBmatcher.cc:1118-1241) on
+ * records -- what SearchAndFuse runs per keyframe of CorrectedSim3 (S/src/GlobalOptimize.cpp:406-432, C/src/LoopClosing.cc:594-620).  Scw = Converter::toCvMat(g2oScw),
+ * 16 floats; the rest as corb_fuse_store.  The search is corb_fuse's with sim3 = 1 (same kernels).  A point takes part unless it is bad or the keyframe RECORD holds
+ * its id at some feature (spAlreadyFound = pKF->GetMapPoints(), :1131, :1143 -- not IsInKeyFrame through the observation list, as the SE3 form tests).  The map's id
+ * index is needed (none: CORB_ERR_ARG).  action[i] (optional) and replace_slot[i]:
+ *   0  not fused (replace_slot -1)
+ *   1  the feature held no point and point i is the first of the list fused into it; with apply != 0 AddObservation and AddMapPoint happen on the records exactly as
+ *      in corb_fuse_store (3: the point's observation list is full, nothing written, CORB_ERR_CAPACITY returned); a point whose list holds the keyframe already
+ *      (it observes the keyframe, the record no longer holds it) keeps its list, as MapPoint::AddObservation returns at once, and enters the feature
+ *   2  the feature holds a non-bad point, from before the call or from an earlier point of this call: replace_slot[i] = its slot = vpReplacePoint[i].  The caller then
+ *      runs corb_mp_store_replace(map, replace_slot[i], mp_slots[i], ...) in ascending i -- pRep->Replace(mvpLoopMapPoints[i]), GlobalOptimize.cpp:423-430.  A feature
+ *      whose id resolves to no record of the index is reported like this too, as corb_fuse_store reports it, with replace_slot -1: there is nothing to replace
+ *   4  the feature holds a point that is bad: counted in *n_fused, nothing is done (:1227-1231)
+ * The actions are decided from the record as it stands before the call, so apply == 0 reports what apply != 0 does. */
+int corb_fuse_sim3_store(CorbKfStore* kf, int slot, CorbMpStore* map, const int32_t* mp_slots, int n_points, const CorbTrackCamera* cam,
+                         const float* Scw /* 16 */, float log_scale_factor, float th, int apply, int32_t* best_idx, int32_t* best_dist, int32_t* replace_slot,
+                         uint8_t* action, int* n_fused);
 /* The tracking / local-mapping / loop-closing scratch of MapPoint's serialised state (C/include/MapPoint.h:52-72) that neither the 112-byte header nor the counters carry:
  * with it a record holds EVERY field the reference's boost archive moves, so a push is a faithful stand-in for the archive.  It lives behind the observation lists of the
- * record (corb_mp_store_record_bytes covers it), is zero after corb_mp_store_put and travels with the record in corb_map_push_ex; the kernels of this library do not read it. */
+ * record (corb_mp_store_record_bytes covers it), is zero after corb_mp_store_put and travels with the record in corb_map_push_ex; the kernels of this library do not read it,
+ * with one exception: corb_loop_correct_store reads and writes corrected_by_kf and corrected_reference. */
 typedef struct CorbMapPointScratch {
     int64_t first_kf_id, first_frame;           /* mnFirstKFid, mnFirstFrame */
     uint64_t track_reference_for_frame, last_frame_seen;      /* mnTrackReferenceForFrame, mnLastFrameSeen */
@@ -1190,6 +1208,53 @@ typedef struct CorbLocalMap {
 } CorbLocalMap;
 int corb_track_update_local_map(CorbCovis* g, CorbKfStore* frames, int slot, const int32_t* prev_kf_slots, int n_prev, int32_t* kf_slots, int kf_cap,
                                 int32_t* mp_slots, uint64_t* mp_ids, int mp_cap, CorbLocalMap* out);
+
+/* ---- the map update that follows a global bundle adjustment (RunGlobalBundleAdjustment, corbslam_server/src/GlobalOptimize.cpp:463-532 = corbslam_client/src/
+ * LoopClosing.cc:684-753): what corb_ba_solve_store with loop_kf != 0 left in TcwGBA / pos_gba / ba_global_for_kf becomes Tcw / world_pos, and keyframes the solve did
+ * not see are corrected through the spanning tree.  "Held" and "non-bad" mean what the section above says; without a map-point index: CORB_ERR_ARG.
+ *   mTcwBefGBA     the 256-byte keyframe header has no room for it: it lives in the graph, one 4x4 float per slot, read and written with the two calls below.  A fresh
+ *                  graph holds the IDENTITY (the reference leaves the matrix uninitialised, KeyFrame.cc:62)
+ *   the walk       the reference's queue, exactly: it starts as origin_slots (mvpKeyFrameOrigins); a pop walks the EXPLICIT child set of the keyframe in ascending id (not
+ *                  the parent fields), skips a child the store does not hold, gives a child whose ba_global_for_kf != loop_kf
+ *                  TcwGBA = (Tcw(child) * Twc) * TcwGBA(popped) and the mark, pushes EVERY held child, marked or not, then does mTcwBefGBA = Tcw, Tcw = TcwGBA.
+ *                  No bad test is made.  So: an unmarked origin is SetPose'd with whatever TcwGBA its record holds; a keyframe listed in two sets (ChangeParent
+ *                  leaves the stale entry) is popped twice and ends with mTcwBefGBA == TcwGBA; of two listers of one unmarked child the earlier queue position
+ *                  computes its pose; a keyframe no origin reaches keeps Tcw and mTcwBefGBA
+ *   queue_cap      bounds the queue, pops included (<= 0: 4 x slots + 64).  The reference does not terminate on a cyclic child set and pops exponentially often on
+ *                  stacked diamonds; a walk that would exceed the bound answers CORB_ERR_CAPACITY BEFORE anything is committed (records, graph and *out unchanged)
+ *   the points     every slot of the map-point index: a bad point is passed over; ba_global_for_kf == loop_kf: world_pos = pos_gba (n_points_set); else, with the
+ *                  reference keyframe held and marked after the walk: Xc = Rcw_bef*p + tcw_bef, p = Rwc*Xc + twc with its mTcwBefGBA and the inverse of its Tcw as they
+ *                  stand -- a keyframe the walk never reached contributes its STORED mTcwBefGBA (n_points_moved); else the point is left alone (n_points_skipped).
+ *                  Normal and distances are not touched: the reference calls no UpdateNormalAndDepth here
+ *   arithmetic     float products as corb_rebase_map_store makes them (exact products summed in double, left to right, one rounding), `A*x + b` one more float add;
+ *                  Twc is SetPose's: Rwc = Rcw^T, Ow = -(Rwc*tcw).  Every output is reproducible bit for bit (tests/loopfix_reference.py)
+ * n_popped = queue entries in all, n_reached = distinct keyframes among them, n_revisited = n_popped - n_reached, n_propagated = poses composed.
+ * Locks: the graph, then each store once as corb_fuse_store does. */
+/* CorrectLoop's propagation (GlobalOptimize.cpp:253-338 = LoopClosing.cc:436-522) for mpCurrentKF = cur_slot and mg2oScw = Scw (8 doubles: quaternion x y z w, t, s --
+ * the layout corb_optimize_essential_graph takes as S).  The set is GetVectorCovisibleKeyFrames() of cur_slot as corb_covis_query answers it (ids the store does not
+ * hold are dropped) plus the current keyframe.
+ *   walk order     CorrectedSim3 / NonCorrectedSim3 are pointer-keyed std::maps in the reference (LoopClosing.h:51); here the walk is in ASCENDING KEYFRAME ID, and
+ *                  kf_slots[0 .. n) with the two n x 8 arrays come back in that order.  More than cap members: CORB_ERR_CAPACITY with *n set and nothing written
+ *   the Sim3s      Tic = Tiw*Twc in float (products as corb_rebase_map_store makes them); Sic = Sim3(Ric, tic, 1); CorrectedSiw = Sic * Scw, for the current keyframe
+ *                  Scw itself; NonCorrected = Sim3(Riw, tiw, 1).  The g2o::Sim3 parts are FP64 in the reference's operation order
+ *   the points     a map point is corrected ONCE, by the first member in walk order that holds it -- a per-feature id of that record that resolves to a non-bad record; a
+ *                  point whose scratch corrected_by_kf equals the current keyframe's id on entry is skipped.  p <- CorrectedSwi.map(Siw.map(p)) in FP64, rounded to
+ *                  float; the scratch fields corrected_by_kf = id(cur) and corrected_reference = id(corrector) are written.  These kernels are the first of the library
+ *                  to read and write CorbMapPointScratch fields (corb_mp_store_set_scratch says the kernels do not read the scratch: these two are the exception)
+ *   :320           UpdateNormalAndDepth is applied when scale_factor > 0 (0: the three fields are left alone, as in corb_ba_solve_store).  It runs in the middle of
+ *                  the reference's walk and so meets a mixture of poses: an observer, or the reference keyframe, that belongs to the set and comes BEFORE the
+ *                  corrector in walk order has its corrected pose; the corrector itself, every later member and every keyframe outside the set have their old one
+ *                  (SetPose at :332 comes after the keyframe's own point loop).  The arithmetic is corb_ba_solve_store's
+ *   the poses      Tcw <- [R | t * (1./s)] of CorrectedSiw for every member (:324-332); no bad or fixed test is made, the reference makes none
+ *   :337           pKFi->UpdateConnections() reads observations only: the caller follows with ONE corb_covis_update(g, kf_slots, n, 15, ...), whose "as if one after the
+ *                  other in list order" rule makes that equal
+ * No output depends on the order the device's atomics land in.  Locks: the graph, then each store once as corb_fuse_store does. */
+int corb_loop_correct_store(CorbCovis* g, int cur_slot, const double* Scw /* 8 */, float scale_factor, int32_t* kf_slots, double* corrected /* n x 8 */,
+                            double* non_corrected /* n x 8 */, int cap, int* n, int* n_points_corrected);
+typedef struct CorbGbaPropagation { int32_t n_popped, n_reached, n_propagated, n_revisited, n_points_set, n_points_moved, n_points_skipped; } CorbGbaPropagation;
+int corb_gba_propagate_store(CorbCovis* g, const int32_t* origin_slots, int n_origins, uint64_t loop_kf, int queue_cap, CorbGbaPropagation* out);
+int corb_covis_set_pose_before_gba(CorbCovis* g, int slot, const float* T /* 16, row-major */);
+int corb_covis_get_pose_before_gba(CorbCovis* g, int slot, float* T /* 16 */);
 
 #ifdef __cplusplus
 }
