@@ -49,6 +49,7 @@ EXPORTS = [
     "corb_covis_set_tree", "corb_covis_get_tree", "corb_covis_add_child", "corb_covis_erase_child", "corb_covis_change_parent", "corb_covis_reparent_children",
     "corb_track_update_local_map",
     "corb_loop_correct_store", "corb_fuse_sim3_store", "corb_gba_propagate_store", "corb_covis_set_pose_before_gba", "corb_covis_get_pose_before_gba",
+    "corb_scratch_fill", "corb_scratch_report", "corb_scratch_read",
 ]
 
 
@@ -266,6 +267,9 @@ def load():
     L.corb_ba_solve_ex.argtypes = [C.POINTER(_BAProblem), C.c_int, C.c_int, C.c_void_p, C.POINTER(_BAResult), C.c_int, C.POINTER(BAOptions)]
     L.corb_ba_solve_devflat.argtypes = [C.POINTER(_BAProblem), C.c_int, C.c_int, C.POINTER(_BAResult), C.c_int, C.POINTER(BAOptions)]
     L.corb_spd_solve.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.c_int]
+    L.corb_scratch_fill.argtypes = [C.c_int, C.c_int, C.c_uint32, C.c_uint64, C.POINTER(C.c_uint64)]
+    L.corb_scratch_report.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_int), C.POINTER(C.c_uint64)]
+    L.corb_scratch_read.argtypes = [C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.c_void_p]
     L.corb_ba_solve_staged.argtypes = [C.POINTER(_BAProblem), C.POINTER(BAStage), C.c_int, C.c_void_p, C.POINTER(_BAResult), C.c_void_p, C.c_int, C.POINTER(BAOptions)]
     L.corb_search_by_projection_reloc.restype = C.c_int
     L.corb_search_by_projection_reloc.argtypes = [C.POINTER(_KeyFrameView), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_int), C.c_int]
@@ -505,6 +509,28 @@ def release_scratch(device=0):
     n = C.c_uint64(0)
     _chk(load().corb_release_scratch(int(device), C.byref(n)), "corb_release_scratch")
     return int(n.value)
+
+
+def scratch_fill(lane, word, min_bytes, device=0):
+    """corb_scratch_fill (test aid): the lane's arena as one chunk of at least `min_bytes`, every 32-bit word of it, of the staging and of the pinned block = `word`;
+    returns the chunk's capacity."""
+    cap = C.c_uint64(0)
+    _chk(load().corb_scratch_fill(int(device), int(lane), C.c_uint32(int(word)), C.c_uint64(int(min_bytes)), C.byref(cap)), "corb_scratch_fill")
+    return int(cap.value)
+
+
+def scratch_report(lane, device=0):
+    """corb_scratch_report (test aid): (arena capacity, number of chunks, staging capacity) of the lane"""
+    cap = C.c_uint64(0); n = C.c_int(0); st = C.c_uint64(0)
+    _chk(load().corb_scratch_report(int(device), int(lane), C.byref(cap), C.byref(n), C.byref(st)), "corb_scratch_report")
+    return int(cap.value), int(n.value), int(st.value)
+
+
+def scratch_read(lane, offset, nbytes, device=0):
+    """corb_scratch_read (test aid): `nbytes` bytes at `offset` of the lane's single arena chunk as a uint8 array"""
+    out = np.empty(int(nbytes), np.uint8)
+    _chk(load().corb_scratch_read(int(device), int(lane), C.c_uint64(int(offset)), C.c_uint64(int(nbytes)), _p(out)), "corb_scratch_read")
+    return out
 
 
 def pinned_empty(shape, dtype):

@@ -457,6 +457,20 @@ int corb_ba_solve_devflat(const CorbBAProblem* problem, int iterations, int robu
  * meaningless).  Exposed for tests and for adapters with their own small dense systems. */
 int corb_spd_solve(const double* A, int n, const double* b, double* x, int* info, int device);
 
+/* TEST AIDS on the two workspace lanes of a device (lane 0: the per-frame calls and corb_spd_solve; lane 1: every bundle adjustment and the essential graph).  Every call
+ * that takes a lane bump-allocates its device scratch from the lane's arena and starts at the same base address as the call before it, so it finds that call's leftovers;
+ * the rule the library keeps is that a call reads no byte of the arena, of the lane's page-locked staging or of its 4 KB page-locked block that it has not written itself.
+ * These three functions let a test put a lane into a chosen dirty state and look at it afterwards.  They take the lane's mutex and are no part of any call's work; a client
+ * has no use for them.
+ *   fill:   the arena becomes ONE chunk of max(min_bytes, its current total capacity) bytes; every 32-bit word of it, of the staging (if there is one) and of the
+ *           page-locked block is set to `word`; synchronises; *capacity (optional) = the chunk's size.  If the chunk cannot be allocated the call fails and leaves
+ *           the arena empty, as corb_release_scratch does.
+ *   report: *capacity = the arena's total bytes, *n_chunks = its chunks (0 after corb_release_scratch, > 1 never between calls), *staging_capacity = the staging's bytes.
+ *   read:   `bytes` bytes at `offset` of the single chunk into `out`; CORB_ERR_ARG if the arena is not exactly one chunk or the range leaves it. */
+int corb_scratch_fill(int device, int lane, uint32_t word, uint64_t min_bytes, uint64_t* capacity);
+int corb_scratch_report(int device, int lane, uint64_t* capacity, int* n_chunks, uint64_t* staging_capacity);
+int corb_scratch_read(int device, int lane, uint64_t offset, uint64_t bytes, void* out);
+
 /* One optimize() call plus the outlier test that follows it.  Sequences of stages express
  *   Optimizer::LocalBundleAdjustment (C/src/Optimizer.cc:487-838): {5, robust, 5.991, 7.815, check_depth=1},
  *                                                                   {10, non-robust, 5.991, 7.815, check_depth=1, allow_reactivate=1}
