@@ -52,9 +52,25 @@ EXPORTS = [
     "corb_scratch_fill", "corb_scratch_report", "corb_scratch_read",
 ]
 
+# include/corb_voc_train.h: vocabulary training and export, an offline tool beside the drop-in boundary (exported from the same library)
+TRAIN_EXPORTS = ("corb_voc_train", "corb_voc_train_store", "corb_voc_get", "corb_voc_save_text")
+
 
 class CorbError(RuntimeError):
     pass
+
+
+class VocTrainOptions(C.Structure):
+    _fields_ = [("k", C.c_int32), ("L", C.c_int32), ("max_iterations", C.c_int32), ("reserved", C.c_int32), ("seed", C.c_uint64)]
+
+
+class VocTrainStats(C.Structure):
+    _fields_ = [(f, C.c_int32) for f in ("nodes", "words", "kmeans_nodes", "trivial_nodes", "short_nodes", "max_iterations_seen", "capped_nodes", "empty_cluster_events")] + \
+               [(f, C.c_int32 * 10) for f in ("level_nodes", "level_max_iterations", "level_launches", "level_small_nodes", "level_large_nodes")] + \
+               [("launches", C.c_int32), ("small_limit", C.c_int32), ("elapsed_ms", C.c_double)]
+
+    def as_dict(self):
+        return dict((f, list(getattr(self, f)) if f.startswith("level_") else getattr(self, f)) for f, _ in self._fields_)
 
 
 class LocalMap(C.Structure):
@@ -383,6 +399,13 @@ def load():
     L.corb_bow_profile.argtypes = [C.c_int, C.c_int]
     L.corb_bow_profile_read.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int)]
     L.corb_kf_store_compute_bow.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    for name in TRAIN_EXPORTS:
+        if not hasattr(L, name):
+            raise CorbError("libcorb_accel.so lacks %s (include/corb_voc_train.h): rebuild it" % name)
+    L.corb_voc_train.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(VocTrainOptions), C.c_int, C.POINTER(C.c_void_p), C.POINTER(VocTrainStats)]
+    L.corb_voc_train_store.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(VocTrainOptions), C.POINTER(C.c_void_p), C.POINTER(VocTrainStats)]
+    L.corb_voc_get.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+    L.corb_voc_save_text.argtypes = [C.c_void_p, C.c_char_p, C.c_int]
     _lib = L
     return L
 
@@ -1401,6 +1424,45 @@ class Vocabulary:
         self = cls.__new__(cls); self.h = C.c_void_p(); self.device = device
         _chk(load().corb_voc_load_text(os.fsencode(path), device, C.byref(self.h)), "corb_voc_load_text")
         return self
+
+    train_stats = None          # of a trained vocabulary: CorbVocTrainStats as a dict
+
+    @classmethod
+    def train(cls, sets, k, L, seed, max_iterations=100, device=0):
+        """TemplatedVocabulary::create(training_features, k, L) on the device (corb_voc_train): sets = one [n, 32] descriptor array per training image, empty ones allowed"""
+        sets = [np.ascontiguousarray(d, np.uint8).reshape(-1, 32) for d in sets]
+        off = np.zeros(len(sets) + 1, np.int32); off[1:] = np.cumsum([len(d) for d in sets])
+        desc = np.ascontiguousarray(np.concatenate(sets)) if sets else np.zeros((0, 32), np.uint8)
+        return cls._train_raw(desc, off, k, L, seed, max_iterations, device)
+
+    @classmethod
+    def _train_raw(cls, desc, off, k, L, seed, max_iterations, device):
+        self = cls.__new__(cls); self.h = C.c_void_p(); self.device = device
+        opt = VocTrainOptions(int(k), int(L), int(max_iterations), 0, int(seed) & (2 ** 64 - 1)); st = VocTrainStats()
+        _chk(load().corb_voc_train(_p(desc), _p(np.ascontiguousarray(off, np.int32)), len(off) - 1, C.byref(opt), device, C.byref(self.h), C.byref(st)), "corb_voc_train")
+        self.train_stats = st.as_dict()
+        return self
+
+    @classmethod
+    def train_store(cls, store, slots, k, L, seed, max_iterations=100):
+        """corb_voc_train_store: every slot of a KeyFrameStore is one training image; the descriptors stay on the device"""
+        self = cls.__new__(cls); self.h = C.c_void_p(); self.device = getattr(store, "device", 0)
+        sl = np.ascontiguousarray(slots, np.int32)
+        opt = VocTrainOptions(int(k), int(L), int(max_iterations), 0, int(seed) & (2 ** 64 - 1)); st = VocTrainStats()
+        _chk(load().corb_voc_train_store(store.h, _p(sl), len(sl), C.byref(opt), C.byref(self.h), C.byref(st)), "corb_voc_train_store")
+        self.train_stats = st.as_dict()
+        return self
+
+    def flat(self, cap_nodes=None):
+        """corb_voc_get: the flat arrays of the vocabulary, as dbow_reference.Vocabulary.flat() names them"""
+        i = self.info(); n = i["n_nodes"] - 1 if cap_nodes is None else int(cap_nodes)
+        p = np.zeros(n, np.int32); lf = np.zeros(n, np.int32); d = np.zeros((n, 32), np.uint8); w = np.zeros(n, np.float64); got = C.c_int(0)
+        _chk(load().corb_voc_get(self.h, _p(p), _p(lf), _p(d), _p(w), n, C.byref(got)), "corb_voc_get")
+        return dict(k=i["k"], L=i["L"], scoring=0, weighting=0, parent=p, is_leaf=lf, descriptor=d, weight=w)
+
+    def save_text(self, path, digits=0):
+        """corb_voc_save_text: the reference's saveToTextFile; digits = 17 reloads bit for bit"""
+        _chk(load().corb_voc_save_text(self.h, os.fsencode(path), int(digits)), "corb_voc_save_text")
 
     def close(self):
         if self.h:

@@ -30,6 +30,15 @@ struct BowDbDev {
     double* score_out;                                            // [capacity]
 };
 #define BOW_NO_POS 0x7F7F7F7F
+
+// a vocabulary handle: the host form and its upload.  voc_finish (corb_bow.cpp) uploads v->host and hands the handle out, or frees it and returns the error.
+struct CorbVoc {
+    int device = 0;
+    BowVocHost host;
+    BowVocView dev{};                 // device pointers
+    std::vector<void*> allocs;
+};
+int voc_finish(CorbVoc* v, int device, CorbVoc** out, const char* who);
 #define BOW_MAX_SETS 65535          // descriptor sets per transform call: the sets are one grid dimension
 
 // corb_bow_profile: event pairs per launch, and wall-clock ticks of the two in-order sums (ticks[0] the norm loop of bow_build_kernel, [1] that kernel's lane 0 in all;
@@ -38,5 +47,6 @@ struct BowProfile { CorbProfiler* prof; unsigned long long* ticks; };
 BowProfile corb_bow_profile_state();
 
 void corb_launch_bow_transform(const BowVocView& v, const BowSetDev* sets, int n_sets, int max_n, int levelsup, int32_t* feat_word, uint32_t* feat_node, hipStream_t s, int* rc_attr = nullptr);
+void corb_launch_bow_descend(const BowVocView& v, const BowSetDev* sets, int n_sets, int max_n, int32_t* feat_word, uint32_t* feat_node, hipStream_t s);      // the descent alone, levelsup 0
 void corb_launch_kfdb_detect(const BowDbDev& d, int kind, int query_entry, int query_words, unsigned long long query_id, int n_connected, float min_score, hipStream_t s);
 void corb_launch_kfdb_score(const BowDbDev& d, int entry_a, int words_a, const int* entries_b, int n, hipStream_t s);

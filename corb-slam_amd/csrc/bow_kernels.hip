@@ -312,6 +312,15 @@ void corb_launch_bow_transform(const BowVocView& v, const BowSetDev* sets, int n
     CORB_LAUNCH(pf.prof, "bow_build_kernel", bow_build_kernel, dim3(n_sets), dim3(256), (size_t)P * 16, s, v, sets, feat_word, feat_node, pf.ticks);
 }
 
+// the descent alone: vocabulary training counts the images of every word with it (sets[i] needs desc, n and feat_off only; any number of features per set)
+void corb_launch_bow_descend(const BowVocView& v, const BowSetDev* sets, int n_sets, int max_n, int32_t* feat_word, uint32_t* feat_node, hipStream_t s)
+{
+    if (n_sets <= 0 || n_sets > BOW_MAX_SETS || max_n <= 0) return;
+    const BowProfile pf = corb_bow_profile_state();
+    if (v.k <= 16) CORB_LAUNCH(pf.prof, "bow_descend_kernel", bow_descend_kernel<16>, dim3((max_n + 15) / 16, n_sets), dim3(256), 0, s, v, sets, 0, feat_word, feat_node);
+    else CORB_LAUNCH(pf.prof, "bow_descend_kernel", bow_descend_kernel<32>, dim3((max_n + 7) / 8, n_sets), dim3(256), 0, s, v, sets, 0, feat_word, feat_node);
+}
+
 void corb_launch_kfdb_detect(const BowDbDev& d, int kind, int q, int nq, unsigned long long id, int n_conn, float min_score, hipStream_t s)
 {
     const int n_sc = nq > n_conn ? nq : n_conn, g_sc = (((n_sc > 2 ? n_sc : 2) + 255) / 256), g_e = (d.capacity + 3) / 4;

@@ -114,6 +114,7 @@ struct BowVocHost {
     std::vector<int> child_first, child_count, slot_node, node_word;
     std::vector<unsigned long long> slot_desc;
     std::vector<double> word_weight;
+    std::vector<double> node_weight;        // [n_nodes] as given, inner nodes too (corb_voc_get returns them)
     BowVocView view() const { return BowVocView{k, L, n_nodes, n_words, child_first.data(), child_count.data(), slot_desc.data(), slot_node.data(), node_word.data(), word_weight.data()}; }
 };
 
@@ -125,9 +126,10 @@ inline std::string bow_voc_build(int k, int L, int scoring, int weighting, int n
     if (scoring != 0 || weighting != 0) return "only L1_NORM scoring (0) with TF_IDF weighting (0) is supported";
     if (n < 1 || !parent || !is_leaf || !desc || !weight) return "empty vocabulary";
     BowVocHost& v = *out; v = BowVocHost(); v.k = k; v.L = L; v.n_nodes = n + 1;
-    v.child_first.assign(n + 1, 0); v.child_count.assign(n + 1, 0); v.node_word.assign(n + 1, -1);
+    v.child_first.assign(n + 1, 0); v.child_count.assign(n + 1, 0); v.node_word.assign(n + 1, -1); v.node_weight.assign(n + 1, 0.0);
     for (int i = 1; i <= n; i++) {
         const int p = parent[i - 1];
+        v.node_weight[i] = weight[i - 1];
         if (p < 0 || p >= i) { snprintf(msg, sizeof msg, "node %d: parent %d is not before it", i, p); return msg; }
         if (v.node_word[p] >= 0) { snprintf(msg, sizeof msg, "node %d: its parent %d is a leaf", i, p); return msg; }
         if (++v.child_count[p] > k) { snprintf(msg, sizeof msg, "node %d has more than k = %d children", p, k); return msg; }

@@ -57,13 +57,6 @@ extern "C" int corb_bow_profile_read(CorbKernelTime* out, int cap, int* n)
     return CORB_OK;
 }
 
-struct CorbVoc {
-    int device = 0;
-    BowVocHost host;
-    BowVocView dev{};                 // device pointers
-    std::vector<void*> allocs;
-};
-
 template <class T> static hipError_t voc_upload(CorbVoc* v, const T** out, const std::vector<T>& src)
 {
     void* p = nullptr; hipError_t e = hipMalloc(&p, std::max(src.size(), (size_t)1) * sizeof(T)); if (e != hipSuccess) return e;
@@ -71,7 +64,7 @@ template <class T> static hipError_t voc_upload(CorbVoc* v, const T** out, const
     return src.empty() ? hipSuccess : hipMemcpy(p, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice);
 }
 
-static int voc_finish(CorbVoc* v, int device, CorbVoc** out, const char* who)
+int voc_finish(CorbVoc* v, int device, CorbVoc** out, const char* who)
 {
     int rc = corb_select_device(device); if (rc) { delete v; return rc; }
     v->device = device;

@@ -24,6 +24,7 @@
 //     with the oracle (tests/test_gpu_host.py).
 #pragma once
 #include "corb_host.hpp"
+#include <corb_voc_train.h>
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -978,6 +979,22 @@ public:
     ~ORBVocabulary() { if (h_) corb_voc_destroy(h_); }
     bool loadFromTextFile(const std::string& path, int device = 0) { if (h_) { corb_voc_destroy(h_); h_ = nullptr; } return corb_voc_load_text(path.c_str(), device, &h_) == CORB_OK; }
     void create(const CorbVocDesc& d, int device = 0) { if (h_) { corb_voc_destroy(h_); h_ = nullptr; } check(corb_voc_create(&d, device, &h_), "corb_voc_create"); }
+    // TemplatedVocabulary::create(training_features, k, L) (:592-600) on the device (include/corb_voc_train.h): one vector of descriptors per training image; `seed`
+    // stands where the source seeds rand() from the clock, max_iterations bounds the k-means loop the source leaves unbounded (stats->capped_nodes tells)
+    template <class Desc> void create(const std::vector<std::vector<Desc>>& training_features, int k, int L, uint64_t seed = 0, int max_iterations = 100, int device = 0, CorbVocTrainStats* stats = nullptr)
+    {
+        std::vector<int32_t> off(1, 0); std::vector<uint8_t> d;
+        for (const auto& image : training_features) {
+            for (const auto& f : image) { const uint8_t* r = adapt::desc_row(f, 0); d.insert(d.end(), r, r + 32); }
+            off.push_back((int32_t)(d.size() / 32));
+        }
+        d.resize(d.size() + 32);
+        const CorbVocTrainOptions o{k, L, max_iterations, 0, seed};
+        if (h_) { corb_voc_destroy(h_); h_ = nullptr; }
+        check(corb_voc_train(d.data(), off.data(), (int)training_features.size(), &o, device, &h_, stats), "corb_voc_train");
+    }
+    // saveToTextFile (:1429-1449): weight_digits 0 writes the source's bytes, 17 a file that reloads bit for bit
+    void saveToTextFile(const std::string& path, int weight_digits = 0) const { check(corb_voc_save_text(h_, path.c_str(), weight_digits), "corb_voc_save_text"); }
     unsigned size() const { int32_t w = 0; if (h_) corb_voc_info(h_, nullptr, nullptr, nullptr, &w); return (unsigned)w; }
     bool empty() const { return size() == 0; }
     template <class Desc, class BowVec, class FeatVec> void transform(const std::vector<Desc>& features, BowVec& v, FeatVec& fv, int levelsup) const
