@@ -54,6 +54,9 @@ EXPORTS = [
 
 # include/corb_voc_train.h: vocabulary training and export, an offline tool beside the drop-in boundary (exported from the same library)
 TRAIN_EXPORTS = ("corb_voc_train", "corb_voc_train_store", "corb_voc_get", "corb_voc_save_text")
+# include/corb_keyframe_insert.h: keyframe insertion on records, bound the same way
+KFINSERT_EXPORTS = ("corb_kfi_create", "corb_kfi_destroy", "corb_kfi_create_stereo_points", "corb_kfi_need_keyframe_counts", "corb_kfi_process_new_keyframe",
+                    "corb_kfi_map_point_culling")
 
 
 class CorbError(RuntimeError):
@@ -406,6 +409,19 @@ def load():
     L.corb_voc_train_store.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(VocTrainOptions), C.POINTER(C.c_void_p), C.POINTER(VocTrainStats)]
     L.corb_voc_get.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
     L.corb_voc_save_text.argtypes = [C.c_void_p, C.c_char_p, C.c_int]
+    for name in KFINSERT_EXPORTS:
+        if not hasattr(L, name):
+            raise CorbError("libcorb_accel.so lacks %s (include/corb_keyframe_insert.h): rebuild it" % name)
+    L.corb_kfi_create.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
+    L.corb_kfi_destroy.argtypes = [C.c_void_p]; L.corb_kfi_destroy.restype = None
+    L.corb_kfi_create_stereo_points.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(TrackCamera), C.c_float, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_int32,
+                                                C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.corb_kfi_need_keyframe_counts.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_float, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.corb_kfi_process_new_keyframe.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_void_p,
+                                                C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.corb_kfi_map_point_culling.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_uint64, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                             C.POINTER(C.c_int), C.POINTER(C.c_int)]
     _lib = L
     return L
 
@@ -2039,6 +2055,69 @@ class MapPointStore:
     def build_index(self, first, n):
         """corb_mp_store_build_index: the mnId -> slot table the tracking calls on records look map points up in"""
         _chk(load().corb_mp_store_build_index(self.h, int(first), int(n)), "corb_mp_store_build_index")
+
+
+ERR_CAPACITY = -2                # CORB_ERR_CAPACITY
+
+
+class KeyframeInserter:
+    """Keyframe insertion on records (include/corb_keyframe_insert.h): the stereo points of CreateNewKeyFrame / StereoInitialization / UpdateLastFrame, the counts of
+    NeedNewKeyFrame, ProcessNewKeyFrame's association loop and MapPointCulling.  One handle per client: it owns the calls' device scratch and a stream.  A call that
+    answers CORB_ERR_CAPACITY returns its complete outputs with capacity_error = True instead of raising (nothing was written)."""
+
+    def __init__(self, max_features, max_recent, device=0):
+        self.h = C.c_void_p(); self.F = max_features; self.R = max_recent
+        _chk(load().corb_kfi_create(device, int(max_features), int(max_recent), C.byref(self.h)), "corb_kfi_create")
+
+    def close(self):
+        if self.h:
+            load().corb_kfi_destroy(self.h); self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @staticmethod
+    def _rc(rc, what):
+        if rc != ERR_CAPACITY:
+            _chk(rc, what)
+        return rc == ERR_CAPACITY
+
+    def CreateStereoPoints(self, kf, slot, mp_store, cam, th_depth, mode=1, apply=False, first_mp_slot=0, first_mp_id=0, client_id=0, frame_id=0, mirror=None, mirror_slot=-1):
+        """corb_kfi_create_stereo_points: dict(order, kind, x3d, n_visited, n_created, capacity_error)"""
+        n = max(kf._n_features(slot), 1)
+        order = np.zeros(n, np.int32); kind = np.zeros(n, np.uint8); x3d = np.zeros((n, 3), np.float32); nv = C.c_int(0); nc = C.c_int(0)
+        rc = load().corb_kfi_create_stereo_points(self.h, kf.h, int(slot), mp_store.h, C.byref(cam), C.c_float(th_depth), int(mode), int(bool(apply)), int(first_mp_slot),
+                                                  int(first_mp_id), int(client_id), int(frame_id), mirror.h if mirror is not None else None, int(mirror_slot),
+                                                  _p(order), _p(kind), _p(x3d), C.byref(nv), C.byref(nc))
+        full = self._rc(rc, "corb_kfi_create_stereo_points")
+        return dict(order=order[: nv.value].copy(), kind=kind[: nv.value].copy(), x3d=x3d[: nc.value].copy(), n_visited=nv.value, n_created=nc.value, capacity_error=full)
+
+    def NeedKeyFrameCounts(self, frames, cur_slot, mp_store, th_depth, kf, ref_slot, min_obs, kf_first, kf_n):
+        """corb_kfi_need_keyframe_counts: (nTrackedClose, nNonTrackedClose, nRefMatches)"""
+        a = C.c_int(0); b = C.c_int(0); c = C.c_int(0)
+        _chk(load().corb_kfi_need_keyframe_counts(self.h, frames.h, int(cur_slot), mp_store.h, C.c_float(th_depth), kf.h, int(ref_slot), int(min_obs), int(kf_first), int(kf_n),
+                                                  C.byref(a), C.byref(b), C.byref(c)), "corb_kfi_need_keyframe_counts")
+        return a.value, b.value, c.value
+
+    def ProcessNewKeyFrame(self, kf, slot, mp_store, kf_first, kf_n, scale_factor=1.2, apply=False):
+        """corb_kfi_process_new_keyframe: dict(kind, recent_slots, n_added, capacity_error)"""
+        n = max(kf._n_features(slot), 1)
+        kind = np.zeros(n, np.uint8); recent = np.zeros(n, np.int32); na = C.c_int(0); nr = C.c_int(0)
+        rc = load().corb_kfi_process_new_keyframe(self.h, kf.h, int(slot), mp_store.h, int(kf_first), int(kf_n), C.c_float(scale_factor), int(bool(apply)), _p(kind), _p(recent),
+                                                  C.byref(na), C.byref(nr))
+        full = self._rc(rc, "corb_kfi_process_new_keyframe")
+        return dict(kind=kind[: kf._n_features(slot)].copy(), recent_slots=recent[: nr.value].copy(), n_added=na.value, capacity_error=full)
+
+    def MapPointCulling(self, mp_store, recent_slots, cur_kf_id, th_obs, kf, kf_first, kf_n, apply=False):
+        """corb_kfi_map_point_culling: dict(decision, kept_slots, n_culled)"""
+        sl = np.ascontiguousarray(recent_slots, np.int32); n = len(sl)
+        dec = np.zeros(max(n, 1), np.uint8); kept = np.zeros(max(n, 1), np.int32); nk = C.c_int(0); ncu = C.c_int(0)
+        _chk(load().corb_kfi_map_point_culling(self.h, mp_store.h, _p(sl) if n else None, n, int(cur_kf_id), int(th_obs), kf.h, int(kf_first), int(kf_n), int(bool(apply)),
+                                               _p(dec), _p(kept), C.byref(nk), C.byref(ncu)), "corb_kfi_map_point_culling")
+        return dict(decision=dec[:n].copy(), kept_slots=kept[: nk.value].copy(), n_culled=ncu.value)
 
 
 def map_push_plan(headers, root, kf_capacity, mp_capacity, kf_dst_first, mp_dst_first=None):

@@ -7,10 +7,9 @@
 // (double accumulation, one rounding), cv::norm / Mat::dot = double sums (numerics contract).  The kernel is a few waves of dependent FP64 per call and
 // latency bound: one lane per pair, the 4x4 A and V of the Jacobi iteration in registers (every index below is a compile-time constant after unrolling).
 #include "newpoints_internal.h"
+#include "kfinsert_math.h"              // NpCam, np_cam_finish, np_unproject_uv: shared with kfinsert_kernels.hip
 
 namespace {
-
-struct NpCam { float T[12]; float Ow[3]; float fx, fy, cx, cy, invfx, invfy; };
 
 __device__ __forceinline__ void np_load_cam(const NpSide& s, NpCam& c)
 {
@@ -18,10 +17,7 @@ __device__ __forceinline__ void np_load_cam(const NpSide& s, NpCam& c)
 #pragma unroll
     for (int k = 0; k < 12; k++) c.T[k] = T[k];
     c.fx = s.hdr ? s.hdr->m.fx : s.fx; c.fy = s.hdr ? s.hdr->m.fy : s.fy; c.cx = s.hdr ? s.hdr->m.cx : s.cx; c.cy = s.hdr ? s.hdr->m.cy : s.cy;
-    c.invfx = 1.0f / c.fx; c.invfy = 1.0f / c.fy;                      // Frame.cc: invfx = 1.0f / fx
-    // Ow = -Rcw^T * tcw : exact negation of the transposed rotation, then cv::gemm (proj_host.h camera_centre)
-#pragma unroll
-    for (int i = 0; i < 3; i++) { double s_ = 0; for (int k = 0; k < 3; k++) s_ += (double)(-c.T[k * 4 + i]) * (double)c.T[k * 4 + 3]; c.Ow[i] = (float)s_; }
+    np_cam_finish(c);                                                  // invfx = 1.0f / fx; Ow = -Rcw^T * tcw
 }
 // Rcw.row(r).dot(x3Dt) : Mat::dot, a double sum
 __device__ __forceinline__ double np_rowdot(const NpCam& c, int r, const float* X)
@@ -90,12 +86,7 @@ __device__ __forceinline__ float np_cos_stereo(float mb, float depth)
     return (float)((d * d - h * h) / (d * d + h * h));
 }
 // KeyFrame::UnprojectStereo (C/src/KeyFrame.cc:741-754): Twc = [Rcw^T | Ow]
-__device__ __forceinline__ void np_unproject(const NpCam& c, const CorbKeyPoint& k, float z, float* X)
-{
-    const float x = (k.x - c.cx) * z * c.invfx, y = (k.y - c.cy) * z * c.invfy;
-#pragma unroll
-    for (int i = 0; i < 3; i++) X[i] = (float)((double)c.T[0 * 4 + i] * (double)x + (double)c.T[1 * 4 + i] * (double)y + (double)c.T[2 * 4 + i] * (double)z + (double)c.Ow[i]);
-}
+__device__ __forceinline__ void np_unproject(const NpCam& c, const CorbKeyPoint& k, float z, float* X) { np_unproject_uv(c, k.x, k.y, z, X); }
 // reprojection test of one keyframe (:334-379); bf is the CURRENT keyframe's in both (:349, :372)
 __device__ __forceinline__ bool np_reproj_ok(const NpCam& c, const float* X, float z, const CorbKeyPoint& k, float ur, bool stereo, float bf, float sigma2)
 {

@@ -3,13 +3,8 @@
 // record(handle) -> the keyframe's record.  Device code only.
 #pragma once
 #include "store_internal.h"
+#include "kfinsert_math.h"             // bas_camera_center: stated once for the kernels and the host check
 
-// camera centre from a pose (KeyFrame::SetPose: Ow = -Rwc * tcw in float, KeyFrame.cc:120-135)
-__device__ __forceinline__ void bas_camera_center(const float* T, float* Ow)
-{
-#pragma unroll
-    for (int a = 0; a < 3; a++) Ow[a] = -(T[0 * 4 + a] * T[3] + T[1 * 4 + a] * T[7] + T[2 * 4 + a] * T[11]);
-}
 // the first `kept` observations of the record; mvScaleFactors rebuilt from scale_factor as ORBextractor.cc:418-424 does
 template <class Lookup>
 __device__ __forceinline__ void corb_update_normal_depth(const Lookup& L, CorbMapPointRecord* h, const unsigned long long* okf, const uint32_t* oidx, int kept, const RecLayout& KL, float scale_factor)

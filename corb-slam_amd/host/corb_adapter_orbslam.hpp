@@ -25,12 +25,14 @@
 #pragma once
 #include "corb_host.hpp"
 #include <corb_voc_train.h>
+#include <corb_keyframe_insert.h>
 #include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <cstdlib>
 #include <cstring>
 #include <functional>
+#include <list>
 #include <map>
 #include <set>
 #include <thread>
@@ -524,6 +526,77 @@ public:
     }
 };
 
+
+// ---- the moment a tracked frame becomes a keyframe, on records (include/corb_keyframe_insert.h) ----
+//   Tracking::CreateNewKeyFrame / StereoInitialization / UpdateLastFrame's point creation     Tracking.cc:1096-1158, 524-540, 830-883
+//   LocalMapping::ProcessNewKeyFrame's association loop                                          LocalMapping.cc:132-151
+//   LocalMapping::MapPointCulling                                                                LocalMapping.cc:161-188
+// The keyframe / frame is the record MapStoreT::PutKeyFrame (or a front-end) filed in `slot`; nothing is flattened but ids and slots.  One object per client: it owns
+// the calls' device scratch (CorbKfInsert).  A CORB_ERR_CAPACITY answer is thrown like every other error: nothing was written.
+template <class KeyFrame, class MapPoint>
+class KeyFrameInsertT {
+public:
+    KeyFrameInsertT(int maxFeatures, int maxRecent, int device = 0) { check(corb_kfi_create(device, maxFeatures, maxRecent, &h_), "corb_kfi_create"); }
+    KeyFrameInsertT(const KeyFrameInsertT&) = delete; KeyFrameInsertT& operator=(const KeyFrameInsertT&) = delete;
+    ~KeyFrameInsertT() { if (h_) corb_kfi_destroy(h_); }
+    CorbKfInsert* handle() const { return h_; }
+
+    // vOrder[j] = feature of visited entry j, vKind[j] (1, 2: created), vX3D = 3 floats per created point: the k-th is record firstMpSlot + k with id firstMpId + k
+    struct StereoPoints { std::vector<int32_t> vOrder; std::vector<uint8_t> vKind; std::vector<float> vX3D; int nCreated = 0; };
+    // F = pKF (KeyFrame*, modes 0 / 1) or the last Frame (mode 2): only its N is read, the features are the record's
+    template <class FrameLike>
+    StereoPoints CreateStereoPoints(const FrameLike& F, CorbKfStore* kf, int slot, CorbMpStore* map, const CorbTrackCamera& cam, float thDepth, int mode, bool apply,
+                                    int firstMpSlot, uint64_t firstMpId, int clientId, long frameId, CorbKfStore* mirror = nullptr, int mirrorSlot = -1)
+    {
+        const size_t N = (size_t)std::max(F.N, 1);
+        StereoPoints o; o.vOrder.resize(N); o.vKind.resize(N); o.vX3D.resize(3 * N);
+        int nVisited = 0;
+        check(corb_kfi_create_stereo_points(h_, kf, slot, map, &cam, thDepth, mode, apply ? 1 : 0, firstMpSlot, firstMpId, clientId, (int64_t)frameId, mirror, mirrorSlot,
+                                            o.vOrder.data(), o.vKind.data(), o.vX3D.data(), &nVisited, &o.nCreated), "corb_kfi_create_stereo_points");
+        o.vOrder.resize((size_t)nVisited); o.vKind.resize((size_t)nVisited); o.vX3D.resize(3 * (size_t)o.nCreated);
+        return o;
+    }
+    // nTrackedClose, nNonTrackedClose (Tracking.cc:1026-1035) of the frame record; nRefMatches = mpReferenceKF->TrackedMapPoints(nMinObs) of record refSlot
+    struct KeyFrameCounts { int nTrackedClose = 0, nNonTrackedClose = 0, nRefMatches = 0; };
+    KeyFrameCounts NeedNewKeyFrameCounts(CorbKfStore* frames, int curSlot, CorbMpStore* map, float thDepth, CorbKfStore* kf, int refSlot, int nMinObs, int kfFirst, int kfN)
+    {
+        KeyFrameCounts c;
+        check(corb_kfi_need_keyframe_counts(h_, frames, curSlot, map, thDepth, kf, refSlot, nMinObs, kfFirst, kfN, &c.nTrackedClose, &c.nNonTrackedClose, &c.nRefMatches),
+              "corb_kfi_need_keyframe_counts");
+        return c;
+    }
+    // vKind per feature (3: the observation was added), vRecentSlots = the map-point slots that enter mlpRecentAddedMapPoints, in feature order
+    struct Association { std::vector<uint8_t> vKind; std::vector<int32_t> vRecentSlots; int nAdded = 0; };
+    Association ProcessNewKeyFrame(KeyFrame* pKF, CorbKfStore* kf, int slot, CorbMpStore* map, int kfFirst, int kfN, float scaleFactor, bool apply)
+    {
+        const size_t N = (size_t)std::max(pKF->N, 1);
+        Association o; o.vKind.resize(N); o.vRecentSlots.resize(N);
+        int nRecent = 0;
+        check(corb_kfi_process_new_keyframe(h_, kf, slot, map, kfFirst, kfN, scaleFactor, apply ? 1 : 0, o.vKind.data(), o.vRecentSlots.data(), &o.nAdded, &nRecent),
+              "corb_kfi_process_new_keyframe");
+        o.vKind.resize((size_t)pKF->N); o.vRecentSlots.resize((size_t)nRecent);
+        return o;
+    }
+    // mlpRecentAddedMapPoints is walked as the reference walks it: an entry whose decision is not 0 leaves the list.  slotOf(pMP) = its record's slot.  Returns the
+    // decisions in list order (2, 3: SetBadFlag was done on the records when apply; the objects are the caller's to mark).
+    template <class SlotOf>
+    std::vector<uint8_t> MapPointCulling(std::list<MapPoint*>& lRecent, SlotOf slotOf, CorbMpStore* map, unsigned long nCurrentKFid, bool bMonocular, CorbKfStore* kf,
+                                         int kfFirst, int kfN, bool apply)
+    {
+        std::vector<int32_t> slots; slots.reserve(lRecent.size());
+        for (MapPoint* pMP : lRecent) slots.push_back((int32_t)slotOf(pMP));
+        std::vector<uint8_t> decision(std::max<size_t>(slots.size(), 1)); std::vector<int32_t> kept(std::max<size_t>(slots.size(), 1));
+        int nKept = 0, nCulled = 0;
+        check(corb_kfi_map_point_culling(h_, map, slots.data(), (int)slots.size(), (uint64_t)nCurrentKFid, bMonocular ? 2 : 3, kf, kfFirst, kfN, apply ? 1 : 0,
+                                         decision.data(), kept.data(), &nKept, &nCulled), "corb_kfi_map_point_culling");
+        decision.resize(slots.size());
+        size_t i = 0;
+        for (auto lit = lRecent.begin(); lit != lRecent.end(); i++) { if (decision[i] != 0) lit = lRecent.erase(lit); else ++lit; }
+        return decision;
+    }
+private:
+    CorbKfInsert* h_ = nullptr;
+};
 
 // ---- the tracking thread on device-resident records (corb_track_*, include/corb_accel.h): a Frame lives in a slot of a keyframe store, the client's map in a
 // map-point store; the calls below are Tracking::TrackWithMotionModel / TrackLocalMap's matcher and optimiser calls with the reference's argument meaning.
@@ -1297,6 +1370,7 @@ namespace accel {
 using ORBmatcher = corb::adapt::ORBmatcherT<KeyFrame, Frame, MapPoint, cv::Mat>;
 using Optimizer = corb::adapt::OptimizerT<KeyFrame, Frame, MapPoint, Cache, cv::Mat>;
 using MapStore = corb::adapt::MapStoreT<KeyFrame, MapPoint, cv::Mat>;
+using KeyFrameInsert = corb::adapt::KeyFrameInsertT<KeyFrame, MapPoint>;
 using FrameStore = corb::adapt::FrameStoreT<Frame, MapPoint, cv::Mat>;
 using Sim3Solver = corb::Sim3Solver<KeyFrame, MapPoint>;
 using PnPsolver = corb::PnPsolver<Frame, KeyFrame, MapPoint>;
