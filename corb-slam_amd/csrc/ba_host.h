@@ -22,11 +22,7 @@
 #include <memory>
 #include <thread>
 #include <vector>
-
-void corb_set_error(const char* fmt, ...);
-int corb_select_device(int device);
-
-#define HIPCHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { corb_set_error("%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); return CORB_ERR_HIP; } } while (0)
+#include "host_util.h"
 
 #define BA_TRACE(what) do { static const bool t_ = getenv("CORB_BA_TRACE") != nullptr; if (t_) { fprintf(stderr, "[corb_ba trace] %s\n", what); fflush(stderr); } } while (0)
 struct Lap {                          // CORB_BA_TIMING=1: host-side phase times of a call on stderr (development aid)

@@ -1,7 +1,7 @@
 // corb_ba_store.cpp -- Optimizer::GlobalBundleAdjustemnt on store records (see include/corb_accel.h: corb_ba_solve_store).
 // What the server rank runs after a map push and the re-basing (corbslam_server/src/GlobalOptimize.cpp:435-547 -> corbslam_client/src/Optimizer.cc:43-270):
 // the graph is derived on the device from the keyframe / map-point records, solved, and the estimates are written back into the records.
-#include "store_host.h"
+#include "record_call.h"
 #include "ba_store_internal.h"
 static_assert(sizeof(CorbBAOptions) == 32, "CorbBAOptions: scale_factor fills what was padding -- the struct's size is part of the C-ABI");
 #include "ba_host.h"
@@ -63,9 +63,7 @@ static int build_graph(const char* who, CorbKfStore* kf, const int32_t* kf_slots
     if (n_kf) HIPCHK(hipMemcpyAsync(dks, kf_slots, sizeof(int) * (size_t)n_kf, hipMemcpyHostToDevice, s));
     if (n_mp) HIPCHK(hipMemcpyAsync(dms, mp_slots, sizeof(int) * (size_t)n_mp, hipMemcpyHostToDevice, s));
     d.kf_slots = dks; d.mp_slots = dms;
-    size_t cap = 64; while (cap < 2 * (size_t)n_kf) cap <<= 1;
-    HIPCHK(buf.alloc(&d.tab.keys, cap)); HIPCHK(buf.alloc(&d.tab.vals, cap)); d.tab.mask = (unsigned int)(cap - 1);
-    HIPCHK(hipMemsetAsync(d.tab.keys, 0xFF, cap * 8, s));
+    { const int rc_ = id_table_scratch(buf, n_kf, d.tab, false, s); if (rc_) return rc_; }
     HIPCHK(buf.alloc(&d.poses, (size_t)n_kf * 16)); HIPCHK(buf.alloc(&d.intr, (size_t)n_kf * 5)); HIPCHK(buf.alloc(&d.pose_fixed, (size_t)n_kf)); HIPCHK(buf.alloc(&d.kf_bad, (size_t)n_kf));
     HIPCHK(buf.alloc(&d.points, (size_t)n_mp * 3)); HIPCHK(buf.alloc(&d.point_fixed, (size_t)n_mp)); HIPCHK(buf.alloc(&d.mp_bad, (size_t)n_mp));
     HIPCHK(buf.alloc(&d.edge_cnt, (size_t)n_mp + 1)); HIPCHK(buf.alloc(&d.edge_off, (size_t)n_mp + 1)); HIPCHK(buf.alloc(&d.status, 1));
@@ -138,8 +136,8 @@ extern "C" int corb_ba_solve_store(CorbKfStore* kf, const int32_t* kf_slots, int
     int rc = check_slots("corb_ba_solve_store", kf, kf_slots, n_kf, mp, mp_slots, n_mp); if (rc) return rc;
     if (!r || iterations < 0) { corb_set_error("corb_ba_solve_store: bad argument"); return CORB_ERR_ARG; }
     rc = corb_select_device(kf->device); if (rc) return rc;
-    std::lock_guard<std::mutex> lk_kf(kf->mu); std::lock_guard<std::mutex> lk_mp(mp->mu);
-    HIPCHK(hipStreamSynchronize(kf->stream)); HIPCHK(hipStreamSynchronize(mp->stream));
+    RecordCall call; call.hold(nullptr, kf, nullptr, mp);
+    rc = call.join(); if (rc) return rc;
     lap("store: slot checks + locks");
     hipStream_t s = mp->stream;
     DevBuf buf;
@@ -177,8 +175,8 @@ extern "C" int corb_local_ba_store(CorbKfStore* kf, const int32_t* kf_slots, int
     if (stop_flag && *stop_flag) return CORB_OK;                  // if(pbStopFlag) if(*pbStopFlag) return; (Optimizer.cc:706-708): nothing is touched
     rc = corb_select_device(kf->device); if (rc) return rc;
     Lap lap(STORE_LAP);
-    std::lock_guard<std::mutex> lk_kf(kf->mu); std::lock_guard<std::mutex> lk_mp(mp->mu);
-    HIPCHK(hipStreamSynchronize(kf->stream)); HIPCHK(hipStreamSynchronize(mp->stream));
+    RecordCall call; call.hold(nullptr, kf, nullptr, mp);
+    rc = call.join(); if (rc) return rc;
     hipStream_t s = mp->stream;
     lap("locks + stream syncs");
     // the store's scratch, grown to what the previous calls asked for

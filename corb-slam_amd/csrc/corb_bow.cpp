@@ -11,9 +11,7 @@
 #include <string>
 #include <mutex>
 
-void corb_set_error(const char* fmt, ...);
-int corb_select_device(int device);
-#define HIPCHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { corb_set_error("%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); return CORB_ERR_HIP; } } while (0)
+#include "host_util.h"
 
 static_assert(sizeof(BowKfState) == sizeof(CorbKfDbState) && sizeof(CorbKfDbState) == 32, "CorbKfDbState is BowKfState, field for field");
 static_assert(BOW_MAX_FEATURES == CORB_BOW_MAX_FEATURES, "the LDS limit of bow_build_kernel");

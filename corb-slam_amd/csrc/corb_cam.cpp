@@ -7,7 +7,7 @@
 #include <cstring>
 #include <map>
 
-#define HIPCHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { corb_set_error("%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); return CORB_ERR_HIP; } } while (0)
+#include "host_util.h"
 
 struct CorbRgbd {
     CorbOrb* orb = nullptr;

@@ -13,9 +13,7 @@
 #include <mutex>
 #include <vector>
 
-void corb_set_error(const char* fmt, ...);
-int corb_select_device(int device);
-#define HIPCHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { corb_set_error("%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); return CORB_ERR_HIP; } } while (0)
+#include "host_util.h"
 
 // ---- RCCL (librccl.so loaded on first use: a process that never pushes a map does not pay for it) ----
 namespace {
@@ -366,6 +364,7 @@ int push_exchange(CorbComm* c, const CorbMapPush* p, int root, const std::vector
     //                while it PACKS (always into the staging buffer: an in-place message would have to stay locked until it is read), the receiving rank locks
     //                its destination stores while it copies, between the barriers (CorbComm::exchange).
     // An asynchronous push (begin ... wait) leaves the records in flight unlocked in between: that window is the caller's to keep (include/corb_accel.h).
+    // The order is record_locks.h's (keyframe store, then map); the locks are this function's own because the in-process transport releases them early.
     std::unique_lock<std::mutex> lk_kf, lk_mp;
     if (p->kf) lk_kf = std::unique_lock<std::mutex>(p->kf->mu);
     if (p->mp) lk_mp = std::unique_lock<std::mutex>(p->mp->mu);

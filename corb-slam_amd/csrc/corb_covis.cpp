@@ -6,8 +6,6 @@
 #include <vector>
 #include <algorithm>
 
-#define HIPCHK COVIS_HIPCHK
-
 extern "C" int corb_covis_create(CorbKfStore* kf, CorbMpStore* mp, int max_connections, CorbCovis** out)
 {
     if (!out || !kf || !mp || max_connections > COVIS_MAX_CONNECTIONS) { corb_set_error("corb_covis_create: bad argument (max_connections <= %d)", COVIS_MAX_CONNECTIONS); return CORB_ERR_ARG; }

@@ -9,14 +9,10 @@
 #include <cmath>
 #include <cfloat>
 #include <cstring>
-
-void corb_set_error(const char* fmt, ...);
-int corb_select_device(int device);
+#include "host_util.h"
 
 
 struct GPool : CorbScratch { GPool() : CorbScratch(1) {} };     // long-optimisation lane
-
-#define HIPCHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { corb_set_error("%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); return CORB_ERR_HIP; } } while (0)
 
 extern "C" int corb_optimize_essential_graph(int n_keyframes, double* S, const uint8_t* fixed, int n_edges, const int32_t* vi, const int32_t* vj,
                                              const double* measurement, int iterations, int fix_scale, float* Tiw_out, int n_points,

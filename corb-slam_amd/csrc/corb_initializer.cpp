@@ -7,9 +7,7 @@
 #include <vector>
 #include <algorithm>
 
-void corb_set_error(const char* fmt, ...);
-int corb_select_device(int device);
-#define HIPCHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { corb_set_error("%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); return CORB_ERR_HIP; } } while (0)
+#include "host_util.h"
 
 static_assert(sizeof(InitResult) == sizeof(CorbInitResult) && sizeof(CorbInitResult) == 264, "CorbInitResult is InitResult, field for field");
 static_assert(INIT_OK == CORB_INIT_OK && INIT_NO_MODEL == CORB_INIT_NO_MODEL && INIT_H_DEGENERATE == CORB_INIT_H_DEGENERATE && INIT_AMBIGUOUS == CORB_INIT_AMBIGUOUS &&

@@ -2,14 +2,10 @@
 // stream, one synchronisation and one read-back per call.  No workspace lane: every temporary lives in the CorbKfInsert handle -- an output block on the device with a
 // page-locked mirror, the list / slot scratch, and two id tables (first occurrences; the keyframes at hand), both refilled by every call that reads them.
 #include "kfinsert_internal.h"
-#include "store_host.h"
+#include "record_call.h"
 #include "../../include/corb_keyframe_insert.h"
 #include <algorithm>
 #include <cstring>
-
-void corb_set_error(const char* fmt, ...);
-int corb_select_device(int device);
-#define HIPCHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { corb_set_error("%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); return CORB_ERR_HIP; } } while (0)
 
 struct CorbKfInsert {
     int device = 0, F = 0, R = 0;
@@ -23,52 +19,21 @@ struct CorbKfInsert {
 };
 
 namespace {
-unsigned int table_cap(long long entries) { unsigned int cap = 64; while ((long long)cap < 2 * std::max<long long>(entries, 1)) cap <<= 1; return cap; }
-int table_alloc(CorbIdTable& t, unsigned int cap)
+// a table of the handle's holds at least `entries` ids (it only grows)
+int table_room(CorbIdTable& t, long long entries)
 {
-    if (t.keys && t.mask + 1 >= cap) return CORB_OK;
-    if (t.keys) { (void)hipFree(t.keys); t.keys = nullptr; t.vals = nullptr; }
-    char* mem = nullptr;
-    HIPCHK(hipMalloc((void**)&mem, (size_t)cap * 12));
-    t.keys = reinterpret_cast<unsigned long long*>(mem); t.vals = reinterpret_cast<int*>(mem + (size_t)cap * 8); t.mask = cap - 1;
-    return CORB_OK;
-}
-// empty, ready for corb_idtab_insert_min
-int table_clear(const CorbIdTable& t, hipStream_t s)
-{
-    HIPCHK(hipMemsetAsync(t.keys, 0xFF, (size_t)(t.mask + 1) * 8, s));
-    HIPCHK(hipMemsetAsync(t.vals, 0x7F, (size_t)(t.mask + 1) * 4, s));
-    return CORB_OK;
+    const size_t cap = id_table_capacity(entries);
+    return t.keys && (size_t)t.mask + 1 >= cap ? CORB_OK : id_table_own(t, cap, 0);
 }
 // mnId -> slot of the keyframes [kf_first, kf_first + kf_n), as corb_mp_store_replace builds it
 int index_keyframes(CorbKfInsert* h, const CorbKfStore* kf, int kf_first, int kf_n)
 {
-    int rc = table_alloc(h->kfid, table_cap(kf_n)); if (rc) return rc;
-    rc = table_clear(h->kfid, h->stream); if (rc) return rc;
+    int rc = table_room(h->kfid, kf_n); if (rc) return rc;
+    rc = id_table_clear(h->kfid, true, h->stream); if (rc) return rc;
     corb_launch_kf_index(kf->base, kf->L.bytes, kf_first, kf_n, h->kfid, h->stream);
     return CORB_OK;
 }
 bool range_ok(const CorbKfStore* kf, int kf_first, int kf_n) { return kf && kf_first >= 0 && kf_n >= 0 && (long long)kf_first + kf_n <= kf->capacity; }
-// the locks of a call: the handle, the keyframe store(s) by address, the map
-struct Locks {
-    std::unique_lock<std::mutex> lk_h, lk_a, lk_b, lk_map;
-    Locks(CorbKfInsert* h, CorbKfStore* a, CorbKfStore* b, CorbMpStore* map)
-    {
-        lk_h = std::unique_lock<std::mutex>(h->mu);
-        CorbKfStore* lo = a ? a : b; CorbKfStore* hi = (a && b && b != a) ? b : nullptr;
-        if (hi && hi < lo) std::swap(lo, hi);
-        if (lo) lk_a = std::unique_lock<std::mutex>(lo->mu);
-        if (hi) lk_b = std::unique_lock<std::mutex>(hi->mu);
-        if (map) lk_map = std::unique_lock<std::mutex>(map->mu);
-    }
-};
-int slot_count(const char* who, const CorbKfStore* kf, int slot)
-{
-    const int n = kf->host[slot].n;
-    if (n < 0) corb_set_error("%s: slot %d is empty (or was filled without a host-known feature count)", who, slot);
-    return n;
-}
-bool has_index(const CorbMpStore* map) { return map->idt.keys && map->idt_valid; }
 size_t al16(size_t v) { return (v + 15) & ~(size_t)15; }
 }  // namespace
 
@@ -85,7 +50,7 @@ extern "C" int corb_kfi_create(int device, int max_features, int max_recent, Cor
     if (e == hipSuccess) e = hipMalloc((void**)&h->out, h->out_bytes);
     if (e == hipSuccess) e = hipHostMalloc((void**)&h->host, std::max(h->out_bytes, m * 4));
     if (e == hipSuccess) e = hipMalloc((void**)&h->slots, m * 4);
-    if (e != hipSuccess || table_alloc(h->first, table_cap((long long)m)) != CORB_OK || table_alloc(h->kfid, 64) != CORB_OK) {
+    if (e != hipSuccess || table_room(h->first, (long long)m) != CORB_OK || table_room(h->kfid, 0) != CORB_OK) {
         if (e != hipSuccess) corb_set_error("corb_kfi_create: %s", hipGetErrorString(e));
         corb_kfi_destroy(h); return CORB_ERR_HIP;
     }
@@ -122,14 +87,14 @@ extern "C" int corb_kfi_create_stereo_points(CorbKfInsert* h, CorbKfStore* kf, i
     if (apply && (first_mp_slot < 0 || first_mp_slot > map->capacity)) { corb_set_error("%s: bad first map-point slot", who); return CORB_ERR_ARG; }
     if (apply && mode != 2 && map->O < 1) { corb_set_error("%s: the map-point store holds no observation per point", who); return CORB_ERR_CAPACITY; }
     int rc = corb_select_device(h->device); if (rc) return rc;
-    Locks lk(h, kf, mirror, map);
-    const int n = slot_count(who, kf, slot); if (n < 0) return CORB_ERR_ARG;
+    RecordCall call; call.hold(&h->mu, kf, mirror, map);
+    const int n = record_slot_count(who, kf, slot); if (n < 0) return CORB_ERR_ARG;
     if (mirror && mirror->host[mirror_slot].n < n) { corb_set_error("%s: the mirror slot is empty or holds fewer features than the keyframe", who); return CORB_ERR_ARG; }
-    if (mode != 0 && !has_index(map)) { corb_set_error("%s: the map-point store has no current id index (corb_mp_store_build_index after the last put / push)", who); return CORB_ERR_ARG; }
+    if (mode != 0) { rc = record_need_index(who, map); if (rc) return rc; }
     *n_visited = 0; *n_created = 0;
     if (n == 0) return CORB_OK;
     if (!order || !kind || !x3d) { corb_set_error("%s: NULL output", who); return CORB_ERR_ARG; }
-    HIPCHK(hipStreamSynchronize(kf->stream)); if (mirror && mirror != kf) HIPCHK(hipStreamSynchronize(mirror->stream)); HIPCHK(hipStreamSynchronize(map->stream));
+    rc = call.join(); if (rc) return rc;
 
     KfiPointsDev d; memset(&d, 0, sizeof(d));
     d.rec = kf->rec(slot); d.F = kf->F;
@@ -163,12 +128,12 @@ extern "C" int corb_kfi_need_keyframe_counts(CorbKfInsert* h, CorbKfStore* frame
         ref_slot >= kf->capacity) { corb_set_error("%s: bad argument", who); return CORB_ERR_ARG; }
     if (frames->device != h->device || map->device != h->device || kf->device != h->device) { corb_set_error("%s: the stores and the handle live on different devices", who); return CORB_ERR_ARG; }
     int rc = corb_select_device(h->device); if (rc) return rc;
-    Locks lk(h, frames, kf, map);
-    const int n_cur = slot_count(who, frames, cur_slot); if (n_cur < 0) return CORB_ERR_ARG;
-    const int n_ref = ref_slot < 0 ? 0 : slot_count(who, kf, ref_slot); if (n_ref < 0) return CORB_ERR_ARG;
-    if (!has_index(map)) { corb_set_error("%s: the map-point store has no current id index (corb_mp_store_build_index after the last put / push)", who); return CORB_ERR_ARG; }
+    RecordCall call; call.hold(&h->mu, frames, kf, map);
+    const int n_cur = record_slot_count(who, frames, cur_slot); if (n_cur < 0) return CORB_ERR_ARG;
+    const int n_ref = ref_slot < 0 ? 0 : record_slot_count(who, kf, ref_slot); if (n_ref < 0) return CORB_ERR_ARG;
+    rc = record_need_index(who, map); if (rc) return rc;
     *n_tracked_close = *n_non_tracked_close = *n_ref_matches = 0;
-    HIPCHK(hipStreamSynchronize(frames->stream)); if (kf != frames) HIPCHK(hipStreamSynchronize(kf->stream)); HIPCHK(hipStreamSynchronize(map->stream));
+    rc = call.join(); if (rc) return rc;
     rc = index_keyframes(h, kf, kf_first, kf_n); if (rc) return rc;
     KfiCountsDev d; memset(&d, 0, sizeof(d));
     d.cur = frames->rec(cur_slot); d.cur_F = frames->F; d.n_cur = n_cur; d.th_depth = th_depth;
@@ -195,9 +160,9 @@ extern "C" int corb_kfi_process_new_keyframe(CorbKfInsert* h, CorbKfStore* kf, i
     if (kf->device != h->device || map->device != h->device || kf->F > h->F) { corb_set_error("%s: the stores and the handle live on different devices, or the store holds more features per record than the handle (%d)", who, h->F); return CORB_ERR_ARG; }
     if (map->O > 1024) { corb_set_error("%s: more than 1024 observations per map point", who); return CORB_ERR_ARG; }
     int rc = corb_select_device(h->device); if (rc) return rc;
-    Locks lk(h, kf, nullptr, map);
-    const int n = slot_count(who, kf, slot); if (n < 0) return CORB_ERR_ARG;
-    if (!has_index(map)) { corb_set_error("%s: the map-point store has no current id index (corb_mp_store_build_index after the last put / push)", who); return CORB_ERR_ARG; }
+    RecordCall call; call.hold(&h->mu, kf, nullptr, map);
+    const int n = record_slot_count(who, kf, slot); if (n < 0) return CORB_ERR_ARG;
+    rc = record_need_index(who, map); if (rc) return rc;
     *n_added = 0; *n_recent = 0;
     if (n == 0) return CORB_OK;
     if (!kind || !recent_slots) { corb_set_error("%s: NULL output", who); return CORB_ERR_ARG; }
@@ -206,9 +171,9 @@ extern "C" int corb_kfi_process_new_keyframe(CorbKfInsert* h, CorbKfStore* kf, i
         if (h->desc) { (void)hipFree(h->desc); h->desc = nullptr; h->desc_words = 0; }
         HIPCHK(hipMalloc((void**)&h->desc, words * 8)); h->desc_words = words;
     }
-    HIPCHK(hipStreamSynchronize(kf->stream)); HIPCHK(hipStreamSynchronize(map->stream));
+    rc = call.join(); if (rc) return rc;
     rc = index_keyframes(h, kf, kf_first, kf_n); if (rc) return rc;
-    rc = table_clear(h->first, h->stream); if (rc) return rc;
+    rc = id_table_clear(h->first, true, h->stream); if (rc) return rc;
     KfiAssocDev d; memset(&d, 0, sizeof(d));
     d.rec = kf->rec(slot); d.F = kf->F; d.n = n;
     d.mp_base = map->base; d.mp_bytes = map->L.bytes; d.max_obs = map->O; d.idt = map->idt;
@@ -239,10 +204,10 @@ extern "C" int corb_kfi_map_point_culling(CorbKfInsert* h, CorbMpStore* map, con
     *n_kept = 0; *n_culled = 0;
     if (n == 0) return CORB_OK;
     int rc = corb_select_device(h->device); if (rc) return rc;
-    Locks lk(h, kf, nullptr, map);
-    HIPCHK(hipStreamSynchronize(kf->stream)); HIPCHK(hipStreamSynchronize(map->stream));
+    RecordCall call; call.hold(&h->mu, kf, nullptr, map);
+    rc = call.join(); if (rc) return rc;
     rc = index_keyframes(h, kf, kf_first, kf_n); if (rc) return rc;
-    rc = table_clear(h->first, h->stream); if (rc) return rc;
+    rc = id_table_clear(h->first, true, h->stream); if (rc) return rc;
     memcpy(h->host, recent_slots, (size_t)n * 4);
     HIPCHK(hipMemcpyAsync(h->slots, h->host, (size_t)n * 4, hipMemcpyHostToDevice, h->stream));
     KfiCullDev d; memset(&d, 0, sizeof(d));

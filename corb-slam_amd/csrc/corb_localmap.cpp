@@ -6,7 +6,6 @@
 #include <vector>
 #include <algorithm>
 
-#define HIPCHK COVIS_HIPCHK
 static_assert(sizeof(CorbLocalMap) == 32 && offsetof(LocalMapHead, status) == 32, "LocalMapHead starts with CorbLocalMap");
 
 extern "C" int corb_track_update_local_map(CorbCovis* g, CorbKfStore* frames, int slot, const int32_t* prev_kf_slots, int n_prev, int32_t* kf_slots, int kf_cap,
@@ -20,7 +19,7 @@ extern "C" int corb_track_update_local_map(CorbCovis* g, CorbKfStore* frames, in
     int rc = corb_select_device(g->kf->device); if (rc) return rc;
     CovisCall c; rc = c.begin(g, who, true, frames); if (rc) return rc;
     // under the locks: the frame's slot and the previous local keyframes hold filled records (as the other calls on records ask of their slots)
-    if (frames->host[slot].n < 0) { corb_set_error("%s: slot %d is empty (or was filled without a host-known feature count)", who, slot); return CORB_ERR_ARG; }
+    if (record_slot_count(who, frames, slot) < 0) return CORB_ERR_ARG;
     for (int i = 0; i < n_prev; i++) if (g->kf->host[prev_kf_slots[i]].n < 0) { corb_set_error("%s: previous local keyframe %d (slot %d) is an empty slot", who, i, prev_kf_slots[i]); return CORB_ERR_ARG; }
     CorbScratch& pool = *c.scratch;
     const int M = g->R.M, K = g->kf->capacity;

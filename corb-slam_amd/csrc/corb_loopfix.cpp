@@ -6,7 +6,6 @@
 #include <vector>
 #include <algorithm>
 
-#define HIPCHK COVIS_HIPCHK
 static_assert(sizeof(CorbGbaPropagation) == 28 && offsetof(GbaHead, status) == 28, "GbaHead starts with CorbGbaPropagation");
 
 extern "C" int corb_loop_correct_store(CorbCovis* g, int cur_slot, const double* Scw, float scale_factor, int32_t* kf_slots, double* corrected, double* non_corrected,

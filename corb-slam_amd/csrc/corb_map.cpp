@@ -2,13 +2,10 @@
 #include "corb_internal.h"
 #include "corb_workspace.h"
 #include <vector>
+#include "host_util.h"
 
-void corb_set_error(const char* fmt, ...);
-int corb_select_device(int device);
 void corb_launch_distinctive(const unsigned long long* desc, const int* offset, int n_points, int* best_idx, int* status, hipStream_t s);
 void corb_launch_rebase(const float* To2n, float* poses, int n_poses, float* points, int n_points, hipStream_t s);
-
-#define HIPCHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { corb_set_error("%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); return CORB_ERR_HIP; } } while (0)
 
 extern "C" int corb_distinctive_descriptors(const uint8_t* desc, const int32_t* offset, int n_points, int32_t* best_idx, int device)
 {

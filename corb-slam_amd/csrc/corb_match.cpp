@@ -10,10 +10,8 @@
 #include <algorithm>
 #include <cstring>
 
-void corb_set_error(const char* fmt, ...);
-int corb_select_device(int device);
+#include "host_util.h"
 
-#define HIPCHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { corb_set_error("%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); return CORB_ERR_HIP; } } while (0)
 
 namespace {
 struct DevArena {          // one allocation, bump-carved, freed on scope exit

@@ -3,14 +3,9 @@
 // triangulation and the new MapPoint records with one synchronisation and one read-back).
 #include "newpoints_internal.h"
 #include "match_internal.h"
-#include "store_host.h"
-#include "corb_workspace.h"
+#include "record_call.h"
 #include <cstring>
 #include <vector>
-
-void corb_set_error(const char* fmt, ...);
-int corb_select_device(int device);
-#define HIPCHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { corb_set_error("%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); return CORB_ERR_HIP; } } while (0)
 
 namespace {
 bool side_ok(const CorbNewPointSide* s)
@@ -76,18 +71,16 @@ extern "C" int corb_create_new_map_points_store(CorbKfStore* kf, int cur_slot, c
     if (apply && (!map || map->device != kf->device || first_mp_slot < 0 || first_mp_slot > map->capacity)) { corb_set_error("%s: bad map-point store / first slot", who); return CORB_ERR_ARG; }
     if (apply && map->O < 2) { corb_set_error("%s: the map-point store holds fewer than two observations per point", who); return CORB_ERR_CAPACITY; }
     int rc = corb_select_device(kf->device); if (rc) return rc;
-    // lock order of the calls on records (corb_fuse_store): the keyframe store, the map, then the workspace lane
-    std::unique_lock<std::mutex> lk_kf(kf->mu), lk_map;
-    if (apply) lk_map = std::unique_lock<std::mutex>(map->mu);
+    RecordCall call; call.hold(nullptr, kf, nullptr, apply ? map : nullptr);            // (the map is written only when the points are applied)
     const CorbKfStore::Host& hc = kf->host[cur_slot];
-    if (hc.n < 0 || !hc.header_valid) { corb_set_error("%s: slot %d is empty (or was filled without a host-known feature count)", who, cur_slot); return CORB_ERR_ARG; }
+    if (record_slot_count(who, kf, cur_slot, true) < 0) return CORB_ERR_ARG;
     for (int j = 0; j < n_nb; j++) if (kf->host[nb_slots[j]].n < 0 || !kf->host[nb_slots[j]].header_valid) { corb_set_error("%s: neighbour slot %d is empty", who, nb_slots[j]); return CORB_ERR_ARG; }
     const int n1 = hc.n;
     for (int j = 0; j <= n_nb; j++) pair_offset[j] = 0;
     *n_new = 0;
     if (n_nb == 0 || n1 == 0) return CORB_OK;
     if (!pairs || !x3d || !status || !source) { corb_set_error("%s: NULL output", who); return CORB_ERR_ARG; }
-    HIPCHK(hipStreamSynchronize(kf->stream)); if (apply) HIPCHK(hipStreamSynchronize(map->stream));
+    rc = call.join(); if (rc) return rc;
 
     // the common vocabulary nodes of every neighbour, from the host mirror of the node ids
     std::vector<int> pa, pb, com_off((size_t)n_nb + 1, 0);

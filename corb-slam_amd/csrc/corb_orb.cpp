@@ -1,7 +1,7 @@
 // corb_orb.cpp -- C-ABI host side of the ORB extractor and the stereo front-end (see include/corb_accel.h).
 // Mirrors the constructor arithmetic of ORB_SLAM2::ORBextractor (corbslam_client/src/ORBextractor.cc:410-470)
 // and owns device memory, one HIP stream per handle and the launch sequence.  No CPU compute fallback.
-#include "corb_internal.h"
+#include "host_util.h"
 #include "orb_handle.h"
 #include <cmath>
 #include <cfloat>
@@ -35,8 +35,6 @@ extern "C" int corb_pinned_alloc(size_t bytes, void** out)
     return CORB_OK;
 }
 extern "C" int corb_pinned_free(void* p) { return (!p || hipHostFree(p) == hipSuccess) ? CORB_OK : CORB_ERR_HIP; }
-
-#define HIPCHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { corb_set_error("%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); return CORB_ERR_HIP; } } while (0)
 
 static inline int cv_round(double v) { return (int)lrint(v); }            // cvRound (round-half-even)
 static inline int cv_floor(double v) { int i = cv_round(v); float d = (float)(v - i); return i - (d < 0); }

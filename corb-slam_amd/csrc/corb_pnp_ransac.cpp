@@ -1,16 +1,11 @@
 // corb_pnp_ransac.cpp -- C-ABI host side of the PnPsolver RANSAC (include/corb_accel.h, last section): the host-array form (corb_pnp_ransac) and the form on records
 // (corb_pnp_ransac_store).  All candidates of a call are queued on one stream with one synchronisation and one read-back; SetRansacParameters' adjustments and cap and the list of records are assembled here, after the read-back.
 #include "pnp_ransac_internal.h"
-#include "store_host.h"
-#include "corb_workspace.h"
+#include "record_call.h"
 #include <cmath>
 #include <cstring>
 #include <vector>
 #include <algorithm>
-
-void corb_set_error(const char* fmt, ...);
-int corb_select_device(int device);
-#define HIPCHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { corb_set_error("%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); return CORB_ERR_HIP; } } while (0)
 
 namespace {
 #define PNR_MAX_ITERATIONS 65535
@@ -190,11 +185,9 @@ extern "C" int corb_pnp_ransac_store(CorbKfStore* frames, int slot, CorbMpStore*
     if (!frames || !map || !cam || slot < 0 || slot >= frames->capacity || frames->device != map->device || n_candidates < 0 || (n_candidates > 0 && (!matched_ids || !n_corr)) ||
         cam->nlevels < 1 || cam->nlevels > CORB_MAX_LEVELS) { corb_set_error("%s: bad argument", who); return CORB_ERR_ARG; }
     int rc = corb_select_device(frames->device); if (rc) return rc;
-    // lock order of the calls on records (corb_fuse_store): the keyframe store, the map, then the workspace lane
-    std::unique_lock<std::mutex> lk_kf(frames->mu), lk_map(map->mu);
-    const int n1 = frames->host[slot].n;
-    if (n1 < 0) { corb_set_error("%s: slot %d is empty (or was filled without a host-known feature count)", who, slot); return CORB_ERR_ARG; }
-    if (!map->idt.keys || !map->idt_valid) { corb_set_error("%s: the map-point store has no current id index (corb_mp_store_build_index after the last put / push)", who); return CORB_ERR_ARG; }
+    RecordCall call; call.hold(nullptr, frames, nullptr, map);
+    const int n1 = record_slot_count(who, frames, slot); if (n1 < 0) return CORB_ERR_ARG;
+    rc = record_need_index(who, map); if (rc) return rc;
     const PnrParams a{probability, min_inliers, max_iterations, min_set, epsilon, th2, tail_iterations, rand_values, max_records};
     const PnrOut o{ransac_max_its, ransac_min_inliers, n_records, records, best_flags, refined_flags, n1, counts, pose_out, refine_pose_out};
     if (!pnr_args_ok(who, n_candidates, a, o)) return CORB_ERR_ARG;
@@ -202,7 +195,7 @@ extern "C" int corb_pnp_ransac_store(CorbKfStore* frames, int slot, CorbMpStore*
     for (int c = 0; c < n_candidates; c++) n_corr[c] = 0;
     if (index) for (size_t i = 0; i < (size_t)n_candidates * n1; i++) index[i] = -1;
     if (n_candidates == 0 || n1 == 0) return CORB_OK;
-    HIPCHK(hipStreamSynchronize(frames->stream)); HIPCHK(hipStreamSynchronize(map->stream));
+    rc = call.join(); if (rc) return rc;
     const int stride_its = max_iterations + tail_iterations;
     std::vector<PnrCand> cand((size_t)n_candidates);
     for (int c = 0; c < n_candidates; c++) { PnrCand& cd = cand[c]; memset(&cd, 0, sizeof(cd)); cd.n = n1; cd.its = stride_its; }

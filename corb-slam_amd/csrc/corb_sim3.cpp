@@ -4,9 +4,7 @@
 #include <vector>
 #include <cmath>
 #include <cstring>
-
-void corb_set_error(const char* fmt, ...);
-int corb_select_device(int device);
+#include "host_util.h"
 
 
 namespace {
@@ -35,8 +33,6 @@ void quat_to_R(const double* q, double* R)
     R[6] = txz - twy; R[7] = tyz + twx; R[8] = 1 - (txx + tyy);
 }
 }  // namespace
-
-#define HIPCHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { corb_set_error("%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); return CORB_ERR_HIP; } } while (0)
 
 extern "C" int corb_optimize_sim3(const CorbSim3Problem* problems, int n_problems, double* R12, double* t12, double* s12, float th2, int fix_scale,
                                   uint8_t* const* removed, int32_t* n_inliers, int32_t* iterations, int device)

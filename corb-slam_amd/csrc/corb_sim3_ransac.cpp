@@ -2,16 +2,11 @@
 // records (corb_sim3_ransac_store).  All candidates of a call are queued on one stream with one synchronisation and one read-back; SetRansacParameters' cap and the
 // rule that turns the per-hypothesis inlier counts into iterate()'s returns are stated once, here, for both.
 #include "sim3_ransac_internal.h"
-#include "store_host.h"
-#include "corb_workspace.h"
+#include "record_call.h"
 #include <cmath>
 #include <cstring>
 #include <vector>
 #include <algorithm>
-
-void corb_set_error(const char* fmt, ...);
-int corb_select_device(int device);
-#define HIPCHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { corb_set_error("%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); return CORB_ERR_HIP; } } while (0)
 
 namespace {
 #define S3R_MAX_ITERATIONS 65535
@@ -156,12 +151,10 @@ extern "C" int corb_sim3_ransac_store(CorbKfStore* kf, int slot1, const int32_t*
     for (int c = 0; c < n_candidates; c++)
         if (slots2[c] < 0 || slots2[c] >= kf->capacity || slots2[c] == slot1 || cam2[c].nlevels < 1 || cam2[c].nlevels > CORB_MAX_LEVELS) { corb_set_error("%s: candidate %d: bad slot or camera", who, c); return CORB_ERR_ARG; }
     int rc = corb_select_device(kf->device); if (rc) return rc;
-    // lock order of the calls on records (corb_fuse_store): the keyframe store, the map, then the workspace lane
-    std::unique_lock<std::mutex> lk_kf(kf->mu), lk_map(map->mu);
-    const int n1 = kf->host[slot1].n;
-    if (n1 < 0) { corb_set_error("%s: slot %d is empty (or was filled without a host-known feature count)", who, slot1); return CORB_ERR_ARG; }
+    RecordCall call; call.hold(nullptr, kf, nullptr, map);
+    const int n1 = record_slot_count(who, kf, slot1); if (n1 < 0) return CORB_ERR_ARG;
     for (int c = 0; c < n_candidates; c++) if (kf->host[slots2[c]].n < 0) { corb_set_error("%s: candidate slot %d is empty", who, slots2[c]); return CORB_ERR_ARG; }
-    if (!map->idt.keys || !map->idt_valid) { corb_set_error("%s: the map-point store has no current id index (corb_mp_store_build_index after the last put / push)", who); return CORB_ERR_ARG; }
+    rc = record_need_index(who, map); if (rc) return rc;
     const S3rParams a{probability, min_inliers, max_iterations, fix_scale ? 1 : 0, rand_values, max_events};
     const S3rOut o{ransac_max_its, n_events, events, inlier_flags, n1, counts, q_out};
     if (!s3r_args_ok(who, n_candidates, a, o)) return CORB_ERR_ARG;
@@ -169,7 +162,7 @@ extern "C" int corb_sim3_ransac_store(CorbKfStore* kf, int slot1, const int32_t*
     for (int c = 0; c < n_candidates; c++) n_corr[c] = 0;
     if (index1) for (size_t i = 0; i < (size_t)n_candidates * n1; i++) index1[i] = -1;
     if (n_candidates == 0 || n1 == 0) return CORB_OK;
-    HIPCHK(hipStreamSynchronize(kf->stream)); HIPCHK(hipStreamSynchronize(map->stream));
+    rc = call.join(); if (rc) return rc;
     std::vector<S3rCand> cand((size_t)n_candidates);
     for (int c = 0; c < n_candidates; c++) {
         S3rCand& cd = cand[c]; memset(&cd, 0, sizeof(cd));

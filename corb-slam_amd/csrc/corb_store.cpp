@@ -5,18 +5,13 @@
 // whole records between the ranks' device buffers (xGMI), no serialisation, no host staging.
 #include "match_internal.h"
 #include "store_internal.h"
-#include "store_host.h"
-#include "corb_workspace.h"
+#include "record_call.h"
 #include <dlfcn.h>
 #include <string>
 #include <algorithm>
 #include <cstring>
 #include <mutex>
 #include <vector>
-
-void corb_set_error(const char* fmt, ...);
-int corb_select_device(int device);
-#define HIPCHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { corb_set_error("%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); return CORB_ERR_HIP; } } while (0)
 
 extern "C" int corb_kf_store_create(int device, int capacity, int max_features, CorbKfStore** out)
 {
@@ -200,22 +195,23 @@ extern "C" int corb_kf_store_get(CorbKfStore* s, int slot, CorbKeyPoint* kp, uin
 }
 
 // ---- matchers on slots: the kernels of corb_match.cpp on the records' device arrays ----
-static int two_slots(CorbKfStore* a, int sa, CorbKfStore* b, int sb, const char* who)
+// `call` holds the two stores (a == b: one) from here on: the caller keeps it until its last read of host[]
+static int two_slots(RecordCall& call, CorbKfStore* a, int sa, CorbKfStore* b, int sb, const char* who)
 {
     int rc = slot_ok(a, sa, who); if (rc) return rc;
     rc = slot_ok(b, sb, who); if (rc) return rc;
     if (a->device != b->device) { corb_set_error("%s: the two stores live on different devices", who); return CORB_ERR_ARG; }
     rc = corb_select_device(a->device); if (rc) return rc;
-    { std::lock_guard<std::mutex> lk(a->mu); rc = refresh_host(a, sa); if (rc) return rc; }
-    { std::lock_guard<std::mutex> lk(b->mu); rc = refresh_host(b, sb); if (rc) return rc; }
-    HIPCHK(hipStreamSynchronize(a->stream)); HIPCHK(hipStreamSynchronize(b->stream));      // pending fills of the two records
-    return CORB_OK;
+    call.hold(nullptr, a, b, nullptr);
+    rc = refresh_host(a, sa); if (rc) return rc;
+    rc = refresh_host(b, sb); if (rc) return rc;
+    return call.join();                                                                    // pending fills of the two records
 }
 
 extern "C" int corb_search_by_bow_slots(int variant, CorbKfStore* A, int sa, CorbKfStore* B, int sb, float nnratio, int check_orientation, int32_t* match, int* n_matches)
 {
     if ((variant != 0 && variant != 1) || !n_matches) { corb_set_error("corb_search_by_bow_slots: bad argument"); return CORB_ERR_ARG; }
-    int rc = two_slots(A, sa, B, sb, "corb_search_by_bow_slots"); if (rc) return rc;
+    RecordCall call; int rc = two_slots(call, A, sa, B, sb, "corb_search_by_bow_slots"); if (rc) return rc;
     const CorbKfStore::Host& ha = A->host[sa]; const CorbKfStore::Host& hb = B->host[sb];
     const int n1 = ha.n, n2 = hb.n, n_out = variant == 0 ? n2 : n1;
     *n_matches = 0;
@@ -251,7 +247,7 @@ extern "C" int corb_search_for_triangulation_slots(CorbKfStore* A, int sa, CorbK
                                                    const float* sigma2_2, int nlevels, int only_stereo, int check_orientation, int32_t* pairs, int* n_matches)
 {
     if (!F12 || !scale2 || !sigma2_2 || nlevels < 1 || nlevels > CORB_MAX_LEVELS || !n_matches) { corb_set_error("corb_search_for_triangulation_slots: bad argument"); return CORB_ERR_ARG; }
-    int rc = two_slots(A, sa, B, sb, "corb_search_for_triangulation_slots"); if (rc) return rc;
+    RecordCall call; int rc = two_slots(call, A, sa, B, sb, "corb_search_for_triangulation_slots"); if (rc) return rc;
     const CorbKfStore::Host& ha = A->host[sa]; const CorbKfStore::Host& hb = B->host[sb];
     const int n1 = ha.n, n2 = hb.n;
     *n_matches = 0;
@@ -274,7 +270,7 @@ extern "C" int corb_search_for_triangulation_slots(CorbKfStore* A, int sa, CorbK
                               {(void**)&dsc, scale2, (size_t)nlevels * 4}, {(void**)&dsg, sigma2_2, (size_t)nlevels * 4}, {(void**)&dinit, init.data(), n_init * 4}}));
     dmatch = dinit; dbin = dinit + n1; dhist = dinit + 2 * (size_t)n1; dnq = dhist + CORB_HISTO_LENGTH + 1;      // hist[HISTO_LENGTH] = n_matches
     HIPCHK(pool.alloc(&dq1, (size_t)n1)); HIPCHK(pool.alloc(&dq2, (size_t)n1));
-    HIPCHK(hipStreamSynchronize(A->stream)); if (B != A) HIPCHK(hipStreamSynchronize(B->stream));      // records are written on the stores' streams
+    rc = call.join(); if (rc) return rc;                                                               // records are written on the stores' streams
     corb_launch_tri_queries((const int*)(ra + A->L.fv_off), (const int*)(ra + A->L.fv_idx), (const uint8_t*)(ra + A->L.flags), (const float*)(ra + A->L.ur),
                             dpa, dpb, (int)pa.size(), only_stereo ? 1 : 0, dq1, dq2, dnq, pool.stream);
     CorbTriDev d;
@@ -487,14 +483,11 @@ extern "C" int corb_rebase_map_store(const float* To2n, CorbKfStore* kf, const i
     for (int i = 0; i < n_mp; i++) if (mp_slots[i] < 0 || mp_slots[i] >= mp->capacity) { corb_set_error("corb_rebase_map_store: map point slot out of range"); return CORB_ERR_ARG; }
     if (n_kf == 0 && n_mp == 0) return CORB_OK;
     int rc = corb_select_device(kf ? kf->device : mp->device); if (rc) return rc;
-    // the stores' documented lock order (keyframes, then map points), held until the re-based records are complete: a solve, a tracking call or the packing /
+    // the stores' locks (record_locks.h), held until the re-based records are complete: a solve, a tracking call or the packing /
     // receiving phase of a push from another host thread sees the map either before or after the re-basing.  NOT covered: the window of an asynchronous push
     // between corb_map_push_begin and _wait, during which the records in flight belong to the push (include/corb_accel.h) -- the caller keeps re-basing out of it.
-    std::unique_lock<std::mutex> lk_kf, lk_mp;
-    if (kf) lk_kf = std::unique_lock<std::mutex>(kf->mu);
-    if (mp) lk_mp = std::unique_lock<std::mutex>(mp->mu);
-    if (kf) HIPCHK(hipStreamSynchronize(kf->stream));
-    if (mp) HIPCHK(hipStreamSynchronize(mp->stream));
+    RecordCall call; call.hold(nullptr, kf, nullptr, mp);
+    rc = call.join(); if (rc) return rc;
     CorbScratch pool(0);
     float* dT; int *dks, *dms;
     HIPCHK(pool.upload_block({{(void**)&dT, To2n, 64}, {(void**)&dks, kf_slots, (size_t)n_kf * 4}, {(void**)&dms, mp_slots, (size_t)n_mp * 4}}));
@@ -560,13 +553,10 @@ extern "C" int corb_mp_store_replace(CorbMpStore* map, int slot_this, int slot_i
     if (status) *status = 0;
     if (slot_this == slot_into) { if (status) *status = 1; return CORB_OK; }
     int rc = corb_select_device(map->device); if (rc) return rc;
-    std::lock_guard<std::mutex> lk(kf->mu); std::lock_guard<std::mutex> lk2(map->mu);       // (always in this order)
-    HIPCHK(hipStreamSynchronize(kf->stream)); HIPCHK(hipStreamSynchronize(map->stream));
+    RecordCall call; call.hold(nullptr, kf, nullptr, map);
+    rc = call.join(); if (rc) return rc;
     CorbScratch pool(0);
-    CorbIdTable kfid; unsigned int cap = 64; while (cap < 2u * (unsigned int)(kf_n > 0 ? kf_n : 1)) cap <<= 1;
-    HIPCHK(pool.alloc(&kfid.keys, (size_t)cap)); HIPCHK(pool.alloc(&kfid.vals, (size_t)cap)); kfid.mask = cap - 1;
-    HIPCHK(hipMemsetAsync(kfid.keys, 0xFF, (size_t)cap * 8, pool.stream));
-    HIPCHK(hipMemsetAsync(kfid.vals, 0x7F, (size_t)cap * 4, pool.stream));               // (kf_index_kernel: corb_idtab_insert_min)
+    CorbIdTable kfid; rc = id_table_scratch(pool, kf_n, kfid, true, pool.stream); if (rc) return rc;      // (kf_index_kernel: corb_idtab_insert_min)
     unsigned long long* desc = nullptr; int* dst = nullptr;
     HIPCHK(pool.alloc(&desc, (size_t)map->O * 4)); HIPCHK(pool.alloc(&dst, 1));
     HIPCHK(hipMemsetAsync(dst, 0, 4, pool.stream));

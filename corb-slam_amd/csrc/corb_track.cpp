@@ -2,7 +2,7 @@
 // map point crosses PCIe; the host contributes the two poses, the camera and the launch sizes it already knows (the stores' feature counts).  The matchers run
 // the kernels of the host-pointer route (corb_proj.cpp) under the host rules both routes share (proj_host.h).
 #include "track_internal.h"
-#include "store_host.h"
+#include "record_call.h"
 #include "proj_host.h"
 
 using namespace proj_host;
@@ -12,47 +12,21 @@ void corb_pose_to_T(const double* p7, float* T);
 void corb_pose_optimization_stages(CorbBAStage* st);
 
 namespace {
-// id -> value hash table for `n` ids: a power of two, at most half full
-unsigned int id_table_capacity(int n) { unsigned int cap = 64; while (cap < 2u * (unsigned int)(n > 0 ? n : 1)) cap <<= 1; return cap; }
-// an empty table that lives as long as the call
-int id_table_scratch(CorbScratch& pool, int n, CorbIdTable& t)
-{
-    const unsigned int cap = id_table_capacity(n);
-    HIPCHK(pool.alloc(&t.keys, (size_t)cap)); HIPCHK(pool.alloc(&t.vals, (size_t)cap)); t.mask = cap - 1;
-    HIPCHK(hipMemsetAsync(t.keys, 0xFF, (size_t)cap * 8, pool.stream));
-    return CORB_OK;
-}
-
-// What every call on records does before it touches one, in this order: the argument checks that read no store state; the device; the locks (keyframe store or
-// stores by address, then the map -- the workspace lane is taken after them); and only under the locks the feature counts of the slots, which a put from
-// another thread may change until then.  The caller initialises its outputs from n / n2, takes its early return, and synchronises.
-struct RecordCall {
-    std::unique_lock<std::mutex> lk_a, lk_b, lk_map;
-    CorbKfStore* kf = nullptr; CorbKfStore* kf2 = nullptr; CorbMpStore* map = nullptr;
+// A tracking call's opening (record_call.h): its argument checks, the device, the locks, and under them the counts and the id index
+struct TrackCall : RecordCall {
     int n = 0, n2 = 0;                                   // features of (kf, slot) and of (kf2, slot2)
     // args_ok: the caller's own argument test; need_index: the call resolves MapPoint ids through the map's id index; kf2 / slot2: a second record, in `kf` or in another store
     int open(const char* who, bool args_ok, CorbKfStore* kf_, int slot, CorbMpStore* map_, const CorbTrackCamera* cam, bool need_index, CorbKfStore* kf2_ = nullptr, int slot2 = -1)
     {
-        kf = kf_; kf2 = kf2_; map = map_;
-        if (!kf || !map || !cam || slot < 0 || slot >= kf->capacity) { corb_set_error("%s: bad store / slot", who); return CORB_ERR_ARG; }
-        if (kf->device != map->device) { corb_set_error("%s: the stores live on different devices", who); return CORB_ERR_ARG; }
+        if (!kf_ || !map_ || !cam || slot < 0 || slot >= kf_->capacity) { corb_set_error("%s: bad store / slot", who); return CORB_ERR_ARG; }
+        if (kf_->device != map_->device) { corb_set_error("%s: the stores live on different devices", who); return CORB_ERR_ARG; }
         if (cam->nlevels < 1 || cam->nlevels > CORB_MAX_LEVELS || !(cam->max_x > cam->min_x) || !(cam->max_y > cam->min_y)) { corb_set_error("%s: bad camera", who); return CORB_ERR_ARG; }
-        if (!args_ok || (kf2 && (slot2 < 0 || slot2 >= kf2->capacity || kf2->device != kf->device || (kf2 == kf && slot2 == slot)))) { corb_set_error("%s: bad argument", who); return CORB_ERR_ARG; }
-        int rc = corb_select_device(kf->device); if (rc) return rc;
-        CorbKfStore* lo = kf; CorbKfStore* hi = (kf2 && kf2 != kf) ? kf2 : nullptr;
-        if (hi && hi < lo) std::swap(lo, hi);
-        lk_a = std::unique_lock<std::mutex>(lo->mu); if (hi) lk_b = std::unique_lock<std::mutex>(hi->mu);
-        lk_map = std::unique_lock<std::mutex>(map->mu);
-        n = kf->host[slot].n;
-        if (n < 0) { corb_set_error("%s: slot %d is empty (or was filled without a host-known feature count)", who, slot); return CORB_ERR_ARG; }
-        if (need_index && (!map->idt.keys || !map->idt_valid)) { corb_set_error("%s: the map-point store has no current id index (corb_mp_store_build_index after the last put / push)", who); return CORB_ERR_ARG; }
+        if (!args_ok || (kf2_ && (slot2 < 0 || slot2 >= kf2_->capacity || kf2_->device != kf_->device || (kf2_ == kf_ && slot2 == slot)))) { corb_set_error("%s: bad argument", who); return CORB_ERR_ARG; }
+        int rc = corb_select_device(kf_->device); if (rc) return rc;
+        hold(nullptr, kf_, kf2_, map_);
+        if ((n = record_slot_count(who, kf, slot)) < 0) return CORB_ERR_ARG;
+        if (need_index) { rc = record_need_index(who, map); if (rc) return rc; }
         if (kf2 && (n2 = kf2->host[slot2].n) < 0) { corb_set_error("%s: bad argument", who); return CORB_ERR_ARG; }
-        return CORB_OK;
-    }
-    // the stores' own streams may still be filling the records: the call runs on the lane's stream after them
-    int sync()
-    {
-        HIPCHK(hipStreamSynchronize(kf->stream)); if (kf2 && kf2 != kf) HIPCHK(hipStreamSynchronize(kf2->stream)); HIPCHK(hipStreamSynchronize(map->stream));
         return CORB_OK;
     }
 };
@@ -79,15 +53,10 @@ extern "C" int corb_mp_store_build_index(CorbMpStore* s, int first, int n)
     if (!s || first < 0 || n < 0 || (long long)first + n > s->capacity) { corb_set_error("corb_mp_store_build_index: bad store / slot range"); return CORB_ERR_ARG; }
     int rc = corb_select_device(s->device); if (rc) return rc;
     std::lock_guard<std::mutex> lk(s->mu);
-    const unsigned int cap = id_table_capacity(n);
-    if (!s->idt.keys || s->idt.mask + 1 != cap) {
-        if (s->idt.keys) { (void)hipFree(s->idt.keys); s->idt.keys = nullptr; s->idt.vals = nullptr; }
-        char* mem = nullptr;
-        HIPCHK(hipMalloc((void**)&mem, (size_t)cap * 12 + 256));
-        s->idt.keys = reinterpret_cast<unsigned long long*>(mem); s->idt.vals = reinterpret_cast<int*>(mem + (size_t)cap * 8); s->idt.mask = cap - 1;
-    }
-    int* dup = reinterpret_cast<int*>(reinterpret_cast<char*>(s->idt.keys) + (size_t)cap * 12);
-    HIPCHK(hipMemsetAsync(s->idt.keys, 0xFF, (size_t)cap * 8, s->stream));
+    const size_t cap = id_table_capacity(n);
+    if (!s->idt.keys || (size_t)s->idt.mask + 1 != cap) { rc = id_table_own(s->idt, cap, 256); if (rc) return rc; }         // (the tail: the duplicate flag)
+    int* dup = reinterpret_cast<int*>(reinterpret_cast<char*>(s->idt.keys) + cap * 12);
+    rc = id_table_clear(s->idt, false, s->stream); if (rc) return rc;
     HIPCHK(hipMemsetAsync(dup, 0, 4, s->stream));
     track_launch_index_store(s->base, s->L.bytes, first, n, s->idt, dup, s->stream);
     HIPCHK(hipGetLastError());
@@ -105,13 +74,13 @@ extern "C" int corb_track_search_last_frame(CorbKfStore* frames, int cur_slot, i
                                             const CorbTrackCamera* cam, float th, int mono, float nnratio, int check_orientation, int32_t* match, int* n_matches)
 {
     const char* who = "corb_track_search_last_frame";
-    RecordCall call; int rc = call.open(who, Tcw && Tlw && n_matches, frames, cur_slot, map, cam, true, frames, last_slot); if (rc) return rc;
+    TrackCall call; int rc = call.open(who, Tcw && Tlw && n_matches, frames, cur_slot, map, cam, true, frames, last_slot); if (rc) return rc;
     const int n = call.n, nq = call.n2;
     *n_matches = 0;
     if (match) for (int i = 0; i < n; i++) match[i] = -1;
     if (n == 0 || nq == 0) return CORB_OK;
     if (proj_too_large(n, nq)) { corb_set_error("%s: frame too large", who); return CORB_ERR_ARG; }
-    rc = call.sync(); if (rc) return rc;
+    rc = call.join(); if (rc) return rc;
     CorbScratch pool(0);
     TrackDev t; memset(&t, 0, sizeof(t));
     t.cur = frames->rec(cur_slot); t.last = frames->rec(last_slot); t.F = frames->F; t.mp_base = map->base; t.mp_bytes = map->L.bytes; t.idt = map->idt; t.n_cur = n; t.n_last = nq;
@@ -132,13 +101,13 @@ extern "C" int corb_track_search_last_frame(CorbKfStore* frames, int cur_slot, i
 extern "C" int corb_track_pose_optimization(CorbKfStore* frames, int slot, CorbMpStore* map, const CorbTrackCamera* cam, const float* Tcw_in, float* Tcw_out,
                                             int discard_outliers, uint8_t* outlier, int32_t* n_inliers)
 {
-    RecordCall call; int rc = call.open("corb_track_pose_optimization", Tcw_in && Tcw_out, frames, slot, map, cam, true); if (rc) return rc;
+    TrackCall call; int rc = call.open("corb_track_pose_optimization", Tcw_in && Tcw_out, frames, slot, map, cam, true); if (rc) return rc;
     const int n = call.n;
     memcpy(Tcw_out, Tcw_in, sizeof(float) * 16);
     if (n_inliers) *n_inliers = 0;
     if (outlier) memset(outlier, 0, (size_t)n);
     if (n == 0) return CORB_OK;
-    rc = call.sync(); if (rc) return rc;
+    rc = call.join(); if (rc) return rc;
     CorbScratch pool(0);
     TrackPoseDev t; memset(&t, 0, sizeof(t));
     t.cur = frames->rec(slot); t.F = frames->F; t.n_cur = n; t.mp_base = map->base; t.mp_bytes = map->L.bytes; t.idt = map->idt;
@@ -179,18 +148,18 @@ extern "C" int corb_track_search_local_points(CorbKfStore* frames, int slot, Cor
                                               int* n_matches, int* n_in_view)
 {
     const char* who = "corb_track_search_local_points";
-    RecordCall call; int rc = call.open(who, Tcw && n_matches && n_local >= 0 && (n_local == 0 || local_ids) && log_scale_factor > 0, frames, slot, map, cam, true); if (rc) return rc;
+    TrackCall call; int rc = call.open(who, Tcw && n_matches && n_local >= 0 && (n_local == 0 || local_ids) && log_scale_factor > 0, frames, slot, map, cam, true); if (rc) return rc;
     const int n = call.n, nq = n_local;
     *n_matches = 0; if (n_in_view) *n_in_view = 0;
     if (match) for (int i = 0; i < n; i++) match[i] = -1;
     if (tracked && nq) memset(tracked, 0, sizeof(CorbTrackedPoint) * (size_t)nq);
     if (n == 0) return CORB_OK;
     if (proj_too_large(n, nq)) { corb_set_error("%s: too large (%d features, %d points)", who, n, nq); return CORB_ERR_ARG; }
-    rc = call.sync(); if (rc) return rc;
+    rc = call.join(); if (rc) return rc;
     CorbScratch pool(0);
     TrackLocalDev t; memset(&t, 0, sizeof(t));
     t.cur = frames->rec(slot); t.F = frames->F; t.n_cur = n; t.mp_base = map->base; t.mp_bytes = map->L.bytes; t.idt = map->idt; t.n_local = nq;
-    rc = id_table_scratch(pool, n, t.inframe); if (rc) return rc;
+    rc = id_table_scratch(pool, n, t.inframe, false, pool.stream); if (rc) return rc;
     unsigned long long* dids = nullptr;
     if (nq > 0) HIPCHK(pool.upload_block({{(void**)&dids, local_ids, (size_t)nq * 8}})); else HIPCHK(pool.alloc(&dids, 1));
     t.ids = dids;
@@ -224,13 +193,13 @@ extern "C" int corb_fuse_store(CorbKfStore* kf, int slot, CorbMpStore* map, cons
 {
     const char* who = "corb_fuse_store";
     int rc = check_mp_slots(who, map, mp_slots, n_points); if (rc) return rc;
-    RecordCall call; rc = call.open(who, n_points >= 0 && (n_points == 0 || (mp_slots && best_idx && best_dist)) && Tcw && n_fused && log_scale_factor > 0, kf, slot, map, cam, false); if (rc) return rc;
+    TrackCall call; rc = call.open(who, n_points >= 0 && (n_points == 0 || (mp_slots && best_idx && best_dist)) && Tcw && n_fused && log_scale_factor > 0, kf, slot, map, cam, false); if (rc) return rc;
     const int n = call.n, nq = n_points;
     *n_fused = 0;
     for (int i = 0; i < nq; i++) { best_idx[i] = -1; best_dist[i] = 256; if (action) action[i] = 0; }
     if (n == 0 || nq == 0) return CORB_OK;
     if (proj_too_large(n, nq)) { corb_set_error("%s: too large (%d features, %d points)", who, n, nq); return CORB_ERR_ARG; }
-    rc = call.sync(); if (rc) return rc;
+    rc = call.join(); if (rc) return rc;
     CorbScratch pool(0);
     FuseStoreDev t; memset(&t, 0, sizeof(t));
     t.kf_rec = kf->rec(slot); t.F = kf->F; t.n_feat = n; t.mp_base = map->base; t.mp_bytes = map->L.bytes; t.max_obs = map->O; t.n_points = nq; t.apply = apply ? 1 : 0;
@@ -269,13 +238,13 @@ extern "C" int corb_fuse_sim3_store(CorbKfStore* kf, int slot, CorbMpStore* map,
 {
     const char* who = "corb_fuse_sim3_store";
     int rc = check_mp_slots(who, map, mp_slots, n_points); if (rc) return rc;
-    RecordCall call; rc = call.open(who, n_points >= 0 && (n_points == 0 || (mp_slots && best_idx && best_dist && replace_slot)) && Scw && n_fused && log_scale_factor > 0, kf, slot, map, cam, true); if (rc) return rc;
+    TrackCall call; rc = call.open(who, n_points >= 0 && (n_points == 0 || (mp_slots && best_idx && best_dist && replace_slot)) && Scw && n_fused && log_scale_factor > 0, kf, slot, map, cam, true); if (rc) return rc;
     const int n = call.n, nq = n_points;
     *n_fused = 0;
     for (int i = 0; i < nq; i++) { best_idx[i] = -1; best_dist[i] = 256; replace_slot[i] = -1; if (action) action[i] = 0; }
     if (n == 0 || nq == 0) return CORB_OK;
     if (proj_too_large(n, nq)) { corb_set_error("%s: too large (%d features, %d points)", who, n, nq); return CORB_ERR_ARG; }
-    rc = call.sync(); if (rc) return rc;
+    rc = call.join(); if (rc) return rc;
     CorbScratch pool(0);
     FuseStoreDev t; memset(&t, 0, sizeof(t));
     t.kf_rec = kf->rec(slot); t.F = kf->F; t.n_feat = n; t.mp_base = map->base; t.mp_bytes = map->L.bytes; t.max_obs = map->O; t.n_points = nq; t.apply = apply ? 1 : 0; t.mpid = map->idt;
@@ -314,18 +283,18 @@ extern "C" int corb_track_search_reloc(CorbKfStore* frames, int cur_slot, CorbKf
                                        const float* Tcw, float log_scale_factor, float th, int orb_dist, int check_orientation, int32_t* match, int* n_matches)
 {
     const char* who = "corb_track_search_reloc";
-    RecordCall call; int rc = call.open(who, kfs && Tcw && n_matches && log_scale_factor > 0, frames, cur_slot, map, cam, true, kfs, kf_slot); if (rc) return rc;
+    TrackCall call; int rc = call.open(who, kfs && Tcw && n_matches && log_scale_factor > 0, frames, cur_slot, map, cam, true, kfs, kf_slot); if (rc) return rc;
     const int n = call.n, nq = call.n2;
     *n_matches = 0;
     if (match) for (int i = 0; i < n; i++) match[i] = -1;
     if (n == 0 || nq == 0) return CORB_OK;
     if (proj_too_large(n, nq)) { corb_set_error("%s: too large (%d features, %d points)", who, n, nq); return CORB_ERR_ARG; }
-    rc = call.sync(); if (rc) return rc;
+    rc = call.join(); if (rc) return rc;
     CorbScratch pool(0);
     RelocStoreDev t; memset(&t, 0, sizeof(t));
     t.cur = frames->rec(cur_slot); t.F_cur = frames->F; t.n_cur = n; t.kf = kfs->rec(kf_slot); t.F_kf = kfs->F; t.n_kf = nq;
     t.mp_base = map->base; t.mp_bytes = map->L.bytes; t.idt = map->idt;
-    rc = id_table_scratch(pool, n, t.inframe); if (rc) return rc;
+    rc = id_table_scratch(pool, n, t.inframe, false, pool.stream); if (rc) return rc;
     HIPCHK(pool.alloc(&t.pts, (size_t)nq)); HIPCHK(pool.alloc(&t.qdesc, (size_t)nq * 4)); HIPCHK(pool.alloc(&t.claimed, (size_t)n));
     ProjBuffers pb; rc = pb.alloc(pool, n, nq, true, 0); if (rc) return rc;
     t.match = pb.res;
@@ -348,21 +317,21 @@ extern "C" int corb_search_by_projection_scw_store(CorbKfStore* kf, int slot, Co
 {
     const char* who = "corb_search_by_projection_scw_store";
     int rc = check_mp_slots(who, map, mp_slots, n_points); if (rc) return rc;
-    RecordCall call; rc = call.open(who, n_points >= 0 && (n_points == 0 || mp_slots) && Scw && n_matches && log_scale_factor > 0, kf, slot, map, cam, false); if (rc) return rc;
+    TrackCall call; rc = call.open(who, n_points >= 0 && (n_points == 0 || mp_slots) && Scw && n_matches && log_scale_factor > 0, kf, slot, map, cam, false); if (rc) return rc;
     const int n = call.n, nq = n_points;
     if (n > 0 && !matched_ids) { corb_set_error("%s: bad argument", who); return CORB_ERR_ARG; }
     *n_matches = 0;
     if (match) for (int i = 0; i < n; i++) match[i] = -1;
     if (n == 0 || nq == 0) return CORB_OK;
     if (proj_too_large(n, nq)) { corb_set_error("%s: too large (%d features, %d points)", who, n, nq); return CORB_ERR_ARG; }
-    rc = call.sync(); if (rc) return rc;
+    rc = call.join(); if (rc) return rc;
     CorbScratch pool(0);
     ScwStoreDev t; memset(&t, 0, sizeof(t));
     t.kf_rec = kf->rec(slot); t.F = kf->F; t.n_feat = n; t.mp_base = map->base; t.mp_bytes = map->L.bytes; t.n_points = nq;
     int* dslots = nullptr; unsigned long long* dmatched = nullptr;
     HIPCHK(pool.upload_block({{(void**)&dslots, mp_slots, (size_t)nq * 4}, {(void**)&dmatched, matched_ids, (size_t)n * 8}}));
     t.mp_slots = dslots; t.matched = dmatched;
-    rc = id_table_scratch(pool, n, t.found); if (rc) return rc;
+    rc = id_table_scratch(pool, n, t.found, false, pool.stream); if (rc) return rc;
     HIPCHK(pool.alloc(&t.pts, (size_t)nq)); HIPCHK(pool.alloc(&t.qdesc, (size_t)nq * 4)); HIPCHK(pool.alloc(&t.claimed, (size_t)n));
     ProjBuffers pb; rc = pb.alloc(pool, n, nq, true, 0); if (rc) return rc;
     t.match = pb.res;
@@ -389,13 +358,13 @@ extern "C" int corb_search_by_sim3_store(CorbKfStore* kf, int slot1, int slot2, 
                                          int32_t* match12, uint64_t* match12_ids, int* n_found)
 {
     const char* who = "corb_search_by_sim3_store";
-    RecordCall call; int rc = call.open(who, T1w && T2w && R12 && t12 && match12 && n_found && log_scale_factor > 0 && s12 > 0, kf, slot1, map, cam, true, kf, slot2); if (rc) return rc;
+    TrackCall call; int rc = call.open(who, T1w && T2w && R12 && t12 && match12 && n_found && log_scale_factor > 0 && s12 > 0, kf, slot1, map, cam, true, kf, slot2); if (rc) return rc;
     const int N1 = call.n, N2 = call.n2;
     *n_found = 0;
     for (int i = 0; i < N1; i++) { match12[i] = -1; if (match12_ids) match12_ids[i] = CORB_NO_MAP_POINT; }
     if (N1 == 0 || N2 == 0) return CORB_OK;
     if (N1 > PROJ_MAX_FEATURES || N2 > PROJ_MAX_FEATURES) { corb_set_error("%s: keyframe too large", who); return CORB_ERR_ARG; }
-    rc = call.sync(); if (rc) return rc;
+    rc = call.join(); if (rc) return rc;
     CorbScratch pool(0);
     Sim3StoreDev t; memset(&t, 0, sizeof(t));
     t.kf1 = kf->rec(slot1); t.kf2 = kf->rec(slot2); t.F = kf->F; t.n1 = N1; t.n2 = N2;

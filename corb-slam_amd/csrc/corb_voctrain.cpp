@@ -11,8 +11,7 @@
 #include <cstdlib>
 #include <cstring>
 
-void corb_set_error(const char* fmt, ...);
-int corb_select_device(int device);
+#include "host_util.h"
 
 static_assert(CORB_VOC_TRAIN_MAX_LEVELS == VT_MAX_LEVELS, "per-level statistics");
 

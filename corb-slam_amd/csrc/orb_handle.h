@@ -6,7 +6,7 @@
 #include <mutex>
 #include <vector>
 
-void corb_set_error(const char* fmt, ...);
+#include "host_util.h"
 
 struct CorbOrb {
     CorbOrbConfig cfg;

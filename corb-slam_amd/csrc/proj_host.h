@@ -8,10 +8,8 @@
 #include <cstring>
 #include <vector>
 
-void corb_set_error(const char* fmt, ...);
-int corb_select_device(int device);
+#include "host_util.h"
 
-#define HIPCHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { corb_set_error("%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); return CORB_ERR_HIP; } } while (0)
 
 #define PROJ_MAX_FEATURES 6000        // target features of one call (the resolution kernels keep per-feature state of one frame in LDS)
 #define PROJ_MAX_QUERIES 60000        // projected points of one call

@@ -157,3 +157,49 @@ def test_local_windows_and_essential_graph_beside_a_busy_second_thread(corb, syn
                 assert all(np.asarray(r[k]).tobytes() == np.asarray(ref[k]).tobytes() for k in keys)
     finally:
         stop[0] = True; t.join(); sf.close()
+
+
+def test_matchers_on_slots_from_threads_that_name_the_stores_in_opposite_order(corb, synth):
+    """corb_search_by_bow_slots / corb_search_for_triangulation_slots hold both stores' locks (lower address first, one lock when the stores are one) until their last
+    read of the host mirror.  Two threads name A and B in opposite argument order while a third rewrites slot (A, 0): no deadlock, and every output equals the serial
+    one.  The third thread rewrites the slot's FeatureVector and flags (set_bow, set_flags: the node ids the matchers read on the host, and identical bytes on the
+    device); a put of the features themselves would clear the FeatureVector until the next set_bow, and the outputs would then depend on the interleaving."""
+    import time
+    from test_oracle_match import _make
+    rng = np.random.default_rng(2024)
+    A = corb.KeyFrameStore(2, 64); B = corb.KeyFrameStore(2, 64)
+    for (sa, sb), (n1, n2) in (((0, 1), (51, 49)), ((1, 0), (47, 53))):          # (A, sa) and (B, sb) see the same scene
+        d1, a1, v1, fv1, d2, a2, v2, fv2 = _make(rng, synth, n1, n2, 6)
+        for st, slot, n, d, a, v, fv in ((A, sa, n1, d1, a1, v1, fv1), (B, sb, n2, d2, a2, v2, fv2)):
+            kp = np.zeros(n, corb.KP_DTYPE); kp["angle"] = a; kp["x"], kp["y"] = rng.uniform(0, 1241, n), rng.uniform(0, 376, n); kp["octave"] = rng.integers(0, 8, n)
+            ur = np.where(rng.random(n) < 0.6, kp["x"] - 5, -1).astype(np.float32)
+            st.put(slot, kp, d, ur, None, keyframe_id=10 * slot + (st is B)); st.set_bow(slot, fv); st.set_flags(slot, v)
+            if st is A and slot == 0: fv_a0, flags_a0 = fv, v
+    F12 = np.array([[0, 0, 0], [0, 0, -1], [0, 1, 0]], np.float32) + rng.normal(0, 1e-4, (3, 3)).astype(np.float32)
+    scale = (np.float32(1.2) ** np.arange(8)).astype(np.float32); sigma2 = scale * scale
+    calls = [lambda: A.SearchByBoW(0, B, 1, 0.9, True, 0), lambda: B.SearchByBoW(1, A, 0, 0.9, True, 0),
+             lambda: A.SearchForTriangulation(0, B, 1, F12, 600.0, 180.0, scale, sigma2, False), lambda: B.SearchForTriangulation(1, A, 0, F12, 600.0, 180.0, scale, sigma2, False),
+             lambda: A.SearchByBoW(0, A, 1, 0.9, True, 1)]                        # (A == B: one lock)
+    t0 = time.perf_counter()
+    ref = [c() for c in calls]
+    serial = time.perf_counter() - t0
+    assert sum(n for _, n in ref) > 0                                            # (the comparison below is not one of empty outputs)
+    out = {0: [], 1: []}
+    def search(t):
+        order = (0, 1, 2, 3, 4) if t == 0 else (1, 0, 3, 2, 4)
+        for _ in range(20):
+            out[t].append([(k, calls[k]()) for k in order])
+    def reput():
+        for _ in range(20):
+            A.set_bow(0, fv_a0); A.set_flags(0, flags_a0)
+    threads = [threading.Thread(target=search, args=(0,), daemon=True), threading.Thread(target=search, args=(1,), daemon=True), threading.Thread(target=reput, daemon=True)]
+    deadline = time.perf_counter() + max(10.0, 50 * serial)
+    for t in threads: t.start()
+    for t in threads: t.join(max(0.0, deadline - time.perf_counter()))
+    assert not any(t.is_alive() for t in threads), "the calls did not finish: the stores' locks were taken in two orders"
+    for t in (0, 1):
+        assert len(out[t]) == 20
+        for rnd in out[t]:
+            for k, (m, n) in rnd:
+                assert n == ref[k][1] and m.tobytes() == ref[k][0].tobytes(), (t, k)
+    A.close(); B.close()
