@@ -57,6 +57,9 @@ TRAIN_EXPORTS = ("corb_voc_train", "corb_voc_train_store", "corb_voc_get", "corb
 # include/corb_keyframe_insert.h: keyframe insertion on records, bound the same way
 KFINSERT_EXPORTS = ("corb_kfi_create", "corb_kfi_destroy", "corb_kfi_create_stereo_points", "corb_kfi_need_keyframe_counts", "corb_kfi_process_new_keyframe",
                     "corb_kfi_map_point_culling")
+# include/corb_map_publish.h: the server -> clients publish on records, bound the same way
+PUBLISH_EXPORTS = ("corb_pub_create", "corb_pub_destroy", "corb_pub_message_layout", "corb_pub_pack", "corb_pub_message", "corb_pub_message_read", "corb_pub_apply",
+                   "corb_map_publish_plan", "corb_map_publish_messages", "corb_map_publish")
 
 
 class CorbError(RuntimeError):
@@ -192,6 +195,31 @@ MP_SCRATCH_DTYPE = np.dtype([("first_kf_id", "<i8"), ("first_frame", "<i8"), ("t
 PUSH_HEADER_DTYPE = np.dtype([("status", "<i4"), ("n_kf", "<i4"), ("n_mp", "<i4"), ("kf_record_bytes", "<i4"), ("mp_record_bytes", "<i4")])
 NO_MAP_POINT = 0xFFFFFFFFFFFFFFFF
 KF_BAD, KF_FIXED, MP_BAD, MP_FIXED = 1, 2, 1, 2
+
+
+KF_POSE_PACKET_DTYPE = np.dtype([("id", "<u8"), ("Tcw", "<f4", 16)])                                                     # CorbKeyFramePosePacket (72 bytes)
+MP_POSE_PACKET_DTYPE = np.dtype([("id", "<u8"), ("pos", "<f4", 3), ("pad", "<u4")])                                    # CorbMapPointPosePacket (24 bytes)
+PUBLISH_TRANSFORM_DTYPE = np.dtype([("client_id", "<i4"), ("pad", "<i4"), ("T", "<f4", 16), ("Tinv", "<f4", 16)])      # CorbPublishTransform (136 bytes)
+PUBLISH_HEADER_DTYPE = np.dtype([("status", "<i4"), ("kf_record_bytes", "<i4"), ("mp_record_bytes", "<i4"), ("counts", "<i4", 5)])
+assert KF_POSE_PACKET_DTYPE.itemsize == 72 and MP_POSE_PACKET_DTYPE.itemsize == 24 and PUBLISH_TRANSFORM_DTYPE.itemsize == 136 and PUBLISH_HEADER_DTYPE.itemsize == 32
+
+
+class _PublishOutputs(C.Structure):
+    _fields_ = [("kind_kf_new", C.c_void_p), ("kind_mp_new", C.c_void_p), ("kind_kf_upd", C.c_void_p), ("kind_mp_upd", C.c_void_p), ("kf_new_slots", C.c_void_p),
+                ("mp_new_slots", C.c_void_p), ("n_kf_inserted", C.c_int32), ("n_mp_inserted", C.c_int32), ("n_kf_updated", C.c_int32), ("n_mp_updated", C.c_int32),
+                ("no_transform", C.c_int32)]
+
+
+class _PublishPack(C.Structure):
+    _fields_ = [("kf", C.c_void_p), ("new_kf_slots", C.c_void_p), ("n_new_kf", C.c_int32), ("upd_kf_slots", C.c_void_p), ("n_upd_kf", C.c_int32),
+                ("mp", C.c_void_p), ("new_mp_slots", C.c_void_p), ("n_new_mp", C.c_int32), ("upd_mp_slots", C.c_void_p), ("n_upd_mp", C.c_int32),
+                ("trans_client_id", C.c_void_p), ("trans", C.c_void_p), ("n_trans", C.c_int32)]
+
+
+class _PublishApply(C.Structure):
+    _fields_ = [("client_id", C.c_int32), ("dst_kf", C.c_void_p), ("kf_first", C.c_int32), ("kf_n", C.c_int32), ("kf_free_first", C.c_int32), ("kf_room", C.c_int32),
+                ("dst_mp", C.c_void_p), ("mp_first", C.c_int32), ("mp_n", C.c_int32), ("mp_free_first", C.c_int32), ("mp_room", C.c_int32), ("apply", C.c_int32),
+                ("out", C.POINTER(_PublishOutputs))]
 
 
 class _MapPush(C.Structure):
@@ -422,6 +450,20 @@ def load():
                                                 C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.corb_kfi_map_point_culling.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_uint64, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                              C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    for name in PUBLISH_EXPORTS:
+        if not hasattr(L, name):
+            raise CorbError("libcorb_accel.so lacks %s (include/corb_map_publish.h): rebuild it" % name)
+    L.corb_pub_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
+    L.corb_pub_destroy.argtypes = [C.c_void_p]; L.corb_pub_destroy.restype = None
+    L.corb_pub_message_layout.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+    L.corb_pub_pack.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
+    L.corb_pub_message.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    L.corb_pub_message_read.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
+    L.corb_pub_apply.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int32, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                 C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_PublishOutputs)]
+    L.corb_map_publish_plan.argtypes = [C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_int)]
+    L.corb_map_publish_messages.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.c_void_p, C.POINTER(C.c_int)]
+    L.corb_map_publish.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(_PublishPack), C.POINTER(_PublishApply)]
     _lib = L
     return L
 
@@ -2120,6 +2162,103 @@ class KeyframeInserter:
         return dict(decision=dec[:n].copy(), kept_slots=kept[: nk.value].copy(), n_culled=ncu.value)
 
 
+def publish_message_layout(counts, kf_record_bytes, mp_record_bytes):
+    """corb_pub_message_layout: byte offsets of sections A..E and the message's size.  Pure host arithmetic."""
+    c = np.ascontiguousarray(counts, np.int32); off = np.zeros(6, np.int64)
+    _chk(load().corb_pub_message_layout(_p(c), int(kf_record_bytes), int(mp_record_bytes), _p(off)), "corb_pub_message_layout")
+    return off
+
+
+class _PublishResult:
+    """the caller's arrays of a CorbPublishOutputs, sized from the counts and the rooms, and the dict they make"""
+
+    def __init__(self, counts, kf_room, mp_room):
+        self.counts = [int(x) for x in counts[:4]]
+        self.kinds = [np.zeros(max(n, 1), np.uint8) for n in self.counts]
+        self.kf_slots = np.zeros(max(min(self.counts[0], kf_room), 1), np.int32); self.mp_slots = np.zeros(max(min(self.counts[1], mp_room), 1), np.int32)
+        self.c = _PublishOutputs(_p(self.kinds[0]), _p(self.kinds[1]), _p(self.kinds[2]), _p(self.kinds[3]), _p(self.kf_slots), _p(self.mp_slots), 0, 0, 0, 0, 0)
+
+    def as_dict(self, counts=None, capacity_error=False):
+        n = self.counts if counts is None else [int(x) for x in counts[:4]]
+        c = self.c
+        return dict(kind_kf_new=self.kinds[0][: n[0]].copy(), kind_mp_new=self.kinds[1][: n[1]].copy(), kind_kf_upd=self.kinds[2][: n[2]].copy(), kind_mp_upd=self.kinds[3][: n[3]].copy(),
+                    kf_new_slots=self.kf_slots[: min(c.n_kf_inserted, len(self.kf_slots))].copy(), mp_new_slots=self.mp_slots[: min(c.n_mp_inserted, len(self.mp_slots))].copy(),
+                    n_kf_inserted=c.n_kf_inserted, n_mp_inserted=c.n_mp_inserted, n_kf_updated=c.n_kf_updated, n_mp_updated=c.n_mp_updated, no_transform=c.no_transform,
+                    capacity_error=capacity_error)
+
+
+class MapPublisher:
+    """The server -> clients publish on records (include/corb_map_publish.h): pack on the server's stores, apply on a client's.  One handle per rank: it owns the
+    message buffer, the calls' device scratch and a stream.  An apply that answers CORB_ERR_CAPACITY returns its complete outputs with capacity_error = True
+    instead of raising (nothing was written)."""
+
+    def __init__(self, device=0):
+        self.h = C.c_void_p(); self.device = device
+        _chk(load().corb_pub_create(device, C.byref(self.h)), "corb_pub_create")
+
+    def close(self):
+        if self.h:
+            load().corb_pub_destroy(self.h); self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @staticmethod
+    def _pack_args(kf, new_kf_slots, upd_kf_slots, mp, new_mp_slots, upd_mp_slots, trans):
+        """trans: {client id: 4x4} or a list of (client id, 4x4) (a list may name an id twice: the call refuses it)"""
+        items = sorted(trans.items()) if isinstance(trans, dict) else list(trans)
+        ids = np.array([int(k) for k, _ in items], np.int32); T = np.ascontiguousarray([np.asarray(t, np.float32).reshape(16) for _, t in items], np.float32).reshape(-1, 16)
+        lists = [np.ascontiguousarray(x, np.int32) for x in (new_kf_slots, upd_kf_slots, new_mp_slots, upd_mp_slots)]
+        return ids, T, lists
+
+    def pack(self, kf, new_kf_slots=(), upd_kf_slots=(), mp=None, new_mp_slots=(), upd_mp_slots=(), trans=()):
+        """corb_pub_pack: the five sections into the handle's message buffer"""
+        ids, T, (a, c, b, d) = self._pack_args(kf, new_kf_slots, upd_kf_slots, mp, new_mp_slots, upd_mp_slots, trans)
+        _chk(load().corb_pub_pack(self.h, kf.h if kf is not None else None, _p(a) if len(a) else None, len(a), _p(c) if len(c) else None, len(c),
+                                  mp.h if mp is not None else None, _p(b) if len(b) else None, len(b), _p(d) if len(d) else None, len(d),
+                                  _p(ids) if len(ids) else None, _p(T) if len(ids) else None, len(ids)), "corb_pub_pack")
+
+    def message(self):
+        """corb_pub_message: dict(ptr, bytes, counts, kf_record_bytes, mp_record_bytes) of the last pack"""
+        ptr = C.c_void_p(); n = C.c_int64(0); counts = np.zeros(5, np.int32); kb = C.c_int32(0); mb = C.c_int32(0)
+        _chk(load().corb_pub_message(self.h, C.byref(ptr), C.byref(n), _p(counts), C.byref(kb), C.byref(mb)), "corb_pub_message")
+        return dict(ptr=ptr.value, bytes=n.value, counts=counts, kf_record_bytes=kb.value, mp_record_bytes=mb.value)
+
+    def message_bytes(self):
+        """corb_pub_message_read: the message on the host"""
+        m = self.message(); buf = np.zeros(max(m["bytes"], 1), np.uint8)
+        _chk(load().corb_pub_message_read(self.h, _p(buf), m["bytes"]), "corb_pub_message_read")
+        return buf[: m["bytes"]]
+
+    def apply(self, msg, client_id, kf, kf_first, kf_n, kf_free_first, kf_room, mp=None, mp_first=0, mp_n=0, mp_free_first=0, mp_room=0, apply=True):
+        """corb_pub_apply of a message() dict (this handle's or another's on the same device): the outputs as a dict"""
+        counts = np.ascontiguousarray(msg["counts"], np.int32)
+        r = _PublishResult(counts, kf_room if kf is not None else 0, mp_room if mp is not None else 0)
+        rc = load().corb_pub_apply(self.h, msg["ptr"], _p(counts), msg["kf_record_bytes"], msg["mp_record_bytes"], int(client_id), kf.h if kf is not None else None, int(kf_first), int(kf_n),
+                                   int(kf_free_first), int(kf_room), mp.h if mp is not None else None, int(mp_first), int(mp_n), int(mp_free_first), int(mp_room), int(bool(apply)), C.byref(r.c))
+        if rc != ERR_CAPACITY:
+            _chk(rc, "corb_pub_apply")
+        return r.as_dict(capacity_error=rc == ERR_CAPACITY)
+
+
+def map_publish_plan(headers, root):
+    """corb_map_publish_plan: (verdict code, failing rank) of a publish from what the ranks contributed to the header all-gather.  Pure host arithmetic."""
+    h = np.ascontiguousarray(headers, PUBLISH_HEADER_DTYPE); who = C.c_int(-1)
+    rc = load().corb_map_publish_plan(len(h), int(root), _p(h), C.byref(who))
+    return rc, who.value
+
+
+def map_publish_messages(headers, rank, root):
+    """corb_map_publish_messages: (sends, recvs) rank `rank` posts for a publish with these gathered headers.  Pure host arithmetic."""
+    h = np.ascontiguousarray(headers, PUBLISH_HEADER_DTYPE); W = len(h)
+    sends = np.zeros(max(W, 1), PUSH_MSG_DTYPE); recvs = np.zeros(1, PUSH_MSG_DTYPE); ns = C.c_int(0); nr = C.c_int(0)
+    _chk(load().corb_map_publish_messages(W, int(rank), int(root), _p(h), _p(sends), C.byref(ns), _p(recvs), C.byref(nr)), "corb_map_publish_messages")
+    return sends[: ns.value].copy(), recvs[: nr.value].copy()
+
+
 def map_push_plan(headers, root, kf_capacity, mp_capacity, kf_dst_first, mp_dst_first=None):
     """corb_map_push_plan: (verdict code, failing rank) of a push from what the ranks contributed to the header all-gather.  Pure host arithmetic."""
     h = np.ascontiguousarray(headers, PUSH_HEADER_DTYPE)
@@ -2261,6 +2400,28 @@ class Comm:
                      _p(kd), _p(md), _p(kc), _p(mc))
         _chk(load().corb_map_push_ex(self.h, C.byref(p), root), "corb_map_push_ex")
         return (kc, mc) if self.rank == root else None
+
+    def map_publish(self, pub, root=0, pack=None, apply=None, max_counts=None):
+        """corb_map_publish (collective).  The root passes pack = dict(kf, new_kf_slots, upd_kf_slots, mp, new_mp_slots, upd_mp_slots, trans) and gets None; every
+        other rank passes apply = dict(client_id, kf, kf_first, kf_n, kf_free_first, kf_room, mp, mp_first, mp_n, mp_free_first, mp_room, apply) and max_counts =
+        the largest (A, B, C, D) counts it expects, and gets corb_pub_apply's outputs as a dict (the kind arrays have max_counts entries)."""
+        if pack is not None:
+            ids, T, (a, c, b, d) = MapPublisher._pack_args(pack.get("kf"), pack.get("new_kf_slots", ()), pack.get("upd_kf_slots", ()), pack.get("mp"), pack.get("new_mp_slots", ()),
+                                                           pack.get("upd_mp_slots", ()), pack.get("trans", ()))
+            kf, mp = pack.get("kf"), pack.get("mp")
+            p = _PublishPack(kf.h if kf is not None else None, _p(a) if len(a) else None, len(a), _p(c) if len(c) else None, len(c), mp.h if mp is not None else None,
+                             _p(b) if len(b) else None, len(b), _p(d) if len(d) else None, len(d), _p(ids) if len(ids) else None, _p(T) if len(ids) else None, len(ids))
+            _chk(load().corb_map_publish(self.h, pub.h, int(root), C.byref(p), None), "corb_map_publish")
+            return None
+        kf, mp = apply.get("kf"), apply.get("mp")
+        r = _PublishResult(max_counts, apply.get("kf_room", 0) if kf is not None else 0, apply.get("mp_room", 0) if mp is not None else 0)
+        q = _PublishApply(int(apply["client_id"]), kf.h if kf is not None else None, int(apply.get("kf_first", 0)), int(apply.get("kf_n", 0)), int(apply.get("kf_free_first", 0)),
+                          int(apply.get("kf_room", 0)), mp.h if mp is not None else None, int(apply.get("mp_first", 0)), int(apply.get("mp_n", 0)), int(apply.get("mp_free_first", 0)),
+                          int(apply.get("mp_room", 0)), int(bool(apply.get("apply", True))), C.pointer(r.c))
+        rc = load().corb_map_publish(self.h, pub.h, int(root), None, C.byref(q))
+        if rc != ERR_CAPACITY:
+            _chk(rc, "corb_map_publish")
+        return r.as_dict(capacity_error=rc == ERR_CAPACITY)
 
     def map_push_setup(self, root, kf=None, mp=None, kf_dst_first=None, mp_dst_first=None):
         """corb_map_push_setup (collective, once): the root's layout to every rank, for the asynchronous pushes"""

@@ -2,8 +2,7 @@
 // transport, the push's bookkeeping as a pure function (corb_map_push_plan), and the collective-safe push itself.
 // Replaces, for the hot path, the boost-text-archive service batches of corbslam_client/src/Cache.cc:322-375 / DataDriver.cc:135-193 and their server
 // side corbslam_server/src/MapFusion.cpp:31-190: a push is a handful of messages of whole records between the ranks' device buffers.
-#include "store_host.h"
-#include "corb_workspace.h"
+#include "comm_internal.h"
 #include <dlfcn.h>
 #include <string>
 #include <algorithm>
@@ -17,7 +16,6 @@
 
 // ---- RCCL (librccl.so loaded on first use: a process that never pushes a map does not pay for it) ----
 namespace {
-typedef struct ncclComm* ncclComm_t;
 struct ncclUniqueId_ { char internal[128]; };
 struct Rccl {
     void* lib = nullptr;
@@ -92,109 +90,66 @@ extern "C" int corb_comm_test_rccl_exchange(const CorbRcclFns* fns, const CorbPu
 }
 #define NCCLCHK(call) do { int e_ = (call); if (e_ != 0) { corb_set_error("%s failed: %s", #call, rccl().GetErrorString ? rccl().GetErrorString(e_) : "rccl error"); return CORB_ERR_HIP; } } while (0)
 
-// ---- transports ----
-namespace {
-struct Msg { void* ptr; size_t bytes; int peer; };
-
-// in-process transport: `world` communicators share one hub; every rank is driven by its own host thread
-struct LocalHub {
-    int world = 1;
-    std::mutex mu; std::condition_variable cv;
-    int arrived = 0; unsigned long long generation = 0;
-    std::vector<int> table;                              // all-gather staging
-    std::vector<std::vector<Msg>> posted;                // posted[sender] = the sends of the current exchange (peer = receiver)
-    void barrier() {
-        std::unique_lock<std::mutex> lk(mu);
-        const unsigned long long g = generation;
-        if (++arrived == world) { arrived = 0; generation++; cv.notify_all(); }
-        else cv.wait(lk, [&] { return generation != g; });
+// ---- transports (the object: comm_internal.h) ----
+// every rank contributes n ints; all[r * n + k] = rank r's k-th
+int CorbComm::all_gather(const int* mine, int n, int* all)
+{
+    if (world == 1) { memcpy(all, mine, sizeof(int) * (size_t)n); return CORB_OK; }      // a single rank has nothing to gather (two stream round trips otherwise)
+    if (hub) {
+        { std::lock_guard<std::mutex> lk(hub->mu); if ((int)hub->table.size() < world * n) hub->table.resize((size_t)world * n); }
+        hub->barrier();                                              // (the table has its size on every rank's view)
+        memcpy(&hub->table[(size_t)rank * n], mine, sizeof(int) * n);
+        hub->barrier();
+        memcpy(all, hub->table.data(), sizeof(int) * (size_t)world * n);
+        hub->barrier();                                              // nobody overwrites the table while another rank still reads it
+        return CORB_OK;
     }
-};
+    if (n * (world + 1) > d_ints_cap) { corb_set_error("corb_comm: all-gather of %d ints per rank exceeds the staging buffer", n); return CORB_ERR_ARG; }
+    HIPCHK(hipMemcpyAsync(d_ints + (size_t)world * n, mine, sizeof(int) * n, hipMemcpyHostToDevice, stream));
+    NCCLCHK(rccl().AllGather(d_ints + (size_t)world * n, d_ints, (size_t)n, NCCL_INT32, comm, stream));
+    HIPCHK(hipMemcpyAsync(all, d_ints, sizeof(int) * (size_t)world * n, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    return CORB_OK;
 }
-
-struct CorbComm {
-    int rank = 0, world = 1, device = 0;
-    hipStream_t stream = nullptr;
-    // RCCL
-    ncclComm_t comm = nullptr; int* d_ints = nullptr; int d_ints_cap = 0;
-    // in-process
-    std::shared_ptr<LocalHub> hub;
-    // staging buffers of the outgoing records (kept between pushes: a hipMalloc / hipFree pair per push cost more than the 1.5 MB transfer it served)
-    char* stage_kf = nullptr; size_t stage_kf_cap = 0; char* stage_mp = nullptr; size_t stage_mp_cap = 0;
-    int* stage_slots = nullptr; size_t stage_slots_cap = 0;
-    // asynchronous push: the root's layout (corb_map_push_setup) and the push in flight
-    bool layout_set = false; int layout_root = -1, layout_kf_cap = 0, layout_mp_cap = 0, layout_kf_bytes = 0, layout_mp_bytes = 0;
-    std::vector<int32_t> layout_kf_first, layout_mp_first;
-    const CorbKfStore* layout_kf_store = nullptr; const CorbMpStore* layout_mp_store = nullptr;      // the root's stores the layout describes (begin must be handed the same)
-    hipEvent_t push_done = nullptr; bool in_flight = false; int flight_rc = CORB_OK;
-    CorbMapPush flight_push; int flight_root = -1; std::vector<CorbPushHeader> flight_hdr;
-    int reserve(char*& buf, size_t& cap, size_t need) {
-        if (need <= cap) return CORB_OK;
-        if (buf) (void)hipFree(buf);
-        buf = nullptr; cap = 0;
-        const size_t grow = std::max(need, (size_t)1 << 20);
-        if (hipMalloc((void**)&buf, grow) != hipSuccess) { corb_set_error("corb_comm: staging buffer of %zu bytes could not be allocated", grow); return CORB_ERR_HIP; }
-        cap = grow; return CORB_OK;
-    }
-
-    // every rank contributes n ints; all[r * n + k] = rank r's k-th
-    int all_gather(const int* mine, int n, int* all) {
-        if (world == 1) { memcpy(all, mine, sizeof(int) * (size_t)n); return CORB_OK; }      // a single rank has nothing to gather (two stream round trips otherwise)
-        if (hub) {
-            { std::lock_guard<std::mutex> lk(hub->mu); if ((int)hub->table.size() < world * n) hub->table.resize((size_t)world * n); }
-            hub->barrier();                                              // (the table has its size on every rank's view)
-            memcpy(&hub->table[(size_t)rank * n], mine, sizeof(int) * n);
-            hub->barrier();
-            memcpy(all, hub->table.data(), sizeof(int) * (size_t)world * n);
-            hub->barrier();                                              // nobody overwrites the table while another rank still reads it
-            return CORB_OK;
+// device buffers; messages between a pair of ranks match in posting order; returns when this rank's sends and receives are complete
+// wait = false (RCCL only): the messages are enqueued on the communicator's stream, completion is the caller's event
+// dst_a / dst_b (in-process transport): the mutexes of the stores this rank RECEIVES into, held while it copies -- between the two barriers, where no other
+// rank holds a store lock (each took its source stores' only while it packed, before the first barrier): ranks that share stores cannot deadlock
+int CorbComm::exchange(const std::vector<Msg>& sends, const std::vector<Msg>& recvs, bool wait, std::mutex* dst_a, std::mutex* dst_b)
+{
+    if (hub) {
+        { std::lock_guard<std::mutex> lk(hub->mu); hub->posted[rank] = sends; }
+        hub->barrier();
+        std::unique_lock<std::mutex> la, lb;
+        if (!recvs.empty()) { if (dst_a) la = std::unique_lock<std::mutex>(*dst_a); if (dst_b && dst_b != dst_a) lb = std::unique_lock<std::mutex>(*dst_b); }
+        std::vector<size_t> next(world, 0);                          // per sender: the next of its messages addressed to this rank
+        int rc = CORB_OK;
+        for (const Msg& r : recvs) {
+            const std::vector<Msg>& from = hub->posted[r.peer];
+            size_t& k = next[r.peer];
+            while (k < from.size() && from[k].peer != rank) k++;
+            if (k >= from.size() || from[k].bytes != r.bytes) { corb_set_error("corb_comm (in-process): receive from rank %d has no matching send", r.peer); rc = CORB_ERR_ARG; break; }
+            if (r.bytes && hipMemcpyAsync(r.ptr, from[k].ptr, r.bytes, hipMemcpyDeviceToDevice, stream) != hipSuccess) { corb_set_error("corb_comm (in-process): device-to-device copy failed"); rc = CORB_ERR_HIP; break; }
+            k++;
         }
-        if (n * (world + 1) > d_ints_cap) { corb_set_error("corb_comm: all-gather of %d ints per rank exceeds the staging buffer", n); return CORB_ERR_ARG; }
-        HIPCHK(hipMemcpyAsync(d_ints + (size_t)world * n, mine, sizeof(int) * n, hipMemcpyHostToDevice, stream));
-        NCCLCHK(rccl().AllGather(d_ints + (size_t)world * n, d_ints, (size_t)n, NCCL_INT32, comm, stream));
-        HIPCHK(hipMemcpyAsync(all, d_ints, sizeof(int) * (size_t)world * n, hipMemcpyDeviceToHost, stream));
-        HIPCHK(hipStreamSynchronize(stream));
-        return CORB_OK;
+        if (hipStreamSynchronize(stream) != hipSuccess && rc == CORB_OK) { corb_set_error("corb_comm (in-process): stream synchronisation failed"); rc = CORB_ERR_HIP; }
+        if (lb.owns_lock()) lb.unlock();
+        if (la.owns_lock()) la.unlock();
+        hub->barrier();                                              // the senders' buffers are free again
+        return rc;
     }
-    // device buffers; messages between a pair of ranks match in posting order; returns when this rank's sends and receives are complete
-    // wait = false (RCCL only): the messages are enqueued on the communicator's stream, completion is the caller's event
-    // dst_a / dst_b (in-process transport): the mutexes of the stores this rank RECEIVES into, held while it copies -- between the two barriers, where no other
-    // rank holds a store lock (each took its source stores' only while it packed, before the first barrier): ranks that share stores cannot deadlock
-    int exchange(const std::vector<Msg>& sends, const std::vector<Msg>& recvs, bool wait = true, std::mutex* dst_a = nullptr, std::mutex* dst_b = nullptr) {
-        if (hub) {
-            { std::lock_guard<std::mutex> lk(hub->mu); hub->posted[rank] = sends; }
-            hub->barrier();
-            std::unique_lock<std::mutex> la, lb;
-            if (!recvs.empty()) { if (dst_a) la = std::unique_lock<std::mutex>(*dst_a); if (dst_b && dst_b != dst_a) lb = std::unique_lock<std::mutex>(*dst_b); }
-            std::vector<size_t> next(world, 0);                          // per sender: the next of its messages addressed to this rank
-            int rc = CORB_OK;
-            for (const Msg& r : recvs) {
-                const std::vector<Msg>& from = hub->posted[r.peer];
-                size_t& k = next[r.peer];
-                while (k < from.size() && from[k].peer != rank) k++;
-                if (k >= from.size() || from[k].bytes != r.bytes) { corb_set_error("corb_comm (in-process): receive from rank %d has no matching send", r.peer); rc = CORB_ERR_ARG; break; }
-                if (r.bytes && hipMemcpyAsync(r.ptr, from[k].ptr, r.bytes, hipMemcpyDeviceToDevice, stream) != hipSuccess) { corb_set_error("corb_comm (in-process): device-to-device copy failed"); rc = CORB_ERR_HIP; break; }
-                k++;
-            }
-            if (hipStreamSynchronize(stream) != hipSuccess && rc == CORB_OK) { corb_set_error("corb_comm (in-process): stream synchronisation failed"); rc = CORB_ERR_HIP; }
-            if (lb.owns_lock()) lb.unlock();
-            if (la.owns_lock()) la.unlock();
-            hub->barrier();                                              // the senders' buffers are free again
-            return rc;
-        }
-        std::vector<CorbPushMsg> sm(sends.size()), rm(recvs.size()); std::vector<char*> sp(sends.size() + 1), rp(recvs.size() + 1);
-        for (size_t i = 0; i < sends.size(); i++) { sm[i].peer = sends[i].peer; sm[i].kind = 0; sm[i].first_record = 0; sm[i].n_records = 0; sm[i].bytes = (int64_t)sends[i].bytes; sp[i] = (char*)sends[i].ptr; }
-        for (size_t i = 0; i < recvs.size(); i++) { rm[i].peer = recvs[i].peer; rm[i].kind = 0; rm[i].first_record = 0; rm[i].n_records = 0; rm[i].bytes = (int64_t)recvs[i].bytes; rp[i] = (char*)recvs[i].ptr; }
-        CorbRcclFns f;
-        f.group_start = rccl().GroupStart; f.group_end = rccl().GroupEnd;
-        f.send = reinterpret_cast<int (*)(const void*, size_t, int, int, void*, void*)>(rccl().Send);
-        f.recv = reinterpret_cast<int (*)(void*, size_t, int, int, void*, void*)>(rccl().Recv);
-        const int rc = rccl_exchange(f, comm, stream, sm.data(), (int)sm.size(), rm.data(), (int)rm.size(), sp.data(), rp.data());
-        if (rc) return rc;
-        if (wait) HIPCHK(hipStreamSynchronize(stream));
-        return CORB_OK;
-    }
-};
+    std::vector<CorbPushMsg> sm(sends.size()), rm(recvs.size()); std::vector<char*> sp(sends.size() + 1), rp(recvs.size() + 1);
+    for (size_t i = 0; i < sends.size(); i++) { sm[i].peer = sends[i].peer; sm[i].kind = 0; sm[i].first_record = 0; sm[i].n_records = 0; sm[i].bytes = (int64_t)sends[i].bytes; sp[i] = (char*)sends[i].ptr; }
+    for (size_t i = 0; i < recvs.size(); i++) { rm[i].peer = recvs[i].peer; rm[i].kind = 0; rm[i].first_record = 0; rm[i].n_records = 0; rm[i].bytes = (int64_t)recvs[i].bytes; rp[i] = (char*)recvs[i].ptr; }
+    CorbRcclFns f;
+    f.group_start = rccl().GroupStart; f.group_end = rccl().GroupEnd;
+    f.send = reinterpret_cast<int (*)(const void*, size_t, int, int, void*, void*)>(rccl().Send);
+    f.recv = reinterpret_cast<int (*)(void*, size_t, int, int, void*, void*)>(rccl().Recv);
+    const int rc = rccl_exchange(f, comm, stream, sm.data(), (int)sm.size(), rm.data(), (int)rm.size(), sp.data(), rp.data());
+    if (rc) return rc;
+    if (wait) HIPCHK(hipStreamSynchronize(stream));
+    return CORB_OK;
+}
 
 extern "C" int corb_comm_unique_id(void* id128)
 {

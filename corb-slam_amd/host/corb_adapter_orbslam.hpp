@@ -26,6 +26,7 @@
 #include "corb_host.hpp"
 #include <corb_voc_train.h>
 #include <corb_keyframe_insert.h>
+#include <corb_map_publish.h>
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -596,6 +597,73 @@ public:
     }
 private:
     CorbKfInsert* h_ = nullptr;
+};
+
+// ---- the server -> clients publish on records (include/corb_map_publish.h) ----
+//   server: MapFusion::runPubTopic / resentGlobalMapToClient -> PubToClient::pub*ToClients             S/src/MapFusion.cpp:315-430, S/src/PubToClient.cpp:24-163
+//   client: Cache::subNewInsertKeyFramesFromServer / subNewInsertMapPointFromServer / subUpdated*      C/src/Cache.cc:446-634
+// One object per rank: it owns the message buffer and the calls' device scratch (CorbMapPublisher).  resentGlobalMapToClient is Pack fed 50 keyframe and 2000
+// map-point handles per round.
+template <class Mat>
+class MapPublishT {
+public:
+    explicit MapPublishT(int device = 0) { check(corb_pub_create(device, &h_), "corb_pub_create"); }
+    MapPublishT(const MapPublishT&) = delete; MapPublishT& operator=(const MapPublishT&) = delete;
+    ~MapPublishT() { if (h_) corb_pub_destroy(h_); }
+    CorbMapPublisher* handle() const { return h_; }
+
+    // the four sets and transMs -> slot lists and the table.  A set is any ordered container of light handles with mnId (std::set<LightKeyFrame> iterates in
+    // ascending id, and so do the slot lists); kfSlotOf(id) / mpSlotOf(id) = the slot of the server's record, negative for a handle the cache does not resolve,
+    // which is skipped as `if( tKF )` skips it (PubToClient.cpp:32-33).
+    struct PackLists { std::vector<int32_t> newKF, updKF, newMP, updMP, clientIds; std::vector<float> trans; };
+    template <class KFSet, class MPSet, class KfSlotOf, class MpSlotOf>
+    static PackLists Lists(const KFSet& newKFs, const MPSet& newMPs, const KFSet& updKFs, const MPSet& updMPs, KfSlotOf kfSlotOf, MpSlotOf mpSlotOf, const std::map<int, Mat>& transMs)
+    {
+        PackLists L;
+        for (const auto& l : newKFs) { const int s = (int)kfSlotOf(l.mnId); if (s >= 0) L.newKF.push_back(s); }
+        for (const auto& l : newMPs) { const int s = (int)mpSlotOf(l.mnId); if (s >= 0) L.newMP.push_back(s); }
+        for (const auto& l : updKFs) { const int s = (int)kfSlotOf(l.mnId); if (s >= 0) L.updKF.push_back(s); }
+        for (const auto& l : updMPs) { const int s = (int)mpSlotOf(l.mnId); if (s >= 0) L.updMP.push_back(s); }
+        for (const auto& t : transMs) { L.clientIds.push_back((int32_t)t.first); for (int r = 0; r < 4; r++) for (int c = 0; c < 4; c++) L.trans.push_back(matf(t.second, r, c)); }
+        return L;
+    }
+    template <class KFSet, class MPSet, class KfSlotOf, class MpSlotOf>
+    void Pack(CorbKfStore* kf, CorbMpStore* mp, const KFSet& newKFs, const MPSet& newMPs, const KFSet& updKFs, const MPSet& updMPs, KfSlotOf kfSlotOf, MpSlotOf mpSlotOf,
+              const std::map<int, Mat>& transMs)
+    {
+        const PackLists L = Lists(newKFs, newMPs, updKFs, updMPs, kfSlotOf, mpSlotOf, transMs);
+        check(corb_pub_pack(h_, kf, L.newKF.data(), (int)L.newKF.size(), L.updKF.data(), (int)L.updKF.size(), mp, L.newMP.data(), (int)L.newMP.size(), L.updMP.data(),
+                            (int)L.updMP.size(), L.clientIds.data(), L.trans.data(), (int)L.clientIds.size()), "corb_pub_pack");
+    }
+    struct Message { void* ptr = nullptr; int64_t bytes = 0; int32_t counts[5] = {0, 0, 0, 0, 0}; int32_t kfRecordBytes = 0, mpRecordBytes = 0; };
+    Message GetMessage() const
+    {
+        Message m; check(corb_pub_message(h_, &m.ptr, &m.bytes, m.counts, &m.kfRecordBytes, &m.mpRecordBytes), "corb_pub_message");
+        return m;
+    }
+    // what the four callbacks did with a message: kinds per entry (A, B: 1 own, 2 held, 3 accepted; C, D: 0 unknown, 1 not fixed, 2 moved), the slots the accepted
+    // records went to, in message order.  The caller then does addKeyFrametoDB / AddKeyFrameFromServer for vNewKFSlots on its own structures: corb_kfdb_add for the
+    // keyframe database entry, corb_covis_update for the covisibility rows (Cache.cc:483-484).  bFull: CORB_ERR_CAPACITY -- nothing was written.
+    struct Applied { std::vector<uint8_t> vKindNewKF, vKindNewMP, vKindUpdKF, vKindUpdMP; std::vector<int32_t> vNewKFSlots, vNewMPSlots; int nUpdatedKF = 0, nUpdatedMP = 0; bool bNoTransform = false, bFull = false; };
+    Applied Apply(const Message& m, int clientId, CorbKfStore* kf, int kfFirst, int kfN, int kfFreeFirst, int kfRoom, CorbMpStore* mp, int mpFirst, int mpN, int mpFreeFirst, int mpRoom,
+                  bool apply = true)
+    {
+        Applied a;
+        a.vKindNewKF.resize((size_t)std::max(m.counts[0], 1)); a.vKindNewMP.resize((size_t)std::max(m.counts[1], 1)); a.vKindUpdKF.resize((size_t)std::max(m.counts[2], 1));
+        a.vKindUpdMP.resize((size_t)std::max(m.counts[3], 1)); a.vNewKFSlots.resize((size_t)std::max(std::min(m.counts[0], kfRoom), 1)); a.vNewMPSlots.resize((size_t)std::max(std::min(m.counts[1], mpRoom), 1));
+        CorbPublishOutputs o; std::memset(&o, 0, sizeof(o));
+        o.kind_kf_new = a.vKindNewKF.data(); o.kind_mp_new = a.vKindNewMP.data(); o.kind_kf_upd = a.vKindUpdKF.data(); o.kind_mp_upd = a.vKindUpdMP.data();
+        o.kf_new_slots = a.vNewKFSlots.data(); o.mp_new_slots = a.vNewMPSlots.data();
+        const int rc = corb_pub_apply(h_, m.ptr, m.counts, m.kfRecordBytes, m.mpRecordBytes, clientId, kf, kfFirst, kfN, kfFreeFirst, kfRoom, mp, mpFirst, mpN, mpFreeFirst, mpRoom,
+                                      apply ? 1 : 0, &o);
+        if (rc != CORB_ERR_CAPACITY) check(rc, "corb_pub_apply");
+        a.bFull = rc == CORB_ERR_CAPACITY; a.bNoTransform = o.no_transform != 0; a.nUpdatedKF = o.n_kf_updated; a.nUpdatedMP = o.n_mp_updated;
+        a.vKindNewKF.resize((size_t)m.counts[0]); a.vKindNewMP.resize((size_t)m.counts[1]); a.vKindUpdKF.resize((size_t)m.counts[2]); a.vKindUpdMP.resize((size_t)m.counts[3]);
+        a.vNewKFSlots.resize((size_t)std::min(o.n_kf_inserted, std::min(m.counts[0], kfRoom))); a.vNewMPSlots.resize((size_t)std::min(o.n_mp_inserted, std::min(m.counts[1], mpRoom)));
+        return a;
+    }
+private:
+    CorbMapPublisher* h_ = nullptr;
 };
 
 // ---- the tracking thread on device-resident records (corb_track_*, include/corb_accel.h): a Frame lives in a slot of a keyframe store, the client's map in a
@@ -1371,6 +1439,7 @@ using ORBmatcher = corb::adapt::ORBmatcherT<KeyFrame, Frame, MapPoint, cv::Mat>;
 using Optimizer = corb::adapt::OptimizerT<KeyFrame, Frame, MapPoint, Cache, cv::Mat>;
 using MapStore = corb::adapt::MapStoreT<KeyFrame, MapPoint, cv::Mat>;
 using KeyFrameInsert = corb::adapt::KeyFrameInsertT<KeyFrame, MapPoint>;
+using MapPublish = corb::adapt::MapPublishT<cv::Mat>;
 using FrameStore = corb::adapt::FrameStoreT<Frame, MapPoint, cv::Mat>;
 using Sim3Solver = corb::Sim3Solver<KeyFrame, MapPoint>;
 using PnPsolver = corb::PnPsolver<Frame, KeyFrame, MapPoint>;
