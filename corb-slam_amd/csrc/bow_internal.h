@@ -2,6 +2,7 @@
 #pragma once
 #include "corb_internal.h"
 #include "bow_math.h"
+#include "owned_hip.h"
 
 // one descriptor set of a transform: where its features are and where its two vectors go (device pointers; every pointer is valid, unwanted outputs go to scratch)
 struct BowSetDev {
@@ -36,7 +37,7 @@ struct CorbVoc {
     int device = 0;
     BowVocHost host;
     BowVocView dev{};                 // device pointers
-    std::vector<void*> allocs;
+    DevList allocs;
 };
 int voc_finish(CorbVoc* v, int device, CorbVoc** out, const char* who);
 #define BOW_MAX_SETS 65535          // descriptor sets per transform call: the sets are one grid dimension

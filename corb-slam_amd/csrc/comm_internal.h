@@ -3,7 +3,7 @@
 #pragma once
 #include "store_host.h"
 #include "corb_workspace.h"
-#include "host_util.h"
+#include "owned_hip.h"
 #include <algorithm>
 #include <condition_variable>
 #include <memory>
@@ -31,27 +31,24 @@ struct LocalHub {
 
 struct CorbComm {
     int rank = 0, world = 1, device = 0;
-    hipStream_t stream = nullptr;
+    OwnedStream stream;
     // RCCL
-    ncclComm_t comm = nullptr; int* d_ints = nullptr; int d_ints_cap = 0;
+    ncclComm_t comm = nullptr; DevMem d_ints; int d_ints_cap = 0;
     // in-process
     std::shared_ptr<LocalHub> hub;
     // staging buffers of the outgoing records (kept between pushes: a hipMalloc / hipFree pair per push cost more than the 1.5 MB transfer it served)
-    char* stage_kf = nullptr; size_t stage_kf_cap = 0; char* stage_mp = nullptr; size_t stage_mp_cap = 0;
-    int* stage_slots = nullptr; size_t stage_slots_cap = 0;
+    DevMem stage_kf, stage_mp, stage_slots;
     // asynchronous push: the root's layout (corb_map_push_setup) and the push in flight
     bool layout_set = false; int layout_root = -1, layout_kf_cap = 0, layout_mp_cap = 0, layout_kf_bytes = 0, layout_mp_bytes = 0;
     std::vector<int32_t> layout_kf_first, layout_mp_first;
     const CorbKfStore* layout_kf_store = nullptr; const CorbMpStore* layout_mp_store = nullptr;      // the root's stores the layout describes (begin must be handed the same)
-    hipEvent_t push_done = nullptr; bool in_flight = false; int flight_rc = CORB_OK;
+    OwnedEvent push_done; bool in_flight = false; int flight_rc = CORB_OK;
     CorbMapPush flight_push; int flight_root = -1; std::vector<CorbPushHeader> flight_hdr;
-    int reserve(char*& buf, size_t& cap, size_t need) {
-        if (need <= cap) return CORB_OK;
-        if (buf) (void)hipFree(buf);
-        buf = nullptr; cap = 0;
+    // a staging buffer holds at least `need` bytes: exactly that when it grows, 1 MB at the least
+    int room(DevMem& buf, size_t need) {
         const size_t grow = std::max(need, (size_t)1 << 20);
-        if (hipMalloc((void**)&buf, grow) != hipSuccess) { corb_set_error("corb_comm: staging buffer of %zu bytes could not be allocated", grow); return CORB_ERR_HIP; }
-        cap = grow; return CORB_OK;
+        if (buf.room(need, grow) != hipSuccess) { corb_set_error("corb_comm: staging buffer of %zu bytes could not be allocated", grow); return CORB_ERR_HIP; }
+        return CORB_OK;
     }
 
     // every rank contributes n ints; all[r * n + k] = rank r's k-th

@@ -5,6 +5,7 @@
 // per-edge / per-vertex arithmetic runs in ba_kernels.hip; the dense reduced camera system is factorised
 // by the hand-written blocked Cholesky of dense_chol.hip.  The host only sequences launches and reads back 3 scalars per trial.
 #include "ba_host.h"
+#include "owned_hip.h"
 #include <algorithm>
 #include <atomic>
 #include <mutex>
@@ -257,18 +258,19 @@ int corb_ba_solve_device(const CorbBADeviceProblem* dp, int iterations, int robu
 #define BA_HOST_FAST_MIN_POSES 257          // the PCG solver's range (auto choice): smaller problems keep the host path and its session / staging features
 struct HostFastBuf {                         // per device: grown by the calls, given back by corb_release_scratch; one call at a time per device
     std::mutex mu; int device = -1;
-    char* dev = nullptr; size_t dev_cap = 0; char* pin[2] = {nullptr, nullptr}; size_t pin_cap = 0;
-    hipStream_t stream = nullptr; hipEvent_t ev[2] = {nullptr, nullptr};
+    OwnedStream stream; OwnedEvent ev[2];
+    DevMem dev; PinnedMem pin[2];
     size_t release() {                       // (the caller holds mu and has selected the device)
-        size_t freed = dev_cap;
-        if (stream) { (void)hipStreamSynchronize(stream); (void)hipStreamDestroy(stream); stream = nullptr; }
-        for (int i = 0; i < 2; i++) { if (ev[i]) { (void)hipEventDestroy(ev[i]); ev[i] = nullptr; } if (pin[i]) { (void)hipHostFree(pin[i]); pin[i] = nullptr; freed += pin_cap; } }
-        if (dev) (void)hipFree(dev);
-        dev = nullptr; dev_cap = 0; pin_cap = 0; device = -1;
+        size_t freed = dev.cap() + pin[0].cap() + pin[1].cap();
+        if (stream) (void)hipStreamSynchronize(stream);
+        stream.reset();
+        for (int i = 0; i < 2; i++) { ev[i].reset(); pin[i].reset(); }
+        dev.reset(); device = -1;
         return freed;
     }
 };
-static HostFastBuf& hostfast(int device) { static HostFastBuf b[64]; return b[device < 0 || device >= 64 ? 0 : device]; }
+// (never deleted: the buffers go with corb_release_scratch or with the process, not with static destructors that would run after the HIP runtime's)
+static HostFastBuf& hostfast(int device) { static HostFastBuf* const b = new HostFastBuf[64]; return b[device < 0 || device >= 64 ? 0 : device]; }
 size_t ba_host_fast_release(int device)
 {
     HostFastBuf& B = hostfast(device);
@@ -287,16 +289,15 @@ static int ba_solve_host_via_device(const CorbBAProblem* p, int iterations, int 
     const size_t o_poses = 0, o_pf = o_poses + al(64 * K), o_pts = o_pf + al(K), o_xf = o_pts + al(12 * M), o_intr = o_xf + al(M), o_off = o_intr + al(20 * K),
                  o_edges = o_off + al(4 * (M + 1)), total = o_edges + al(sizeof(CorbBAEdge) * E);
     const size_t CH = (size_t)32 << 20;
-    if (B.device != device || B.dev_cap < total || !B.pin[0] || !B.stream) {
-        if (B.dev) (void)hipFree(B.dev);
-        B.dev = nullptr; B.dev_cap = 0;
-        if (hipMalloc((void**)&B.dev, total + (total >> 3)) != hipSuccess) { (void)hipGetLastError(); return CORB_OK; }      // no room: the host path
-        B.dev_cap = total + (total >> 3); B.device = device;
-        for (int i = 0; i < 2; i++) if (!B.pin[i] && hipHostMalloc((void**)&B.pin[i], CH, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); return CORB_OK; }
-        B.pin_cap = CH;
-        if (!B.stream && hipStreamCreateWithFlags(&B.stream, hipStreamNonBlocking) != hipSuccess) return CORB_ERR_HIP;
-        for (int i = 0; i < 2; i++) if (!B.ev[i] && hipEventCreateWithFlags(&B.ev[i], hipEventDisableTiming) != hipSuccess) return CORB_ERR_HIP;
+    if (B.device != device || B.dev.cap() < total || !B.pin[0] || !B.stream) {
+        B.dev.reset();
+        if (B.dev.room(total + (total >> 3)) != hipSuccess) { (void)hipGetLastError(); return CORB_OK; }      // no room: the host path
+        B.device = device;
+        for (int i = 0; i < 2; i++) if (B.pin[i].room(CH) != hipSuccess) { (void)hipGetLastError(); return CORB_OK; }
+        if (!B.stream && B.stream.create() != hipSuccess) return CORB_ERR_HIP;
+        for (int i = 0; i < 2; i++) if (!B.ev[i] && B.ev[i].create(hipEventDisableTiming) != hipSuccess) return CORB_ERR_HIP;
     }
+    char* const dev = B.dev.as<char>(); char* const pin[2] = {B.pin[0].as<char>(), B.pin[1].as<char>()};
     // the small arrays, then the edges in chunks: worker threads copy a chunk into a page-locked buffer (checking it), the DMA of the previous chunk runs meanwhile
     std::vector<float> intr(5 * K + 1);
     for (size_t k = 0; k < K; k++) ba_intrinsics(p, (int)k, &intr[5 * k]);
@@ -312,7 +313,7 @@ static int ba_solve_host_via_device(const CorbBAProblem* p, int iterations, int 
         for (size_t done = 0; done < pc.bytes; done += per_chunk) {
             const size_t nb = std::min(per_chunk, pc.bytes - done);
             if (used[cur]) HIPCHK(hipEventSynchronize(B.ev[cur]));
-            char* dst = B.pin[cur]; const char* src = pc.src + done;
+            char* dst = pin[cur]; const char* src = pc.src + done;
             auto work = [&](int t) {
                 const size_t n_units = nb / unit, u0 = n_units * t / NT, u1 = n_units * (t + 1) / NT;
                 memcpy(dst + u0 * unit, src + u0 * unit, (u1 - u0) * unit);
@@ -327,7 +328,7 @@ static int ba_solve_host_via_device(const CorbBAProblem* p, int iterations, int 
             if (nb < ((size_t)1 << 20)) { for (int t = 0; t < NT; t++) work(t); }
             else { std::vector<std::thread> th; for (int t = 1; t < NT; t++) th.emplace_back(work, t); work(0); for (auto& x : th) x.join(); }
             if (bad.load()) break;
-            HIPCHK(hipMemcpyAsync(B.dev + pc.off + done, dst, nb, hipMemcpyHostToDevice, B.stream));
+            HIPCHK(hipMemcpyAsync(dev + pc.off + done, dst, nb, hipMemcpyHostToDevice, B.stream));
             HIPCHK(hipEventRecord(B.ev[cur], B.stream)); used[cur] = true; cur ^= 1;
         }
         if (bad.load()) break;
@@ -336,9 +337,9 @@ static int ba_solve_host_via_device(const CorbBAProblem* p, int iterations, int 
     if (bad.load() == 2) { HIPCHK(hipStreamSynchronize(B.stream)); return CORB_OK; }              // edges not grouped by point: the host path sorts them
     CorbBADeviceProblem dp; memset(&dp, 0, sizeof(dp));
     dp.n_poses = (int)K; dp.n_points = (int)M; dp.n_edges = (int)E;
-    dp.poses = (float*)(B.dev + o_poses); dp.pose_fixed = (const uint8_t*)(B.dev + o_pf); dp.points = (float*)(B.dev + o_pts); dp.point_fixed = (const uint8_t*)(B.dev + o_xf);
-    dp.intr = (const float*)(B.dev + o_intr); dp.edges = (const CorbBAEdge*)(B.dev + o_edges); dp.edge_off = (const int*)(B.dev + o_off);
-    ba_launch_edge_offsets(dp.edges, (int)E, (int)M, (int*)(B.dev + o_off), B.stream);
+    dp.poses = (float*)(dev + o_poses); dp.pose_fixed = (const uint8_t*)(dev + o_pf); dp.points = (float*)(dev + o_pts); dp.point_fixed = (const uint8_t*)(dev + o_xf);
+    dp.intr = (const float*)(dev + o_intr); dp.edges = (const CorbBAEdge*)(dev + o_edges); dp.edge_off = (const int*)(dev + o_off);
+    ba_launch_edge_offsets(dp.edges, (int)E, (int)M, (int*)(dev + o_off), B.stream);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(B.stream));
     *taken = true;
@@ -353,11 +354,11 @@ static int ba_solve_host_via_device(const CorbBAProblem* p, int iterations, int 
         while (copied < o.bytes) {
             while (issued < o.bytes && issued - copied < 2 * CH) {
                 const size_t nb = std::min(CH, o.bytes - issued);
-                HIPCHK(hipMemcpyAsync(B.pin[ci], B.dev + o.off + issued, nb, hipMemcpyDeviceToHost, B.stream));
+                HIPCHK(hipMemcpyAsync(pin[ci], dev + o.off + issued, nb, hipMemcpyDeviceToHost, B.stream));
                 HIPCHK(hipEventRecord(B.ev[ci], B.stream)); len[ci] = nb; issued += nb; ci ^= 1;
             }
             HIPCHK(hipEventSynchronize(B.ev[cc]));
-            memcpy(o.dst + copied, B.pin[cc], len[cc]); copied += len[cc]; cc ^= 1;
+            memcpy(o.dst + copied, pin[cc], len[cc]); copied += len[cc]; cc ^= 1;
         }
     }
     return CORB_OK;
@@ -404,11 +405,11 @@ extern "C" int corb_ba_solve_devflat(const CorbBAProblem* p, int iterations, int
     { std::vector<int> cur(off.begin(), off.end() - 1); for (size_t i = 0; i < E; i++) ge[(size_t)cur[(size_t)p->edges[i].point]++] = p->edges[i]; }
     std::vector<float> intr(5 * K + 1);
     for (size_t k = 0; k < K; k++) ba_intrinsics(p, (int)k, &intr[5 * k]);
-    struct Dev { std::vector<void*> v; ~Dev() { for (void* q : v) (void)hipFree(q); } void* get(size_t bytes) { void* q = nullptr; if (hipMalloc(&q, bytes ? bytes : 1) != hipSuccess) return nullptr; v.push_back(q); return q; } } dev;
+    DevList dev_mem; auto dev_get = [&](size_t bytes) -> void* { char* q = nullptr; return dev_mem.add(&q, bytes) == hipSuccess ? q : nullptr; };
     CorbBADeviceProblem dp; memset(&dp, 0, sizeof(dp));
     dp.n_poses = (int)K; dp.n_points = (int)M; dp.n_edges = (int)E;
-    dp.poses = (float*)dev.get(64 * K); uint8_t* dpf = (uint8_t*)dev.get(K); dp.points = (float*)dev.get(12 * M); uint8_t* dxf = (uint8_t*)dev.get(M);
-    CorbBAEdge* de = (CorbBAEdge*)dev.get(sizeof(CorbBAEdge) * E); float* di = (float*)dev.get(20 * K); int* doff = (int*)dev.get(4 * (M + 1));
+    dp.poses = (float*)dev_get(64 * K); uint8_t* dpf = (uint8_t*)dev_get(K); dp.points = (float*)dev_get(12 * M); uint8_t* dxf = (uint8_t*)dev_get(M);
+    CorbBAEdge* de = (CorbBAEdge*)dev_get(sizeof(CorbBAEdge) * E); float* di = (float*)dev_get(20 * K); int* doff = (int*)dev_get(4 * (M + 1));
     if (!dp.poses || !dpf || !dp.points || !dxf || !de || !di || !doff) { corb_set_error("corb_ba_solve_devflat: allocation failed"); return CORB_ERR_HIP; }
     dp.pose_fixed = dpf; dp.point_fixed = dxf; dp.edges = de; dp.intr = di; dp.edge_off = doff;
     if (K) { HIPCHK(hipMemcpy(dp.poses, p->poses, 64 * K, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(dpf, p->pose_fixed, K, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(di, intr.data(), 20 * K, hipMemcpyHostToDevice)); }

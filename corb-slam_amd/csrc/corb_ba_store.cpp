@@ -14,14 +14,13 @@ namespace {
 const char* const STORE_LAP = "[corb_lba_store] %-24s %8.3f ms\n";      // (Lap: this file's phases are sub-millisecond)
 struct DevBuf {                       // device memory of one call: bumped out of an arena when the caller lends one (the local BA), else hipMalloc'ed (a config-5 global BA
                                       // needs ~1 GB: not taken from the per-device arena, which never shrinks)
-    std::vector<void*> ptrs;
+    DevList spill;
     char* arena = nullptr; size_t cap = 0, used = 0, asked = 0;
-    ~DevBuf() { for (void* p : ptrs) (void)hipFree(p); }
     template <class T> hipError_t alloc(T** out, size_t n) {
         const size_t bytes = (((n ? n : 1) * sizeof(T)) + 255) & ~(size_t)255;
         asked += bytes;
         if (used + bytes <= cap) { *out = (T*)(arena + used); used += bytes; return hipSuccess; }
-        void* p = nullptr; hipError_t e = hipMalloc(&p, bytes); if (e == hipSuccess) { ptrs.push_back(p); *out = (T*)p; } return e;
+        return spill.add(reinterpret_cast<char**>(out), bytes);
     }
 };
 struct HostStage {                    // page-locked host memory of one call, same scheme (pageable std::vector beyond the arena)
@@ -51,7 +50,7 @@ static int build_graph(const char* who, CorbKfStore* kf, const int32_t* kf_slots
 {
     memset(&d, 0, sizeof(d));
     d.n_kf = n_kf; d.n_mp = n_mp; d.n_local = n_local; d.max_features = kf->F; d.max_obs = mp->O;
-    d.kf_base = kf->base; d.kf_bytes = kf->L.bytes; d.mp_base = mp->base; d.mp_bytes = mp->L.bytes;
+    d.kf_base = kf->base(); d.kf_bytes = kf->L.bytes; d.mp_base = mp->base(); d.mp_bytes = mp->L.bytes;
     int *dks, *dms;
     HIPCHK(buf.alloc(&dks, (size_t)n_kf)); HIPCHK(buf.alloc(&dms, (size_t)n_mp));
     if (hs) {                                                     // through page-locked staging: the uploads are enqueued, not waited for
@@ -180,21 +179,12 @@ extern "C" int corb_local_ba_store(CorbKfStore* kf, const int32_t* kf_slots, int
     hipStream_t s = mp->stream;
     lap("locks + stream syncs");
     // the store's scratch, grown to what the previous calls asked for
-    if (mp->lba_dev_want > mp->lba_dev_cap || mp->lba_dev_cap == 0) {
-        if (mp->lba_dev) (void)hipFree(mp->lba_dev);
-        mp->lba_dev = nullptr; mp->lba_dev_cap = 0;
-        // (at least 16 MB / 2 MB: a map's first windows grow from call to call, and a call that outgrows its scratch pays hipMalloc'ed arrays and pageable copies)
-        const size_t cap = std::min(std::max(mp->lba_dev_want + mp->lba_dev_want / 2, (size_t)16 << 20), (size_t)256 << 20);
-        if (hipMalloc((void**)&mp->lba_dev, cap) == hipSuccess) mp->lba_dev_cap = cap; else { mp->lba_dev = nullptr; (void)hipGetLastError(); }
-    }
-    if (mp->lba_host_want > mp->lba_host_cap || mp->lba_host_cap == 0) {
-        if (mp->lba_host) (void)hipHostFree(mp->lba_host);
-        mp->lba_host = nullptr; mp->lba_host_cap = 0;
-        const size_t cap = std::min(std::max(mp->lba_host_want + mp->lba_host_want / 2, (size_t)2 << 20), (size_t)64 << 20);
-        if (hipHostMalloc((void**)&mp->lba_host, cap) == hipSuccess) mp->lba_host_cap = cap; else { mp->lba_host = nullptr; (void)hipGetLastError(); }
-    }
-    DevBuf buf; buf.arena = mp->lba_dev; buf.cap = mp->lba_dev_cap;
-    HostStage hs; hs.arena = mp->lba_host; hs.cap = mp->lba_host_cap;
+    // (at least 16 MB / 2 MB: a map's first windows grow from call to call, and a call that outgrows its scratch pays hipMalloc'ed arrays and pageable copies.
+    // No room for the scratch: the call allocates what it needs)
+    if (mp->lba_dev.room(std::max(mp->lba_dev_want, (size_t)1), std::min(std::max(mp->lba_dev_want + mp->lba_dev_want / 2, (size_t)16 << 20), (size_t)256 << 20)) != hipSuccess) (void)hipGetLastError();
+    if (mp->lba_host.room(std::max(mp->lba_host_want, (size_t)1), std::min(std::max(mp->lba_host_want + mp->lba_host_want / 2, (size_t)2 << 20), (size_t)64 << 20)) != hipSuccess) (void)hipGetLastError();
+    DevBuf buf; buf.arena = mp->lba_dev.as<char>(); buf.cap = mp->lba_dev.cap();
+    HostStage hs; hs.arena = mp->lba_host.as<char>(); hs.cap = mp->lba_host.cap();
     struct Want { CorbMpStore* m; DevBuf* b; HostStage* h; ~Want() { m->lba_dev_want = std::max(m->lba_dev_want, std::min(b->asked, (size_t)256 << 20)); m->lba_host_want = std::max(m->lba_host_want, std::min(h->asked, (size_t)64 << 20)); } } want{mp, &buf, &hs};
     BAStoreDev d; int n_edges = 0;
     // Round 5: the window's problem stays on the device -- flattened there, the optimize() calls and the classifications between them run where the estimates are
@@ -205,7 +195,7 @@ extern "C" int corb_local_ba_store(CorbKfStore* kf, const int32_t* kf_slots, int
     rc = build_graph("corb_local_ba_store", kf, kf_slots, n_local, n_kf, mp, mp_slots, n_mp, buf, d, &n_edges, s, &hs, dev_route ? edge_bound : 0); if (rc) return rc;
     lap("graph from records");
     if (dev_route) {
-        if (!mp->lba_event) HIPCHK(hipEventCreateWithFlags(&mp->lba_event, hipEventDisableTiming));
+        if (!mp->lba_event) HIPCHK(mp->lba_event.create(hipEventDisableTiming));
         HIPCHK(hipEventRecord(mp->lba_event, s));
         uint8_t* d_outl; HIPCHK(buf.alloc(&d_outl, edge_bound));
         CorbBADeviceProblem dp; memset(&dp, 0, sizeof(dp));

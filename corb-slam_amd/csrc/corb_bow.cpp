@@ -23,7 +23,11 @@ extern "C" int corb_bow_profile(int enable, int device)
 {
     int rc = corb_select_device(device); if (rc) return rc;
     std::lock_guard<std::mutex> lk(g_prof_mu);
-    if (enable && !g_ticks) { HIPCHK(hipMalloc((void**)&g_ticks, 4 * sizeof(unsigned long long))); HIPCHK(hipMemset(g_ticks, 0, 4 * sizeof(unsigned long long))); }
+    if (enable && !g_ticks) {
+        static DevMem* const mem = new DevMem;                // (never deleted: it goes with the process, not with static destructors behind the HIP runtime's)
+        HIPCHK(mem->room(4 * sizeof(unsigned long long))); HIPCHK(hipMemset(mem->as<void>(), 0, 4 * sizeof(unsigned long long)));
+        g_ticks = mem->as<unsigned long long>();
+    }
     if (enable) g_prof.reserve(256);
     g_prof.enabled = enable != 0; g_prof_device = device;
     return CORB_OK;
@@ -57,8 +61,8 @@ extern "C" int corb_bow_profile_read(CorbKernelTime* out, int cap, int* n)
 
 template <class T> static hipError_t voc_upload(CorbVoc* v, const T** out, const std::vector<T>& src)
 {
-    void* p = nullptr; hipError_t e = hipMalloc(&p, std::max(src.size(), (size_t)1) * sizeof(T)); if (e != hipSuccess) return e;
-    v->allocs.push_back(p); *out = (const T*)p;
+    T* p = nullptr; hipError_t e = v->allocs.add(&p, src.size()); if (e != hipSuccess) return e;
+    *out = p;
     return src.empty() ? hipSuccess : hipMemcpy(p, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice);
 }
 
@@ -72,7 +76,6 @@ int voc_finish(CorbVoc* v, int device, CorbVoc** out, const char* who)
         voc_upload(v, &v->dev.slot_desc, h.slot_desc) != hipSuccess || voc_upload(v, &v->dev.slot_node, h.slot_node) != hipSuccess ||
         voc_upload(v, &v->dev.node_word, h.node_word) != hipSuccess || voc_upload(v, &v->dev.word_weight, h.word_weight) != hipSuccess) {
         corb_set_error("%s: %d nodes: allocation or upload failed", who, h.n_nodes);
-        for (void* p : v->allocs) (void)hipFree(p);
         delete v; return CORB_ERR_HIP;
     }
     *out = v;
@@ -97,13 +100,7 @@ extern "C" int corb_voc_load_text(const char* path, int device, CorbVoc** out)
     if (!err.empty()) { corb_set_error("corb_voc_load_text: %s", err.c_str()); delete v; return CORB_ERR_ARG; }
     return voc_finish(v, device, out, "corb_voc_load_text");
 }
-extern "C" void corb_voc_destroy(CorbVoc* v)
-{
-    if (!v) return;
-    (void)hipSetDevice(v->device);
-    for (void* p : v->allocs) (void)hipFree(p);
-    delete v;
-}
+extern "C" void corb_voc_destroy(CorbVoc* v) { handle_destroy(v); }
 extern "C" int corb_voc_info(const CorbVoc* v, int32_t* k, int32_t* L, int32_t* n_nodes, int32_t* n_words)
 {
     if (!v) { corb_set_error("corb_voc_info: bad argument"); return CORB_ERR_ARG; }
@@ -161,11 +158,11 @@ struct CorbKfDb {
     int device = 0;
     CorbVoc* voc = nullptr;
     BowDbDev d{};
-    hipStream_t stream = nullptr;
+    OwnedStream stream;
     std::mutex mu;
-    std::vector<void*> allocs;
-    int32_t* pinned = nullptr;                  // [2 * capacity + 2] page-locked: connected list / entry lists up, candidates down
-    double* pinned_score = nullptr;             // [capacity]
+    DevList allocs;
+    PinnedMem pinned;                           // [2 * capacity + 2] ints: connected list / entry lists up, candidates down
+    PinnedMem pinned_score;                     // [capacity] doubles
     std::vector<int> n_words;                   // host mirror: words of an entry's BowVector, -1 = none
     std::vector<char> live;
     uint32_t next_seq = 1;
@@ -173,21 +170,11 @@ struct CorbKfDb {
 
 template <class T> static hipError_t db_alloc(CorbKfDb* db, T** out, size_t n, int fill)
 {
-    void* p = nullptr; hipError_t e = hipMalloc(&p, std::max(n, (size_t)1) * sizeof(T)); if (e != hipSuccess) return e;
-    db->allocs.push_back(p); *out = (T*)p;
-    return hipMemset(p, fill, std::max(n, (size_t)1) * sizeof(T));
+    hipError_t e = db->allocs.add(out, n); if (e != hipSuccess) return e;
+    return hipMemset(*out, fill, std::max(n, (size_t)1) * sizeof(T));
 }
 
-extern "C" void corb_kfdb_destroy(CorbKfDb* db)
-{
-    if (!db) return;
-    (void)hipSetDevice(db->device);
-    if (db->stream) { (void)hipStreamSynchronize(db->stream); (void)hipStreamDestroy(db->stream); }
-    for (void* p : db->allocs) (void)hipFree(p);
-    if (db->pinned) (void)hipHostFree(db->pinned);
-    if (db->pinned_score) (void)hipHostFree(db->pinned_score);
-    delete db;
-}
+extern "C" void corb_kfdb_destroy(CorbKfDb* db) { handle_destroy(db); }
 
 extern "C" int corb_kfdb_create(CorbVoc* voc, int capacity, int max_words, CorbKfDb** out)
 {
@@ -207,10 +194,9 @@ extern "C" int corb_kfdb_create(CorbVoc* voc, int capacity, int max_words, CorbK
         db_alloc(db, &d.ctr, 2, 0) == hipSuccess && db_alloc(db, &d.pushed, c, 0) == hipSuccess && db_alloc(db, &d.first_word, c, 0) == hipSuccess &&
         db_alloc(db, &d.skey, P, 0) == hipSuccess && db_alloc(db, &d.sent, P, 0) == hipSuccess && db_alloc(db, &d.acc, c, 0) == hipSuccess && db_alloc(db, &d.best, c, 0) == hipSuccess &&
         db_alloc(db, &d.first_pos, c, 0x7F) == hipSuccess && db_alloc(db, &d.out, c + 1, 0) == hipSuccess && db_alloc(db, &d.score_out, c, 0) == hipSuccess &&
-        hipStreamCreateWithFlags(&db->stream, hipStreamNonBlocking) == hipSuccess && hipHostMalloc((void**)&db->pinned, (2 * c + 2) * 4) == hipSuccess &&
-        hipHostMalloc((void**)&db->pinned_score, c * 8) == hipSuccess;
-    if (!ok) { corb_set_error("corb_kfdb_create: %d entries x %d words: allocation failed", capacity, max_words); corb_kfdb_destroy(db); return CORB_ERR_HIP; }
-    { const hipError_t e = hipDeviceSynchronize(); if (e != hipSuccess) { corb_set_error("corb_kfdb_create: %s", hipGetErrorString(e)); corb_kfdb_destroy(db); return CORB_ERR_HIP; } }
+        db->stream.create() == hipSuccess && db->pinned.room((2 * c + 2) * 4) == hipSuccess && db->pinned_score.room(c * 8) == hipSuccess;
+    if (!ok) { corb_set_error("corb_kfdb_create: %d entries x %d words: allocation failed", capacity, max_words); handle_destroy(db); return CORB_ERR_HIP; }
+    { const hipError_t e = hipDeviceSynchronize(); if (e != hipSuccess) { corb_set_error("corb_kfdb_create: %s", hipGetErrorString(e)); handle_destroy(db); return CORB_ERR_HIP; } }
     *out = db;
     return CORB_OK;
 }
@@ -319,13 +305,13 @@ extern "C" int corb_kfdb_score(CorbKfDb* db, int a, const int32_t* entries_b, in
     if (db->n_words[a] < 0) { corb_set_error("%s: entry %d has no BowVector", who, a); return CORB_ERR_ARG; }
     for (int i = 0; i < n; i++) if (entries_b[i] < 0 || entries_b[i] >= db->d.capacity || db->n_words[entries_b[i]] < 0) { corb_set_error("%s: entries_b[%d] is outside the database or has no BowVector", who, i); return CORB_ERR_ARG; }
     if (n == 0) return CORB_OK;
-    memcpy(db->pinned, entries_b, (size_t)n * 4);
-    HIPCHK(hipMemcpyAsync(db->d.conn_list, db->pinned, (size_t)n * 4, hipMemcpyHostToDevice, db->stream));
+    memcpy(db->pinned.as<int32_t>(), entries_b, (size_t)n * 4);
+    HIPCHK(hipMemcpyAsync(db->d.conn_list, db->pinned.as<int32_t>(), (size_t)n * 4, hipMemcpyHostToDevice, db->stream));
     corb_launch_kfdb_score(db->d, a, db->n_words[a], db->d.conn_list, n, db->stream);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(db->pinned_score, db->d.score_out, (size_t)n * 8, hipMemcpyDeviceToHost, db->stream));
+    HIPCHK(hipMemcpyAsync(db->pinned_score.as<double>(), db->d.score_out, (size_t)n * 8, hipMemcpyDeviceToHost, db->stream));
     HIPCHK(hipStreamSynchronize(db->stream));
-    memcpy(score, db->pinned_score, (size_t)n * 8);
+    memcpy(score, db->pinned_score.as<double>(), (size_t)n * 8);
     return CORB_OK;
 }
 
@@ -342,10 +328,10 @@ extern "C" int corb_kfdb_detect(CorbKfDb* db, int kind, int q, uint64_t query_id
     if (db->n_words[q] < 0) { corb_set_error("%s: the query entry %d has no BowVector", who, q); return CORB_ERR_ARG; }
     *n = 0;
     const int c = db->d.capacity, want = std::min(cap, c);
-    if (n_connected) { memcpy(db->pinned, connected, (size_t)n_connected * 4); HIPCHK(hipMemcpyAsync(db->d.conn_list, db->pinned, (size_t)n_connected * 4, hipMemcpyHostToDevice, db->stream)); }
+    if (n_connected) { memcpy(db->pinned.as<int32_t>(), connected, (size_t)n_connected * 4); HIPCHK(hipMemcpyAsync(db->d.conn_list, db->pinned.as<int32_t>(), (size_t)n_connected * 4, hipMemcpyHostToDevice, db->stream)); }
     corb_launch_kfdb_detect(db->d, kind, q, db->n_words[q], query_id, n_connected, min_score, db->stream);
     HIPCHK(hipGetLastError());
-    int32_t* back = db->pinned + c;
+    int32_t* back = db->pinned.as<int32_t>() + c;
     HIPCHK(hipMemcpyAsync(back, db->d.out, ((size_t)want + 1) * 4, hipMemcpyDeviceToHost, db->stream));
     HIPCHK(hipStreamSynchronize(db->stream));
     *n = back[0];

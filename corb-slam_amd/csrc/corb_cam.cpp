@@ -18,7 +18,7 @@ struct CorbRgbd {
     uint8_t* d_stage = nullptr;              // [max_frames][in_frame_bytes]: the captured chains read it, so it never moves
     uint8_t* d_result = nullptr;             // [max_frames][frame_bytes] (corb_rgbd_frames)
     std::map<int, hipGraphExec_t> frame_graph;
-    hipEvent_t ev_t[4] = {};
+    OwnedEvent ev_t[4];
 };
 
 extern "C" int corb_rgbd_create(const CorbCameraConfig* cfg, CorbRgbd** out)
@@ -105,11 +105,11 @@ extern "C" int corb_rgbd_create(const CorbCameraConfig* cfg, CorbRgbd** out)
 extern "C" void corb_rgbd_destroy(CorbRgbd* h)
 {
     if (!h) return;
-    (void)hipSetDevice(h->orb->cfg.device);
-    if (h->orb->stream) (void)hipStreamSynchronize(h->orb->stream);
+    CorbOrb* orb = h->orb;
+    (void)corb_select_device(orb->device);
+    if (orb->stream) (void)hipStreamSynchronize(orb->stream);
     for (auto& g : h->frame_graph) if (g.second) (void)hipGraphExecDestroy(g.second);
-    for (auto e : h->ev_t) if (e) (void)hipEventDestroy(e);
-    corb_orb_destroy(h->orb); delete h;
+    delete h; corb_orb_destroy(orb);
 }
 extern "C" CorbOrb* corb_rgbd_orb(CorbRgbd* h) { return h ? h->orb : nullptr; }
 
@@ -187,7 +187,7 @@ extern "C" int corb_rgbd_frames(CorbRgbd* h, int n_frames, const uint8_t* input,
     HIPCHK(hipSetDevice(o->cfg.device));
     corb_join(o);
     hipStream_t st = o->stream;
-    if (timing && !h->ev_t[0]) for (auto& e : h->ev_t) HIPCHK(hipEventCreate(&e));
+    if (timing && !h->ev_t[0]) for (auto& e : h->ev_t) HIPCHK(e.create(hipEventDefault));
     CorbProfiler* prof = o->prof.enabled ? &o->prof : nullptr;
     auto chain = [&](CorbProfiler* pr) {
         corb_launch_cam_ingest(h->c, 0, n_frames, o->p, st, pr);

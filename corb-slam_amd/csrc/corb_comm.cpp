@@ -105,9 +105,10 @@ int CorbComm::all_gather(const int* mine, int n, int* all)
         return CORB_OK;
     }
     if (n * (world + 1) > d_ints_cap) { corb_set_error("corb_comm: all-gather of %d ints per rank exceeds the staging buffer", n); return CORB_ERR_ARG; }
-    HIPCHK(hipMemcpyAsync(d_ints + (size_t)world * n, mine, sizeof(int) * n, hipMemcpyHostToDevice, stream));
-    NCCLCHK(rccl().AllGather(d_ints + (size_t)world * n, d_ints, (size_t)n, NCCL_INT32, comm, stream));
-    HIPCHK(hipMemcpyAsync(all, d_ints, sizeof(int) * (size_t)world * n, hipMemcpyDeviceToHost, stream));
+    int* const ints = d_ints.as<int>();
+    HIPCHK(hipMemcpyAsync(ints + (size_t)world * n, mine, sizeof(int) * n, hipMemcpyHostToDevice, stream));
+    NCCLCHK(rccl().AllGather(ints + (size_t)world * n, ints, (size_t)n, NCCL_INT32, comm, stream));
+    HIPCHK(hipMemcpyAsync(all, ints, sizeof(int) * (size_t)world * n, hipMemcpyDeviceToHost, stream));
     HIPCHK(hipStreamSynchronize(stream));
     return CORB_OK;
 }
@@ -169,7 +170,7 @@ extern "C" int corb_comm_create(const void* id128, int rank, int world, int devi
     ncclUniqueId_ id; memcpy(id.internal, id128, 128);
     if (rccl().CommInitRank(&c->comm, world, id, rank) != 0) { corb_set_error("ncclCommInitRank failed (rank %d of %d)", rank, world); delete c; return CORB_ERR_HIP; }
     c->d_ints_cap = (2 * world + 16) * (world + 1);          // headers (5 ints per rank) and the layout of corb_map_push_setup (2 world + 6 ints per rank)
-    if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess || hipMalloc((void**)&c->d_ints, sizeof(int) * (size_t)c->d_ints_cap) != hipSuccess) {
+    if (c->stream.create() != hipSuccess || c->d_ints.room(sizeof(int) * (size_t)c->d_ints_cap) != hipSuccess) {
         corb_set_error("corb_comm_create: stream / buffer allocation failed"); (void)rccl().CommDestroy(c->comm); delete c; return CORB_ERR_HIP;
     }
     *out = c;
@@ -186,7 +187,7 @@ extern "C" int corb_comm_create_local(int world, const int* devices, CorbComm** 
         CorbComm* c = nullptr;
         if (rc == CORB_OK) {
             c = new CorbComm(); c->rank = r; c->world = world; c->device = dev; c->hub = hub;
-            if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) { corb_set_error("corb_comm_create_local: stream creation failed"); delete c; c = nullptr; rc = CORB_ERR_HIP; }
+            if (c->stream.create() != hipSuccess) { corb_set_error("corb_comm_create_local: stream creation failed"); delete c; c = nullptr; rc = CORB_ERR_HIP; }
         }
         if (!c) { for (int q = 0; q < r; q++) { corb_comm_destroy(out[q]); out[q] = nullptr; } return rc; }
         out[r] = c;
@@ -195,16 +196,9 @@ extern "C" int corb_comm_create_local(int world, const int* devices, CorbComm** 
 }
 extern "C" void corb_comm_destroy(CorbComm* c)
 {
-    if (!c) return;
-    (void)hipSetDevice(c->device);
-    if (c->stream) { (void)hipStreamSynchronize(c->stream); (void)hipStreamDestroy(c->stream); }
-    if (c->d_ints) (void)hipFree(c->d_ints);
-    if (c->stage_kf) (void)hipFree(c->stage_kf);
-    if (c->stage_mp) (void)hipFree(c->stage_mp);
-    if (c->stage_slots) (void)hipFree(c->stage_slots);
-    if (c->push_done) (void)hipEventDestroy(c->push_done);
-    if (c->comm && rccl().ok) (void)rccl().CommDestroy(c->comm);
-    delete c;
+    const ncclComm_t comm = c ? c->comm : nullptr;
+    handle_destroy(c);
+    if (comm && rccl().ok) (void)rccl().CommDestroy(comm);
 }
 extern "C" int corb_comm_rank(const CorbComm* c) { return c ? c->rank : -1; }
 extern "C" int corb_comm_world(const CorbComm* c) { return c ? c->world : 0; }
@@ -267,18 +261,18 @@ int stage_records(CorbComm* c, bool kf_store, const char* base, size_t rec_bytes
     bool run = in_place_ok;
     for (int i = 1; i < n && run; i++) run = slots[i] == slots[0] + i;
     if (run) { *ptr = const_cast<char*>(base) + (size_t)slots[0] * rec_bytes; return CORB_OK; }
-    char*& buf = kf_store ? c->stage_kf : c->stage_mp; size_t& cap = kf_store ? c->stage_kf_cap : c->stage_mp_cap;
-    int rc = c->reserve(buf, cap, rec_bytes * (size_t)n);
+    DevMem& stage = kf_store ? c->stage_kf : c->stage_mp;
+    int rc = c->room(stage, rec_bytes * (size_t)n);
     if (rc) return rc;
+    char* const buf = stage.as<char>();
     *ptr = buf;
-    char* sl = reinterpret_cast<char*>(c->stage_slots); size_t slcap = c->stage_slots_cap * sizeof(int);
     // (keyframe and map-point slot lists share the buffer: the second list goes behind the first)
-    const size_t off = kf_store ? 0 : (c->stage_slots_cap / 2) * sizeof(int);
-    if (slcap < 2 * sizeof(int) * (size_t)n + off) {
-        rc = c->reserve(sl, slcap, 4 * sizeof(int) * (size_t)std::max(n, 4096)); c->stage_slots = reinterpret_cast<int*>(sl); c->stage_slots_cap = slcap / sizeof(int);
+    const size_t off = kf_store ? 0 : (c->stage_slots.cap() / sizeof(int) / 2) * sizeof(int);
+    if (c->stage_slots.cap() < 2 * sizeof(int) * (size_t)n + off) {
+        rc = c->room(c->stage_slots, 4 * sizeof(int) * (size_t)std::max(n, 4096));
         if (rc) return rc;
     }
-    int* dslots = c->stage_slots + (kf_store ? 0 : c->stage_slots_cap / 2);
+    int* dslots = c->stage_slots.as<int>() + (kf_store ? 0 : c->stage_slots.cap() / sizeof(int) / 2);
     if (hipMemcpyAsync(dslots, slots, sizeof(int) * (size_t)n, hipMemcpyHostToDevice, stream) != hipSuccess) { corb_set_error("map push: slot list upload failed"); return CORB_ERR_HIP; }
     corb_launch_gather_records(base, rec_bytes, dslots, n, buf, stream);
     if (hipGetLastError() != hipSuccess) { corb_set_error("map push: record packing failed"); return CORB_ERR_HIP; }
@@ -331,7 +325,7 @@ int push_exchange(CorbComm* c, const CorbMapPush* p, int root, const std::vector
     std::vector<Msg> sends, recvs;
     for (int i = 0; i < ns; i++) {
         const bool kf = sm[i].kind == 0; char* ptr = nullptr;
-        note(stage_records(c, kf, kf ? p->kf->base : p->mp->base, kf ? p->kf->L.bytes : p->mp->L.bytes, kf ? p->kf_slots : p->mp_slots, sm[i].n_records, !is_root && !c->hub, c->stream, wait || (bool)c->hub, &ptr));
+        note(stage_records(c, kf, kf ? p->kf->base() : p->mp->base(), kf ? p->kf->L.bytes : p->mp->L.bytes, kf ? p->kf_slots : p->mp_slots, sm[i].n_records, !is_root && !c->hub, c->stream, wait || (bool)c->hub, &ptr));
         sends.push_back({ptr, (size_t)sm[i].bytes, sm[i].peer});
     }
     for (int i = 0; i < nr; i++) {
@@ -434,7 +428,7 @@ extern "C" int corb_map_push_setup(CorbComm* c, int root, CorbKfStore* kf, CorbM
     c->layout_root = root; c->layout_kf_cap = L[1]; c->layout_kf_bytes = L[2]; c->layout_mp_cap = L[3]; c->layout_mp_bytes = L[4];
     c->layout_kf_first.assign(L + 6, L + 6 + W);
     if (L[5]) c->layout_mp_first.assign(L + 6 + W, L + 6 + 2 * W); else c->layout_mp_first.clear();
-    if (!c->push_done && hipEventCreateWithFlags(&c->push_done, hipEventDisableTiming) != hipSuccess) { corb_set_error("corb_map_push_setup: event creation failed"); return CORB_ERR_HIP; }
+    if (!c->push_done && c->push_done.create(hipEventDisableTiming) != hipSuccess) { corb_set_error("corb_map_push_setup: event creation failed"); return CORB_ERR_HIP; }
     c->layout_kf_store = c->rank == root ? kf : nullptr; c->layout_mp_store = c->rank == root ? mp : nullptr;
     c->layout_set = true;
     return CORB_OK;

@@ -16,41 +16,33 @@ extern "C" int corb_covis_create(CorbKfStore* kf, CorbMpStore* mp, int max_conne
     const size_t cells = (size_t)kf->capacity * M, heads = ((size_t)kf->capacity * 4 + 255) & ~(size_t)255;
     const size_t bytes = cells * 24 + 2 * heads;
     CorbCovis* g = new CorbCovis();
-    g->kf = kf; g->mp = mp;
-    if (hipMalloc((void**)&g->mem, bytes) != hipSuccess) { corb_set_error("corb_covis_create: %d rows x %d connections: allocation failed", kf->capacity, M); delete g; return CORB_ERR_HIP; }
+    g->kf = kf; g->mp = mp; g->device = kf->device;
+    if (g->mem.room(bytes) != hipSuccess) { corb_set_error("corb_covis_create: %d rows x %d connections: allocation failed", kf->capacity, M); delete g; return CORB_ERR_HIP; }
+    char* const mem = g->mem.as<char>();
     g->R.M = M;
-    g->R.all_id = reinterpret_cast<unsigned long long*>(g->mem); g->R.ord_id = g->R.all_id + cells;
+    g->R.all_id = reinterpret_cast<unsigned long long*>(mem); g->R.ord_id = g->R.all_id + cells;
     g->R.all_w = reinterpret_cast<int*>(g->R.ord_id + cells); g->R.ord_w = g->R.all_w + cells;
-    g->R.n_all = reinterpret_cast<int*>(g->mem + cells * 24); g->R.n_ord = reinterpret_cast<int*>(g->mem + cells * 24 + heads);
-    if (hipMemset(g->mem, 0, bytes) != hipSuccess) { corb_set_error("corb_covis_create: hipMemset failed"); (void)hipFree(g->mem); delete g; return CORB_ERR_HIP; }
+    g->R.n_all = reinterpret_cast<int*>(mem + cells * 24); g->R.n_ord = reinterpret_cast<int*>(mem + cells * 24 + heads);
+    if (hipMemset(mem, 0, bytes) != hipSuccess) { corb_set_error("corb_covis_create: hipMemset failed"); delete g; return CORB_ERR_HIP; }
     // the spanning tree beside the rows: parent ids, child sets, then the two per-slot ints
     const size_t tree_bytes = (((size_t)kf->capacity * 8 + 255) & ~(size_t)255) + cells * 8 + 2 * heads;
-    if (hipMalloc((void**)&g->tree_mem, tree_bytes) != hipSuccess) { corb_set_error("corb_covis_create: %d child sets x %d ids: allocation failed", kf->capacity, M); (void)hipFree(g->mem); delete g; return CORB_ERR_HIP; }
-    g->T.parent = reinterpret_cast<unsigned long long*>(g->tree_mem); g->T.child_id = reinterpret_cast<unsigned long long*>(g->tree_mem + (((size_t)kf->capacity * 8 + 255) & ~(size_t)255));
+    if (g->tree_mem.room(tree_bytes) != hipSuccess) { corb_set_error("corb_covis_create: %d child sets x %d ids: allocation failed", kf->capacity, M); delete g; return CORB_ERR_HIP; }
+    char* const tree_mem = g->tree_mem.as<char>();
+    g->T.parent = reinterpret_cast<unsigned long long*>(tree_mem); g->T.child_id = reinterpret_cast<unsigned long long*>(tree_mem + (((size_t)kf->capacity * 8 + 255) & ~(size_t)255));
     g->T.first = reinterpret_cast<int*>(g->T.child_id + cells); g->T.n_child = reinterpret_cast<int*>(reinterpret_cast<char*>(g->T.first) + heads);
     covis_launch_tree_init(g->T, kf->capacity, nullptr);                                          // none / first connection / no children
     // (a wait for the stream of the launch alone: the device's other streams, other clients' stores among them, are not waited for)
-    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(nullptr) != hipSuccess) { corb_set_error("corb_covis_create: the tree's initialisation failed"); (void)hipFree(g->tree_mem); (void)hipFree(g->mem); delete g; return CORB_ERR_HIP; }
+    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(nullptr) != hipSuccess) { corb_set_error("corb_covis_create: the tree's initialisation failed"); delete g; return CORB_ERR_HIP; }
     // mTcwBefGBA beside the tree (the record's header has no room for it).  The reference leaves the matrix uninitialised (KeyFrame.cc:62); here it starts as the identity
     std::vector<float> eye((size_t)kf->capacity * 16, 0.f);
     for (size_t i = 0; i < (size_t)kf->capacity; i++) eye[i * 16] = eye[i * 16 + 5] = eye[i * 16 + 10] = eye[i * 16 + 15] = 1.f;
-    if (hipMalloc((void**)&g->bef, eye.size() * 4 + 256) != hipSuccess || hipMemcpy(g->bef, eye.data(), eye.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
-        corb_set_error("corb_covis_create: %d poses before the global BA: allocation failed", kf->capacity);
-        if (g->bef) (void)hipFree(g->bef);
-        (void)hipFree(g->tree_mem); (void)hipFree(g->mem); delete g; return CORB_ERR_HIP;
+    if (g->bef_mem.room(eye.size() * 4 + 256) != hipSuccess || hipMemcpy(g->bef(), eye.data(), eye.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
+        corb_set_error("corb_covis_create: %d poses before the global BA: allocation failed", kf->capacity); delete g; return CORB_ERR_HIP;
     }
     *out = g;
     return CORB_OK;
 }
-extern "C" void corb_covis_destroy(CorbCovis* g)
-{
-    if (!g) return;
-    (void)hipSetDevice(g->kf->device);
-    if (g->mem) (void)hipFree(g->mem);
-    if (g->tree_mem) (void)hipFree(g->tree_mem);
-    if (g->bef) (void)hipFree(g->bef);
-    delete g;
-}
+extern "C" void corb_covis_destroy(CorbCovis* g) { handle_destroy(g); }
 
 namespace {
 int slot_ok(CorbCovis* g, int slot, const char* who) { return covis_slot_ok(g, slot, who); }

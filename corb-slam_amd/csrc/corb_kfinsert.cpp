@@ -3,38 +3,32 @@
 // page-locked mirror, the list / slot scratch, and two id tables (first occurrences; the keyframes at hand), both refilled by every call that reads them.
 #include "kfinsert_internal.h"
 #include "record_call.h"
+#include "owned_hip.h"
 #include "../../include/corb_keyframe_insert.h"
 #include <algorithm>
 #include <cstring>
 
 struct CorbKfInsert {
     int device = 0, F = 0, R = 0;
-    hipStream_t stream = nullptr;
+    OwnedStream stream;
     std::mutex mu;
-    char* out = nullptr; char* host = nullptr; size_t out_bytes = 0;      // [4 ints | 4-byte arrays | byte arrays] of the running call, and its page-locked mirror
-    int* slots = nullptr;                                                 // [max(F, R)] the recent list on the device / the map-point slot per feature
-    CorbIdTable first{nullptr, nullptr, 0};                               // sized for max(F, R) entries
-    CorbIdTable kfid{nullptr, nullptr, 0};                                // grown to the largest keyframe range a call named
-    unsigned long long* desc = nullptr; size_t desc_words = 0;            // grown to features x max_observations x 4
+    DevMem out; PinnedMem host; size_t out_bytes = 0;                     // [4 ints | 4-byte arrays | byte arrays] of the running call, and its page-locked mirror
+    DevMem slots;                                                         // [max(F, R)] the recent list on the device / the map-point slot per feature
+    OwnedIdTable first;                                                   // sized for max(F, R) entries
+    OwnedIdTable kfid;                                                    // grown to the largest keyframe range a call named
+    DevMem desc;                                                          // grown to features x max_observations x 4 words of 8 bytes
 };
 
 namespace {
-// a table of the handle's holds at least `entries` ids (it only grows)
-int table_room(CorbIdTable& t, long long entries)
-{
-    const size_t cap = id_table_capacity(entries);
-    return t.keys && (size_t)t.mask + 1 >= cap ? CORB_OK : id_table_own(t, cap, 0);
-}
 // mnId -> slot of the keyframes [kf_first, kf_first + kf_n), as corb_mp_store_replace builds it
 int index_keyframes(CorbKfInsert* h, const CorbKfStore* kf, int kf_first, int kf_n)
 {
-    int rc = table_room(h->kfid, kf_n); if (rc) return rc;
-    rc = id_table_clear(h->kfid, true, h->stream); if (rc) return rc;
-    corb_launch_kf_index(kf->base, kf->L.bytes, kf_first, kf_n, h->kfid, h->stream);
+    HIPCHK(h->kfid.room(kf_n));
+    int rc = id_table_clear(h->kfid, true, h->stream); if (rc) return rc;
+    corb_launch_kf_index(kf->base(), kf->L.bytes, kf_first, kf_n, h->kfid, h->stream);
     return CORB_OK;
 }
 bool range_ok(const CorbKfStore* kf, int kf_first, int kf_n) { return kf && kf_first >= 0 && kf_n >= 0 && (long long)kf_first + kf_n <= kf->capacity; }
-size_t al16(size_t v) { return (v + 15) & ~(size_t)15; }
 }  // namespace
 
 extern "C" int corb_kfi_create(int device, int max_features, int max_recent, CorbKfInsert** out)
@@ -46,33 +40,18 @@ extern "C" int corb_kfi_create(int device, int max_features, int max_recent, Cor
     h->device = device; h->F = max_features; h->R = max_recent;
     const size_t m = (size_t)std::max(max_features, std::max(max_recent, 1));
     h->out_bytes = al16(16 + m * 16 + m);
-    hipError_t e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipMalloc((void**)&h->out, h->out_bytes);
-    if (e == hipSuccess) e = hipHostMalloc((void**)&h->host, std::max(h->out_bytes, m * 4));
-    if (e == hipSuccess) e = hipMalloc((void**)&h->slots, m * 4);
-    if (e != hipSuccess || table_room(h->first, (long long)m) != CORB_OK || table_room(h->kfid, 0) != CORB_OK) {
-        if (e != hipSuccess) corb_set_error("corb_kfi_create: %s", hipGetErrorString(e));
-        corb_kfi_destroy(h); return CORB_ERR_HIP;
-    }
+    hipError_t e = h->stream.create();
+    if (e == hipSuccess) e = h->out.room(h->out_bytes);
+    if (e == hipSuccess) e = h->host.room(std::max(h->out_bytes, m * 4));
+    if (e == hipSuccess) e = h->slots.room(m * 4);
+    if (e == hipSuccess) e = h->first.room((long long)m);
+    if (e == hipSuccess) e = h->kfid.room(0);
+    if (e != hipSuccess) { corb_set_error("corb_kfi_create: %s", hipGetErrorString(e)); handle_destroy(h); return CORB_ERR_HIP; }
     *out = h;
     return CORB_OK;
 }
 
-extern "C" void corb_kfi_destroy(CorbKfInsert* h)
-{
-    if (!h) return;
-    if (corb_select_device(h->device) == CORB_OK) {
-        if (h->stream) (void)hipStreamSynchronize(h->stream);
-        if (h->out) (void)hipFree(h->out);
-        if (h->host) (void)hipHostFree(h->host);
-        if (h->slots) (void)hipFree(h->slots);
-        if (h->first.keys) (void)hipFree(h->first.keys);
-        if (h->kfid.keys) (void)hipFree(h->kfid.keys);
-        if (h->desc) (void)hipFree(h->desc);
-        if (h->stream) (void)hipStreamDestroy(h->stream);
-    }
-    delete h;
-}
+extern "C" void corb_kfi_destroy(CorbKfInsert* h) { handle_destroy(h); }
 
 extern "C" int corb_kfi_create_stereo_points(CorbKfInsert* h, CorbKfStore* kf, int slot, CorbMpStore* map, const CorbTrackCamera* cam, float th_depth, int mode, int apply,
                                              int first_mp_slot, uint64_t first_mp_id, int32_t client_id, int64_t frame_id, CorbKfStore* mirror, int mirror_slot,
@@ -99,21 +78,21 @@ extern "C" int corb_kfi_create_stereo_points(CorbKfInsert* h, CorbKfStore* kf, i
     KfiPointsDev d; memset(&d, 0, sizeof(d));
     d.rec = kf->rec(slot); d.F = kf->F;
     if (mirror) { d.mirror = mirror->rec(mirror_slot); d.mirror_F = mirror->F; }
-    d.mp_base = map->base; d.mp_bytes = map->L.bytes; d.max_obs = map->O; d.mp_capacity = map->capacity; d.idt = map->idt;
+    d.mp_base = map->base(); d.mp_bytes = map->L.bytes; d.max_obs = map->O; d.mp_capacity = map->capacity; d.idt = map->idt;
     d.cap = n; d.P = 2; while (d.P < n) d.P <<= 1;
     d.th_depth = th_depth; d.mode = mode; d.apply = apply ? 1 : 0; d.first_mp_slot = first_mp_slot; d.first_mp_id = first_mp_id; d.client_id = client_id; d.frame_id = frame_id;
     d.fx = cam->fx; d.fy = cam->fy; d.cx = cam->cx; d.cy = cam->cy; d.nlevels = cam->nlevels;
     for (int l = 0; l < CORB_MAX_LEVELS; l++) d.scale[l] = l < cam->nlevels ? cam->scale[l] : 1.f;
     const size_t off_order = 16, off_x3d = off_order + (size_t)n * 4, off_kind = off_x3d + (size_t)n * 12, bytes = off_kind + (size_t)n;
-    d.counts = reinterpret_cast<int*>(h->out); d.order = reinterpret_cast<int*>(h->out + off_order); d.x3d = reinterpret_cast<float*>(h->out + off_x3d);
-    d.kind = reinterpret_cast<unsigned char*>(h->out + off_kind);
+    d.counts = h->out.as<int>(); d.order = reinterpret_cast<int*>(h->out.as<char>() + off_order); d.x3d = reinterpret_cast<float*>(h->out.as<char>() + off_x3d);
+    d.kind = reinterpret_cast<unsigned char*>(h->out.as<char>() + off_kind);
     corb_launch_kfi_points(d, h->stream);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(h->host, h->out, bytes, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(h->host.as<char>(), h->out.as<char>(), bytes, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
-    const int* cnt = reinterpret_cast<const int*>(h->host);
+    const int* cnt = h->host.as<const int>();
     const int visited = std::min(std::max(cnt[0], 0), n), created = std::min(std::max(cnt[1], 0), visited);
-    memcpy(order, h->host + off_order, (size_t)visited * 4); memcpy(kind, h->host + off_kind, (size_t)visited); memcpy(x3d, h->host + off_x3d, (size_t)created * 12);
+    memcpy(order, h->host.as<char>() + off_order, (size_t)visited * 4); memcpy(kind, h->host.as<char>() + off_kind, (size_t)visited); memcpy(x3d, h->host.as<char>() + off_x3d, (size_t)created * 12);
     *n_visited = visited; *n_created = created;
     if (apply && cnt[2]) { corb_set_error("%s: %d new map points, the store has room for %d from slot %d; no record was written", who, created, map->capacity - first_mp_slot, first_mp_slot); return CORB_ERR_CAPACITY; }
     if (apply && created > 0) map->idt_valid = false;          // the slots hold other ids now: corb_mp_store_build_index again before the calls that resolve ids
@@ -139,15 +118,15 @@ extern "C" int corb_kfi_need_keyframe_counts(CorbKfInsert* h, CorbKfStore* frame
     d.cur = frames->rec(cur_slot); d.cur_F = frames->F; d.n_cur = n_cur; d.th_depth = th_depth;
     if (ref_slot >= 0) { d.ref = kf->rec(ref_slot); d.ref_F = kf->F; d.n_ref = n_ref; }
     d.min_obs = min_obs;
-    d.mp_base = map->base; d.mp_bytes = map->L.bytes; d.max_obs = map->O; d.idt = map->idt;
-    d.kf_base = kf->base; d.kf_bytes = kf->L.bytes; d.kf_F = kf->F; d.kfid = h->kfid;
-    d.counts = reinterpret_cast<int*>(h->out);
+    d.mp_base = map->base(); d.mp_bytes = map->L.bytes; d.max_obs = map->O; d.idt = map->idt;
+    d.kf_base = kf->base(); d.kf_bytes = kf->L.bytes; d.kf_F = kf->F; d.kfid = h->kfid;
+    d.counts = h->out.as<int>();
     HIPCHK(hipMemsetAsync(d.counts, 0, 16, h->stream));
     corb_launch_kfi_counts(d, h->stream);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(h->host, h->out, 16, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(h->host.as<char>(), h->out.as<char>(), 16, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
-    const int* cnt = reinterpret_cast<const int*>(h->host);
+    const int* cnt = h->host.as<const int>();
     *n_tracked_close = cnt[0]; *n_non_tracked_close = cnt[1]; *n_ref_matches = cnt[2];
     return CORB_OK;
 }
@@ -167,27 +146,24 @@ extern "C" int corb_kfi_process_new_keyframe(CorbKfInsert* h, CorbKfStore* kf, i
     if (n == 0) return CORB_OK;
     if (!kind || !recent_slots) { corb_set_error("%s: NULL output", who); return CORB_ERR_ARG; }
     const size_t words = (size_t)n * map->O * 4;
-    if (apply && words > h->desc_words) {
-        if (h->desc) { (void)hipFree(h->desc); h->desc = nullptr; h->desc_words = 0; }
-        HIPCHK(hipMalloc((void**)&h->desc, words * 8)); h->desc_words = words;
-    }
+    if (apply) HIPCHK(h->desc.room(words * 8));
     rc = call.join(); if (rc) return rc;
     rc = index_keyframes(h, kf, kf_first, kf_n); if (rc) return rc;
     rc = id_table_clear(h->first, true, h->stream); if (rc) return rc;
     KfiAssocDev d; memset(&d, 0, sizeof(d));
     d.rec = kf->rec(slot); d.F = kf->F; d.n = n;
-    d.mp_base = map->base; d.mp_bytes = map->L.bytes; d.max_obs = map->O; d.idt = map->idt;
-    d.kf_base = kf->base; d.kf_bytes = kf->L.bytes; d.kfid = h->kfid; d.first = h->first; d.scale_factor = scale_factor;
+    d.mp_base = map->base(); d.mp_bytes = map->L.bytes; d.max_obs = map->O; d.idt = map->idt;
+    d.kf_base = kf->base(); d.kf_bytes = kf->L.bytes; d.kfid = h->kfid; d.first = h->first; d.scale_factor = scale_factor;
     const size_t off_recent = 16, off_kind = off_recent + (size_t)n * 4, bytes = off_kind + (size_t)n;
-    d.counts = reinterpret_cast<int*>(h->out); d.recent = reinterpret_cast<int*>(h->out + off_recent); d.kind = reinterpret_cast<unsigned char*>(h->out + off_kind);
-    d.mslot = h->slots; d.desc = h->desc;
+    d.counts = h->out.as<int>(); d.recent = reinterpret_cast<int*>(h->out.as<char>() + off_recent); d.kind = reinterpret_cast<unsigned char*>(h->out.as<char>() + off_kind);
+    d.mslot = h->slots.as<int>(); d.desc = h->desc.as<unsigned long long>();
     corb_launch_kfi_assoc(d, apply ? 1 : 0, h->stream);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(h->host, h->out, bytes, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(h->host.as<char>(), h->out.as<char>(), bytes, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
-    const int* cnt = reinterpret_cast<const int*>(h->host);
+    const int* cnt = h->host.as<const int>();
     const int recent = std::min(std::max(cnt[1], 0), n);
-    memcpy(kind, h->host + off_kind, (size_t)n); memcpy(recent_slots, h->host + off_recent, (size_t)recent * 4);
+    memcpy(kind, h->host.as<char>() + off_kind, (size_t)n); memcpy(recent_slots, h->host.as<char>() + off_recent, (size_t)recent * 4);
     *n_added = cnt[0]; *n_recent = recent;
     if (cnt[2]) { corb_set_error("%s: the observation list of a map point the keyframe is added to is full (max_observations = %d); nothing was written", who, map->O); return CORB_ERR_CAPACITY; }
     return CORB_OK;
@@ -208,21 +184,21 @@ extern "C" int corb_kfi_map_point_culling(CorbKfInsert* h, CorbMpStore* map, con
     rc = call.join(); if (rc) return rc;
     rc = index_keyframes(h, kf, kf_first, kf_n); if (rc) return rc;
     rc = id_table_clear(h->first, true, h->stream); if (rc) return rc;
-    memcpy(h->host, recent_slots, (size_t)n * 4);
-    HIPCHK(hipMemcpyAsync(h->slots, h->host, (size_t)n * 4, hipMemcpyHostToDevice, h->stream));
+    memcpy(h->host.as<char>(), recent_slots, (size_t)n * 4);
+    HIPCHK(hipMemcpyAsync(h->slots.as<int>(), h->host.as<char>(), (size_t)n * 4, hipMemcpyHostToDevice, h->stream));
     KfiCullDev d; memset(&d, 0, sizeof(d));
-    d.slots = h->slots; d.n = n; d.cur_kf_id = cur_kf_id; d.th_obs = th_obs; d.apply = apply ? 1 : 0;
-    d.mp_base = map->base; d.mp_bytes = map->L.bytes; d.max_obs = map->O;
-    d.kf_base = kf->base; d.kf_bytes = kf->L.bytes; d.kf_F = kf->F; d.kfid = h->kfid; d.first = h->first;
+    d.slots = h->slots.as<int>(); d.n = n; d.cur_kf_id = cur_kf_id; d.th_obs = th_obs; d.apply = apply ? 1 : 0;
+    d.mp_base = map->base(); d.mp_bytes = map->L.bytes; d.max_obs = map->O;
+    d.kf_base = kf->base(); d.kf_bytes = kf->L.bytes; d.kf_F = kf->F; d.kfid = h->kfid; d.first = h->first;
     const size_t off_kept = 16, off_dec = off_kept + (size_t)n * 4, bytes = off_dec + (size_t)n;
-    d.counts = reinterpret_cast<int*>(h->out); d.kept = reinterpret_cast<int*>(h->out + off_kept); d.decision = reinterpret_cast<unsigned char*>(h->out + off_dec);
+    d.counts = h->out.as<int>(); d.kept = reinterpret_cast<int*>(h->out.as<char>() + off_kept); d.decision = reinterpret_cast<unsigned char*>(h->out.as<char>() + off_dec);
     corb_launch_kfi_cull(d, h->stream);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(h->host, h->out, bytes, hipMemcpyDeviceToHost, h->stream));      // (behind the upload on the same stream: the staging block is free again)
+    HIPCHK(hipMemcpyAsync(h->host.as<char>(), h->out.as<char>(), bytes, hipMemcpyDeviceToHost, h->stream));      // (behind the upload on the same stream: the staging block is free again)
     HIPCHK(hipStreamSynchronize(h->stream));
-    const int* cnt = reinterpret_cast<const int*>(h->host);
+    const int* cnt = h->host.as<const int>();
     const int kept = std::min(std::max(cnt[0], 0), n);
-    memcpy(decision, h->host + off_dec, (size_t)n); memcpy(kept_slots, h->host + off_kept, (size_t)kept * 4);
+    memcpy(decision, h->host.as<char>() + off_dec, (size_t)n); memcpy(kept_slots, h->host.as<char>() + off_kept, (size_t)kept * 4);
     *n_kept = kept; *n_culled = cnt[1];
     return CORB_OK;
 }

@@ -72,7 +72,7 @@ extern "C" int corb_gba_propagate_store(CorbCovis* g, const int32_t* origin_slot
     HIPCHK(hipMemsetAsync(d.npop, 0, (size_t)K * 4, pool.stream));
     HIPCHK(hipMemsetAsync(d.winner, 0x7F, (size_t)K * 8, pool.stream));                           // winner and first
     if (n_origins > 0) HIPCHK(pool.h2d(d.queue, origin_slots, (size_t)n_origins * 4));
-    loopfix_launch_gather(g->T, g->R.M, c.S, g->bef, d, pool.stream);
+    loopfix_launch_gather(g->T, g->R.M, c.S, g->bef(), d, pool.stream);
     HIPCHK(hipGetLastError());
     int total = 0;
     HIPCHK(pool.d2h(&total, d.total, 4));
@@ -80,7 +80,7 @@ extern "C" int corb_gba_propagate_store(CorbCovis* g, const int32_t* origin_slot
     HIPCHK(pool.alloc(&d.child, (size_t)std::max(total, 1)));
     loopfix_launch_fill(g->T, g->R.M, c.S, d, pool.stream);
     loopfix_launch_walk(c.S, d, pool.stream);
-    loopfix_launch_commit(c.S, g->bef, d, pool.stream);
+    loopfix_launch_commit(c.S, g->bef(), d, pool.stream);
     loopfix_launch_points(c.S, g->mp->idt_first, g->mp->idt_n, d, pool.stream);
     HIPCHK(hipGetLastError());
     GbaHead head{};
@@ -97,7 +97,7 @@ extern "C" int corb_covis_set_pose_before_gba(CorbCovis* g, int slot, const floa
     if (!T) { corb_set_error("corb_covis_set_pose_before_gba: bad argument"); return CORB_ERR_ARG; }
     rc = corb_select_device(g->kf->device); if (rc) return rc;
     std::lock_guard<std::mutex> lk(g->mu);
-    HIPCHK(hipMemcpy(g->bef + (size_t)slot * 16, T, 64, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(g->bef() + (size_t)slot * 16, T, 64, hipMemcpyHostToDevice));
     return CORB_OK;
 }
 
@@ -107,6 +107,6 @@ extern "C" int corb_covis_get_pose_before_gba(CorbCovis* g, int slot, float* T)
     if (!T) { corb_set_error("corb_covis_get_pose_before_gba: bad argument"); return CORB_ERR_ARG; }
     rc = corb_select_device(g->kf->device); if (rc) return rc;
     std::lock_guard<std::mutex> lk(g->mu);
-    HIPCHK(hipMemcpy(T, g->bef + (size_t)slot * 16, 64, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(T, g->bef() + (size_t)slot * 16, 64, hipMemcpyDeviceToHost));
     return CORB_OK;
 }

@@ -132,8 +132,8 @@ extern "C" int corb_create_new_map_points_store(CorbKfStore* kf, int cur_slot, c
     }
     NpApplyDev a; memset(&a, 0, sizeof(a));
     a.n_nb = n_nb; a.n1 = n1; a.apply = apply ? 1 : 0; a.match = dmatch; a.x3d = dx3d; a.status = dstatus; a.winner = dwinner; a.rank = drank; a.totals = dtotals;
-    a.kf_base = kf->base; a.kf_bytes = L.bytes; a.F = kf->F; a.cur_slot = cur_slot; a.nb_slots = dslots;
-    if (apply) { a.mp_base = map->base; a.mp_bytes = map->L.bytes; a.max_obs = map->O; a.mp_capacity = map->capacity; a.first_mp_slot = first_mp_slot; a.first_mp_id = first_mp_id; a.client_id = client_id; }
+    a.kf_base = kf->base(); a.kf_bytes = L.bytes; a.F = kf->F; a.cur_slot = cur_slot; a.nb_slots = dslots;
+    if (apply) { a.mp_base = map->base(); a.mp_bytes = map->L.bytes; a.max_obs = map->O; a.mp_capacity = map->capacity; a.first_mp_slot = first_mp_slot; a.first_mp_id = first_mp_id; a.client_id = client_id; }
     a.nlevels = cam->nlevels; for (int l = 0; l < CORB_MAX_LEVELS; l++) a.scale[l] = l < cam->nlevels ? cam->scale[l] : 1.f;
     corb_launch_newpoints_apply(a, pool.stream);
     HIPCHK(hipGetLastError());

@@ -104,7 +104,7 @@ extern "C" int corb_orb_create(const CorbOrbConfig* cfg, CorbOrb** out)
     int rc = corb_select_device(cfg->device);
     if (rc != CORB_OK) return rc;
     CorbOrb* h = new CorbOrb();
-    h->cfg = *cfg;
+    h->cfg = *cfg; h->device = cfg->device;
     const int nl = cfg->nlevels;
     // ---- ORBextractor::ORBextractor (ORBextractor.cc:415-469) ----
     h->scale[0] = 1.0f; h->sigma2[0] = 1.0f;
@@ -257,49 +257,30 @@ extern "C" int corb_orb_create(const CorbOrbConfig* cfg, CorbOrb** out)
             hipMemcpy(h->dp, &p, sizeof(p), hipMemcpyHostToDevice) != hipSuccess ||
             hipMemset(p.status, 0, NI * sizeof(int)) != hipSuccess || hipMemset(p.out_count, 0, NI * sizeof(int)) != hipSuccess ||
             hipMemset(p.pyr, 0, NI * arena) != hipSuccess || hipMemset(p.blur, 0, NI * arena) != hipSuccess ||
-            hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess ||
-            hipHostMalloc((void**)&h->h_status, NI * sizeof(int)) != hipSuccess ||
-            hipHostMalloc((void**)&h->h_count, NI * sizeof(int)) != hipSuccess ||
-            hipMalloc((void**)&h->d_stage, (size_t)cfg->width * cfg->height + 256) != hipSuccess ||
-            hipHostMalloc((void**)&h->h_img, (size_t)cfg->width * cfg->height) != hipSuccess ||
-            hipHostMalloc((void**)&h->h_kp, (size_t)p.out_cap * sizeof(CorbKeyPoint)) != hipSuccess ||
-            hipHostMalloc((void**)&h->h_desc, (size_t)p.out_cap * 32) != hipSuccess ||
-            hipHostMalloc((void**)&h->h_f32, (size_t)p.out_cap * 2 * sizeof(float)) != hipSuccess ||
-            hipHostMalloc((void**)&h->h_misc, 8 * sizeof(int)) != hipSuccess) {
+            h->stream.create() != hipSuccess ||
+            h->h_status.room(NI * sizeof(int)) != hipSuccess ||
+            h->h_count.room(NI * sizeof(int)) != hipSuccess ||
+            h->d_stage.room((size_t)cfg->width * cfg->height + 256) != hipSuccess ||
+            h->h_img.room((size_t)cfg->width * cfg->height) != hipSuccess ||
+            h->h_kp.room((size_t)p.out_cap * sizeof(CorbKeyPoint)) != hipSuccess ||
+            h->h_desc.room((size_t)p.out_cap * 32) != hipSuccess ||
+            h->h_f32.room((size_t)p.out_cap * 2 * sizeof(float)) != hipSuccess ||
+            h->h_misc.room(8 * sizeof(int)) != hipSuccess) {
             corb_set_error("device initialisation failed: %s", hipGetErrorString(hipGetLastError()));
             corb_orb_destroy(h); return CORB_ERR_HIP;
         }
     }
     if (const char* e = getenv("CORB_PARTS")) h->parts = std::max(1, std::min(CORB_MAX_PARTS, atoi(e)));
     for (int i = 0; i < CORB_MAX_PARTS; i++)
-        if (hipEventCreateWithFlags(&h->ev_stage[i], hipEventDisableTiming) != hipSuccess) { corb_set_error("event creation failed: %s", hipGetErrorString(hipGetLastError())); corb_orb_destroy(h); return CORB_ERR_HIP; }
+        if (h->ev_stage[i].create(hipEventDisableTiming) != hipSuccess) { corb_set_error("event creation failed: %s", hipGetErrorString(hipGetLastError())); corb_orb_destroy(h); return CORB_ERR_HIP; }
     *out = h;
     return CORB_OK;
 }
 
 extern "C" void corb_orb_destroy(CorbOrb* h)
 {
-    if (!h) return;
-    (void)hipSetDevice(h->cfg.device);
-    if (h->stream) { (void)hipStreamSynchronize(h->stream); (void)hipStreamDestroy(h->stream); }
-    for (int i = 0; i < CORB_MAX_PARTS - 1; i++) {
-        if (h->side[i]) { (void)hipStreamSynchronize(h->side[i]); (void)hipStreamDestroy(h->side[i]); }
-        if (h->ev_done[i]) (void)hipEventDestroy(h->ev_done[i]);
-    }
-    for (int i = 0; i < CORB_MAX_PARTS; i++) if (h->ev_stage[i]) (void)hipEventDestroy(h->ev_stage[i]);
-    for (void* ptr : h->allocs) (void)hipFree(ptr);
-    if (h->h_status) (void)hipHostFree(h->h_status);
-    if (h->h_count) (void)hipHostFree(h->h_count);
-    if (h->d_stage) (void)hipFree(h->d_stage);
-    if (h->d_stage_batch) (void)hipFree(h->d_stage_batch);
-    if (h->h_img) (void)hipHostFree(h->h_img);
-    if (h->h_kp) (void)hipHostFree(h->h_kp);
-    if (h->h_desc) (void)hipHostFree(h->h_desc);
-    if (h->h_f32) (void)hipHostFree(h->h_f32);
-    if (h->h_misc) (void)hipHostFree(h->h_misc);
-    if (h->d_cand_tmp) (void)hipFree(h->d_cand_tmp);
-    if (h->d_cand_n) (void)hipFree(h->d_cand_n);
-    delete h;
+    if (h) { (void)corb_select_device(h->device); for (auto& side : h->side) if (side) (void)hipStreamSynchronize(side); }
+    handle_destroy(h);
 }
 
 extern "C" int corb_orb_tables(const CorbOrb* h, float* scale, float* inv_scale, float* sigma2, float* inv_sigma2,
@@ -325,8 +306,8 @@ extern "C" int corb_orb_upload(CorbOrb* h, int image, const uint8_t* img, int st
     const CorbLevel& L0 = h->p.lv[0];
     uint8_t* plane = h->p.pyr + (size_t)image * h->p.arena_per_image + L0.plane_off;
     if (stride == h->cfg.width) {                       // contiguous image: one 1-D copy into the staging buffer, rows laid out on the device
-        HIPCHK(hipMemcpyAsync(h->d_stage, img, (size_t)h->cfg.width * h->cfg.height, hipMemcpyHostToDevice, h->stream));
-        corb_launch_ingest(h->d_stage, h->cfg.width, h->cfg.height, 1, plane, L0.pitch, 0, h->stream);
+        HIPCHK(hipMemcpyAsync(h->d_stage.as<uint8_t>(), img, (size_t)h->cfg.width * h->cfg.height, hipMemcpyHostToDevice, h->stream));
+        corb_launch_ingest(h->d_stage.as<uint8_t>(), h->cfg.width, h->cfg.height, 1, plane, L0.pitch, 0, h->stream);
         HIPCHK(hipGetLastError());
     } else
         HIPCHK(hipMemcpy2DAsync(plane, L0.pitch, img, stride, h->cfg.width, h->cfg.height, hipMemcpyHostToDevice, h->stream));
@@ -341,16 +322,13 @@ extern "C" int corb_orb_upload_batch(CorbOrb* h, int first_image, int n_images, 
     HIPCHK(hipSetDevice(h->cfg.device));
     corb_join(h);
     const size_t img_bytes = (size_t)h->cfg.width * h->cfg.height, bytes = img_bytes * n_images;
-    if (h->stage_batch_bytes < bytes) {
+    if (h->d_stage_batch.cap() < bytes + 256) {
         HIPCHK(hipStreamSynchronize(h->stream));
-        if (h->d_stage_batch) (void)hipFree(h->d_stage_batch);
-        h->d_stage_batch = nullptr; h->stage_batch_bytes = 0;
-        HIPCHK(hipMalloc((void**)&h->d_stage_batch, bytes + 256));
-        h->stage_batch_bytes = bytes;
+        HIPCHK(h->d_stage_batch.room(bytes + 256));
     }
     const CorbLevel& L0 = h->p.lv[0];
-    HIPCHK(hipMemcpyAsync(h->d_stage_batch, imgs, bytes, hipMemcpyHostToDevice, h->stream));
-    corb_launch_ingest(h->d_stage_batch, h->cfg.width, h->cfg.height, n_images, h->p.pyr + (size_t)first_image * h->p.arena_per_image + L0.plane_off, L0.pitch,
+    HIPCHK(hipMemcpyAsync(h->d_stage_batch.as<uint8_t>(), imgs, bytes, hipMemcpyHostToDevice, h->stream));
+    corb_launch_ingest(h->d_stage_batch.as<uint8_t>(), h->cfg.width, h->cfg.height, n_images, h->p.pyr + (size_t)first_image * h->p.arena_per_image + L0.plane_off, L0.pitch,
                        h->p.arena_per_image, h->stream);
     HIPCHK(hipGetLastError());
     return CORB_OK;
@@ -403,28 +381,28 @@ extern "C" int corb_orb_sync(CorbOrb* h)
     HIPCHK(hipSetDevice(h->cfg.device));
     const int n = h->last_n_images > 0 ? h->last_n_images : h->cfg.max_images;
     corb_join(h);
-    HIPCHK(hipMemcpyAsync(h->h_status, h->p.status, n * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(h->h_status.as<int>(), h->p.status, n * sizeof(int), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
-    for (int i = 0; i < n; i++) if (h->h_status[i] != 0) { corb_set_error("image %d: internal buffer overflow (status %d)", i, h->h_status[i]); return CORB_ERR_OVERFLOW; }
+    for (int i = 0; i < n; i++) if (h->h_status.as<int>()[i] != 0) { corb_set_error("image %d: internal buffer overflow (status %d)", i, h->h_status.as<int>()[i]); return CORB_ERR_OVERFLOW; }
     return CORB_OK;
 }
 
 // enqueue the download of one image's results into the pinned staging area (count, status, keypoints, descriptors)
 static int corb_orb_stage_results(CorbOrb* h, int image)
 {
-    HIPCHK(hipMemcpyAsync(h->h_misc, h->p.out_count + image, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipMemcpyAsync(h->h_misc + 1, h->p.status + image, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipMemcpyAsync(h->h_kp, h->p.out_kp + (size_t)image * h->p.out_cap, (size_t)h->p.out_cap * sizeof(CorbKeyPoint), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipMemcpyAsync(h->h_desc, h->p.out_desc + (size_t)image * h->p.out_cap * 32, (size_t)h->p.out_cap * 32, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(h->h_misc.as<int>(), h->p.out_count + image, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(h->h_misc.as<int>() + 1, h->p.status + image, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(h->h_kp.as<CorbKeyPoint>(), h->p.out_kp + (size_t)image * h->p.out_cap, (size_t)h->p.out_cap * sizeof(CorbKeyPoint), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(h->h_desc.as<uint8_t>(), h->p.out_desc + (size_t)image * h->p.out_cap * 32, (size_t)h->p.out_cap * 32, hipMemcpyDeviceToHost, h->stream));
     return CORB_OK;
 }
 static int corb_orb_unstage(CorbOrb* h, CorbKeyPoint* keypoints, uint8_t* descriptors, int cap, int* n)
 {
-    const int cnt = h->h_misc[0];
+    const int cnt = h->h_misc.as<int>()[0];
     *n = cnt;
     if (cnt > cap) { corb_set_error("corb_orb_fetch: %d keypoints > capacity %d", cnt, cap); return CORB_ERR_CAPACITY; }
-    if (keypoints && cnt > 0) memcpy(keypoints, h->h_kp, (size_t)cnt * sizeof(CorbKeyPoint));
-    if (descriptors && cnt > 0) memcpy(descriptors, h->h_desc, (size_t)cnt * 32);
+    if (keypoints && cnt > 0) memcpy(keypoints, h->h_kp.as<CorbKeyPoint>(), (size_t)cnt * sizeof(CorbKeyPoint));
+    if (descriptors && cnt > 0) memcpy(descriptors, h->h_desc.as<uint8_t>(), (size_t)cnt * 32);
     return CORB_OK;
 }
 extern "C" int corb_orb_fetch(CorbOrb* h, int image, CorbKeyPoint* keypoints, uint8_t* descriptors, int cap, int* n)
@@ -450,14 +428,14 @@ extern "C" int corb_orb_extract(CorbOrb* h, const uint8_t* img, int width, int h
     corb_join(h);
     std::lock_guard<std::mutex> lk(h->stage_mu);
     // image -> pinned staging (one host memcpy) -> device (asynchronous DMA); run; results -> pinned staging; ONE synchronisation
-    for (int y = 0; y < height; y++) memcpy(h->h_img + (size_t)y * width, img + (size_t)y * stride, (size_t)width);
+    for (int y = 0; y < height; y++) memcpy(h->h_img.as<uint8_t>() + (size_t)y * width, img + (size_t)y * stride, (size_t)width);
     const CorbLevel& L0 = h->p.lv[0];
-    HIPCHK(hipMemcpyAsync(h->d_stage, h->h_img, (size_t)width * height, hipMemcpyHostToDevice, h->stream));
-    corb_launch_ingest(h->d_stage, width, height, 1, h->p.pyr + L0.plane_off, L0.pitch, 0, h->stream);
+    HIPCHK(hipMemcpyAsync(h->d_stage.as<uint8_t>(), h->h_img.as<uint8_t>(), (size_t)width * height, hipMemcpyHostToDevice, h->stream));
+    corb_launch_ingest(h->d_stage.as<uint8_t>(), width, height, 1, h->p.pyr + L0.plane_off, L0.pitch, 0, h->stream);
     int rc = corb_orb_run(h, 1); if (rc) return rc;
     rc = corb_orb_stage_results(h, 0); if (rc) return rc;
     HIPCHK(hipStreamSynchronize(h->stream));
-    if (h->h_misc[1] != 0) { corb_set_error("image 0: internal buffer overflow (status %d)", h->h_misc[1]); return CORB_ERR_OVERFLOW; }
+    if (h->h_misc.as<int>()[1] != 0) { corb_set_error("image 0: internal buffer overflow (status %d)", h->h_misc.as<int>()[1]); return CORB_ERR_OVERFLOW; }
     return corb_orb_unstage(h, keypoints, descriptors, cap, n);
 }
 
@@ -483,19 +461,15 @@ extern "C" int corb_orb_fetch_candidates(CorbOrb* h, int image, int level, CorbK
     HIPCHK(hipSetDevice(h->cfg.device));
     corb_join(h);
     const int need = h->p.lv[level].cand_cap;
-    if (h->cand_tmp_cap < need) {
-        if (h->d_cand_tmp) (void)hipFree(h->d_cand_tmp);
-        HIPCHK(hipMalloc((void**)&h->d_cand_tmp, (size_t)need * sizeof(CorbKeyPoint)));
-        h->cand_tmp_cap = need;
-    }
-    if (!h->d_cand_n) HIPCHK(hipMalloc((void**)&h->d_cand_n, sizeof(int)));
-    corb_launch_candidates(h->dp, image, level, h->d_cand_tmp, need, h->d_cand_n, h->stream);
+    HIPCHK(h->d_cand_tmp.room((size_t)need * sizeof(CorbKeyPoint)));
+    HIPCHK(h->d_cand_n.room(sizeof(int)));
+    corb_launch_candidates(h->dp, image, level, h->d_cand_tmp.as<CorbKeyPoint>(), need, h->d_cand_n.as<int>(), h->stream);
     int cnt = 0;
-    HIPCHK(hipMemcpyAsync(&cnt, h->d_cand_n, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(&cnt, h->d_cand_n.as<int>(), sizeof(int), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     *n = cnt;
     if (cnt > cap) return CORB_ERR_CAPACITY;
-    if (cnt > 0 && out) HIPCHK(hipMemcpy(out, h->d_cand_tmp, (size_t)cnt * sizeof(CorbKeyPoint), hipMemcpyDeviceToHost));
+    if (cnt > 0 && out) HIPCHK(hipMemcpy(out, h->d_cand_tmp.as<CorbKeyPoint>(), (size_t)cnt * sizeof(CorbKeyPoint), hipMemcpyDeviceToHost));
     return CORB_OK;
 }
 
@@ -538,7 +512,7 @@ struct CorbStereo {
     uint8_t* d_result = nullptr;
     std::map<int, hipGraphExec_t> frame_graph;
     const void* graph_stage = nullptr;       // the staging buffer the captured chains read from (corb_orb_upload_batch may replace it: the chains are then captured again)
-    hipEvent_t ev_t[4] = {};
+    OwnedEvent ev_t[4];
 };
 
 extern "C" int corb_stereo_create(const CorbStereoConfig* cfg, CorbStereo** out)
@@ -590,11 +564,11 @@ extern "C" int corb_stereo_create(const CorbStereoConfig* cfg, CorbStereo** out)
 extern "C" void corb_stereo_destroy(CorbStereo* h)
 {
     if (!h) return;
-    (void)hipSetDevice(h->orb->cfg.device);
-    if (h->orb->stream) (void)hipStreamSynchronize(h->orb->stream);
+    CorbOrb* orb = h->orb;
+    (void)corb_select_device(orb->device);
+    if (orb->stream) (void)hipStreamSynchronize(orb->stream);
     for (auto& g : h->frame_graph) if (g.second) (void)hipGraphExecDestroy(g.second);
-    for (auto e : h->ev_t) if (e) (void)hipEventDestroy(e);
-    corb_orb_destroy(h->orb); delete h;
+    delete h; corb_orb_destroy(orb);
 }
 extern "C" CorbOrb* corb_stereo_orb(CorbStereo* h) { return h ? h->orb : nullptr; }
 
@@ -664,32 +638,27 @@ extern "C" int corb_stereo_frames(CorbStereo* h, int n_frames, const uint8_t* im
     corb_join(o);
     hipStream_t st = o->stream;
     const size_t img_bytes = (size_t)o->cfg.width * o->cfg.height, in_bytes = img_bytes * 2 * n_frames;
-    if (o->stage_batch_bytes < in_bytes || !h->d_result || h->graph_stage != o->d_stage_batch) {
+    if (o->d_stage_batch.cap() < in_bytes + 256 || !h->d_result || h->graph_stage != o->d_stage_batch.as<void>()) {
         HIPCHK(hipStreamSynchronize(st));
         for (auto& g : h->frame_graph) if (g.second) (void)hipGraphExecDestroy(g.second);      // (the captured chains hold the staging addresses)
         h->frame_graph.clear();
-        if (o->stage_batch_bytes < in_bytes) {
-            if (o->d_stage_batch) (void)hipFree(o->d_stage_batch);
-            o->d_stage_batch = nullptr; o->stage_batch_bytes = 0;
-            const size_t want = img_bytes * 2 * std::min(h->max_frames, std::max(n_frames, 8));     // (room for the usual small frame counts: no re-capture when n grows)
-            HIPCHK(hipMalloc((void**)&o->d_stage_batch, want + 256));
-            o->stage_batch_bytes = want;
-        }
+        const size_t want = img_bytes * 2 * std::min(h->max_frames, std::max(n_frames, 8));         // (room for the usual small frame counts: no re-capture when n grows)
+        HIPCHK(o->d_stage_batch.room(in_bytes + 256, want + 256));
         if (!h->d_result) { if (dalloc(o, &h->d_result, (size_t)h->max_frames * h->lay.frame_bytes)) return CORB_ERR_HIP; HIPCHK(hipMemsetAsync(h->d_result, 0, (size_t)h->max_frames * h->lay.frame_bytes, st)); }
-        h->graph_stage = o->d_stage_batch;
+        h->graph_stage = o->d_stage_batch.as<void>();
     }
-    if (timing && !h->ev_t[0]) for (auto& e : h->ev_t) HIPCHK(hipEventCreate(&e));
+    if (timing && !h->ev_t[0]) for (auto& e : h->ev_t) HIPCHK(e.create(hipEventDefault));
     CorbProfiler* prof = o->prof.enabled ? &o->prof : nullptr;
     auto chain = [&](CorbProfiler* pr) {
         const CorbLevel& L0 = o->p.lv[0];
-        corb_launch_ingest(o->d_stage_batch, o->cfg.width, o->cfg.height, 2 * n_frames, o->p.pyr + L0.plane_off, L0.pitch, o->p.arena_per_image, st);
+        corb_launch_ingest(o->d_stage_batch.as<uint8_t>(), o->cfg.width, o->cfg.height, 2 * n_frames, o->p.pyr + L0.plane_off, L0.pitch, o->p.arena_per_image, st);
         corb_launch_orb_pipeline(o->p, 0, 2 * n_frames, o->octree_lds, st, pr);
         corb_launch_stereo(o->p, h->s, 0, n_frames, st, pr);
         corb_launch_stereo_pack(o->p, h->s, 0, n_frames, h->d_result, h->lay, st, pr);
     };
     static const bool no_graph = corb_dev_env("CORB_FRAME_NO_GRAPH") != nullptr;      // -DCORB_DEV builds only: the launches one by one (A/B of the capture)
     if (timing) HIPCHK(hipEventRecord(h->ev_t[0], st));
-    HIPCHK(hipMemcpyAsync(o->d_stage_batch, images, in_bytes, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(o->d_stage_batch.as<uint8_t>(), images, in_bytes, hipMemcpyHostToDevice, st));
     if (timing) HIPCHK(hipEventRecord(h->ev_t[1], st));
     if (prof || no_graph) chain(prof);
     else {
@@ -732,16 +701,16 @@ extern "C" int corb_stereo_fetch_matches(CorbStereo* h, int frame, float* u_righ
     HIPCHK(hipSetDevice(o->cfg.device));
     corb_join(o);
     std::lock_guard<std::mutex> lk(o->stage_mu);
-    HIPCHK(hipMemcpyAsync(o->h_misc + 2, o->p.out_count + 2 * frame, sizeof(int), hipMemcpyDeviceToHost, o->stream));
-    HIPCHK(hipMemcpyAsync(o->h_misc + 3, h->s.n_matched + frame, sizeof(int), hipMemcpyDeviceToHost, o->stream));
-    HIPCHK(hipMemcpyAsync(o->h_f32, h->s.u_right + (size_t)frame * o->p.out_cap, (size_t)o->p.out_cap * sizeof(float), hipMemcpyDeviceToHost, o->stream));
-    HIPCHK(hipMemcpyAsync(o->h_f32 + o->p.out_cap, h->s.depth + (size_t)frame * o->p.out_cap, (size_t)o->p.out_cap * sizeof(float), hipMemcpyDeviceToHost, o->stream));
+    HIPCHK(hipMemcpyAsync(o->h_misc.as<int>() + 2, o->p.out_count + 2 * frame, sizeof(int), hipMemcpyDeviceToHost, o->stream));
+    HIPCHK(hipMemcpyAsync(o->h_misc.as<int>() + 3, h->s.n_matched + frame, sizeof(int), hipMemcpyDeviceToHost, o->stream));
+    HIPCHK(hipMemcpyAsync(o->h_f32.as<float>(), h->s.u_right + (size_t)frame * o->p.out_cap, (size_t)o->p.out_cap * sizeof(float), hipMemcpyDeviceToHost, o->stream));
+    HIPCHK(hipMemcpyAsync(o->h_f32.as<float>() + o->p.out_cap, h->s.depth + (size_t)frame * o->p.out_cap, (size_t)o->p.out_cap * sizeof(float), hipMemcpyDeviceToHost, o->stream));
     HIPCHK(hipStreamSynchronize(o->stream));
-    const int cnt = o->h_misc[2];
-    *n = cnt; if (n_matched) *n_matched = o->h_misc[3];
+    const int cnt = o->h_misc.as<int>()[2];
+    *n = cnt; if (n_matched) *n_matched = o->h_misc.as<int>()[3];
     if (cnt > cap) return CORB_ERR_CAPACITY;
-    if (u_right && cnt > 0) memcpy(u_right, o->h_f32, (size_t)cnt * sizeof(float));
-    if (depth && cnt > 0) memcpy(depth, o->h_f32 + o->p.out_cap, (size_t)cnt * sizeof(float));
+    if (u_right && cnt > 0) memcpy(u_right, o->h_f32.as<float>(), (size_t)cnt * sizeof(float));
+    if (depth && cnt > 0) memcpy(depth, o->h_f32.as<float>() + o->p.out_cap, (size_t)cnt * sizeof(float));
     return CORB_OK;
 }
 

@@ -204,7 +204,7 @@ extern "C" int corb_pnp_ransac_store(CorbKfStore* frames, int slot, CorbMpStore*
     d.n_cand = n_candidates; d.cap = n1; d.stride_its = stride_its; d.min_set = min_set; d.th2 = th2; d.min_inliers = min_inliers; d.epsilon = epsilon;
     d.kf = frames->rec(slot); d.F = frames->F; d.nlevels = cam->nlevels;
     for (int l = 0; l < CORB_MAX_LEVELS; l++) d.scale[l] = l < cam->nlevels ? cam->scale[l] : 1.f;
-    d.mp_base = map->base; d.mp_bytes = map->L.bytes; d.idt = map->idt;
+    d.mp_base = map->base(); d.mp_bytes = map->L.bytes; d.idt = map->idt;
     HIPCHK(pool.upload_block({{(void**)&d.cand, cand.data(), cand.size() * sizeof(PnrCand)}, {(void**)&d.matched, matched_ids, (size_t)n_candidates * n1 * 8},
                               {(void**)&d.rand_values, rand_values, (size_t)n_candidates * stride_its * min_set * 4}}));
     static thread_local std::vector<PnrHyp> h_hyp, h_ref; static thread_local std::vector<unsigned long long> h_mask, h_ref_mask; std::vector<int> h_n, h_index;

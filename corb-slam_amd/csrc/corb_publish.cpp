@@ -6,46 +6,27 @@
 #include "publish_math.h"
 #include "record_call.h"
 #include "comm_internal.h"
+#include "owned_hip.h"
 #include <algorithm>
 #include <cstring>
 #include <string>
 
 struct CorbMapPublisher {
     int device = 0;
-    hipStream_t stream = nullptr;
+    OwnedStream stream;
     std::mutex mu;
-    char* msg = nullptr; size_t msg_cap = 0;                              // the message of the last pack
+    DevMem msg;                                                           // the message of the last pack
     int32_t counts[5] = {0, 0, 0, 0, 0}; int kf_bytes = 0, mp_bytes = 0; int64_t msg_bytes = 0;
-    char* recv = nullptr; size_t recv_cap = 0;                            // what corb_map_publish received
-    char* out = nullptr; size_t out_cap = 0;                              // the output block of an apply
-    char* host = nullptr; size_t host_cap = 0;                            // page-locked: a pack's slot lists and table on their way up, an apply's output block on its way down
-    char* scr = nullptr; size_t scr_cap = 0;                              // a pack's slot lists; an apply's ranks, positions, targets and workgroup counts
-    CorbIdTable kfid{nullptr, nullptr, 0}, first[2] = {{nullptr, nullptr, 0}, {nullptr, nullptr, 0}}, last[2] = {{nullptr, nullptr, 0}, {nullptr, nullptr, 0}};
+    DevMem recv;                                                          // what corb_map_publish received
+    DevMem out;                                                           // the output block of an apply
+    PinnedMem host;                                                       // a pack's slot lists and table on their way up, an apply's output block on its way down
+    DevMem scr;                                                           // a pack's slot lists; an apply's ranks, positions, targets and workgroup counts
+    OwnedIdTable kfid, first[2], last[2];
 };
 
 namespace {
-size_t al16(size_t v) { return (v + 15) & ~(size_t)15; }
-int grow_dev(char*& buf, size_t& cap, size_t need)
-{
-    if (need <= cap) return CORB_OK;
-    if (buf) { (void)hipFree(buf); buf = nullptr; cap = 0; }
-    const size_t want = std::max(need + need / 4, (size_t)4096);
-    HIPCHK(hipMalloc((void**)&buf, want)); cap = want;
-    return CORB_OK;
-}
-int grow_host(char*& buf, size_t& cap, size_t need)
-{
-    if (need <= cap) return CORB_OK;
-    if (buf) { (void)hipHostFree(buf); buf = nullptr; cap = 0; }
-    const size_t want = std::max(need + need / 4, (size_t)4096);
-    HIPCHK(hipHostMalloc((void**)&buf, want)); cap = want;
-    return CORB_OK;
-}
-int table_room(CorbIdTable& t, long long entries)
-{
-    const size_t cap = id_table_capacity(entries);
-    return t.keys && (size_t)t.mask + 1 >= cap ? CORB_OK : id_table_own(t, cap, 0);
-}
+// a buffer of the handle's holds at least `need` bytes: a quarter more than asked when it grows, 4096 at the least
+template <class Mem> int grow(Mem& buf, size_t need) { HIPCHK(buf.room(need, std::max(need + need / 4, (size_t)4096))); return CORB_OK; }
 int layout(const int32_t* counts, int kfb, int mpb, int64_t* off)
 {
     for (int k = 0; k < 5; k++) if (counts[k] < 0) return CORB_ERR_ARG;
@@ -83,43 +64,43 @@ int pack_check(const char* who, CorbMapPublisher* h, const CorbPublishPack* p, R
     }
     int rc = corb_select_device(h->device); if (rc) return rc;
     const size_t n_slots = (size_t)p->n_new_kf + p->n_new_mp + p->n_upd_kf + p->n_upd_mp;
-    rc = grow_dev(h->scr, h->scr_cap, n_slots * 4); if (rc) return rc;
-    rc = grow_host(h->host, h->host_cap, al16(n_slots * 4) + E.size() * sizeof(CorbPublishTransform)); if (rc) return rc;
+    rc = grow(h->scr, n_slots * 4); if (rc) return rc;
+    rc = grow(h->host, al16(n_slots * 4) + E.size() * sizeof(CorbPublishTransform)); if (rc) return rc;
     call.hold(nullptr, p->kf, nullptr, p->mp);                            // (the handle is the caller's to lock)
     for (int pass = 0; pass < 2; pass++) {
         const int32_t* s = pass ? p->upd_kf_slots : p->new_kf_slots; const int n = pass ? p->n_upd_kf : p->n_new_kf;
         for (int i = 0; i < n; i++) if (record_slot_count(who, p->kf, s[i]) < 0) return CORB_ERR_ARG;
     }
-    if ((size_t)off[5] > h->msg_cap) { h->msg_bytes = 0; memset(h->counts, 0, sizeof(h->counts)); }      // (the last refusal is behind: a buffer that grows drops the message it held)
-    return grow_dev(h->msg, h->msg_cap, (size_t)off[5]);
+    if ((size_t)off[5] > h->msg.cap()) { h->msg_bytes = 0; memset(h->counts, 0, sizeof(h->counts)); }      // (the last refusal is behind: a buffer that grows drops the message it held)
+    return grow(h->msg, (size_t)off[5]);
 }
 // the pack itself, under the locks pack_check took; ends with the handle's one synchronisation
 int pack_run(CorbMapPublisher* h, const CorbPublishPack* p, const RecordCall& call, const std::vector<CorbPublishTransform>& E, const int32_t* counts, const int64_t* off)
 {
     h->msg_bytes = 0; memset(h->counts, 0, sizeof(h->counts));            // (a pack that fails from here on leaves no message)
     int rc = call.join(); if (rc) return rc;
-    int32_t* hs = reinterpret_cast<int32_t*>(h->host); int* ds = reinterpret_cast<int*>(h->scr);
+    int32_t* hs = h->host.as<int32_t>(); int* ds = h->scr.as<int>();
     const int n[4] = {p->n_new_kf, p->n_new_mp, p->n_upd_kf, p->n_upd_mp};
     const int32_t* lists[4] = {p->new_kf_slots, p->new_mp_slots, p->upd_kf_slots, p->upd_mp_slots};
     size_t at[4], total = 0;
     for (int k = 0; k < 4; k++) { at[k] = total; if (n[k]) memcpy(hs + total, lists[k], (size_t)n[k] * 4); total += (size_t)n[k]; }
     if (total) HIPCHK(hipMemcpyAsync(ds, hs, total * 4, hipMemcpyHostToDevice, h->stream));
     if (!E.empty()) {
-        char* he = h->host + al16(total * 4);
+        char* he = h->host.as<char>() + al16(total * 4);
         memcpy(he, E.data(), E.size() * sizeof(CorbPublishTransform));
-        HIPCHK(hipMemcpyAsync(h->msg + off[4], he, E.size() * sizeof(CorbPublishTransform), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(hipMemcpyAsync(h->msg.as<char>() + off[4], he, E.size() * sizeof(CorbPublishTransform), hipMemcpyHostToDevice, h->stream));
     }
     // the few bytes between a section's end and the next multiple of 16 travel too: zero
     const int64_t end[5] = {off[0] + (int64_t)n[0] * (p->kf ? (int64_t)p->kf->L.bytes : 0), off[1] + (int64_t)n[1] * (p->mp ? (int64_t)p->mp->L.bytes : 0),
                             off[2] + (int64_t)n[2] * (int64_t)sizeof(CorbKeyFramePosePacket), off[3] + (int64_t)n[3] * (int64_t)sizeof(CorbMapPointPosePacket),
                             off[4] + (int64_t)E.size() * (int64_t)sizeof(CorbPublishTransform)};
-    for (int k = 0; k < 5; k++) if (off[k + 1] > end[k]) HIPCHK(hipMemsetAsync(h->msg + end[k], 0, (size_t)(off[k + 1] - end[k]), h->stream));
-    if (n[0]) corb_launch_gather_records(p->kf->base, p->kf->L.bytes, ds + at[0], n[0], h->msg + off[0], h->stream);
-    if (n[1]) corb_launch_gather_records(p->mp->base, p->mp->L.bytes, ds + at[1], n[1], h->msg + off[1], h->stream);
+    for (int k = 0; k < 5; k++) if (off[k + 1] > end[k]) HIPCHK(hipMemsetAsync(h->msg.as<char>() + end[k], 0, (size_t)(off[k + 1] - end[k]), h->stream));
+    if (n[0]) corb_launch_gather_records(p->kf->base(), p->kf->L.bytes, ds + at[0], n[0], h->msg.as<char>() + off[0], h->stream);
+    if (n[1]) corb_launch_gather_records(p->mp->base(), p->mp->L.bytes, ds + at[1], n[1], h->msg.as<char>() + off[1], h->stream);
     PubPackDev d; memset(&d, 0, sizeof(d));
-    if (p->kf) { d.kf_base = p->kf->base; d.kf_bytes = p->kf->L.bytes; }
-    if (p->mp) { d.mp_base = p->mp->base; d.mp_bytes = p->mp->L.bytes; }
-    d.upd_kf = ds + at[2]; d.n_upd_kf = n[2]; d.upd_mp = ds + at[3]; d.n_upd_mp = n[3]; d.sec_c = h->msg + off[2]; d.sec_d = h->msg + off[3];
+    if (p->kf) { d.kf_base = p->kf->base(); d.kf_bytes = p->kf->L.bytes; }
+    if (p->mp) { d.mp_base = p->mp->base(); d.mp_bytes = p->mp->L.bytes; }
+    d.upd_kf = ds + at[2]; d.n_upd_kf = n[2]; d.upd_mp = ds + at[3]; d.n_upd_mp = n[3]; d.sec_c = h->msg.as<char>() + off[2]; d.sec_d = h->msg.as<char>() + off[3];
     pub_launch_pack_poses(d, h->stream);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(h->stream));
@@ -177,59 +158,58 @@ int apply_core(const char* who, CorbMapPublisher* h, const char* msg, const int3
     size_t ints = 0; auto take = [&](size_t n) { const size_t at = ints; ints += (n + 3) & ~(size_t)3; return at; };
     const size_t i_ra = take(nA), i_pa = take(nA), i_rb = take(nB), i_pb = take(nB), i_tc = take(nC), i_td = take(nD), i_ca = take(wa), i_oa = take((size_t)wa + 1), i_sa = take(sa),
                  i_cb = take(wb), i_ob = take((size_t)wb + 1), i_sb = take(sb);
-    rc = grow_dev(h->out, h->out_cap, out_bytes); if (rc) return rc;
-    rc = grow_host(h->host, h->host_cap, out_bytes); if (rc) return rc;
-    rc = grow_dev(h->scr, h->scr_cap, ints * 4); if (rc) return rc;
-    if ((rc = table_room(h->kfid, kf ? a->kf_n : 0)) || (rc = table_room(h->first[0], nA)) || (rc = table_room(h->first[1], nB)) || (rc = table_room(h->last[0], nC)) || (rc = table_room(h->last[1], nD))) return rc;
+    rc = grow(h->out, out_bytes); if (rc) return rc;
+    rc = grow(h->host, out_bytes); if (rc) return rc;
+    rc = grow(h->scr, ints * 4); if (rc) return rc;
+    HIPCHK(h->kfid.room(kf ? a->kf_n : 0)); HIPCHK(h->first[0].room(nA)); HIPCHK(h->first[1].room(nB)); HIPCHK(h->last[0].room(nC)); HIPCHK(h->last[1].room(nD));
     // the map's index after the call: in place if the table has room for the new ids too, else a larger table that replaces it once the call has succeeded
-    CorbIdTable grown{nullptr, nullptr, 0};
-    if (a->apply && ub > 0 && id_table_capacity((long long)a->mp_n + ub) > (size_t)mp->idt.mask + 1) { rc = id_table_own(grown, id_table_capacity((long long)a->mp_n + ub), 256); if (rc) return rc; }
-    struct Drop { CorbIdTable& t; ~Drop() { if (t.keys) (void)hipFree(t.keys); } } drop{grown};      // (whatever `grown` still holds at the end is not the map's)
+    OwnedIdTable grown;                                                   // (whatever it still holds at the end is not the map's)
+    if (a->apply && ub > 0 && id_table_capacity((long long)a->mp_n + ub) > (size_t)mp->idt.mask + 1) HIPCHK(grown.own(id_table_capacity((long long)a->mp_n + ub), 256));
 
     rc = call.join(); if (rc) return rc;
-    HIPCHK(hipMemsetAsync(h->out, 0, sizeof(PubState), h->stream));
+    HIPCHK(hipMemsetAsync(h->out.as<char>(), 0, sizeof(PubState), h->stream));
     rc = id_table_clear(h->kfid, true, h->stream); if (rc) return rc;
     for (int k = 0; k < 2; k++) { if ((rc = id_table_clear(h->first[k], true, h->stream)) || (rc = id_table_clear(h->last[k], true, h->stream))) return rc; }
-    if (kf && a->kf_n > 0) corb_launch_kf_index(kf->base, kf->L.bytes, a->kf_first, a->kf_n, h->kfid, h->stream);
+    if (kf && a->kf_n > 0) corb_launch_kf_index(kf->base(), kf->L.bytes, a->kf_first, a->kf_n, h->kfid, h->stream);
 
-    int* S = reinterpret_cast<int*>(h->scr);
+    int* S = h->scr.as<int>();
     PubApplyDev d; memset(&d, 0, sizeof(d));
-    d.st = reinterpret_cast<PubState*>(h->out);
+    d.st = h->out.as<PubState>();
     d.sec_e = reinterpret_cast<const CorbPublishTransform*>(msg + off[4]); d.n_trans = counts[4]; d.client_id = a->client_id; d.apply = a->apply ? 1 : 0;
     PubSide& K = d.s[0]; PubSide& M = d.s[1];
     K.sec_new = msg + off[0]; K.n_new = nA; K.rec_bytes = kf ? kf->L.bytes : 0; K.sec_upd = msg + off[2]; K.n_upd = nC;
-    K.base = kf ? kf->base : nullptr; K.capacity = kf ? kf->capacity : 0; K.free_first = kf ? a->kf_free_first : 0; K.room = kf_room;
+    K.base = kf ? kf->base() : nullptr; K.capacity = kf ? kf->capacity : 0; K.free_first = kf ? a->kf_free_first : 0; K.room = kf_room;
     K.held = h->kfid; K.first = h->first[0]; K.last = h->last[0];
-    K.kind_new = reinterpret_cast<unsigned char*>(h->out + o_ka); K.kind_upd = reinterpret_cast<unsigned char*>(h->out + o_kc); K.new_slots = reinterpret_cast<int*>(h->out + o_sa);
+    K.kind_new = reinterpret_cast<unsigned char*>(h->out.as<char>() + o_ka); K.kind_upd = reinterpret_cast<unsigned char*>(h->out.as<char>() + o_kc); K.new_slots = reinterpret_cast<int*>(h->out.as<char>() + o_sa);
     K.rank = S + i_ra; K.src = S + i_pa; K.target = S + i_tc; K.wg_cnt = S + i_ca; K.wg_off = S + i_oa; K.scan_scratch = S + i_sa;
     M.sec_new = msg + off[1]; M.n_new = nB; M.rec_bytes = mp ? mp->L.bytes : 0; M.sec_upd = msg + off[3]; M.n_upd = nD;
-    M.base = mp ? mp->base : nullptr; M.capacity = mp ? mp->capacity : 0; M.free_first = mp ? a->mp_free_first : 0; M.room = mp_room;
+    M.base = mp ? mp->base() : nullptr; M.capacity = mp ? mp->capacity : 0; M.free_first = mp ? a->mp_free_first : 0; M.room = mp_room;
     M.held = (nB || nD) ? mp->idt : h->last[1] /* (never probed) */; M.first = h->first[1]; M.last = h->last[1];
-    M.kind_new = reinterpret_cast<unsigned char*>(h->out + o_kb); M.kind_upd = reinterpret_cast<unsigned char*>(h->out + o_kd); M.new_slots = reinterpret_cast<int*>(h->out + o_sb);
+    M.kind_new = reinterpret_cast<unsigned char*>(h->out.as<char>() + o_kb); M.kind_upd = reinterpret_cast<unsigned char*>(h->out.as<char>() + o_kd); M.new_slots = reinterpret_cast<int*>(h->out.as<char>() + o_sb);
     M.rank = S + i_rb; M.src = S + i_pb; M.target = S + i_td; M.wg_cnt = S + i_cb; M.wg_off = S + i_ob; M.scan_scratch = S + i_sb;
-    d.kf_hdr = reinterpret_cast<int*>(h->out + o_hdr);
-    d.mp_first = a->mp_first; d.mp_n = a->mp_n; d.new_index = grown.keys ? grown : (mp ? mp->idt : grown);
+    d.kf_hdr = reinterpret_cast<int*>(h->out.as<char>() + o_hdr);
+    d.mp_first = a->mp_first; d.mp_n = a->mp_n; d.new_index = (grown.keys || !mp) ? grown : mp->idt;
     pub_launch_apply(d, h->stream);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(h->host, h->out, out_bytes, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(h->host.as<char>(), h->out.as<char>(), out_bytes, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
 
-    const PubState* st = reinterpret_cast<const PubState*>(h->host);
+    const PubState* st = h->host.as<const PubState>();
     const int ins_a = std::min(std::max(st->n_ins[0], 0), nA), ins_b = std::min(std::max(st->n_ins[1], 0), nB);
     out->n_kf_inserted = ins_a; out->n_mp_inserted = ins_b; out->n_kf_updated = st->n_upd[0]; out->n_mp_updated = st->n_upd[1]; out->no_transform = st->found ? 0 : 1;
-    if (out->kind_kf_new) memcpy(out->kind_kf_new, h->host + o_ka, (size_t)nA);
-    if (out->kind_mp_new) memcpy(out->kind_mp_new, h->host + o_kb, (size_t)nB);
-    if (out->kind_kf_upd) memcpy(out->kind_kf_upd, h->host + o_kc, (size_t)nC);
-    if (out->kind_mp_upd) memcpy(out->kind_mp_upd, h->host + o_kd, (size_t)nD);
-    if (out->kf_new_slots) memcpy(out->kf_new_slots, h->host + o_sa, (size_t)std::min(ins_a, ua) * 4);
-    if (out->mp_new_slots) memcpy(out->mp_new_slots, h->host + o_sb, (size_t)std::min(ins_b, ub) * 4);
+    if (out->kind_kf_new) memcpy(out->kind_kf_new, h->host.as<char>() + o_ka, (size_t)nA);
+    if (out->kind_mp_new) memcpy(out->kind_mp_new, h->host.as<char>() + o_kb, (size_t)nB);
+    if (out->kind_kf_upd) memcpy(out->kind_kf_upd, h->host.as<char>() + o_kc, (size_t)nC);
+    if (out->kind_mp_upd) memcpy(out->kind_mp_upd, h->host.as<char>() + o_kd, (size_t)nD);
+    if (out->kf_new_slots) memcpy(out->kf_new_slots, h->host.as<char>() + o_sa, (size_t)std::min(ins_a, ua) * 4);
+    if (out->mp_new_slots) memcpy(out->mp_new_slots, h->host.as<char>() + o_sb, (size_t)std::min(ins_b, ub) * 4);
     if (st->overflow) {
         corb_set_error("%s: %d new keyframes for %d free slots, %d new map points for %d; nothing was written", who, ins_a, kf_room, ins_b, mp_room);
         return CORB_ERR_CAPACITY;
     }
     if (!st->go) return CORB_OK;
     // the host's mirror of the slots the keyframes went to
-    const int* hdr = reinterpret_cast<const int*>(h->host + o_hdr);
+    const int* hdr = reinterpret_cast<const int*>(h->host.as<char>() + o_hdr);
     for (int k = 0; k < ins_a; k++) {
         CorbKfStore::Host& m = kf->host[a->kf_free_first + k];
         const int n = hdr[4 * k], nodes = hdr[4 * k + 1];
@@ -238,7 +218,7 @@ int apply_core(const char* who, CorbMapPublisher* h, const char* msg, const int3
         m.header_valid = sane && nodes == 0;                              // (a FeatureVector's node ids are fetched by the first call that needs them)
     }
     if (ins_b > 0) {
-        if (grown.keys) { (void)hipFree(mp->idt.keys); mp->idt = grown; grown.keys = nullptr; }
+        if (grown.keys) mp->idt = std::move(grown);
         mp->idt_first = a->mp_first; mp->idt_n = a->mp_n + ins_b; mp->idt_valid = !st->dup;
         if (st->dup) { corb_set_error("%s: the map holds one id twice after the insertion", who); return CORB_ERR_ARG; }
     }
@@ -252,23 +232,12 @@ extern "C" int corb_pub_create(int device, CorbMapPublisher** out)
     *out = nullptr;
     int rc = corb_select_device(device); if (rc) return rc;
     CorbMapPublisher* h = new CorbMapPublisher; h->device = device;
-    if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) { corb_set_error("corb_pub_create: stream creation failed"); delete h; return CORB_ERR_HIP; }
+    if (h->stream.create() != hipSuccess) { corb_set_error("corb_pub_create: stream creation failed"); delete h; return CORB_ERR_HIP; }
     *out = h;
     return CORB_OK;
 }
 
-extern "C" void corb_pub_destroy(CorbMapPublisher* h)
-{
-    if (!h) return;
-    if (corb_select_device(h->device) == CORB_OK) {
-        if (h->stream) (void)hipStreamSynchronize(h->stream);
-        for (char* b : {h->msg, h->recv, h->out, h->scr}) if (b) (void)hipFree(b);
-        if (h->host) (void)hipHostFree(h->host);
-        for (CorbIdTable* t : {&h->kfid, &h->first[0], &h->first[1], &h->last[0], &h->last[1]}) if (t->keys) (void)hipFree(t->keys);
-        if (h->stream) (void)hipStreamDestroy(h->stream);
-    }
-    delete h;
-}
+extern "C" void corb_pub_destroy(CorbMapPublisher* h) { handle_destroy(h); }
 
 extern "C" int corb_pub_message_layout(const int32_t counts[5], int kf_record_bytes, int mp_record_bytes, int64_t offsets[6])
 {
@@ -293,7 +262,7 @@ extern "C" int corb_pub_message(CorbMapPublisher* h, void** device_ptr, int64_t*
 {
     if (!h) { corb_set_error("corb_pub_message: bad argument"); return CORB_ERR_ARG; }
     std::lock_guard<std::mutex> lk(h->mu);
-    if (device_ptr) *device_ptr = h->msg_bytes ? h->msg : nullptr;
+    if (device_ptr) *device_ptr = h->msg_bytes ? h->msg.as<char>() : nullptr;
     if (bytes) *bytes = h->msg_bytes;
     if (counts) memcpy(counts, h->counts, sizeof(h->counts));
     if (kf_record_bytes) *kf_record_bytes = h->kf_bytes;
@@ -308,7 +277,7 @@ extern "C" int corb_pub_message_read(CorbMapPublisher* h, void* host, int64_t ca
     if (cap < h->msg_bytes) { corb_set_error("corb_pub_message_read: the message has %lld bytes", (long long)h->msg_bytes); return CORB_ERR_CAPACITY; }
     if (h->msg_bytes == 0) return CORB_OK;
     int rc = corb_select_device(h->device); if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(host, h->msg, (size_t)h->msg_bytes, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(host, h->msg.as<char>(), (size_t)h->msg_bytes, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     return CORB_OK;
 }
@@ -413,15 +382,15 @@ extern "C" int corb_map_publish(CorbComm* c, CorbMapPublisher* h, int root, cons
     if (is_root) {
         note(pack_run(h, pack, call, E, R.counts, off));   // (into the buffer pack_check reserved: the announced size is there whatever happens)
         call.locks = RecordLocks();                        // packed and waited for: no store lock is held across the transport's barriers
-        for (int r = 0; r < W; r++) if (r != root) sends.push_back({h->msg, (size_t)off[5], r});
+        for (int r = 0; r < W; r++) if (r != root) sends.push_back({h->msg.as<char>(), (size_t)off[5], r});
     } else {
-        note(grow_dev(h->recv, h->recv_cap, (size_t)off[5]));
+        note(grow(h->recv, (size_t)off[5]));
         // (a rank that cannot allocate its receive buffer posts no receive: the in-process transport copies nothing for it; over RCCL the job is lost, as with
         // any rank that runs out of device memory inside a collective)
-        if (h->recv_cap >= (size_t)off[5]) recvs.push_back({h->recv, (size_t)off[5], root});
+        if (h->recv.cap() >= (size_t)off[5]) recvs.push_back({h->recv.as<char>(), (size_t)off[5], root});
     }
     if (W > 1) note(c->exchange(sends, recvs, true));
     if (rc_first != CORB_OK || is_root) return rc_first;
     // ---- 4. every receiver files the message in its own stores; its status is its own ----
-    return apply_core(who, h, h->recv, R.counts, R.kf_record_bytes, R.mp_record_bytes, apply_args);
+    return apply_core(who, h, h->recv.as<char>(), R.counts, R.kf_record_bytes, R.mp_record_bytes, apply_args);
 }

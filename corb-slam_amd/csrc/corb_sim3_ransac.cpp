@@ -174,7 +174,7 @@ extern "C" int corb_sim3_ransac_store(CorbKfStore* kf, int slot1, const int32_t*
     d.n_cand = n_candidates; d.cap = n1; d.max_its = max_iterations; d.min_inliers = min_inliers; d.fix_scale = a.fix_scale;
     d.kf1 = kf->rec(slot1); d.F = kf->F; d.nlevels1 = cam1->nlevels;
     for (int l = 0; l < CORB_MAX_LEVELS; l++) d.scale1[l] = l < cam1->nlevels ? cam1->scale[l] : 1.f;
-    d.mp_base = map->base; d.mp_bytes = map->L.bytes; d.max_obs = map->O; d.idt = map->idt;
+    d.mp_base = map->base(); d.mp_bytes = map->L.bytes; d.max_obs = map->O; d.idt = map->idt;
     HIPCHK(pool.upload_block({{(void**)&d.cand, cand.data(), cand.size() * sizeof(S3rCand)}, {(void**)&d.matched12, matched12_ids, (size_t)n_candidates * n1 * 8},
                               {(void**)&d.rand_values, rand_values, (size_t)n_candidates * max_iterations * 12}}));
     static thread_local std::vector<S3rHyp> h_hyp; static thread_local std::vector<unsigned long long> h_mask; std::vector<int> h_n, h_index1;

@@ -6,6 +6,7 @@
 #include "match_internal.h"
 #include "store_internal.h"
 #include "record_call.h"
+#include "owned_hip.h"
 #include <dlfcn.h>
 #include <string>
 #include <algorithm>
@@ -20,26 +21,16 @@ extern "C" int corb_kf_store_create(int device, int capacity, int max_features, 
     int rc = corb_select_device(device); if (rc) return rc;
     CorbKfStore* s = new CorbKfStore();
     s->device = device; s->capacity = capacity; s->F = max_features; s->L = RecLayout(max_features); s->host.resize(capacity);
-    if (hipMalloc((void**)&s->base, (size_t)capacity * s->L.bytes) != hipSuccess || hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking) != hipSuccess ||
-        hipEventCreateWithFlags(&s->ev, hipEventDisableTiming) != hipSuccess) {
+    if (s->mem.room((size_t)capacity * s->L.bytes) != hipSuccess || s->stream.create() != hipSuccess || s->ev.create(hipEventDisableTiming) != hipSuccess) {
         corb_set_error("corb_kf_store_create: %d keyframes x %zu bytes: allocation failed", capacity, s->L.bytes);
-        if (s->base) (void)hipFree(s->base);
         delete s; return CORB_ERR_HIP;
     }
-    (void)hipMemsetAsync(s->base, 0, (size_t)capacity * s->L.bytes, s->stream);
+    (void)hipMemsetAsync(s->base(), 0, (size_t)capacity * s->L.bytes, s->stream);
     (void)hipStreamSynchronize(s->stream);
     *out = s;
     return CORB_OK;
 }
-extern "C" void corb_kf_store_destroy(CorbKfStore* s)
-{
-    if (!s) return;
-    (void)hipSetDevice(s->device);
-    if (s->stream) { (void)hipStreamSynchronize(s->stream); (void)hipStreamDestroy(s->stream); }
-    if (s->ev) (void)hipEventDestroy(s->ev);
-    if (s->base) (void)hipFree(s->base);
-    delete s;
-}
+extern "C" void corb_kf_store_destroy(CorbKfStore* s) { handle_destroy(s); }
 extern "C" int corb_kf_store_record_bytes(const CorbKfStore* s) { return s ? (int)s->L.bytes : 0; }
 
 static int slot_ok(CorbKfStore* s, int slot, const char* who)
@@ -361,16 +352,15 @@ extern "C" int corb_kf_store_put_batch(CorbKfStore* s, int first, int n, const C
     auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
     const size_t b_meta = (size_t)n * sizeof(CorbKeyFrameMeta), b_off = ((size_t)n + 1) * 4, b_kp = total * 28, b_desc = desc ? total * 32 : 0, b_ur = u_right ? total * 4 : 0,
                  b_dp = depth ? total * 4 : 0, b_id = mp_id ? total * 8 : 0;
-    char* stage = nullptr;
-    HIPCHK(hipMalloc((void**)&stage, al(b_meta) + al(b_off) + al(b_kp) + al(b_desc) + al(b_ur) + al(b_dp) + al(b_id) + 256));
-    struct Guard { char* p; ~Guard() { (void)hipFree(p); } } guard{stage};
+    DevMem staging; HIPCHK(staging.room(al(b_meta) + al(b_off) + al(b_kp) + al(b_desc) + al(b_ur) + al(b_dp) + al(b_id) + 256));
+    char* stage = staging.as<char>();
     size_t o = 0;
     auto put = [&](const void* src, size_t bytes) -> char* { char* d = stage + o; o += al(bytes); if (bytes && hipMemcpyAsync(d, src, bytes, hipMemcpyHostToDevice, s->stream) != hipSuccess) return nullptr; return bytes ? d : nullptr; };
     char* dmeta = put(meta, b_meta); char* doff = put(feat_offset, b_off); char* dkp = put(kp, b_kp); char* ddesc = put(desc, b_desc);
     char* dur = put(u_right, b_ur); char* ddp = put(depth, b_dp); char* did = put(mp_id, b_id);
     if (!dmeta || !doff || (total && !dkp)) { corb_set_error("corb_kf_store_put_batch: upload failed"); return CORB_ERR_HIP; }
     corb_launch_kf_pack_batch((const CorbKeyFrameMeta*)dmeta, (const int*)doff, (const CorbKeyPoint*)dkp, (const uint8_t*)ddesc, (const float*)dur, (const float*)ddp,
-                              (const unsigned long long*)did, n, s->base, first, s->F, s->stream);
+                              (const unsigned long long*)did, n, s->base(), first, s->F, s->stream);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(s->stream));
     for (int i = 0; i < n; i++) { CorbKfStore::Host& h = s->host[first + i]; h.n = feat_offset[i + 1] - feat_offset[i]; h.n_nodes = 0; h.id = meta[i].id; h.node_id.clear(); h.header_valid = true; }
@@ -385,29 +375,17 @@ extern "C" int corb_mp_store_create(int device, int capacity, int max_obs, CorbM
     int rc = corb_select_device(device); if (rc) return rc;
     CorbMpStore* s = new CorbMpStore();
     s->device = device; s->capacity = capacity; s->O = max_obs; s->L = MpLayout(max_obs);
-    if (hipMalloc((void**)&s->base, (size_t)capacity * s->L.bytes) != hipSuccess || hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking) != hipSuccess) {
+    if (s->mem.room((size_t)capacity * s->L.bytes) != hipSuccess || s->stream.create() != hipSuccess) {
         corb_set_error("corb_mp_store_create: %d map points x %zu bytes: allocation failed", capacity, s->L.bytes);
-        if (s->base) (void)hipFree(s->base);
         delete s; return CORB_ERR_HIP;
     }
     // an empty slot reads as a bad map point without observations
-    (void)hipMemsetAsync(s->base, 0, (size_t)capacity * s->L.bytes, s->stream);
+    (void)hipMemsetAsync(s->base(), 0, (size_t)capacity * s->L.bytes, s->stream);
     (void)hipStreamSynchronize(s->stream);
     *out = s;
     return CORB_OK;
 }
-extern "C" void corb_mp_store_destroy(CorbMpStore* s)
-{
-    if (!s) return;
-    (void)hipSetDevice(s->device);
-    if (s->stream) { (void)hipStreamSynchronize(s->stream); (void)hipStreamDestroy(s->stream); }
-    if (s->base) (void)hipFree(s->base);
-    if (s->idt.keys) (void)hipFree(s->idt.keys);
-    if (s->lba_dev) (void)hipFree(s->lba_dev);
-    if (s->lba_host) (void)hipHostFree(s->lba_host);
-    if (s->lba_event) (void)hipEventDestroy(s->lba_event);
-    delete s;
-}
+extern "C" void corb_mp_store_destroy(CorbMpStore* s) { handle_destroy(s); }
 extern "C" int corb_mp_store_record_bytes(const CorbMpStore* s) { return s ? (int)s->L.bytes : 0; }
 
 static int mp_range_ok(CorbMpStore* s, int first, int n, const char* who)
@@ -432,9 +410,8 @@ extern "C" int corb_mp_store_put_host(CorbMpStore* s, int first, int n, const Co
     // staging memory of this call (a batch can be gigabytes: not taken from the per-device arena, which never shrinks)
     const size_t b_hdr = (size_t)n * sizeof(CorbMapPointRecord), b_off = ((size_t)n + 1) * 4, b_kf = total * 8, b_idx = total * 4;
     auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    char* stage = nullptr;
-    HIPCHK(hipMalloc((void**)&stage, al(b_hdr) + al(b_off) + al(b_kf) + al(b_idx) + 256));
-    struct Guard { char* p; ~Guard() { (void)hipFree(p); } } guard{stage};
+    DevMem staging; HIPCHK(staging.room(al(b_hdr) + al(b_off) + al(b_kf) + al(b_idx) + 256));
+    char* stage = staging.as<char>();
     CorbMapPointRecord* dh = (CorbMapPointRecord*)stage; int* doff = (int*)(stage + al(b_hdr));
     unsigned long long* dkf = (unsigned long long*)(stage + al(b_hdr) + al(b_off)); uint32_t* didx = (uint32_t*)(stage + al(b_hdr) + al(b_off) + al(b_kf));
     int* dstat = (int*)(stage + al(b_hdr) + al(b_off) + al(b_kf) + al(b_idx));
@@ -443,7 +420,7 @@ extern "C" int corb_mp_store_put_host(CorbMpStore* s, int first, int n, const Co
     if (total) { HIPCHK(hipMemcpyAsync(dkf, obs_kf_id, b_kf, hipMemcpyHostToDevice, s->stream)); HIPCHK(hipMemcpyAsync(didx, obs_feature_idx, b_idx, hipMemcpyHostToDevice, s->stream)); }
     HIPCHK(hipMemsetAsync(dstat, 0, 4, s->stream));
     s->idt_valid = false;                                   // the slots may hold other ids now: corb_mp_store_build_index again before the tracking calls
-    corb_launch_mp_pack(dh, doff, dkf, didx, n, s->base, first, s->O, dstat, s->stream);
+    corb_launch_mp_pack(dh, doff, dkf, didx, n, s->base(), first, s->O, dstat, s->stream);
     HIPCHK(hipGetLastError());
     int hstat = 0;                                          // the kernel's own range check (the offsets were validated above: it fires only if the caller's arrays changed under the call)
     HIPCHK(hipMemcpyAsync(&hstat, dstat, sizeof(int), hipMemcpyDeviceToHost, s->stream));
@@ -460,12 +437,11 @@ extern "C" int corb_mp_store_get(CorbMpStore* s, int first, int n, CorbMapPointR
     std::lock_guard<std::mutex> lk(s->mu);
     const size_t b_hdr = (size_t)n * sizeof(CorbMapPointRecord), b_kf = obs_kf_id ? (size_t)n * s->O * 8 : 0, b_idx = obs_feature_idx ? (size_t)n * s->O * 4 : 0;
     auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    char* stage = nullptr;
-    HIPCHK(hipMalloc((void**)&stage, al(b_hdr) + al(b_kf) + al(b_idx) + 256));
-    struct Guard { char* p; ~Guard() { (void)hipFree(p); } } guard{stage};
+    DevMem staging; HIPCHK(staging.room(al(b_hdr) + al(b_kf) + al(b_idx) + 256));
+    char* stage = staging.as<char>();
     CorbMapPointRecord* dh = (CorbMapPointRecord*)stage;
     unsigned long long* dkf = obs_kf_id ? (unsigned long long*)(stage + al(b_hdr)) : nullptr; uint32_t* didx = obs_feature_idx ? (uint32_t*)(stage + al(b_hdr) + al(b_kf)) : nullptr;
-    corb_launch_mp_unpack(s->base, first, n, s->O, dh, dkf, didx, s->stream);
+    corb_launch_mp_unpack(s->base(), first, n, s->O, dh, dkf, didx, s->stream);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(records, dh, b_hdr, hipMemcpyDeviceToHost, s->stream));
     if (dkf) HIPCHK(hipMemcpyAsync(obs_kf_id, dkf, b_kf, hipMemcpyDeviceToHost, s->stream));
@@ -491,7 +467,7 @@ extern "C" int corb_rebase_map_store(const float* To2n, CorbKfStore* kf, const i
     CorbScratch pool(0);
     float* dT; int *dks, *dms;
     HIPCHK(pool.upload_block({{(void**)&dT, To2n, 64}, {(void**)&dks, kf_slots, (size_t)n_kf * 4}, {(void**)&dms, mp_slots, (size_t)n_mp * 4}}));
-    corb_launch_rebase_records(dT, kf ? kf->base : nullptr, kf ? kf->L.bytes : 0, dks, n_kf, mp ? mp->base : nullptr, mp ? mp->L.bytes : 0, dms, n_mp, pool.stream);
+    corb_launch_rebase_records(dT, kf ? kf->base() : nullptr, kf ? kf->L.bytes : 0, dks, n_kf, mp ? mp->base() : nullptr, mp ? mp->L.bytes : 0, dms, n_mp, pool.stream);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(pool.stream));
     return CORB_OK;
@@ -510,11 +486,10 @@ static int mp_counters(CorbMpStore* s, int first, int n, CorbMapPointCounters* h
     if (!host) { corb_set_error("%s: NULL array", who); return CORB_ERR_ARG; }
     rc = corb_select_device(s->device); if (rc) return rc;
     std::lock_guard<std::mutex> lk(s->mu);
-    CorbMapPointCounters* d = nullptr;
-    HIPCHK(hipMalloc((void**)&d, (size_t)n * sizeof(CorbMapPointCounters) + 256));
-    struct Guard { void* p; ~Guard() { (void)hipFree(p); } } guard{d};
+    DevMem staging; HIPCHK(staging.room((size_t)n * sizeof(CorbMapPointCounters) + 256));
+    CorbMapPointCounters* d = staging.as<CorbMapPointCounters>();
     if (set) HIPCHK(hipMemcpyAsync(d, host, (size_t)n * sizeof(CorbMapPointCounters), hipMemcpyHostToDevice, s->stream));
-    corb_launch_mp_counters(s->base, s->L.bytes, first, n, d, set, s->stream);
+    corb_launch_mp_counters(s->base(), s->L.bytes, first, n, d, set, s->stream);
     HIPCHK(hipGetLastError());
     if (!set) HIPCHK(hipMemcpyAsync(host, d, (size_t)n * sizeof(CorbMapPointCounters), hipMemcpyDeviceToHost, s->stream));
     HIPCHK(hipStreamSynchronize(s->stream));
@@ -528,11 +503,10 @@ static int mp_scratch(CorbMpStore* s, int first, int n, CorbMapPointScratch* hos
     if (!host) { corb_set_error("%s: NULL array", who); return CORB_ERR_ARG; }
     rc = corb_select_device(s->device); if (rc) return rc;
     std::lock_guard<std::mutex> lk(s->mu);
-    char* d = nullptr;
-    HIPCHK(hipMalloc((void**)&d, (size_t)n * sizeof(CorbMapPointScratch) + 256));
-    struct Guard { void* p; ~Guard() { (void)hipFree(p); } } guard{d};
+    DevMem staging; HIPCHK(staging.room((size_t)n * sizeof(CorbMapPointScratch) + 256));
+    char* d = staging.as<char>();
     if (set) HIPCHK(hipMemcpyAsync(d, host, (size_t)n * sizeof(CorbMapPointScratch), hipMemcpyHostToDevice, s->stream));
-    corb_launch_mp_scratch(s->base, s->L.bytes, s->L.scratch, first, n, d, set, s->stream);
+    corb_launch_mp_scratch(s->base(), s->L.bytes, s->L.scratch, first, n, d, set, s->stream);
     HIPCHK(hipGetLastError());
     if (!set) HIPCHK(hipMemcpyAsync(host, d, (size_t)n * sizeof(CorbMapPointScratch), hipMemcpyDeviceToHost, s->stream));
     HIPCHK(hipStreamSynchronize(s->stream));
@@ -560,7 +534,7 @@ extern "C" int corb_mp_store_replace(CorbMpStore* map, int slot_this, int slot_i
     unsigned long long* desc = nullptr; int* dst = nullptr;
     HIPCHK(pool.alloc(&desc, (size_t)map->O * 4)); HIPCHK(pool.alloc(&dst, 1));
     HIPCHK(hipMemsetAsync(dst, 0, 4, pool.stream));
-    corb_launch_mp_replace(map->base, map->L.bytes, map->O, slot_this, slot_into, kf->base, kf->L.bytes, kf->F, kf_first, kf_n, kfid, desc, dst, pool.stream);
+    corb_launch_mp_replace(map->base(), map->L.bytes, map->O, slot_this, slot_into, kf->base(), kf->L.bytes, kf->F, kf_first, kf_n, kfid, desc, dst, pool.stream);
     HIPCHK(hipGetLastError());
     int* res = static_cast<int*>(pool.pinned());
     HIPCHK(hipMemcpyAsync(res, dst, 4, hipMemcpyDeviceToHost, pool.stream));

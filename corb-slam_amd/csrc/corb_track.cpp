@@ -54,11 +54,11 @@ extern "C" int corb_mp_store_build_index(CorbMpStore* s, int first, int n)
     int rc = corb_select_device(s->device); if (rc) return rc;
     std::lock_guard<std::mutex> lk(s->mu);
     const size_t cap = id_table_capacity(n);
-    if (!s->idt.keys || (size_t)s->idt.mask + 1 != cap) { rc = id_table_own(s->idt, cap, 256); if (rc) return rc; }         // (the tail: the duplicate flag)
+    if (!s->idt.keys || (size_t)s->idt.mask + 1 != cap) HIPCHK(s->idt.own(cap, 256));        // (the tail: the duplicate flag)
     int* dup = reinterpret_cast<int*>(reinterpret_cast<char*>(s->idt.keys) + cap * 12);
     rc = id_table_clear(s->idt, false, s->stream); if (rc) return rc;
     HIPCHK(hipMemsetAsync(dup, 0, 4, s->stream));
-    track_launch_index_store(s->base, s->L.bytes, first, n, s->idt, dup, s->stream);
+    track_launch_index_store(s->base(), s->L.bytes, first, n, s->idt, dup, s->stream);
     HIPCHK(hipGetLastError());
     int h_dup = 0;
     HIPCHK(hipMemcpyAsync(&h_dup, dup, 4, hipMemcpyDeviceToHost, s->stream));
@@ -83,7 +83,7 @@ extern "C" int corb_track_search_last_frame(CorbKfStore* frames, int cur_slot, i
     rc = call.join(); if (rc) return rc;
     CorbScratch pool(0);
     TrackDev t; memset(&t, 0, sizeof(t));
-    t.cur = frames->rec(cur_slot); t.last = frames->rec(last_slot); t.F = frames->F; t.mp_base = map->base; t.mp_bytes = map->L.bytes; t.idt = map->idt; t.n_cur = n; t.n_last = nq;
+    t.cur = frames->rec(cur_slot); t.last = frames->rec(last_slot); t.F = frames->F; t.mp_base = map->base(); t.mp_bytes = map->L.bytes; t.idt = map->idt; t.n_cur = n; t.n_last = nq;
     HIPCHK(pool.alloc(&t.lastp, (size_t)nq)); HIPCHK(pool.alloc(&t.qdesc, (size_t)nq * 4)); HIPCHK(pool.alloc(&t.claimed, (size_t)n));
     ProjBuffers pb; rc = pb.alloc(pool, n, nq, true, 0); if (rc) return rc;
     t.match = pb.res;
@@ -110,7 +110,7 @@ extern "C" int corb_track_pose_optimization(CorbKfStore* frames, int slot, CorbM
     rc = call.join(); if (rc) return rc;
     CorbScratch pool(0);
     TrackPoseDev t; memset(&t, 0, sizeof(t));
-    t.cur = frames->rec(slot); t.F = frames->F; t.n_cur = n; t.mp_base = map->base; t.mp_bytes = map->L.bytes; t.idt = map->idt;
+    t.cur = frames->rec(slot); t.F = frames->F; t.n_cur = n; t.mp_base = map->base(); t.mp_bytes = map->L.bytes; t.idt = map->idt;
     double *dpose, *dcam, *dlast; unsigned char* dact; int* dcnt;
     HIPCHK(pool.alloc(&t.edge_off, 2)); HIPCHK(pool.alloc(&t.stage_limit, 1)); HIPCHK(pool.alloc(&t.pt, (size_t)3 * n)); HIPCHK(pool.alloc(&t.obs, (size_t)3 * n)); HIPCHK(pool.alloc(&t.w, (size_t)n));
     HIPCHK(pool.alloc(&t.dim, (size_t)n)); HIPCHK(pool.alloc(&t.efeat, (size_t)n)); HIPCHK(pool.alloc(&dlast, (size_t)n)); HIPCHK(pool.alloc(&dact, (size_t)n)); HIPCHK(pool.alloc(&dcnt, 4));
@@ -158,7 +158,7 @@ extern "C" int corb_track_search_local_points(CorbKfStore* frames, int slot, Cor
     rc = call.join(); if (rc) return rc;
     CorbScratch pool(0);
     TrackLocalDev t; memset(&t, 0, sizeof(t));
-    t.cur = frames->rec(slot); t.F = frames->F; t.n_cur = n; t.mp_base = map->base; t.mp_bytes = map->L.bytes; t.idt = map->idt; t.n_local = nq;
+    t.cur = frames->rec(slot); t.F = frames->F; t.n_cur = n; t.mp_base = map->base(); t.mp_bytes = map->L.bytes; t.idt = map->idt; t.n_local = nq;
     rc = id_table_scratch(pool, n, t.inframe, false, pool.stream); if (rc) return rc;
     unsigned long long* dids = nullptr;
     if (nq > 0) HIPCHK(pool.upload_block({{(void**)&dids, local_ids, (size_t)nq * 8}})); else HIPCHK(pool.alloc(&dids, 1));
@@ -202,7 +202,7 @@ extern "C" int corb_fuse_store(CorbKfStore* kf, int slot, CorbMpStore* map, cons
     rc = call.join(); if (rc) return rc;
     CorbScratch pool(0);
     FuseStoreDev t; memset(&t, 0, sizeof(t));
-    t.kf_rec = kf->rec(slot); t.F = kf->F; t.n_feat = n; t.mp_base = map->base; t.mp_bytes = map->L.bytes; t.max_obs = map->O; t.n_points = nq; t.apply = apply ? 1 : 0;
+    t.kf_rec = kf->rec(slot); t.F = kf->F; t.n_feat = n; t.mp_base = map->base(); t.mp_bytes = map->L.bytes; t.max_obs = map->O; t.n_points = nq; t.apply = apply ? 1 : 0;
     int* dslots = nullptr;
     HIPCHK(pool.upload_block({{(void**)&dslots, mp_slots, (size_t)nq * 4}}));
     t.mp_slots = dslots;
@@ -247,7 +247,7 @@ extern "C" int corb_fuse_sim3_store(CorbKfStore* kf, int slot, CorbMpStore* map,
     rc = call.join(); if (rc) return rc;
     CorbScratch pool(0);
     FuseStoreDev t; memset(&t, 0, sizeof(t));
-    t.kf_rec = kf->rec(slot); t.F = kf->F; t.n_feat = n; t.mp_base = map->base; t.mp_bytes = map->L.bytes; t.max_obs = map->O; t.n_points = nq; t.apply = apply ? 1 : 0; t.mpid = map->idt;
+    t.kf_rec = kf->rec(slot); t.F = kf->F; t.n_feat = n; t.mp_base = map->base(); t.mp_bytes = map->L.bytes; t.max_obs = map->O; t.n_points = nq; t.apply = apply ? 1 : 0; t.mpid = map->idt;
     int* dslots = nullptr;
     HIPCHK(pool.upload_block({{(void**)&dslots, mp_slots, (size_t)nq * 4}}));
     t.mp_slots = dslots;
@@ -293,7 +293,7 @@ extern "C" int corb_track_search_reloc(CorbKfStore* frames, int cur_slot, CorbKf
     CorbScratch pool(0);
     RelocStoreDev t; memset(&t, 0, sizeof(t));
     t.cur = frames->rec(cur_slot); t.F_cur = frames->F; t.n_cur = n; t.kf = kfs->rec(kf_slot); t.F_kf = kfs->F; t.n_kf = nq;
-    t.mp_base = map->base; t.mp_bytes = map->L.bytes; t.idt = map->idt;
+    t.mp_base = map->base(); t.mp_bytes = map->L.bytes; t.idt = map->idt;
     rc = id_table_scratch(pool, n, t.inframe, false, pool.stream); if (rc) return rc;
     HIPCHK(pool.alloc(&t.pts, (size_t)nq)); HIPCHK(pool.alloc(&t.qdesc, (size_t)nq * 4)); HIPCHK(pool.alloc(&t.claimed, (size_t)n));
     ProjBuffers pb; rc = pb.alloc(pool, n, nq, true, 0); if (rc) return rc;
@@ -327,7 +327,7 @@ extern "C" int corb_search_by_projection_scw_store(CorbKfStore* kf, int slot, Co
     rc = call.join(); if (rc) return rc;
     CorbScratch pool(0);
     ScwStoreDev t; memset(&t, 0, sizeof(t));
-    t.kf_rec = kf->rec(slot); t.F = kf->F; t.n_feat = n; t.mp_base = map->base; t.mp_bytes = map->L.bytes; t.n_points = nq;
+    t.kf_rec = kf->rec(slot); t.F = kf->F; t.n_feat = n; t.mp_base = map->base(); t.mp_bytes = map->L.bytes; t.n_points = nq;
     int* dslots = nullptr; unsigned long long* dmatched = nullptr;
     HIPCHK(pool.upload_block({{(void**)&dslots, mp_slots, (size_t)nq * 4}, {(void**)&dmatched, matched_ids, (size_t)n * 8}}));
     t.mp_slots = dslots; t.matched = dmatched;
@@ -368,7 +368,7 @@ extern "C" int corb_search_by_sim3_store(CorbKfStore* kf, int slot1, int slot2, 
     CorbScratch pool(0);
     Sim3StoreDev t; memset(&t, 0, sizeof(t));
     t.kf1 = kf->rec(slot1); t.kf2 = kf->rec(slot2); t.F = kf->F; t.n1 = N1; t.n2 = N2;
-    t.mp_base = map->base; t.mp_bytes = map->L.bytes; t.max_obs = map->O; t.idt = map->idt;
+    t.mp_base = map->base(); t.mp_bytes = map->L.bytes; t.max_obs = map->O; t.idt = map->idt;
     unsigned long long* dm = nullptr;
     if (matched12_ids) { HIPCHK(pool.upload_block({{(void**)&dm, matched12_ids, (size_t)N1 * 8}})); t.matched12 = dm; }
     HIPCHK(pool.alloc(&t.already1, (size_t)N1)); HIPCHK(pool.alloc(&t.already2, (size_t)N2));

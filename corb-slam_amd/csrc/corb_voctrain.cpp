@@ -25,23 +25,21 @@ const int g_small_limit = [] {
     return (int)std::min<long>(std::max<long>(v, 0), VT_SMALL_MAX);
 }();
 
-// everything a call allocates, freed when it goes out of scope
-struct Owned {
-    std::vector<void*> dev; hipStream_t stream = nullptr;
+// everything a call allocates, freed when it goes out of scope: the stream's work is waited for, the memory goes, then the stream
+struct CallMem {
+    OwnedStream stream; DevList dev;
     template <class T> hipError_t alloc(T** out, size_t n, bool zero = false)
     {
-        void* p = nullptr; const size_t bytes = std::max(n, (size_t)1) * sizeof(T);
-        hipError_t e = hipMalloc(&p, bytes); if (e != hipSuccess) return e;
-        dev.push_back(p); *out = (T*)p;
-        return zero ? hipMemsetAsync(p, 0, bytes, stream) : hipSuccess;
+        hipError_t e = dev.add(out, n); if (e != hipSuccess) return e;
+        return zero ? hipMemsetAsync(*out, 0, std::max(n, (size_t)1) * sizeof(T), stream) : hipSuccess;
     }
     template <class T> hipError_t upload(T** out, const std::vector<T>& src)
     {
         hipError_t e = alloc(out, src.size()); if (e != hipSuccess || src.empty()) return e;
         return hipMemcpyAsync(*out, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice, stream);
     }
-    void release(size_t keep) { while (dev.size() > keep) { (void)hipFree(dev.back()); dev.pop_back(); } }
-    ~Owned() { if (stream) (void)hipStreamSynchronize(stream); release(0); if (stream) (void)hipStreamDestroy(stream); }
+    void release(size_t keep) { dev.release(keep); }
+    ~CallMem() { if (stream) (void)hipStreamSynchronize(stream); }
 };
 
 #define VTCHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { corb_set_error("%s: %s failed: %s", who, #call, hipGetErrorString(e_)); return CORB_ERR_HIP; } } while (0)
@@ -55,7 +53,7 @@ int check_options(const char* who, const CorbVocTrainOptions* opt, long long n_f
 }
 
 // d_desc: [N][4] on the device, already there on ow.stream; offset: host
-int train(const char* who, Owned& ow, const unsigned long long* d_desc, const int32_t* offset, int n_images, const CorbVocTrainOptions& opt, int device, CorbVoc** out, CorbVocTrainStats* stats)
+int train(const char* who, CallMem& ow, const unsigned long long* d_desc, const int32_t* offset, int n_images, const CorbVocTrainOptions& opt, int device, CorbVoc** out, CorbVocTrainStats* stats)
 {
     const auto t0 = std::chrono::steady_clock::now();
     const int N = offset[n_images], k = opt.k, L = opt.L;
@@ -189,8 +187,8 @@ extern "C" int corb_voc_train(const uint8_t* desc, const int32_t* offset, int n_
     int rc = check_options(who, opt, offset[n_images]); if (rc) return rc;
     if (!desc) { corb_set_error("%s: NULL array", who); return CORB_ERR_ARG; }
     rc = corb_select_device(device); if (rc) return rc;
-    Owned ow; unsigned long long* d_desc;
-    VTCHK(hipStreamCreateWithFlags(&ow.stream, hipStreamNonBlocking));
+    CallMem ow; unsigned long long* d_desc;
+    VTCHK(ow.stream.create());
     const size_t N = (size_t)offset[n_images];
     VTCHK(ow.alloc(&d_desc, N * 4));
     VTCHK(hipMemcpyAsync(d_desc, desc, N * 32, hipMemcpyHostToDevice, ow.stream)); VTCHK(hipStreamSynchronize(ow.stream));
@@ -222,8 +220,8 @@ extern "C" int corb_voc_train_store(CorbKfStore* s, const int32_t* slots, int n_
     }
     rc = check_options(who, opt, offset[n_slots]); if (rc) return rc;
     VTCHK(hipStreamSynchronize(s->stream));                             // pending fills of the records
-    Owned ow; unsigned long long* d_desc;
-    VTCHK(hipStreamCreateWithFlags(&ow.stream, hipStreamNonBlocking));
+    CallMem ow; unsigned long long* d_desc;
+    VTCHK(ow.stream.create());
     VTCHK(ow.alloc(&d_desc, (size_t)offset[n_slots] * 4));
     for (int i = 0; i < n_slots; i++) {
         const size_t n = (size_t)(offset[i + 1] - offset[i]);

@@ -8,9 +8,10 @@ struct CorbCovis {
     CorbKfStore* kf = nullptr; CorbMpStore* mp = nullptr;
     CovisRows R{};
     CovisTree T{};
-    char* mem = nullptr;
-    char* tree_mem = nullptr;
-    float* bef = nullptr;                    // [capacity][16] mTcwBefGBA of slot r (C/include/KeyFrame.h:63); a fresh graph holds the identity
+    int device = 0;
+    DevMem mem, tree_mem;                    // what R and T point into
+    DevMem bef_mem;                          // [capacity][16] mTcwBefGBA of slot r (C/include/KeyFrame.h:63); a fresh graph holds the identity
+    float* bef() const { return bef_mem.as<float>(); }
     std::mutex mu;
 };
 
@@ -29,8 +30,8 @@ struct CovisCall {
         if (!pool.stream) { corb_set_error("%s: no workspace stream", who); return CORB_ERR_HIP; }
         int rc = need_points ? record_need_index(who, mp) : CORB_OK; if (rc) return rc;
         rc = record_join(kf->stream, mp->stream, frames ? frames->stream : nullptr); if (rc) return rc;
-        S.kf_base = kf->base; S.kf_bytes = kf->L.bytes; S.F = kf->F; S.kf_capacity = kf->capacity;
-        S.mp_base = mp->base; S.mp_bytes = mp->L.bytes; S.O = mp->O; S.mp_capacity = mp->capacity; S.mpid = mp->idt;
+        S.kf_base = kf->base(); S.kf_bytes = kf->L.bytes; S.F = kf->F; S.kf_capacity = kf->capacity;
+        S.mp_base = mp->base(); S.mp_bytes = mp->L.bytes; S.O = mp->O; S.mp_capacity = mp->capacity; S.mpid = mp->idt;
         rc = id_table_scratch(pool, kf->capacity, S.kfid, true, pool.stream); if (rc) return rc;
         corb_launch_kf_index(S.kf_base, S.kf_bytes, 0, S.kf_capacity, S.kfid, pool.stream);        // "in the cache" (Cache::KeyFrameInCache) means: found in this table
         HIPCHK(hipGetLastError());

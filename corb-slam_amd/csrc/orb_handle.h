@@ -6,19 +6,20 @@
 #include <mutex>
 #include <vector>
 
-#include "host_util.h"
+#include "owned_hip.h"
 
 struct CorbOrb {
+    int device = 0;             // cfg.device
     CorbOrbConfig cfg;
     CorbOrbParams p;            // host copy
     CorbOrbParams* dp = nullptr;
-    hipStream_t stream = nullptr;
+    OwnedStream stream;
     // A run of many images is issued as `parts` part-batches, part 0 on `stream`, part i on side[i-1]; part i starts when part i-1 has
     // launched its FAST kernel (ev_stage), so the parts run half a pipeline apart and the VALU-bound kernels of one meet the
     // latency-bound kernels of the other.  The side streams are joined into `stream` lazily (corb_join), by the next call that touches the
     // results or the inputs -- back-to-back runs keep their phase offset.
-    hipStream_t side[CORB_MAX_PARTS - 1] = {};
-    hipEvent_t ev_stage[CORB_MAX_PARTS] = {}, ev_done[CORB_MAX_PARTS - 1] = {};
+    OwnedStream side[CORB_MAX_PARTS - 1];
+    OwnedEvent ev_stage[CORB_MAX_PARTS], ev_done[CORB_MAX_PARTS - 1];
     int parts = 0;                                // 0: two parts (corb_run_parts); CORB_PARTS fixes another count
     int last_np = 0, max_np = 0;                  // parts of the previous split run; most parts (side streams in use) so far
     bool join_pending = false;
@@ -28,27 +29,23 @@ struct CorbOrb {
     int quota[CORB_MAX_LEVELS];
     int umax[16];
     int last_n_images = 0;
-    std::vector<void*> allocs;
+    DevList allocs;
     CorbProfiler prof;
     std::mutex stage_mu;        // guards the pinned staging area below
-    int* h_status = nullptr;    // pinned
-    int* h_count = nullptr;     // pinned
+    PinnedMem h_status, h_count;                 // [max_images] ints
     // pinned staging of ONE image's input and outputs: the single-image operator (corb_orb_extract) and the fetch calls move their
     // data with true asynchronous DMA and one synchronisation instead of several pageable copies
-    uint8_t* d_stage = nullptr;                  // device staging of one contiguous input image (re-pitched by orb_ingest_kernel)
-    uint8_t* d_stage_batch = nullptr; size_t stage_batch_bytes = 0;   // staging of a whole batch (corb_orb_upload_batch), allocated on first use
-    uint8_t* h_img = nullptr; CorbKeyPoint* h_kp = nullptr; uint8_t* h_desc = nullptr; float* h_f32 = nullptr; int* h_misc = nullptr;
-    CorbKeyPoint* d_cand_tmp = nullptr; int* d_cand_n = nullptr; int cand_tmp_cap = 0;
+    DevMem d_stage;                              // device staging of one contiguous input image (re-pitched by orb_ingest_kernel)
+    DevMem d_stage_batch;                        // staging of a whole batch (corb_orb_upload_batch), allocated on first use: the bytes asked for and 256 more
+    PinnedMem h_img, h_kp, h_desc, h_f32, h_misc;      // bytes, CorbKeyPoint, bytes, floats, 8 ints
+    DevMem d_cand_tmp, d_cand_n;                 // CorbKeyPoint of the largest request; one int
 };
 
 // device allocation owned by the handle (freed by corb_orb_destroy)
 template <class T> static int dalloc(CorbOrb* h, T** out, size_t n)
 {
-    void* ptr = nullptr;
-    const hipError_t e = hipMalloc(&ptr, n * sizeof(T) + 256);
+    const hipError_t e = h->allocs.add(reinterpret_cast<char**>(out), n * sizeof(T) + 256);
     if (e != hipSuccess) { corb_set_error("hipMalloc(%zu) failed: %s", n * sizeof(T) + 256, hipGetErrorString(e)); return CORB_ERR_HIP; }
-    h->allocs.push_back(ptr);
-    *out = (T*)ptr;
     return CORB_OK;
 }
 
@@ -69,8 +66,8 @@ static inline void corb_join(CorbOrb* h)
 static inline hipStream_t corb_side(CorbOrb* h, int i)
 {
     if (!h->side[i]) {
-        (void)hipStreamCreateWithFlags(&h->side[i], hipStreamNonBlocking);
-        (void)hipEventCreateWithFlags(&h->ev_done[i], hipEventDisableTiming);
+        (void)h->side[i].create();
+        (void)h->ev_done[i].create(hipEventDisableTiming);
     }
     return h->side[i];
 }

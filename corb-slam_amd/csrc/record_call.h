@@ -1,7 +1,7 @@
 // record_call.h -- what every call on device-resident records does before it touches one, in this order: the argument checks that read no store state (the
 // caller's own); the device; the locks (record_locks.h); and only under the locks the feature counts of the slots, which a put from another thread may change
 // until then, and the map's id index where ids are resolved.  The caller initialises its outputs from the counts, takes its early return, and only then waits
-// for the stores' streams.  Also the id tables such calls build.  Host code only.
+// for the stores' streams.  Also the id tables such calls build (a table a handle keeps between calls: owned_hip.h).  Host code only.
 #pragma once
 #include "host_util.h"
 #include "store_host.h"
@@ -58,13 +58,4 @@ template <class Pool> int id_table_scratch(Pool& pool, long long entries, CorbId
     const size_t cap = id_table_capacity(entries);
     HIPCHK(pool.alloc(&t.keys, cap)); HIPCHK(pool.alloc(&t.vals, cap)); t.mask = (unsigned int)(cap - 1);
     return id_table_clear(t, for_min, s);
-}
-// a table its owner keeps between calls: one allocation of keys | values | `tail` bytes of the owner's, replacing whatever the table held
-inline int id_table_own(CorbIdTable& t, size_t cap, size_t tail)
-{
-    if (t.keys) { (void)hipFree(t.keys); t.keys = nullptr; t.vals = nullptr; }
-    char* mem = nullptr;
-    HIPCHK(hipMalloc((void**)&mem, cap * 12 + tail));
-    t.keys = reinterpret_cast<unsigned long long*>(mem); t.vals = reinterpret_cast<int*>(mem + cap * 8); t.mask = (unsigned int)(cap - 1);
-    return CORB_OK;
 }
