@@ -60,6 +60,8 @@ KFINSERT_EXPORTS = ("corb_kfi_create", "corb_kfi_destroy", "corb_kfi_create_ster
 # include/corb_map_publish.h: the server -> clients publish on records, bound the same way
 PUBLISH_EXPORTS = ("corb_pub_create", "corb_pub_destroy", "corb_pub_message_layout", "corb_pub_pack", "corb_pub_message", "corb_pub_message_read", "corb_pub_apply",
                    "corb_map_publish_plan", "corb_map_publish_messages", "corb_map_publish")
+# include/corb_stereo_rectify.h: stereo rectification in front of the stereo front-end, bound the same way
+RECTIFY_EXPORTS = ("corb_rect_create", "corb_rect_destroy", "corb_rect_maps", "corb_rect_set_maps", "corb_rect_upload_batch", "corb_rect_frames")
 
 
 class CorbError(RuntimeError):
@@ -170,6 +172,14 @@ class StereoFrameLayout(C.Structure):
 
 class StereoFrameTiming(C.Structure):
     _fields_ = [("ms_upload", C.c_float), ("ms_kernels", C.c_float), ("ms_download", C.c_float)]
+
+
+class RectifyEye(C.Structure):
+    _fields_ = [("K", C.c_double * 9), ("D", C.c_double * 8), ("R", C.c_double * 9), ("P", C.c_double * 12)]
+
+
+class RectifyConfig(C.Structure):
+    _fields_ = [("raw_width", C.c_int32), ("raw_height", C.c_int32), ("left", RectifyEye), ("right", RectifyEye)]
 
 
 class _BAResult(C.Structure):
@@ -464,6 +474,15 @@ def load():
     L.corb_map_publish_plan.argtypes = [C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_int)]
     L.corb_map_publish_messages.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.c_void_p, C.POINTER(C.c_int)]
     L.corb_map_publish.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(_PublishPack), C.POINTER(_PublishApply)]
+    for name in RECTIFY_EXPORTS:
+        if not hasattr(L, name):
+            raise CorbError("libcorb_accel.so lacks %s (include/corb_stereo_rectify.h): rebuild it" % name)
+    L.corb_rect_create.argtypes = [C.POINTER(RectifyConfig), C.c_void_p, C.POINTER(C.c_void_p)]
+    L.corb_rect_destroy.argtypes = [C.c_void_p]; L.corb_rect_destroy.restype = None
+    L.corb_rect_maps.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    L.corb_rect_set_maps.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    L.corb_rect_upload_batch.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+    L.corb_rect_frames.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     _lib = L
     return L
 
@@ -716,6 +735,84 @@ class StereoFrontend:
         n, nm = C.c_int(), C.c_int()
         _chk(self.L.corb_stereo_fetch_matches(self.h, frame, _p(ur), _p(dp), self.orb.cap, C.byref(n), C.byref(nm)), "fetch_matches")
         return dict(kl=kl, dl=dl, kr=kr, dr=dr, u_right=ur[: n.value].copy(), depth=dp[: n.value].copy(), n_matched=nm.value)
+
+
+class StereoRectifier:
+    """What the reference's stereo mains for unrectified cameras do before TrackStereo (Examples/Stereo/stereo_euroc.cc:64-98,136-137): the maps of
+    cv::initUndistortRectifyMap from LEFT / RIGHT {K, D, R, P}, and cv::remap(INTER_LINEAR) of every raw pair, on the device in front of a StereoFrontend
+    (include/corb_stereo_rectify.h).  left / right: (K, D, R, P) with K, R 3x3, P 3x4 and D of 4, 5 or 8 coefficients.  Close it before its front-end."""
+
+    def __init__(self, stereo_frontend, left, right, raw_width, raw_height):
+        self.L = load()
+        self.sf = stereo_frontend
+        self.width, self.height, self.raw_width, self.raw_height = stereo_frontend.orb.width, stereo_frontend.orb.height, int(raw_width), int(raw_height)
+        cfg = RectifyConfig(); cfg.raw_width = self.raw_width; cfg.raw_height = self.raw_height
+        for eye, (K, D, R, P) in ((cfg.left, left), (cfg.right, right)):
+            d = np.zeros(8); dd = np.asarray(D, np.float64).reshape(-1); d[: len(dd)] = dd
+            for name, v, n in (("K", K, 9), ("D", d, 8), ("R", R, 9), ("P", P, 12)):
+                setattr(eye, name, (C.c_double * n)(*np.asarray(v, np.float64).reshape(n)))
+        h = C.c_void_p()
+        _chk(self.L.corb_rect_create(C.byref(cfg), stereo_frontend.h, C.byref(h)), "corb_rect_create")
+        self.h = h
+
+    @staticmethod
+    def read_settings(path):
+        """The `NAME: !!opencv-matrix` blocks (rows, cols, dt, data: [...]) and the plain `NAME: number` entries of an OpenCV FileStorage settings file as a dict
+        (its %YAML:1.0 first line and `data:[` are not YAML a library would read, and none is needed)."""
+        import re
+        txt = open(path).read(); out = {}
+        for m in re.finditer(r"^([A-Za-z_][\w.]*):\s*!!opencv-matrix\s*\n\s*rows:\s*(\d+)\s*\n\s*cols:\s*(\d+)\s*\n\s*dt:\s*(\w+)\s*\n\s*data:\s*\[([^\]]*)\]", txt, re.M):
+            out[m.group(1)] = np.array([float(v) for v in m.group(5).split(",") if v.strip()], np.float64).reshape(int(m.group(2)), int(m.group(3)))
+        for m in re.finditer(r"^([A-Za-z_][\w.]*):\s*([-+0-9.eE]+)\s*$", txt, re.M):
+            out[m.group(1)] = float(m.group(2))
+        return out
+
+    @classmethod
+    def from_settings(cls, stereo_frontend, path):
+        """LEFT.* / RIGHT.* of a settings file (stereo_euroc.cc:64-93); the raw size is LEFT.width x LEFT.height"""
+        s = cls.read_settings(path)
+        need = [e + k for e in ("LEFT.", "RIGHT.") for k in ("K", "D", "R", "P", "width", "height")]
+        if any(k not in s for k in need):
+            raise CorbError("%s: calibration parameters to rectify stereo are missing (%s)" % (path, ", ".join(k for k in need if k not in s)))
+        eye = lambda e: (s[e + ".K"], s[e + ".D"], s[e + ".R"], s[e + ".P"])
+        return cls(stereo_frontend, eye("LEFT"), eye("RIGHT"), int(s["LEFT.width"]), int(s["LEFT.height"]))
+
+    def close(self):
+        if self.h:
+            self.L.corb_rect_destroy(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def maps(self, eye):
+        mx = np.zeros((self.height, self.width), np.float32); my = np.zeros((self.height, self.width), np.float32)
+        _chk(self.L.corb_rect_maps(self.h, eye, _p(mx), _p(my)), "corb_rect_maps")
+        return mx, my
+
+    def set_maps(self, eye, map_x, map_y):
+        mx = np.ascontiguousarray(map_x, np.float32); my = np.ascontiguousarray(map_y, np.float32)
+        assert mx.shape == (self.height, self.width) and my.shape == mx.shape
+        _chk(self.L.corb_rect_set_maps(self.h, eye, _p(mx), _p(my)), "corb_rect_set_maps")
+
+    def _raw(self, packed):
+        assert packed.flags["C_CONTIGUOUS"] and packed.dtype == np.uint8 and packed.shape[1:] == (2, self.raw_height, self.raw_width)
+        return packed.shape[0]
+
+    def upload_batch(self, first, packed):
+        """packed: uint8 [n_frames][2][raw_height][raw_width] (raw left, raw right); afterwards the front-end's run / sync / fetch work unchanged"""
+        _chk(self.L.corb_rect_upload_batch(self.h, first, self._raw(packed), _p(packed)), "corb_rect_upload_batch")
+
+    def frames(self, packed, result=None, timing=None):
+        """corb_rect_frames: StereoFrontend.frames for raw input; returns the result block that StereoFrontend.unpack_frame parses"""
+        n = self._raw(packed)
+        if result is None:
+            result = np.zeros(n * self.sf.frame_layout().frame_bytes, np.uint8)
+        _chk(self.L.corb_rect_frames(self.h, n, _p(packed), _p(result), C.byref(timing) if timing is not None else None), "corb_rect_frames")
+        return result
 
 
 class RgbdFrontend:

@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stddef.h>
+#include <map>
 #include "../../include/corb_accel.h"
 
 // Development switches that leave work out or change the solver's path (CORB_ORB_SKIP, CORB_BA_PC_PERIOD, CORB_BA_SMALL_EDGES) exist only in a
@@ -127,6 +128,18 @@ __device__ __forceinline__ void corb_xcd_remap(int& unit, int& img)
 struct CorbStereoDeviceFrame { const CorbKeyPoint* kp; const uint8_t* desc; const float* u_right; const float* depth; const int* count; int cap; hipStream_t stream; int device; };
 struct CorbStereo;
 int corb_stereo_device_frame(CorbStereo* h, int frame, CorbStereoDeviceFrame* out);
+// corb_stereo_frames with the step that fills the level-0 planes left to the caller (corb_orb.cpp; corb_rectify.cpp feeds it raw images): the one host-to-device
+// copy of `bytes` from `host` to `d_stage`, then planes -> ORB pipeline -> stereo -> pack as one captured chain per n in `graphs`, the one copy back, one
+// synchronisation, the bookkeeping and the overflow rule.  `graphs` hold d_stage and whatever `planes` launches with: their owner clears them when either moves.
+struct CorbProfiler;
+struct CorbFrameInput {
+    const char* who;                                                              // the public call, for messages
+    const void* host; size_t bytes; void* d_stage;
+    void (*planes)(void* ctx, int n_frames, hipStream_t st, CorbProfiler* prof);  // enqueue: staging -> level-0 planes of image slots 0 .. 2 n - 1
+    void* ctx;
+    std::map<int, hipGraphExec_t>* graphs;
+};
+int corb_stereo_frames_chain(CorbStereo* h, int n_frames, const CorbFrameInput& in, void* result, CorbStereoFrameTiming* timing);
 struct CorbRgbd;
 int corb_rgbd_device_frame(CorbRgbd* h, int frame, CorbStereoDeviceFrame* out);      // kp = mvKeysUn (corb_cam.cpp)
 

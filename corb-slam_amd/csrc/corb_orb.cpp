@@ -636,33 +636,51 @@ extern "C" int corb_stereo_frames(CorbStereo* h, int n_frames, const uint8_t* im
     CorbOrb* o = h->orb;
     HIPCHK(hipSetDevice(o->cfg.device));
     corb_join(o);
-    hipStream_t st = o->stream;
     const size_t img_bytes = (size_t)o->cfg.width * o->cfg.height, in_bytes = img_bytes * 2 * n_frames;
-    if (o->d_stage_batch.cap() < in_bytes + 256 || !h->d_result || h->graph_stage != o->d_stage_batch.as<void>()) {
-        HIPCHK(hipStreamSynchronize(st));
+    if (o->d_stage_batch.cap() < in_bytes + 256 || h->graph_stage != o->d_stage_batch.as<void>()) {
+        HIPCHK(hipStreamSynchronize(o->stream));
         for (auto& g : h->frame_graph) if (g.second) (void)hipGraphExecDestroy(g.second);      // (the captured chains hold the staging addresses)
         h->frame_graph.clear();
         const size_t want = img_bytes * 2 * std::min(h->max_frames, std::max(n_frames, 8));         // (room for the usual small frame counts: no re-capture when n grows)
         HIPCHK(o->d_stage_batch.room(in_bytes + 256, want + 256));
-        if (!h->d_result) { if (dalloc(o, &h->d_result, (size_t)h->max_frames * h->lay.frame_bytes)) return CORB_ERR_HIP; HIPCHK(hipMemsetAsync(h->d_result, 0, (size_t)h->max_frames * h->lay.frame_bytes, st)); }
         h->graph_stage = o->d_stage_batch.as<void>();
+    }
+    CorbFrameInput in;
+    in.who = "corb_stereo_frames"; in.host = images; in.bytes = in_bytes; in.d_stage = o->d_stage_batch.as<void>();
+    in.planes = [](void* ctx, int n, hipStream_t st, CorbProfiler*) {
+        CorbOrb* o = static_cast<CorbOrb*>(ctx); const CorbLevel& L0 = o->p.lv[0];
+        corb_launch_ingest(o->d_stage_batch.as<uint8_t>(), o->cfg.width, o->cfg.height, 2 * n, o->p.pyr + L0.plane_off, L0.pitch, o->p.arena_per_image, st);
+    };
+    in.ctx = o; in.graphs = &h->frame_graph;
+    return corb_stereo_frames_chain(h, n_frames, in, result, timing);
+}
+
+// The chain of corb_stereo_frames and corb_rect_frames (corb_internal.h: CorbFrameInput).  The caller has checked its arguments, selected the device and joined
+// the extractor's parts.
+int corb_stereo_frames_chain(CorbStereo* h, int n_frames, const CorbFrameInput& in, void* result, CorbStereoFrameTiming* timing)
+{
+    CorbOrb* o = h->orb;
+    hipStream_t st = o->stream;
+    if (!h->d_result) {
+        HIPCHK(hipStreamSynchronize(st));
+        if (dalloc(o, &h->d_result, (size_t)h->max_frames * h->lay.frame_bytes)) return CORB_ERR_HIP;
+        HIPCHK(hipMemsetAsync(h->d_result, 0, (size_t)h->max_frames * h->lay.frame_bytes, st));
     }
     if (timing && !h->ev_t[0]) for (auto& e : h->ev_t) HIPCHK(e.create(hipEventDefault));
     CorbProfiler* prof = o->prof.enabled ? &o->prof : nullptr;
     auto chain = [&](CorbProfiler* pr) {
-        const CorbLevel& L0 = o->p.lv[0];
-        corb_launch_ingest(o->d_stage_batch.as<uint8_t>(), o->cfg.width, o->cfg.height, 2 * n_frames, o->p.pyr + L0.plane_off, L0.pitch, o->p.arena_per_image, st);
+        in.planes(in.ctx, n_frames, st, pr);
         corb_launch_orb_pipeline(o->p, 0, 2 * n_frames, o->octree_lds, st, pr);
         corb_launch_stereo(o->p, h->s, 0, n_frames, st, pr);
         corb_launch_stereo_pack(o->p, h->s, 0, n_frames, h->d_result, h->lay, st, pr);
     };
     static const bool no_graph = corb_dev_env("CORB_FRAME_NO_GRAPH") != nullptr;      // -DCORB_DEV builds only: the launches one by one (A/B of the capture)
     if (timing) HIPCHK(hipEventRecord(h->ev_t[0], st));
-    HIPCHK(hipMemcpyAsync(o->d_stage_batch.as<uint8_t>(), images, in_bytes, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(in.d_stage, in.host, in.bytes, hipMemcpyHostToDevice, st));
     if (timing) HIPCHK(hipEventRecord(h->ev_t[1], st));
     if (prof || no_graph) chain(prof);
     else {
-        hipGraphExec_t& ge = h->frame_graph[n_frames];
+        hipGraphExec_t& ge = (*in.graphs)[n_frames];
         if (!ge) {
             hipGraph_t graph = nullptr;
             HIPCHK(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
@@ -670,7 +688,7 @@ extern "C" int corb_stereo_frames(CorbStereo* h, int n_frames, const uint8_t* im
             HIPCHK(hipStreamEndCapture(st, &graph));
             const hipError_t e = hipGraphInstantiate(&ge, graph, nullptr, nullptr, 0);
             (void)hipGraphDestroy(graph);
-            if (e != hipSuccess) { ge = nullptr; corb_set_error("corb_stereo_frames: hipGraphInstantiate: %s", hipGetErrorString(e)); return CORB_ERR_HIP; }
+            if (e != hipSuccess) { ge = nullptr; corb_set_error("%s: hipGraphInstantiate: %s", in.who, hipGetErrorString(e)); return CORB_ERR_HIP; }
         }
         HIPCHK(hipGraphLaunch(ge, st));
     }

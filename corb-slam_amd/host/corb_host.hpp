@@ -8,10 +8,12 @@
 //   ORB_SLAM2::ORBmatcher    (corbslam_client/include/ORBmatcher.h:41-107)     -> corb::ORBmatcher
 //   ORB_SLAM2::Optimizer     (corbslam_client/include/Optimizer.h:42-46)       -> corb::Optimizer
 //   Frame::ComputeStereoMatches (corbslam_client/src/Frame.cc:470-644)          -> corb::StereoFrontend
+//   cv::initUndistortRectifyMap + cv::remap of the stereo mains (corbslam_client/Examples/Stereo/stereo_euroc.cc:64-98,136-137) -> corb::StereoRectifier
 //
 // corb_adapter_opencv.hpp layers the exact cv::/KeyFrame signatures on top of this where OpenCV exists.
 #pragma once
 #include <corb_accel.h>
+#include <corb_stereo_rectify.h>
 #include <algorithm>
 #include <cstdint>
 #include <stdexcept>
@@ -147,6 +149,40 @@ public:
     }
 private:
     CorbStereo* h_ = nullptr; int max_frames_, cap_;
+};
+
+// The rectification the reference's stereo mains for unrectified cameras do on the host before TrackStereo (Examples/Stereo/stereo_euroc.cc:64-98,136-137;
+// Examples/ROS/ORB_SLAM2/src/ros_stereo.cc:82-107,161-162), in front of a StereoFrontend (include/corb_stereo_rectify.h).  Constructed from the eight matrices of
+// the settings file, row-major doubles: K, R 3x3, P 3x4, D of up to 8 coefficients (k1, k2, p1, p2, k3, k4, k5, k6).  Destroy it before its front-end.
+class StereoRectifier {
+public:
+    StereoRectifier(StereoFrontend& frontend, const std::vector<double>& K_l, const std::vector<double>& D_l, const std::vector<double>& R_l, const std::vector<double>& P_l,
+                    const std::vector<double>& K_r, const std::vector<double>& D_r, const std::vector<double>& R_r, const std::vector<double>& P_r, int rawWidth, int rawHeight)
+    {
+        check_abi();
+        CorbRectifyConfig cfg{};
+        cfg.raw_width = rawWidth; cfg.raw_height = rawHeight;
+        auto fill = [](double* dst, size_t n, const std::vector<double>& v, bool exact) {
+            if (exact ? v.size() != n : v.size() > n) throw std::invalid_argument("corb::StereoRectifier: a calibration matrix of the wrong size");
+            std::copy(v.begin(), v.end(), dst);
+        };
+        fill(cfg.left.K, 9, K_l, true); fill(cfg.left.D, 8, D_l, false); fill(cfg.left.R, 9, R_l, true); fill(cfg.left.P, 12, P_l, true);
+        fill(cfg.right.K, 9, K_r, true); fill(cfg.right.D, 8, D_r, false); fill(cfg.right.R, 9, R_r, true); fill(cfg.right.P, 12, P_r, true);
+        check(corb_rect_create(&cfg, frontend.handle(), &h_), "corb_rect_create");
+    }
+    ~StereoRectifier() { corb_rect_destroy(h_); }
+    StereoRectifier(const StereoRectifier&) = delete;
+    StereoRectifier& operator=(const StereoRectifier&) = delete;
+    // M1 / M2 of eye 0 (left) / 1 (right): height x width floats each
+    void Maps(int eye, float* mapX, float* mapY) const { check(corb_rect_maps(h_, eye, mapX, mapY), "corb_rect_maps"); }
+    void SetMaps(int eye, const float* mapX, const float* mapY) { check(corb_rect_set_maps(h_, eye, mapX, mapY), "corb_rect_set_maps"); }
+    // cv::remap of both raw images of every frame (per frame the raw left image then the raw right image, tightly packed); then the front-end's Run / Sync / Fetch
+    void UploadBatch(int firstFrame, int nFrames, const uint8_t* rawLeftRight) { check(corb_rect_upload_batch(h_, firstFrame, nFrames, rawLeftRight), "corb_rect_upload_batch"); }
+    // StereoFrontend::Frames for raw input: the same result blocks (StereoFrontend::FrameLayout, StereoFrontend::FromBlock)
+    void Frames(int nFrames, const uint8_t* rawLeftRight, void* resultBlocks, CorbStereoFrameTiming* timing = nullptr) { check(corb_rect_frames(h_, nFrames, rawLeftRight, resultBlocks, timing), "corb_rect_frames"); }
+    CorbRect* handle() const { return h_; }
+private:
+    CorbRect* h_ = nullptr;
 };
 
 // Frame::Frame(RGB-D) / Frame::Frame(monocular) (Frame.cc:119-228) with Tracking::GrabImageRGBD / GrabImageMonocular's input conversions (Tracking.cc:206-264).
