@@ -44,7 +44,7 @@ extern "C" int corb_mono_initialize(const CorbInitProblem* problems, int n_probl
         capN = std::max(capN, p.N); cap1 = std::max(cap1, q.n1);
     }
     const size_t n_rand = (size_t)n_problems * max_iterations * 8;
-    for (size_t i = 0; i < n_rand; i++) if (rand_values[i] < 0) { corb_set_error("%s: rand_values[%zu] is outside [0, 2^31)", who, i); return CORB_ERR_ARG; }
+    if (!ransac_rand_values_ok(who, rand_values, n_rand)) return CORB_ERR_ARG;
     int rc = corb_select_device(device); if (rc) return rc;
     for (int c = 0; c < n_problems; c++) {                                              // Normalize over all keys of each frame (:132-133)
         const CorbInitProblem& q = problems[c];

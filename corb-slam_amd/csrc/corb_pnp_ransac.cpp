@@ -1,8 +1,7 @@
 // corb_pnp_ransac.cpp -- C-ABI host side of the PnPsolver RANSAC (include/corb_accel.h, last section): the host-array form (corb_pnp_ransac) and the form on records
-// (corb_pnp_ransac_store).  All candidates of a call are queued on one stream with one synchronisation and one read-back; SetRansacParameters' adjustments and cap and the list of records are assembled here, after the read-back.
+// (corb_pnp_ransac_store).  All candidates of a call are queued on one stream with one synchronisation and one read-back (ransac_run of ransac_common.h); SetRansacParameters' adjustments and the list of records are assembled here, after the read-back.
 #include "pnp_ransac_internal.h"
 #include "record_call.h"
-#include <cmath>
 #include <cstring>
 #include <vector>
 #include <algorithm>
@@ -27,11 +26,9 @@ bool pnr_args_ok(const char* who, int n_cand, const PnrParams& a, const PnrOut& 
                        who, PNR_MAX_ITERATIONS, PNR_MAX_ITERATIONS);
         return false;
     }
-    const size_t nr = (size_t)n_cand * (a.max_iterations + a.tail) * a.min_set;
-    for (size_t i = 0; i < nr; i++) if (a.rand_values[i] < 0) { corb_set_error("%s: rand_values[%zu] is outside [0, 2^31)", who, i); return false; }
-    return true;
+    return ransac_rand_values_ok(who, a.rand_values, (size_t)n_cand * (a.max_iterations + a.tail) * a.min_set);
 }
-// SetRansacParameters (:166-197) with the reference's own expressions and the host's libm: returns mRansacMaxIts (0 = iterate() sets bNoMore at once, :218-222) and
+// SetRansacParameters (:166-197), its adjustments of nMinInliers and epsilon before the shared cap: returns mRansacMaxIts (0 = iterate() sets bNoMore at once, :218-222) and
 // the adjusted mRansacMinInliers
 int pnr_parameters(int N, const PnrParams& a, int* min_inliers)
 {
@@ -42,22 +39,12 @@ int pnr_parameters(int N, const PnrParams& a, int* min_inliers)
     *min_inliers = nMinInliers;
     if (N < nMinInliers || N <= 0) return 0;
     if (epsilon < (float)nMinInliers / (float)N) epsilon = (float)nMinInliers / (float)N;
-    int nIterations;
-    if (nMinInliers == N) nIterations = 1;
-    else {
-        const double x = std::ceil(std::log(1 - a.probability) / std::log(1 - std::pow((double)epsilon, 3.0)));
-        nIterations = !(x < (double)a.max_iterations) ? a.max_iterations : (x < 1 ? 1 : (int)x);
-    }
-    return std::max(1, std::min(nIterations, a.max_iterations));
+    return ransac_iteration_cap(N, nMinInliers, epsilon, a.probability, a.max_iterations);
 }
 // Rcw.convertTo(CV_32F), tcw.convertTo(CV_32F) into rows 0-2 of a 4 x 4 (:262-268, :339-345)
 void pnr_tcw(const PnpPose& p, float* T)
 {
     for (int i = 0; i < 3; i++) { for (int j = 0; j < 3; j++) T[4 * i + j] = (float)p.R[3 * i + j]; T[4 * i + 3] = (float)p.t[i]; }
-}
-void pnr_flags(const unsigned long long* m, int N, const int* index, int stride, uint8_t* fl)
-{
-    for (int k = 0; k < N; k++) if ((m[k >> 6] >> (k & 63)) & 1ull) { const int f = index ? index[k] : k; if (f >= 0 && f < stride) fl[f] = 1; }
 }
 // the records of one candidate from its read-back: iteration i is a record iff c_i >= m and c_i > every earlier c_j >= m
 void pnr_records(int c, int N, int cap_its, int m, const PnrHyp* hyp, const unsigned long long* mask, const PnrHyp* ref, const unsigned long long* ref_mask, int words,
@@ -77,8 +64,8 @@ void pnr_records(int c, int N, int cap_its, int m, const PnrHyp* hyp, const unsi
             CorbPnPRansacRecord& e = o.records[r];
             e.iteration = i + 1; e.n_inliers = ci; e.n_refined = ref[i].count; e.refine_ok = ref[i].count > m ? 1 : 0;
             pnr_tcw(hyp[i].pose, e.Tcw_best); pnr_tcw(ref[i].pose, e.Tcw_refined);
-            pnr_flags(mask + (size_t)i * words, N, index, o.flags_stride, o.best_flags + r * o.flags_stride);
-            pnr_flags(ref_mask + (size_t)i * words, N, index, o.flags_stride, o.refined_flags + r * o.flags_stride);
+            ransac_scatter_flags(mask + (size_t)i * words, N, index, o.flags_stride, o.best_flags + r * o.flags_stride);
+            ransac_scatter_flags(ref_mask + (size_t)i * words, N, index, o.flags_stride, o.refined_flags + r * o.flags_stride);
             if (o.refine_pose_out) memcpy(o.refine_pose_out + r * 16, &ref[i].pose, sizeof(PnpPose));
         }
         n_rec++;
@@ -97,29 +84,6 @@ void pnr_clear(int n_cand, const PnrParams& a, const PnrOut& o)
     }
     if (o.counts) memset(o.counts, 0, (size_t)n_cand * stride * 4);
     if (o.pose_out) memset(o.pose_out, 0, (size_t)n_cand * stride * 16 * sizeof(double));
-}
-// the call's buffers behind the uploads, the launches, and the one read-back.  Nothing is preset: the host reads a hypothesis only below the candidate's `its`, which
-// the hypothesis kernel has written, and a Refine() only at a record, which the refine kernel has written
-int pnr_run(CorbScratch& pool, PnrDev& d, int grid_its, std::vector<PnrHyp>& h_hyp, std::vector<unsigned long long>& h_mask, std::vector<PnrHyp>& h_ref,
-            std::vector<unsigned long long>& h_ref_mask, std::vector<int>* h_n, std::vector<int>* h_index)
-{
-    const size_t slots = (size_t)d.n_cand * d.cap, nh = (size_t)d.n_cand * d.stride_its;
-    d.words = (d.cap + 63) / 64;
-    HIPCHK(pool.alloc(&d.corr, slots)); HIPCHK(pool.alloc(&d.hyp, nh)); HIPCHK(pool.alloc(&d.mask, nh * d.words));
-    HIPCHK(pool.alloc(&d.ref, nh)); HIPCHK(pool.alloc(&d.ref_mask, nh * d.words));
-    int* scan_scratch = nullptr;
-    if (d.kf) {
-        HIPCHK(pool.alloc(&d.dense, slots)); HIPCHK(pool.alloc(&d.flag, slots + 1)); HIPCHK(pool.alloc(&d.scan, slots + 1)); HIPCHK(pool.alloc(&d.index, slots));
-        HIPCHK(pool.alloc(&d.ncorr, (size_t)d.n_cand)); HIPCHK(pool.alloc(&scan_scratch, corb_scan_scratch_ints(slots)));
-    }
-    corb_launch_pnp_ransac(d, grid_its, scan_scratch, pool.stream);
-    HIPCHK(hipGetLastError());
-    h_hyp.resize(nh); h_mask.resize(nh * d.words); h_ref.resize(nh); h_ref_mask.resize(nh * d.words);
-    HIPCHK(pool.d2h(h_hyp.data(), d.hyp, nh * sizeof(PnrHyp))); HIPCHK(pool.d2h(h_mask.data(), d.mask, nh * d.words * 8));
-    HIPCHK(pool.d2h(h_ref.data(), d.ref, nh * sizeof(PnrHyp))); HIPCHK(pool.d2h(h_ref_mask.data(), d.ref_mask, nh * d.words * 8));
-    if (d.kf) { h_n->resize((size_t)d.n_cand); HIPCHK(pool.d2h(h_n->data(), d.ncorr, (size_t)d.n_cand * 4)); h_index->resize(slots); HIPCHK(pool.d2h(h_index->data(), d.index, slots * 4)); }
-    HIPCHK(pool.fetch_finish());
-    return CORB_OK;
 }
 }  // namespace
 
@@ -163,10 +127,11 @@ extern "C" int corb_pnp_ransac(const CorbPnPRansacProblem* problems, int n_probl
     PnrDev d; memset(&d, 0, sizeof(d));
     d.n_cand = n_problems; d.cap = cap; d.stride_its = max_iterations + tail_iterations; d.min_set = min_set; d.th2 = th2;
     d.min_inliers = min_inliers; d.epsilon = epsilon;
-    HIPCHK(pool.upload_block({{(void**)&d.cand, cand.data(), cand.size() * sizeof(PnrCand)}, {(void**)&d.in, in.data(), rows * 24}, {(void**)&d.ncorr, h_n.data(), h_n.size() * 4},
+    HIPCHK(pool.upload_block({{(void**)&d.cand, cand.data(), cand.size() * sizeof(PnrCand)}, {(void**)&d.in, in.data(), rows * 24}, {(void**)&d.set.ncorr, h_n.data(), h_n.size() * 4},
                               {(void**)&d.rand_values, rand_values, (size_t)n_problems * d.stride_its * min_set * 4}}));
     static thread_local std::vector<PnrHyp> h_hyp, h_ref; static thread_local std::vector<unsigned long long> h_mask, h_ref_mask;
-    rc = pnr_run(pool, d, grid_its, h_hyp, h_mask, h_ref, h_ref_mask, nullptr, nullptr); if (rc) return rc;
+    rc = ransac_run<PnrHyp>(pool, d, false, (size_t)n_problems * d.stride_its, corb_launch_pnp_ransac, grid_its, {{&d.out, &h_hyp, &h_mask}, {&d.ref, &h_ref, &h_ref_mask}}, nullptr, nullptr);
+    if (rc) return rc;
     for (int c = 0; c < n_problems; c++) {
         const size_t h0 = (size_t)c * d.stride_its;
         pnr_records(c, problems[c].n, cap_its[c], m_of[c], h_hyp.data() + h0, h_mask.data() + h0 * d.words, h_ref.data() + h0, h_ref_mask.data() + h0 * d.words,
@@ -192,8 +157,7 @@ extern "C" int corb_pnp_ransac_store(CorbKfStore* frames, int slot, CorbMpStore*
     const PnrOut o{ransac_max_its, ransac_min_inliers, n_records, records, best_flags, refined_flags, n1, counts, pose_out, refine_pose_out};
     if (!pnr_args_ok(who, n_candidates, a, o)) return CORB_ERR_ARG;
     pnr_clear(n_candidates, a, o);
-    for (int c = 0; c < n_candidates; c++) n_corr[c] = 0;
-    if (index) for (size_t i = 0; i < (size_t)n_candidates * n1; i++) index[i] = -1;
+    ransac_corr_preset(n_candidates, n1, n_corr, index);
     if (n_candidates == 0 || n1 == 0) return CORB_OK;
     rc = call.join(); if (rc) return rc;
     const int stride_its = max_iterations + tail_iterations;
@@ -208,15 +172,14 @@ extern "C" int corb_pnp_ransac_store(CorbKfStore* frames, int slot, CorbMpStore*
     HIPCHK(pool.upload_block({{(void**)&d.cand, cand.data(), cand.size() * sizeof(PnrCand)}, {(void**)&d.matched, matched_ids, (size_t)n_candidates * n1 * 8},
                               {(void**)&d.rand_values, rand_values, (size_t)n_candidates * stride_its * min_set * 4}}));
     static thread_local std::vector<PnrHyp> h_hyp, h_ref; static thread_local std::vector<unsigned long long> h_mask, h_ref_mask; std::vector<int> h_n, h_index;
-    rc = pnr_run(pool, d, stride_its, h_hyp, h_mask, h_ref, h_ref_mask, &h_n, &h_index); if (rc) return rc;
+    rc = ransac_run<PnrHyp>(pool, d, true, (size_t)n_candidates * stride_its, corb_launch_pnp_ransac, stride_its, {{&d.out, &h_hyp, &h_mask}, {&d.ref, &h_ref, &h_ref_mask}}, &h_n, &h_index);
+    if (rc) return rc;
     for (int c = 0; c < n_candidates; c++) {
-        const int N = std::min(std::max(h_n[c], 0), n1);
-        n_corr[c] = N;
-        const int* ix = h_index.data() + (size_t)c * n1;
-        if (index) for (int k = 0; k < N; k++) index[(size_t)c * n1 + k] = ix[k];
+        const int N = ransac_corr_out(h_n.data(), h_index.data(), c, n1, n_corr, index);
         int m = 0; const int cap_its = pnr_parameters(N, a, &m);
         const size_t h0 = (size_t)c * stride_its;
-        pnr_records(c, N, cap_its, m, h_hyp.data() + h0, h_mask.data() + h0 * d.words, h_ref.data() + h0, h_ref_mask.data() + h0 * d.words, d.words, ix, a, o);
+        pnr_records(c, N, cap_its, m, h_hyp.data() + h0, h_mask.data() + h0 * d.words, h_ref.data() + h0, h_ref_mask.data() + h0 * d.words, d.words,
+                    h_index.data() + (size_t)c * n1, a, o);
     }
     return CORB_OK;
 }

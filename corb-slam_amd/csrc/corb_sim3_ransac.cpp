@@ -1,9 +1,8 @@
 // corb_sim3_ransac.cpp -- C-ABI host side of the Sim3Solver RANSAC (include/corb_accel.h, last section): the host-array form (corb_sim3_ransac) and the form on
-// records (corb_sim3_ransac_store).  All candidates of a call are queued on one stream with one synchronisation and one read-back; SetRansacParameters' cap and the
-// rule that turns the per-hypothesis inlier counts into iterate()'s returns are stated once, here, for both.
+// records (corb_sim3_ransac_store).  All candidates of a call are queued on one stream with one synchronisation and one read-back (ransac_run); the rule that turns
+// the per-hypothesis inlier counts into iterate()'s returns is stated once, here, for both.  What the PnP route shares is in ransac_common.h.
 #include "sim3_ransac_internal.h"
 #include "record_call.h"
-#include <cmath>
 #include <cstring>
 #include <vector>
 #include <algorithm>
@@ -21,23 +20,10 @@ bool s3r_args_ok(const char* who, int n_cand, const S3rParams& a, const S3rOut& 
         (n_cand > 0 && (!a.rand_values || !o.ransac_max_its || !o.n_events)) || (n_cand > 0 && a.max_events > 0 && (!o.events || !o.inlier_flags))) {
         corb_set_error("%s: bad argument (probability in (0, 1), min_inliers >= 3, 1 <= max_iterations <= %d)", who, S3R_MAX_ITERATIONS); return false;
     }
-    const size_t nr = (size_t)n_cand * a.max_iterations * 3;
-    for (size_t i = 0; i < nr; i++) if (a.rand_values[i] < 0) { corb_set_error("%s: rand_values[%zu] is outside [0, 2^31)", who, i); return false; }
-    return true;
+    return ransac_rand_values_ok(who, a.rand_values, (size_t)n_cand * a.max_iterations * 3);
 }
-// SetRansacParameters (:114-138) with the reference's own expression and the host's libm; 0 = iterate() sets bNoMore at once (:146-150)
-int s3r_cap(int N, const S3rParams& a)
-{
-    if (N < a.min_inliers) return 0;
-    int nIterations;
-    if (a.min_inliers == N) nIterations = 1;
-    else {
-        const float epsilon = (float)a.min_inliers / N;
-        const double x = std::ceil(std::log(1 - a.probability) / std::log(1 - std::pow((double)epsilon, 3.0)));
-        nIterations = !(x < (double)a.max_iterations) ? a.max_iterations : (x < 1 ? 1 : (int)x);
-    }
-    return std::max(1, std::min(nIterations, a.max_iterations));
-}
+// SetRansacParameters (:114-138): epsilon = (float)nMinInliers / N (N >= 1 wherever it is read)
+int s3r_cap(int N, const S3rParams& a) { return ransac_iteration_cap(N, a.min_inliers, (float)a.min_inliers / std::max(N, 1), a.probability, a.max_iterations); }
 // iterate() (:158-201) over the counts c_i of one candidate: iteration i returns iff c_i > minInliers and c_i >= max_{j<i} c_j.  hyp / mask: this candidate's
 // read-back; index1 (record route): mvnIndices1, through which the flags are scattered (:195-197).
 void s3r_events(int c, int N, int cap_its, const S3rHyp* hyp, const unsigned long long* mask, int words, const int* index1, const S3rParams& a, const S3rOut& o)
@@ -55,9 +41,7 @@ void s3r_events(int c, int N, int cap_its, const S3rHyp* hyp, const unsigned lon
             CorbSim3RansacEvent& e = o.events[(size_t)c * a.max_events + n_ev];
             e.iteration = i + 1; e.n_inliers = ci; e.s12 = hyp[i].s;
             memcpy(e.R12, hyp[i].R, sizeof(e.R12)); memcpy(e.t12, hyp[i].t, sizeof(e.t12));
-            uint8_t* fl = o.inlier_flags + ((size_t)c * a.max_events + n_ev) * o.flags_stride;
-            const unsigned long long* m = mask + (size_t)i * words;
-            for (int k = 0; k < N; k++) if ((m[k >> 6] >> (k & 63)) & 1ull) { const int f = index1 ? index1[k] : k; if (f >= 0 && f < o.flags_stride) fl[f] = 1; }
+            ransac_scatter_flags(mask + (size_t)i * words, N, index1, o.flags_stride, o.inlier_flags + ((size_t)c * a.max_events + n_ev) * o.flags_stride);
         }
         n_ev++;
     }
@@ -72,26 +56,6 @@ void s3r_clear(int n_cand, const S3rParams& a, const S3rOut& o)
     }
     if (o.counts) memset(o.counts, 0, (size_t)n_cand * a.max_iterations * 4);
     if (o.q_out) memset(o.q_out, 0, (size_t)n_cand * a.max_iterations * 16);
-}
-// the call's buffers behind the uploads, the launches, and the one read-back (index1 only on the record route).  Nothing is preset: the host reads a hypothesis only where
-// N >= min_inliers and the iteration is below the cap, which the kernel has written, and index1 below N
-int s3r_run(CorbScratch& pool, S3rDev& d, int grid_its, std::vector<int>& h_n, std::vector<S3rHyp>& h_hyp, std::vector<unsigned long long>& h_mask, std::vector<int>* h_index1)
-{
-    const size_t slots = (size_t)d.n_cand * d.cap, nh = (size_t)d.n_cand * d.max_its;
-    d.words = (d.cap + 63) / 64;
-    HIPCHK(pool.alloc(&d.corr, slots)); HIPCHK(pool.alloc(&d.hyp, nh)); HIPCHK(pool.alloc(&d.mask, nh * d.words));
-    int* scan_scratch = nullptr;
-    if (d.kf1) {
-        HIPCHK(pool.alloc(&d.dense, slots)); HIPCHK(pool.alloc(&d.flag, slots + 1)); HIPCHK(pool.alloc(&d.scan, slots + 1)); HIPCHK(pool.alloc(&d.index1, slots));
-        HIPCHK(pool.alloc(&d.ncorr, (size_t)d.n_cand)); HIPCHK(pool.alloc(&scan_scratch, corb_scan_scratch_ints(slots)));
-    }
-    corb_launch_sim3_ransac(d, grid_its, scan_scratch, pool.stream);
-    HIPCHK(hipGetLastError());
-    h_hyp.resize(nh); h_mask.resize(nh * d.words); h_n.resize((size_t)d.n_cand);
-    HIPCHK(pool.d2h(h_hyp.data(), d.hyp, nh * sizeof(S3rHyp))); HIPCHK(pool.d2h(h_mask.data(), d.mask, nh * d.words * 8));
-    if (d.kf1) { HIPCHK(pool.d2h(h_n.data(), d.ncorr, (size_t)d.n_cand * 4)); h_index1->resize(slots); HIPCHK(pool.d2h(h_index1->data(), d.index1, slots * 4)); }
-    HIPCHK(pool.fetch_finish());
-    return CORB_OK;
 }
 }  // namespace
 
@@ -131,10 +95,10 @@ extern "C" int corb_sim3_ransac(const CorbSim3RansacProblem* problems, int n_pro
     CorbScratch pool(0);
     S3rDev d; memset(&d, 0, sizeof(d));
     d.n_cand = n_problems; d.cap = cap; d.max_its = max_iterations; d.min_inliers = min_inliers; d.fix_scale = a.fix_scale;
-    HIPCHK(pool.upload_block({{(void**)&d.cand, cand.data(), cand.size() * sizeof(S3rCand)}, {(void**)&d.in, in.data(), rows * 32}, {(void**)&d.ncorr, h_n.data(), h_n.size() * 4},
+    HIPCHK(pool.upload_block({{(void**)&d.cand, cand.data(), cand.size() * sizeof(S3rCand)}, {(void**)&d.in, in.data(), rows * 32}, {(void**)&d.set.ncorr, h_n.data(), h_n.size() * 4},
                               {(void**)&d.rand_values, rand_values, (size_t)n_problems * max_iterations * 12}}));
-    static thread_local std::vector<S3rHyp> h_hyp; static thread_local std::vector<unsigned long long> h_mask; std::vector<int> n_dev;
-    rc = s3r_run(pool, d, grid_its, n_dev, h_hyp, h_mask, nullptr); if (rc) return rc;
+    static thread_local std::vector<S3rHyp> h_hyp; static thread_local std::vector<unsigned long long> h_mask;
+    rc = ransac_run<S3rHyp>(pool, d, false, (size_t)n_problems * max_iterations, corb_launch_sim3_ransac, grid_its, {{&d.out, &h_hyp, &h_mask}}, nullptr, nullptr); if (rc) return rc;
     for (int c = 0; c < n_problems; c++)
         s3r_events(c, h_n[c], cand[c].its, h_hyp.data() + (size_t)c * max_iterations, h_mask.data() + (size_t)c * max_iterations * d.words, d.words, nullptr, a, o);
     return CORB_OK;
@@ -159,8 +123,7 @@ extern "C" int corb_sim3_ransac_store(CorbKfStore* kf, int slot1, const int32_t*
     const S3rOut o{ransac_max_its, n_events, events, inlier_flags, n1, counts, q_out};
     if (!s3r_args_ok(who, n_candidates, a, o)) return CORB_ERR_ARG;
     s3r_clear(n_candidates, a, o);
-    for (int c = 0; c < n_candidates; c++) n_corr[c] = 0;
-    if (index1) for (size_t i = 0; i < (size_t)n_candidates * n1; i++) index1[i] = -1;
+    ransac_corr_preset(n_candidates, n1, n_corr, index1);
     if (n_candidates == 0 || n1 == 0) return CORB_OK;
     rc = call.join(); if (rc) return rc;
     std::vector<S3rCand> cand((size_t)n_candidates);
@@ -178,13 +141,11 @@ extern "C" int corb_sim3_ransac_store(CorbKfStore* kf, int slot1, const int32_t*
     HIPCHK(pool.upload_block({{(void**)&d.cand, cand.data(), cand.size() * sizeof(S3rCand)}, {(void**)&d.matched12, matched12_ids, (size_t)n_candidates * n1 * 8},
                               {(void**)&d.rand_values, rand_values, (size_t)n_candidates * max_iterations * 12}}));
     static thread_local std::vector<S3rHyp> h_hyp; static thread_local std::vector<unsigned long long> h_mask; std::vector<int> h_n, h_index1;
-    rc = s3r_run(pool, d, max_iterations, h_n, h_hyp, h_mask, &h_index1); if (rc) return rc;
+    rc = ransac_run<S3rHyp>(pool, d, true, (size_t)n_candidates * max_iterations, corb_launch_sim3_ransac, max_iterations, {{&d.out, &h_hyp, &h_mask}}, &h_n, &h_index1); if (rc) return rc;
     for (int c = 0; c < n_candidates; c++) {
-        const int N = std::min(std::max(h_n[c], 0), n1);
-        n_corr[c] = N;
-        const int* ix = h_index1.data() + (size_t)c * n1;
-        if (index1) for (int k = 0; k < N; k++) index1[(size_t)c * n1 + k] = ix[k];
-        s3r_events(c, N, s3r_cap(N, a), h_hyp.data() + (size_t)c * max_iterations, h_mask.data() + (size_t)c * max_iterations * d.words, d.words, ix, a, o);
+        const int N = ransac_corr_out(h_n.data(), h_index1.data(), c, n1, n_corr, index1);
+        s3r_events(c, N, s3r_cap(N, a), h_hyp.data() + (size_t)c * max_iterations, h_mask.data() + (size_t)c * max_iterations * d.words, d.words,
+                   h_index1.data() + (size_t)c * n1, a, o);
     }
     return CORB_OK;
 }

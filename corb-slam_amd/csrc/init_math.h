@@ -13,6 +13,7 @@
 #include <math.h>
 #include <stdint.h>
 #include <string.h>
+#include "ransac_common.h"
 
 #if defined(__HIPCC__)
 #define INIT_HD __host__ __device__ __forceinline__
@@ -174,22 +175,6 @@ INIT_HD void init_svd3(const float* M, InitSvdWork& S, float* U, float* w, float
     INIT_SYNC();
 }
 
-// the 8 draws of one iteration (:87-96): randi = int(rand() / 2^31 * size) over the shrinking vAvailableIndices, each pick replaced by the vector's back (pnp_draw's
-// text for a set of 8)
-INIT_HD void init_draw(const int* r, int N, int* idx)
-{
-    int pos[8], val[8];
-#pragma unroll
-    for (int k = 0; k < 8; k++) {
-        const int size = N - k;
-        const int randi = (int)(((double)r[k] * (1.0 / 2147483648.0)) * (double)size);
-        int v = randi, back = size - 1;
-#pragma unroll
-        for (int j = 0; j < k; j++) { if (pos[j] == randi) v = val[j]; if (pos[j] == size - 1) back = val[j]; }
-        idx[k] = v; pos[k] = randi; val[k] = back;
-    }
-}
-
 // ---- CheckHomography (:337-385) / CheckFundamental (:413-465) for one match: the two terms of the score, whether each is added, the inlier bit ----
 INIT_HD bool init_check_h(const float* h, const float* hi, const InitMatch& m, float invSigmaSquare, float* t1, bool* a1, float* t2, bool* a2)
 {
@@ -246,7 +231,7 @@ INIT_HD void init_hypothesis_body(const InitDev& d, int c, int it, int model, In
     const int N = P.N;
     const size_t h = ((size_t)c * d.max_iterations + it) * 2 + model;
     INIT_LANE0 {
-        init_draw(d.rand_values + ((size_t)c * d.max_iterations + it) * 8, N, W.idx);
+        ransac_draw<8>(d.rand_values + ((size_t)c * d.max_iterations + it) * 8, 8, N, W.idx);
         for (int k = 0; k < 8; k++) W.idx[k] = W.idx[k] < 0 ? 0 : (W.idx[k] > N - 1 ? N - 1 : W.idx[k]);      // (no effect on draws in [0, 2^31))
     }
     INIT_SYNC();

@@ -9,6 +9,7 @@
 // is a serial loop.
 #pragma once
 #include <math.h>
+#include "ransac_common.h"
 
 #if defined(__HIPCC__)
 #define PNP_HD __host__ __device__ __forceinline__
@@ -465,21 +466,4 @@ PNP_HD bool pnp_check_inlier(const double* R, const double* t, const PnpCorr& p,
     const float distX = (float)((double)p.u[0] - ue), distY = (float)((double)p.u[1] - ve);
     const float error2 = distX * distX + distY * distY;
     return error2 < p.max_err;
-}
-
-// the min_set draws of one iteration (:233-246): randi = int(rand() / 2^31 * size) over the shrinking vAvailableIndices, each pick replaced by the vector's back.
-// The vector is 0 .. N-1 apart from the at most min_set positions written so far, kept as (position, value) pairs; a position at or behind the new size is never read.
-PNP_HD void pnp_draw(const int* r, int min_set, int N, int* idx)
-{
-    int pos[8], val[8];
-#pragma unroll
-    for (int k = 0; k < 8; k++) {
-        if (k >= min_set) break;
-        const int size = N - k;
-        const int randi = (int)(((double)r[k] * (1.0 / 2147483648.0)) * (double)size);
-        int v = randi, back = size - 1;
-#pragma unroll
-        for (int j = 0; j < k; j++) { if (pos[j] == randi) v = val[j]; if (pos[j] == size - 1) back = val[j]; }
-        idx[k] = v; pos[k] = randi; val[k] = back;
-    }
 }

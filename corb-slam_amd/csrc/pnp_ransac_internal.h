@@ -4,6 +4,7 @@
 #include "store_internal.h"
 #include "device_util.h"
 #include "pnp_math.h"
+#include "ransac_common.h"
 
 // what one hypothesis, or one record's Refine(), leaves (mask words apart)
 struct PnrHyp { int count, pad; PnpPose pose; };
@@ -23,13 +24,10 @@ struct PnrDev {
     const char* kf; int F; float scale[CORB_MAX_LEVELS]; int nlevels;
     const char* mp_base; size_t mp_bytes; CorbIdTable idt;
     const unsigned long long* matched;    // [n_cand][cap] vpMapPointMatches as MapPoint ids
-    PnpCorr* dense; int* flag; int* scan; // [n_cand][cap] per feature: the correspondence, accepted or not, exclusive scan of the flags (+1 entry)
-    int* index;                           // [n_cand][cap] mvKeyPointIndices
     // both routes
-    PnpCorr* corr; int* ncorr;            // [n_cand][cap] the N accepted correspondences in ascending feature order; [n_cand] N
+    RansacCorrSet<PnpCorr> set;           // per feature of the frame; corr = the N accepted correspondences in ascending feature order, index = mvKeyPointIndices
     const int* rand_values;               // [n_cand][stride_its][min_set]
-    PnrHyp* hyp; unsigned long long* mask;            // [n_cand][stride_its], [n_cand][stride_its][words]
-    PnrHyp* ref; unsigned long long* ref_mask;        // the same for Refine(); written at records only
+    RansacHyps<PnrHyp> out, ref;          // [n_cand][stride_its]: the hypotheses, and the same for Refine() (written at records only)
 };
 // prepare (+ scan + compaction on the record route; scan_scratch: corb_scan_scratch_ints(n_cand * cap) ints), then one wavefront per (iteration, candidate) for the
 // hypotheses and again for Refine()

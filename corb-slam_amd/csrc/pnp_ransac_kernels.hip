@@ -31,7 +31,7 @@ __global__ __launch_bounds__(256) void pnp_ransac_prepare_kernel(PnrDev d)
         const float* r = d.in + 6 * ((size_t)cd.in_off + i);
         o.X[0] = r[0]; o.X[1] = r[1]; o.X[2] = r[2]; o.u[0] = r[3]; o.u[1] = r[4];
         o.max_err = r[5] * d.th2;
-        d.corr[e] = o;
+        d.set.corr[e] = o;
         return;
     }
     // the constructor's filter for feature i of the frame (:79-101): a match that the map's id index resolves to a record that is not bad
@@ -47,24 +47,15 @@ __global__ __launch_bounds__(256) void pnp_ransac_prepare_kernel(PnrDev d)
                 const int oc = min(max(kp.octave, 0), d.nlevels - 1);
                 o.X[0] = m->world_pos[0]; o.X[1] = m->world_pos[1]; o.X[2] = m->world_pos[2]; o.u[0] = kp.x; o.u[1] = kp.y;
                 o.max_err = (d.scale[oc] * d.scale[oc]) * d.th2;                                          // mvLevelSigma2 = scale^2 in float, times th2
-                d.dense[e] = o;
+                d.set.dense[e] = o;
                 ok = 1;
             }
         }
     }
-    d.flag[e] = ok;
+    d.set.flag[e] = ok;
 }
 
-__global__ __launch_bounds__(256) void pnp_ransac_compact_kernel(PnrDev d)
-{
-    const int i = blockIdx.x * 256 + threadIdx.x, c = blockIdx.y;
-    const size_t base = (size_t)c * d.cap;
-    if (i == 0) d.ncorr[c] = d.scan[base + d.cap] - d.scan[base];
-    if (i >= d.cap || !d.flag[base + i]) return;
-    const int k = d.scan[base + i] - d.scan[base];
-    d.corr[base + k] = d.dense[base + i];
-    d.index[base + k] = i;
-}
+__global__ __launch_bounds__(256) void pnp_ransac_compact_kernel(PnrDev d) { ransac_compact(d.set, d.cap); }
 
 // mRansacMinInliers after SetRansacParameters' adjustment (:179-184): int(N * epsilon) is a float product, truncated
 __device__ __forceinline__ int pnr_min_inliers(int N, const PnrDev& d) { return max(max((int)((float)N * d.epsilon), d.min_inliers), d.min_set); }
@@ -77,7 +68,6 @@ __device__ __forceinline__ void pnr_intrinsics(const PnrDev& d, const PnrCand& c
 // CheckInliers (:353-384) over the N correspondences of a candidate with the pose the workgroup holds in LDS; the count comes back in every lane
 __device__ __forceinline__ int pnr_check_inliers(const PnpPose& pose, const double* K, const PnpCorr* corr, int N, int words, unsigned long long* mask)
 {
-    const int lane = threadIdx.x;
     double R[9], t[3], Kr[4];
 #pragma unroll
     for (int k = 0; k < 9; k++) R[k] = pose.R[k];
@@ -85,16 +75,7 @@ __device__ __forceinline__ int pnr_check_inliers(const PnpPose& pose, const doub
     for (int k = 0; k < 3; k++) t[k] = pose.t[k];
 #pragma unroll
     for (int k = 0; k < 4; k++) Kr[k] = K[k];
-    int count = 0;
-    for (int w = 0; w < words; w++) {
-        const int i = w * 64 + lane;
-        bool in = false;
-        if (i < N) in = pnp_check_inlier(R, t, corr[i], Kr);
-        const unsigned long long bits = __ballot(in);
-        if (lane == 0) mask[w] = bits;
-        count += __popcll(bits);
-    }
-    return count;
+    return ransac_inlier_words(N, words, mask, [&](int i) { return pnp_check_inlier(R, t, corr[i], Kr); });
 }
 
 struct PnrShared { PnpWork W; PnpPose pose; double K[4]; int idx[8]; };
@@ -103,12 +84,12 @@ __global__ __launch_bounds__(64) void pnp_ransac_hypothesis_kernel(PnrDev d)
 {
     const int it = blockIdx.x, c = blockIdx.y, lane = threadIdx.x;
     const PnrCand& cd = d.cand[c];
-    const int N = min(d.ncorr[c], d.cap);
+    const int N = min(d.set.ncorr[c], d.cap);
     if (it >= cd.its || it >= d.stride_its || N < pnr_min_inliers(N, d)) return;                    // (wave-uniform; mRansacMinInliers >= min_set)
     __shared__ PnrShared sh;
-    const PnpCorr* corr = d.corr + (size_t)c * d.cap;
+    const PnpCorr* corr = d.set.corr + (size_t)c * d.cap;
     if (lane == 0) {
-        pnp_draw(d.rand_values + (size_t)d.min_set * ((size_t)c * d.stride_its + it), d.min_set, N, sh.idx);
+        ransac_draw<8>(d.rand_values + (size_t)d.min_set * ((size_t)c * d.stride_its + it), d.min_set, N, sh.idx);
         for (int k = 0; k < d.min_set; k++) sh.idx[k] = min(max(sh.idx[k], 0), N - 1);
         pnr_intrinsics(d, cd, sh.K);
     }
@@ -117,33 +98,33 @@ __global__ __launch_bounds__(64) void pnp_ransac_hypothesis_kernel(PnrDev d)
     pnp_compute_pose(S, sh.K, sh.W, sh.pose);
     __syncthreads();
     const size_t h = (size_t)c * d.stride_its + it;
-    const int count = pnr_check_inliers(sh.pose, sh.K, corr, N, d.words, d.mask + h * d.words);
-    if (lane == 0) { d.hyp[h].count = count; d.hyp[h].pad = 0; d.hyp[h].pose = sh.pose; }
+    const int count = pnr_check_inliers(sh.pose, sh.K, corr, N, d.words, d.out.mask + h * d.words);
+    if (lane == 0) { d.out.hyp[h].count = count; d.out.hyp[h].pad = 0; d.out.hyp[h].pose = sh.pose; }
 }
 
 __global__ __launch_bounds__(64) void pnp_ransac_refine_kernel(PnrDev d)
 {
     const int it = blockIdx.x, c = blockIdx.y, lane = threadIdx.x;
     const PnrCand& cd = d.cand[c];
-    const int N = min(d.ncorr[c], d.cap), m = pnr_min_inliers(N, d);
+    const int N = min(d.set.ncorr[c], d.cap), m = pnr_min_inliers(N, d);
     if (it >= cd.its || it >= d.stride_its || N < m) return;
     // a record?  c_i >= m and c_i > every earlier c_j >= m
-    const PnrHyp* hyp = d.hyp + (size_t)c * d.stride_its;
+    const PnrHyp* hyp = d.out.hyp + (size_t)c * d.stride_its;
     const int ci = hyp[it].count;
     if (ci < m) return;
     bool beaten = false;
     for (int j = lane; j < it; j += 64) { const int cj = hyp[j].count; beaten = beaten || (cj >= m && cj >= ci); }
     if (__ballot(beaten) != 0ull) return;
     __shared__ PnrShared sh;
-    const PnpCorr* corr = d.corr + (size_t)c * d.cap;
+    const PnpCorr* corr = d.set.corr + (size_t)c * d.cap;
     if (lane == 0) pnr_intrinsics(d, cd, sh.K);
     __syncthreads();
     const size_t h = (size_t)c * d.stride_its + it;
-    const PnpMaskSet S{corr, d.mask + h * d.words, d.words, ci};
+    const PnpMaskSet S{corr, d.out.mask + h * d.words, d.words, ci};
     pnp_compute_pose(S, sh.K, sh.W, sh.pose);
     __syncthreads();
-    const int count = pnr_check_inliers(sh.pose, sh.K, corr, N, d.words, d.ref_mask + h * d.words);
-    if (lane == 0) { d.ref[h].count = count; d.ref[h].pad = 0; d.ref[h].pose = sh.pose; }
+    const int count = pnr_check_inliers(sh.pose, sh.K, corr, N, d.words, d.ref.mask + h * d.words);
+    if (lane == 0) { d.ref.hyp[h].count = count; d.ref.hyp[h].pad = 0; d.ref.hyp[h].pose = sh.pose; }
 }
 
 }  // namespace
@@ -151,12 +132,7 @@ __global__ __launch_bounds__(64) void pnp_ransac_refine_kernel(PnrDev d)
 void corb_launch_pnp_ransac(const PnrDev& d, int grid_its, int* scan_scratch, hipStream_t s)
 {
     if (d.n_cand <= 0 || d.cap <= 0) return;
-    const dim3 per_corr((d.cap + 255) / 256, d.n_cand);
-    hipLaunchKernelGGL(pnp_ransac_prepare_kernel, per_corr, dim3(256), 0, s, d);
-    if (d.kf) {
-        corb_launch_exclusive_scan(d.flag, d.scan, (size_t)d.n_cand * d.cap, scan_scratch, s);
-        hipLaunchKernelGGL(pnp_ransac_compact_kernel, per_corr, dim3(256), 0, s, d);
-    }
+    ransac_launch_corr_set(pnp_ransac_prepare_kernel, pnp_ransac_compact_kernel, d, d.kf != nullptr, scan_scratch, s);
     if (grid_its <= 0) return;
     hipLaunchKernelGGL(pnp_ransac_hypothesis_kernel, dim3(grid_its, d.n_cand), dim3(64), 0, s, d);
     hipLaunchKernelGGL(pnp_ransac_refine_kernel, dim3(grid_its, d.n_cand), dim3(64), 0, s, d);

@@ -3,6 +3,7 @@
 #include "corb_internal.h"
 #include "store_internal.h"
 #include "device_util.h"
+#include "ransac_common.h"
 
 // one correspondence as CheckInliers reads it: mvX3Dc1 / mvX3Dc2, mvP1im1 / mvP2im2, mvnMaxError1 / mvnMaxError2 (the truncated integers, held as floats)
 struct S3rCorr { float x1[3], x2[3], p1[2], p2[2], th1, th2; };
@@ -25,12 +26,10 @@ struct S3rDev {
     const char* kf1; int F; float scale1[CORB_MAX_LEVELS]; int nlevels1;
     const char* mp_base; size_t mp_bytes; int max_obs; CorbIdTable idt;
     const unsigned long long* matched12;  // [n_cand][cap] vpMatched12 as MapPoint ids
-    S3rCorr* dense; int* flag; int* scan; // [n_cand][cap] per feature of keyframe 1: the correspondence, accepted or not, exclusive scan of the flags (+1 entry)
-    int* index1;                          // [n_cand][cap] mvnIndices1
     // both routes
-    S3rCorr* corr; int* ncorr;            // [n_cand][cap] the N accepted correspondences in ascending i1; [n_cand] N
+    RansacCorrSet<S3rCorr> set;           // per feature of keyframe 1; corr = the N accepted correspondences in ascending i1, index = mvnIndices1
     const int* rand_values;               // [n_cand][max_its][3]
-    S3rHyp* hyp; unsigned long long* mask;      // [n_cand][max_its], [n_cand][max_its][words]
+    RansacHyps<S3rHyp> out;               // [n_cand][max_its]
 };
 // prepare (+ scan + compaction on the record route; scan_scratch: corb_scan_scratch_ints(n_cand * cap) ints), then one wavefront per (candidate, iteration)
 void corb_launch_sim3_ransac(const S3rDev& d, int grid_its, int* scan_scratch, hipStream_t s);

@@ -68,7 +68,7 @@ __global__ __launch_bounds__(256) void sim3_ransac_prepare_kernel(S3rDev d)
         for (int k = 0; k < 3; k++) { o.x1[k] = r[k]; o.x2[k] = r[3 + k]; }
         o.th1 = s3r_threshold(r[6]); o.th2 = s3r_threshold(r[7]);
         s3r_project(o.x1, K1, o.p1); s3r_project(o.x2, K2, o.p2);
-        d.corr[e] = o;
+        d.set.corr[e] = o;
         return;
     }
     // the constructor's filter for feature i1 = i of keyframe 1 (:64-79)
@@ -94,37 +94,16 @@ __global__ __launch_bounds__(256) void sim3_ransac_prepare_kernel(S3rDev d)
                         o.x2[k] = s3r_row(h2->m.Tcw + 4 * k, m2->world_pos, h2->m.Tcw[4 * k + 3]);
                     }
                     s3r_project(o.x1, K1, o.p1); s3r_project(o.x2, K2, o.p2);
-                    d.dense[e] = o;
+                    d.set.dense[e] = o;
                     ok = 1;
                 }
             }
         }
     }
-    d.flag[e] = ok;
+    d.set.flag[e] = ok;
 }
 
-__global__ __launch_bounds__(256) void sim3_ransac_compact_kernel(S3rDev d)
-{
-    const int i = blockIdx.x * 256 + threadIdx.x, c = blockIdx.y;
-    const size_t base = (size_t)c * d.cap;
-    if (i == 0) d.ncorr[c] = d.scan[base + d.cap] - d.scan[base];
-    if (i >= d.cap || !d.flag[base + i]) return;
-    const int k = d.scan[base + i] - d.scan[base];
-    d.corr[base + k] = d.dense[base + i];
-    d.index1[base + k] = i;
-}
-
-// The one statement of the draw rule (:163-177 with DUtils::Random::RandomInt): randi = int(rand() / (RAND_MAX + 1.0) * size) over the shrinking vAvailableIndices,
-// RAND_MAX + 1 = 2^31, each pick replaced by the vector's back.  After the first removal position p0 holds N - 1; after the second, position p1 holds what N - 2 held.
-__device__ __forceinline__ void s3r_draw(int r0, int r1, int r2, int N, int* idx)
-{
-    const double inv = 1.0 / 2147483648.0;
-    const int p0 = (int)(((double)r0 * inv) * (double)N), p1 = (int)(((double)r1 * inv) * (double)(N - 1)), p2 = (int)(((double)r2 * inv) * (double)(N - 2));
-    const int back = (N - 2 == p0) ? N - 1 : N - 2;
-    idx[0] = p0;
-    idx[1] = (p1 == p0) ? N - 1 : p1;
-    idx[2] = (p2 == p1) ? back : ((p2 == p0) ? N - 1 : p2);
-}
+__global__ __launch_bounds__(256) void sim3_ransac_compact_kernel(S3rDev d) { ransac_compact(d.set, d.cap); }
 
 // ComputeCentroid (:215-224): cv::reduce sums a row in float, left to right; C / P.cols multiplies by the double 1.0 / 3 and rounds once
 __device__ __forceinline__ void s3r_centroid(const float P[3][3], float Pr[3][3], float* C)
@@ -292,11 +271,11 @@ __global__ __launch_bounds__(64) void sim3_ransac_hypothesis_kernel(S3rDev d)
 {
     const int it = blockIdx.x, c = blockIdx.y, lane = threadIdx.x;
     const S3rCand& cd = d.cand[c];
-    const int N = min(d.ncorr[c], d.cap);
+    const int N = min(d.set.ncorr[c], d.cap);
     if (it >= cd.its || it >= d.max_its || N < d.min_inliers || N < 3) return;          // (wave-uniform)
-    const S3rCorr* corr = d.corr + (size_t)c * d.cap;
+    const S3rCorr* corr = d.set.corr + (size_t)c * d.cap;
     const int* rv = d.rand_values + 3 * ((size_t)c * d.max_its + it);
-    int idx[3]; s3r_draw(rv[0], rv[1], rv[2], N, idx);
+    int idx[3]; ransac_draw<3>(rv, 3, N, idx);
     float P1[3][3], P2[3][3];
 #pragma unroll
     for (int k = 0; k < 3; k++) {
@@ -322,31 +301,24 @@ __global__ __launch_bounds__(64) void sim3_ransac_hypothesis_kernel(S3rDev d)
     }
     float K1[4], K2[4]; s3r_intrinsics(d, cd, K1, K2);
     // CheckInliers (:340-364): the lanes stride over the correspondences; NaN compares false
-    unsigned long long* mask = d.mask + ((size_t)c * d.max_its + it) * d.words;
-    int count = 0;
-    for (int w = 0; w < d.words; w++) {
-        const int i = w * 64 + lane;
-        bool in = false;
-        if (ok && i < N) {
-            const S3rCorr p = corr[i];
-            float X[3], uv[2];
+    const size_t e = (size_t)c * d.max_its + it;
+    const int count = ransac_inlier_words(N, d.words, d.out.mask + e * d.words, [&](int i) {
+        if (!ok) return false;
+        const S3rCorr p = corr[i];
+        float X[3], uv[2];
 #pragma unroll
-            for (int k = 0; k < 3; k++) X[k] = s3r_row(sR[k], p.x2, h.t[k]);
-            s3r_project(X, K1, uv);
-            const float d1x = p.p1[0] - uv[0], d1y = p.p1[1] - uv[1];
-            const float err1 = (float)((double)d1x * (double)d1x + (double)d1y * (double)d1y);
+        for (int k = 0; k < 3; k++) X[k] = s3r_row(sR[k], p.x2, h.t[k]);
+        s3r_project(X, K1, uv);
+        const float d1x = p.p1[0] - uv[0], d1y = p.p1[1] - uv[1];
+        const float err1 = (float)((double)d1x * (double)d1x + (double)d1y * (double)d1y);
 #pragma unroll
-            for (int k = 0; k < 3; k++) X[k] = s3r_row(sRinv[k], p.x1, tinv[k]);
-            s3r_project(X, K2, uv);
-            const float d2x = uv[0] - p.p2[0], d2y = uv[1] - p.p2[1];
-            const float err2 = (float)((double)d2x * (double)d2x + (double)d2y * (double)d2y);
-            in = err1 < p.th1 && err2 < p.th2;
-        }
-        const unsigned long long bits = __ballot(in);
-        if (lane == 0) mask[w] = bits;
-        count += __popcll(bits);
-    }
-    if (lane == 0) { h.count = count; d.hyp[(size_t)c * d.max_its + it] = h; }
+        for (int k = 0; k < 3; k++) X[k] = s3r_row(sRinv[k], p.x1, tinv[k]);
+        s3r_project(X, K2, uv);
+        const float d2x = uv[0] - p.p2[0], d2y = uv[1] - p.p2[1];
+        const float err2 = (float)((double)d2x * (double)d2x + (double)d2y * (double)d2y);
+        return err1 < p.th1 && err2 < p.th2;
+    });
+    if (lane == 0) { h.count = count; d.out.hyp[e] = h; }
 }
 
 }  // namespace
@@ -354,11 +326,6 @@ __global__ __launch_bounds__(64) void sim3_ransac_hypothesis_kernel(S3rDev d)
 void corb_launch_sim3_ransac(const S3rDev& d, int grid_its, int* scan_scratch, hipStream_t s)
 {
     if (d.n_cand <= 0 || d.cap <= 0) return;
-    const dim3 per_corr((d.cap + 255) / 256, d.n_cand);
-    hipLaunchKernelGGL(sim3_ransac_prepare_kernel, per_corr, dim3(256), 0, s, d);
-    if (d.kf1) {
-        corb_launch_exclusive_scan(d.flag, d.scan, (size_t)d.n_cand * d.cap, scan_scratch, s);
-        hipLaunchKernelGGL(sim3_ransac_compact_kernel, per_corr, dim3(256), 0, s, d);
-    }
+    ransac_launch_corr_set(sim3_ransac_prepare_kernel, sim3_ransac_compact_kernel, d, d.kf1 != nullptr, scan_scratch, s);
     if (grid_its > 0) hipLaunchKernelGGL(sim3_ransac_hypothesis_kernel, dim3(grid_its, d.n_cand), dim3(64), 0, s, d);
 }

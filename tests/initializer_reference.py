@@ -6,7 +6,8 @@ OpenCV calls the reference cannot pin are those of DESIGN.md section 2 and this 
 a float product = double accumulation in ascending k, one rounding.  The functions are vectorised over hypotheses or matches (leading axis)."""
 import math
 import numpy as np
-from pnpsolver_reference import hestenes, draw_set, _quiet, SV_DROP, RAND_RANGE
+from pnpsolver_reference import hestenes, _quiet, SV_DROP, RAND_RANGE
+from ransac_reference import draw_set
 
 f32, f64 = np.float32, np.float64
 OK, NO_MODEL, H_DEGENERATE, AMBIGUOUS, FEW_POINTS, LOW_PARALLAX = range(6)

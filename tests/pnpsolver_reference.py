@@ -6,6 +6,7 @@ their definition: cvSVD of a symmetric matrix = jacobi_eig (cyclic Jacobi, FP64)
 pseudo-inverse's drop rule.  NaN payloads and signs are not part of any reading."""
 import math
 import numpy as np
+from ransac_reference import draw_set, draw_set_literal          # the draws (:233-246): the shared rule and its literal emulation
 
 f32, f64 = np.float32, np.float64
 NO_MAP_POINT = 0xFFFFFFFFFFFFFFFF
@@ -40,31 +41,6 @@ def ransac_parameters(N, probability=0.99, min_inliers=8, max_iterations=300, mi
 def max_errors(sigma2, th2=5.991):
     """mvMaxError[i] = mvSigma2[i] * th2 (:199-201): a float product"""
     return (np.asarray(sigma2, f32) * f32(th2)).astype(f32)
-
-
-# ---- the draws (:233-246) ----
-def draw_set(r, min_set, N):
-    pos, val, out = [], [], []
-    for k in range(min_set):
-        size = N - k
-        randi = int(f64(int(r[k])) / f64(RAND_RANGE) * f64(size))
-        v, back = randi, size - 1
-        for j in range(k):
-            if pos[j] == randi:
-                v = val[j]
-            if pos[j] == size - 1:
-                back = val[j]
-        out.append(v); pos.append(randi); val.append(back)
-    return out
-
-
-def draw_set_literal(r, min_set, N):
-    avail = list(range(N)); out = []
-    for k in range(min_set):
-        randi = int((float(int(r[k])) / (float(RAND_RANGE - 1) + 1.0)) * len(avail))
-        out.append(avail[randi])
-        avail[randi] = avail[-1]; avail.pop()
-    return out
 
 
 # ---- the decompositions ----

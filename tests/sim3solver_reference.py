@@ -5,6 +5,7 @@ cannot pin (cv::eigen -> cyclic Jacobi in float64; atan2 + cv::Rodrigues -> the 
 definition.  compute_sim3(..., q=...) evaluates everything downstream of a GIVEN quaternion: the GPU tests pass the device's."""
 import math
 import numpy as np
+import ransac_reference
 
 f32, f64 = np.float32, np.float64
 NAN32 = np.array([0x7FC00000], np.uint32).view(np.float32)[0]
@@ -49,19 +50,12 @@ def problem(p1c, p2c, sigma2_1, sigma2_2, K1, K2):
 
 
 def draw_triple(r, N):
-    """three picks without replacement from vAvailableIndices = 0 .. N-1 (:163-177): randi = int(rand() / (RAND_MAX + 1.0) * size), the pick replaced by the back"""
-    p0, p1, p2 = [int(f64(int(r[k])) / f64(RAND_RANGE) * f64(N - k)) for k in range(3)]
-    back = N - 1 if N - 2 == p0 else N - 2
-    return p0, (N - 1 if p1 == p0 else p1), (back if p2 == p1 else (N - 1 if p2 == p0 else p2))
+    """three picks without replacement from vAvailableIndices = 0 .. N-1 (:163-177): ransac_reference's draw rule for a set of 3"""
+    return tuple(ransac_reference.draw_set(r, 3, N))
 
 
 def draw_triple_literal(r, N):
-    avail = list(range(N)); out = []
-    for k in range(3):
-        randi = int((float(int(r[k])) / (float(RAND_RANGE - 1) + 1.0)) * len(avail))
-        out.append(avail[randi])
-        avail[randi] = avail[-1]; avail.pop()
-    return tuple(out)
+    return tuple(ransac_reference.draw_set_literal(r, 3, N))
 
 
 def ransac_cap(N, probability=0.99, min_inliers=20, max_iterations=300):
