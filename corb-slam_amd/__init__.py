@@ -1443,7 +1443,7 @@ class Optimizer:
             _chk(load().corb_ba_solve_ex(C.byref(prob), nIterations, int(bRobust), None, C.byref(res), device, C.byref(opt)), "corb_ba_solve_ex")
         return dict(poses=oposes.reshape(-1, 4, 4), points=opoints, chi2=chi2[: res.iters_done + 1],
                     lam=lam[: res.iters_done], iters_done=res.iters_done, trials=res.trials_total,
-                    solver=res.solver_used, pcg_iterations=res.pcg_iterations,
+                    solver=res.solver_used, pcg_iterations=res.pcg_iterations, reserved0=res.reserved0,
                     structure=dict(free_poses=res.free_poses, free_points=res.free_points, active_edges=res.active_edges, nnz_blocks=res.nnz_blocks,
                                    schur_pairs=res.schur_pairs, pc_block=res.pc_block, pc_levels=res.pc_levels),
                     certificate=dict(pcg_residual_max=res.pcg_residual_max, pcg_residual_last=res.pcg_residual_last, grad_inf=res.grad_inf, pcg_refined_trials=res.pcg_refined_trials),
@@ -1471,7 +1471,10 @@ class Optimizer:
         sp = None if stop is None else (C.cast(C.byref(one), C.c_void_p) if stop == "before" else C.cast(C.byref(res, _BAResult.iters_done.offset), C.c_void_p))
         _chk(load().corb_ba_solve_staged(C.byref(prob), st, len(stages), sp, C.byref(res), _p(outl), device, C.byref(opt)), "corb_ba_solve_staged")
         return dict(poses=oposes.reshape(-1, 4, 4), points=opoints, outlier=outl[: len(edges)].copy(), iters_done=res.iters_done,
-                    trials=res.trials_total, ms_total=res.ms_total, device_route=bool(res.reserved0), solver=res.solver_used)
+                    trials=res.trials_total, ms_total=res.ms_total, device_route=bool(res.reserved0), solver=res.solver_used,
+                    pcg_iterations=res.pcg_iterations, pcg_refined_trials=res.pcg_refined_trials, reserved0=res.reserved0,
+                    structure=dict(free_poses=res.free_poses, free_points=res.free_points, active_edges=res.active_edges, nnz_blocks=res.nnz_blocks,
+                                   schur_pairs=res.schur_pairs, pc_block=res.pc_block, pc_levels=res.pc_levels))
 
     @staticmethod
     def LocalBundleAdjustment(*args, **kw):

@@ -24,7 +24,6 @@
 #include <vector>
 #include "host_util.h"
 
-#define BA_TRACE(what) do { static const bool t_ = getenv("CORB_BA_TRACE") != nullptr; if (t_) { fprintf(stderr, "[corb_ba trace] %s\n", what); fflush(stderr); } } while (0)
 struct Lap {                          // CORB_BA_TIMING=1: host-side phase times of a call on stderr (development aid)
     bool on; const char* fmt; std::chrono::steady_clock::time_point t;
     explicit Lap(const char* fmt_ = "[corb_ba] %-28s %8.2f ms\n") : on(getenv("CORB_BA_TIMING") != nullptr), fmt(fmt_), t(std::chrono::steady_clock::now()) {}

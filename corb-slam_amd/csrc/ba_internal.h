@@ -1,6 +1,12 @@
 // ba_internal.h -- device argument block of the bundle-adjustment kernels.
 #pragma once
 #include "corb_internal.h"
+#include <cstdio>
+#include <cstdlib>
+
+// CORB_BA_TRACE=1: launch and branch markers of a BA call on stderr (host code; development aid).  BA_TRACEF: the same with a printf format
+#define BA_TRACEF(...) do { static const bool t_ = getenv("CORB_BA_TRACE") != nullptr; if (t_) { fprintf(stderr, "[corb_ba trace] " __VA_ARGS__); fputc('\n', stderr); fflush(stderr); } } while (0)
+#define BA_TRACE(what) BA_TRACEF("%s", what)
 
 #define BA_EDGE_STRIDE 30     // doubles per edge: A'WA(6) -A'We(3) | JB = (sqrt(w) B)' (18) | r = -sqrt(w) e (3)      (B'WA, the 6x3 Hpl block, lives in hpl[e][18])
 

@@ -1111,6 +1111,7 @@ void ba_launch_backsub_update(const CorbBADev& d, double lambda, double* partial
 {
     const int nv = d.nP > d.nL ? d.nP : d.nL;
     const bool fused = bak && nv > 0 && nblk(nv) <= BA_FUSED_UPDATE_BLOCKS;
+    if (d.lean && d.nL > 0) BA_TRACE(d.backsub_rederive ? "backsub: re-derived from the estimates" : "backsub: stored V blocks (CORB_BA_BACKSUB_V)");
     if (d.nL > 0 && !(fused && d.lean)) { if (d.lean) hipLaunchKernelGGL(ba_backsub_lean_kernel, dim3(nblk(d.nL)), dim3(256), 0, s, d); else hipLaunchKernelGGL(ba_backsub_kernel, dim3(nblk(d.nL)), dim3(256), 0, s, d); }
     if (fused) {
         hipLaunchKernelGGL(ba_update_scale_kernel, dim3(nblk(nv)), dim3(256), 0, s, d, lambda, (ptrdiff_t)(bak - state), partial, scale_out, d.lean && d.nL > 0 ? 1 : 0);

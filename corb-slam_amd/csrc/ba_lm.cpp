@@ -80,6 +80,7 @@ int ba_lm_device(Pool& pool, BAFlat& f, const BAChoice& ch, int iterations, int 
             d.kfrec = kfrec; d.hpp_scratch = 1;
             // round 6: the V blocks in keyframe-list order (ba_v_kf_kernel) wherever the stream form of the row kernel runs; CORB_BA_V_EDGE keeps the edge order (A/B timing)
             static const bool v_edge = getenv("CORB_BA_V_EDGE") != nullptr || getenv("CORB_BA_ROW_UNITS") != nullptr;
+            BA_TRACE(v_edge ? "V blocks: edge order (CORB_BA_V_EDGE / CORB_BA_ROW_UNITS)" : "V blocks: keyframe-list order");
             if (!v_edge) {
                 int* vslot = nullptr; HIPCHK(pool.alloc(&vslot, (size_t)(nE ? nE : 1)));
                 d.v_kf = 1; d.n_list = n_pe; d.vslot = vslot;
@@ -118,6 +119,7 @@ int ba_lm_device(Pool& pool, BAFlat& f, const BAChoice& ch, int iterations, int 
             HIPCHK(pool.alloc(&d.units, (size_t)d.n_units + 1)); HIPCHK(pool.alloc(&d.upart, (size_t)d.n_units * 36 + 36)); HIPCHK(pool.alloc(&d.rpart, (size_t)d.n_wg * BA_ROW_WAVES * 6 + 6));
             ba_launch_rr_units(d, true, s);
             static const bool row_per_unit = getenv("CORB_BA_ROW_UNITS") != nullptr;       // (round 5's per-unit kernel, for A/B timing)
+            BA_TRACE(row_per_unit ? "row schur: per-unit kernel (CORB_BA_ROW_UNITS)" : "row schur: stream kernel");
             if (!row_per_unit) {
                 // round 6: every wavefront's rounds as one padded stream (ba_schur_row_stream_kernel)
                 const size_t nwv = (size_t)d.n_wg * BA_ROW_WAVES;
@@ -149,6 +151,7 @@ int ba_lm_device(Pool& pool, BAFlat& f, const BAChoice& ch, int iterations, int 
             // (pc_pack32, one workgroup per block) unless CORB_BA_PC_SQUARE asks for round 4's square form (a workgroup per 48 rows: for A/B timing)
             HIPCHK(pool.alloc(&d.pc_inv32, (size_t)d.pc_nblk * d.pc_gb * d.pc_gb));
             static const bool pc_square = getenv("CORB_BA_PC_SQUARE") != nullptr;
+            BA_TRACE(pc_square ? "pc step: square blocks (CORB_BA_PC_SQUARE)" : "pc step: packed upper triangles");
             d.pc_split = d.pc_gb / BA_PC_ROWS;
             if (!pc_square) { const int nt = d.pc_gb / 16; HIPCHK(pool.alloc(&d.pc_pack32, (size_t)d.pc_nblk * (nt * (nt + 1) / 2) * 256)); d.pc_split = 1; }
             d.cg_nparts = d.pc_nblk * d.pc_split;
@@ -228,6 +231,7 @@ int ba_lm_device(Pool& pool, BAFlat& f, const BAChoice& ch, int iterations, int 
                 (void)hipGraphDestroy(graph);
             }
     BA_TRACE("graph_launch");
+    BA_TRACE(no_graph ? "cg chunk: kernel by kernel (CORB_BA_NO_GRAPH)" : "cg chunk: graph replay");
             if (no_graph) ba_launch_pcg_chunk(d, n_it, s); else
             HIPCHK(hipGraphLaunch(pcg_graph[gi], s));
             HIPCHK(hipMemcpyAsync(h_flags, d.cg_flag, 2 * sizeof(int), hipMemcpyDeviceToHost, s));
@@ -301,7 +305,9 @@ int ba_lm_device(Pool& pool, BAFlat& f, const BAChoice& ch, int iterations, int 
     // at when a chain is enqueued (a chain of BA_LM_CHAIN iterations runs ~0.35 ms).
     static const bool no_chain = getenv("CORB_BA_NO_CHAIN") != nullptr;       // (the host-driven loop alone: for A/B timing)
     static const int chain_len = getenv("CORB_BA_CHAIN") ? std::max(1, std::min(BA_CHAIN_MAX, atoi(getenv("CORB_BA_CHAIN")))) : BA_LM_CHAIN;      // (for A/B timing)
-    const bool chain_ok = solver == 1 && small_solve && fused_update && d.lean && !phase_ev && sp > 0 && !no_chain;
+    const bool chain_able = solver == 1 && small_solve && fused_update && d.lean && !phase_ev && sp > 0;
+    const bool chain_ok = chain_able && !no_chain;
+    if (chain_able && !chain_ok) BA_TRACE("lm: host-driven loop (CORB_BA_NO_CHAIN)");
     BALMCtl* d_ctl = reuse ? work->d_ctl : nullptr;
     if (chain_ok && !d_ctl) HIPCHK(pool.alloc(&d_ctl, 1));
     if (work && !work->ready && solver == 1 && !fused_small) { work->d = d; work->d_partial = d_partial; work->d_scal = d_scal; work->d_chi_partial = d_chi_partial; work->d_ctl = d_ctl; work->ready = true; }
@@ -316,6 +322,7 @@ int ba_lm_device(Pool& pool, BAFlat& f, const BAChoice& ch, int iterations, int 
         if (chain_ok && (it > 0 || chain_begin) && chi2_fresh) {
             const bool begin = chain_begin; chain_begin = false;
             const int nb = std::min(iterations - it, chain_len);
+            BA_TRACEF("lm: device-decided chain of up to %d iterations", chain_len);
             BALMCtl* hc = reinterpret_cast<BALMCtl*>(static_cast<char*>(pool.pinned()) + 1024);
             BALMCtl* hr = reinterpret_cast<BALMCtl*>(static_cast<char*>(pool.pinned()) + 2048);
             memset(hc, 0, sizeof(BALMCtl));
@@ -340,6 +347,7 @@ int ba_lm_device(Pool& pool, BAFlat& f, const BAChoice& ch, int iterations, int 
                 // ... and the trial's decision (BALMCtl) is taken by the thread of that launch that files the chi2 (round 5: one launch less per trial)
                 static const bool ctl_launch = getenv("CORB_BA_CTL_LAUNCH") != nullptr;      // (the decision as its own one-thread launch, as in round 4: for A/B timing)
                 const int* cb = ctl_launch ? nullptr : d_bad;
+                if (j == 0) BA_TRACE(ctl_launch ? "lm ctl: its own launch (CORB_BA_CTL_LAUNCH)" : "lm ctl: in the chi2 launch");
                 if (nxt && d_chi_partial) ba_launch_build(dc, nullptr, s, d_chi_partial, d_scal + 0, cb, epoch);
                 else ba_launch_error(dc, d_partial, nparts, d_scal + 0, s, cb, epoch);
                 if (ctl_launch) ba_launch_lm_ctl(dc, d_scal, d_bad, epoch, s);

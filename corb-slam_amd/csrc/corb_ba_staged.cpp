@@ -122,6 +122,7 @@ static int single_pose_problem(const CorbBAProblem* p, int n_stages)
 bool corb_ba_staged_device_wanted(const CorbBAStage* stages, int n_stages)
 {
     static const bool host_route = getenv("CORB_LBA_HOST_FLATTEN") != nullptr;      // (the round-4 route -- problem to the host, host flattening --: for A/B timing)
+    if (host_route) BA_TRACE("window: host flattening (CORB_LBA_HOST_FLATTEN)");
     if (host_route || n_stages < 1 || n_stages > FLAT_MAX_STAGES) return false;     // (flat_launch_fixed_edge_outliers replays every stage that ran)
     for (int s = 1; s < n_stages; s++) if (stages[s].reset_estimates) return false;
     return true;
@@ -156,6 +157,7 @@ static int ba_staged_window(BASession& sess, const CorbBADeviceProblem* dp, cons
     BAChoice ch; rc = ba_choose(opt, nP, nE, nL, ch); if (rc) return rc;
     if (ch.solver != 1 || ch.fused_small) return CORB_OK;
     *applicable = 1;
+    BA_TRACE("window: device flattening");
     { const int nnzb = r->nnz_blocks; ba_result_reset(r); r->nnz_blocks = nnzb; }      // (left as it is until the pattern below is laid out)
     r->solver_used = ch.solver; r->free_poses = nP; r->free_points = nL; r->pc_block = 0; r->active_edges = nE; r->reserved0 = 1;      // (the device route ran)
     double* chi_hist = r->chi2; double* lam_hist = r->lambda; r->chi2 = nullptr; r->lambda = nullptr;     // histories are per optimize() call
@@ -322,6 +324,7 @@ extern "C" int corb_ba_solve_staged(const CorbBAProblem* p, const CorbBAStage* s
         bool resets = false; for (int s = 1; s < n_stages; s++) resets = resets || stages[s].reset_estimates != 0;
         static const bool host_stages = getenv("CORB_BA_HOST_STAGES") != nullptr;      // (the classifications on the host, as before round 5: for A/B timing)
         sess.want_dev = n_stages > 1 && !resets && !host_stages; sess.n_sets = n_stages + 1;
+        if (n_stages > 1 && !resets) BA_TRACE(host_stages ? "stages: classified on the host (CORB_BA_HOST_STAGES)" : "stages: classified on the device");
     }
     int n_opt = 0;                                         // optimize() calls done
     for (int s = 0; s < n_stages; s++) {

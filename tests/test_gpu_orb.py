@@ -240,3 +240,34 @@ def test_many_frames_match_oracle(corb, pyorc, synth):
         assert np.array_equal(out["u_right"].view(np.uint32), ur.view(np.uint32)), "mvuRight, frame %d" % s
         assert np.array_equal(out["depth"].view(np.uint32), dp.view(np.uint32)) and out["n_matched"] == nm, "mvDepth, frame %d" % s
     sf.close()
+
+
+def _parts_run(corb, P, n):
+    sf = corb.StereoFrontend(nfeatures=800, scaleFactor=1.3, nlevels=5, iniThFAST=15, minThFAST=5, width=P.shape[3], height=P.shape[2], max_frames=n)
+    sf.upload_batch(0, P); sf.run(n); sf.sync()
+    out = sf.fetch_batch(0, n)
+    sf.close()
+    # entries beyond an image's count are not results: the handle's buffers are not cleared, so those slots hold whatever the device memory held (the other tests
+    # slice [:n]); they are zeroed here so that the whole fetch_batch arrays can be compared as bytes
+    for i, c in enumerate(out["counts"]):
+        out["kp"][i, c:] = np.zeros((), out["kp"].dtype); out["desc"][i, c:] = 0
+    for f in range(n):
+        out["u_right"][f, out["counts"][2 * f]:] = 0; out["depth"][f, out["counts"][2 * f]:] = 0
+    return out
+
+
+@pytest.mark.parametrize("n", [5, 17])
+def test_parts_switch_gives_the_same_bytes(corb, synth, monkeypatch, n):
+    """CORB_PARTS (read when a handle is created) = 1, 3, 4 against the default's two part-batches, on frames of 403 x 263: the odd width and height put partial groups
+    on every level, and neither 5 nor 17 divides by 3 or 4.  Five frames stay below CORB_SPLIT_MIN (32 images: the run is not split, whatever the switch says);
+    seventeen frames are 34 images, which every value above 1 cuts into parts of unequal size."""
+    pairs = [synth.stereo_pair(40 + i, 403, 263) for i in range(5)]
+    P = np.ascontiguousarray(np.stack([np.stack(pairs[i % 5]) for i in range(n)]))
+    monkeypatch.delenv("CORB_PARTS", raising=False)
+    want = _parts_run(corb, P, n)
+    assert want["counts"].min() > 0 and want["n_matched"].min() > 0
+    for v in ("1", "3", "4"):
+        monkeypatch.setenv("CORB_PARTS", v)
+        got = _parts_run(corb, P, n)
+        for k in want:
+            assert got[k].tobytes() == want[k].tobytes(), (v, k)

@@ -245,6 +245,11 @@ def _staged_pair(corb, pyorc, stages, a, order, expect_device, bit_equal=True):
 # bit-equal, and it does not depend on the classification (no edge removed: still different) or on fixed points -- while the 29-free-keyframe window of
 # test_gpu_staged.py stays bit-equal through 15.  Open: pinned as a strict xfail so that it fails loudly once the routes agree again.
 # Its oracle comparison runs with the others; the bit-for-bit comparison of its two routes is the strict xfail below.
+# Recorded with tests/test_gpu_ba_switches.py: CORB_BA_NO_CHAIN=1, CORB_BA_CHAIN=1 and CORB_BA_HOST_STAGES=1 change no byte of either route and none makes them agree (poses
+# differ by 9.3e-10, points by 1.9e-9); the chains are not on this window's path (6 * 23 > 128 rows).  What does separate the routes: ba_schur_mfma_launch takes the split form
+# of the Schur kernel up to BA_SMALL_SPLIT_MAX_UNITS = 128 units, the device window lays out the full pattern (23 * 24 / 2 = 276 units: one wavefront per block), the host
+# flattening the 126 blocks with a shared map point (16 wavefronts per block) -- another summation order.  With the split form compiled out, in an experiment, the two routes of
+# this window are bit-equal; a 16-keyframe window (seed 44008) then still differs, so the kernel's form is not the only cause among windows of this size.
 WINDOW_OPEN = {6: "device and host routes of a 23-free-keyframe window differ in the last bits beyond ~10 LM iterations (open)"}
 
 
