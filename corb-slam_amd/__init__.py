@@ -61,6 +61,8 @@ KFINSERT_EXPORTS = ("corb_kfi_create", "corb_kfi_destroy", "corb_kfi_create_ster
 PUBLISH_EXPORTS = ("corb_pub_create", "corb_pub_destroy", "corb_pub_message_layout", "corb_pub_pack", "corb_pub_message", "corb_pub_message_read", "corb_pub_apply",
                    "corb_map_publish_plan", "corb_map_publish_messages", "corb_map_publish")
 # include/corb_stereo_rectify.h: stereo rectification in front of the stereo front-end, bound the same way
+# the essential graph on records (include/corb_essential_graph.h)
+ESSGRAPH_EXPORTS = ("corb_covis_add_loop_edge", "corb_covis_get_loop_edges", "corb_covis_clear_loop_edges", "corb_essential_graph_plan", "corb_essential_graph_store")
 RECTIFY_EXPORTS = ("corb_rect_create", "corb_rect_destroy", "corb_rect_maps", "corb_rect_set_maps", "corb_rect_upload_batch", "corb_rect_frames")
 
 
@@ -84,6 +86,26 @@ class VocTrainStats(C.Structure):
 class LocalMap(C.Structure):
     """CorbLocalMap: what corb_track_update_local_map reports beside its lists"""
     _fields_ = [("n_kf", C.c_int32), ("n_voted", C.c_int32), ("n_mp", C.c_int32), ("ref_slot", C.c_int32), ("ref_id", C.c_uint64), ("counter_empty", C.c_int32), ("n_cleared", C.c_int32)]
+
+
+class _EssentialGraphInput(C.Structure):
+    _fields_ = [("loop_slot", C.c_int32), ("cur_slot", C.c_int32), ("n_corr", C.c_int32), ("n_lc", C.c_int32), ("corr_slots", C.c_void_p), ("corrected", C.c_void_p),
+                ("non_corrected", C.c_void_p), ("lc_kf", C.c_void_p), ("lc_offset", C.c_void_p), ("lc_slots", C.c_void_p), ("min_weight", C.c_int32), ("pad", C.c_int32)]
+
+
+class EssentialGraphCounts(C.Structure):
+    """CorbEssentialGraphCounts; n_kind: loop connection, tree, loop edge, covisibility; n_suppressed: parent, child, loop edge, bad, not of smaller id, inserted"""
+    _fields_ = [("n_vertices", C.c_int32), ("n_edges", C.c_int32), ("n_kind", C.c_int32 * 4), ("n_dropped", C.c_int32), ("n_lc_below_weight", C.c_int32),
+                ("n_suppressed", C.c_int32 * 6)]
+
+    def as_dict(self):
+        return dict(n_vertices=self.n_vertices, n_edges=self.n_edges, n_kind=list(self.n_kind), n_dropped=self.n_dropped, n_lc_below_weight=self.n_lc_below_weight,
+                    n_suppressed=list(self.n_suppressed))
+
+
+class EssentialGraphResult(C.Structure):
+    _fields_ = [("graph", EssentialGraphCounts), ("iters_done", C.c_int32), ("n_poses_set", C.c_int32), ("n_points_moved", C.c_int32), ("n_points_kept", C.c_int32),
+                ("n_points_skipped", C.c_int32), ("n_points_fixed_ref", C.c_int32)]
 
 
 class GbaPropagation(C.Structure):
@@ -474,6 +496,14 @@ def load():
     L.corb_map_publish_plan.argtypes = [C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_int)]
     L.corb_map_publish_messages.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.c_void_p, C.POINTER(C.c_int)]
     L.corb_map_publish.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(_PublishPack), C.POINTER(_PublishApply)]
+    for name in ESSGRAPH_EXPORTS:
+        if not hasattr(L, name):
+            raise CorbError("libcorb_accel.so lacks %s (include/corb_essential_graph.h): rebuild it" % name)
+    L.corb_covis_add_loop_edge.argtypes = [C.c_void_p, C.c_int, C.c_int]
+    L.corb_covis_get_loop_edges.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+    L.corb_covis_clear_loop_edges.argtypes = [C.c_void_p, C.c_int]
+    L.corb_essential_graph_plan.argtypes = [C.c_void_p, C.POINTER(_EssentialGraphInput), C.c_int, C.c_int] + [C.c_void_p] * 8 + [C.POINTER(EssentialGraphCounts)]
+    L.corb_essential_graph_store.argtypes = [C.c_void_p, C.POINTER(_EssentialGraphInput), C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(EssentialGraphResult)]
     for name in RECTIFY_EXPORTS:
         if not hasattr(L, name):
             raise CorbError("libcorb_accel.so lacks %s (include/corb_stereo_rectify.h): rebuild it" % name)
@@ -1844,6 +1874,66 @@ class Covisibility:
         o = np.ascontiguousarray(np.atleast_1d(origin_slots), np.int32); out = GbaPropagation()
         _chk(load().corb_gba_propagate_store(self.h, _p(o) if len(o) else None, len(o), C.c_uint64(int(loop_kf)), int(queue_cap), C.byref(out)), "corb_gba_propagate_store")
         return out
+
+    # ---- the loop edges (mspLoopEdges per slot) and Optimizer::OptimizeEssentialGraph on records (include/corb_essential_graph.h) ----
+    MAX_LOOP_EDGES = 32          # CORB_COVIS_MAX_LOOP_EDGES
+
+    def AddLoopEdge(self, slot, other_slot):
+        _chk(load().corb_covis_add_loop_edge(self.h, int(slot), int(other_slot)), "corb_covis_add_loop_edge")
+
+    def GetLoopEdges(self, slot, cap=None):
+        """the ids of the set, ascending"""
+        cap = self.MAX_LOOP_EDGES if cap is None else int(cap)
+        ids = np.zeros(max(cap, 1), np.uint64); n = C.c_int(0)
+        _chk(load().corb_covis_get_loop_edges(self.h, int(slot), _p(ids), cap, C.byref(n)), "corb_covis_get_loop_edges")
+        return ids[:n.value].copy()
+
+    def ClearLoopEdges(self, slot):
+        _chk(load().corb_covis_clear_loop_edges(self.h, int(slot)), "corb_covis_clear_loop_edges")
+
+    @staticmethod
+    def _essential_graph_input(loop_slot, cur_slot, corr_slots, corrected, non_corrected, loop_connections, min_weight):
+        """loop_connections: [(key slot, [member slots])] in any order.  Returns the structure and the arrays it points into."""
+        cs = np.ascontiguousarray(corr_slots, np.int32).reshape(-1); n = len(cs)
+        co = np.ascontiguousarray(corrected, np.float64).reshape(n, 8); nc = np.ascontiguousarray(non_corrected, np.float64).reshape(n, 8)
+        lc = list(loop_connections)
+        lk = np.array([k for k, _ in lc], np.int32); off = np.concatenate([[0], np.cumsum([len(v) for _, v in lc])]).astype(np.int32)
+        ls = np.array([x for _, v in lc for x in v], np.int32)
+        keep = (cs, co, nc, lk, off, ls)
+        return _EssentialGraphInput(int(loop_slot), int(cur_slot), n, len(lc), cs.ctypes.data or None, co.ctypes.data or None, nc.ctypes.data or None,
+                                    lk.ctypes.data or None, off.ctypes.data, ls.ctypes.data or None, int(min_weight), 0), keep
+
+    def EssentialGraphPlan(self, loop_slot, cur_slot, corr_slots, corrected, non_corrected, loop_connections, min_weight=100, v_cap=None, e_cap=None):
+        """corb_essential_graph_plan: dict(v_slots, S, fixed, snc, vi, vj, kind, meas, counts).  v_cap / e_cap None: sized by a first call that asks for the counts.
+        A cap too small raises CorbError with (-2); the counts of that call are in self.last_plan_counts."""
+        inp, keep = self._essential_graph_input(loop_slot, cur_slot, corr_slots, corrected, non_corrected, loop_connections, min_weight)
+        cnt = EssentialGraphCounts(); L = load()
+        if v_cap is None or e_cap is None:
+            rc = L.corb_essential_graph_plan(self.h, C.byref(inp), 0, 0, *([None] * 8), C.byref(cnt))
+            if rc not in (0, ERR_CAPACITY):
+                _chk(rc, "corb_essential_graph_plan")
+            v_cap = cnt.n_vertices if v_cap is None else v_cap; e_cap = cnt.n_edges if e_cap is None else e_cap
+        K = max(v_cap, 1); E = max(e_cap, 1)
+        vs = np.zeros(K, np.int32); S = np.zeros((K, 8), np.float64); fx = np.zeros(K, np.uint8); snc = np.zeros((K, 8), np.float64)
+        vi = np.zeros(E, np.int32); vj = np.zeros(E, np.int32); kind = np.zeros(E, np.uint8); meas = np.zeros((E, 8), np.float64)
+        rc = L.corb_essential_graph_plan(self.h, C.byref(inp), int(v_cap), int(e_cap), _p(vs), _p(S), _p(fx), _p(snc), _p(vi), _p(vj), _p(kind), _p(meas), C.byref(cnt))
+        self.last_plan_counts = cnt.as_dict()
+        _chk(rc, "corb_essential_graph_plan")
+        k, e = cnt.n_vertices, cnt.n_edges
+        return dict(v_slots=vs[:k].copy(), S=S[:k].copy(), fixed=fx[:k].copy(), snc=snc[:k].copy(), vi=vi[:e].copy(), vj=vj[:e].copy(), kind=kind[:e].copy(),
+                    meas=meas[:e].copy(), counts=cnt.as_dict())
+
+    def OptimizeEssentialGraph(self, loop_slot, cur_slot, corr_slots, corrected, non_corrected, loop_connections, bFixScale=False, min_weight=100, iterations=20,
+                               scale_factor=0.0, v_cap=None):
+        """corb_essential_graph_store: plan, solve, commit poses and points into the records.  Returns dict(result, chi2, S): the result structure, the chi2 history
+        and the final estimates in vertex order.  v_cap None: the keyframe store's capacity."""
+        inp, keep = self._essential_graph_input(loop_slot, cur_slot, corr_slots, corrected, non_corrected, loop_connections, min_weight)
+        v_cap = self.kf.capacity if v_cap is None else int(v_cap)
+        chi2 = np.zeros(iterations + 1, np.float64); S = np.zeros((max(v_cap, 1), 8), np.float64); out = EssentialGraphResult()
+        rc = load().corb_essential_graph_store(self.h, C.byref(inp), int(iterations), int(bool(bFixScale)), C.c_float(scale_factor), _p(chi2), _p(S), v_cap, C.byref(out))
+        self.last_result = out
+        _chk(rc, "corb_essential_graph_store")
+        return dict(result=out, chi2=chi2[:out.iters_done + 1].copy(), S=S[:out.graph.n_vertices].copy())
 
     def SetPoseBeforeGBA(self, slot, T):
         a = np.ascontiguousarray(T, np.float32).reshape(16)

@@ -39,6 +39,7 @@ extern "C" int corb_covis_create(CorbKfStore* kf, CorbMpStore* mp, int max_conne
     if (g->bef_mem.room(eye.size() * 4 + 256) != hipSuccess || hipMemcpy(g->bef(), eye.data(), eye.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
         corb_set_error("corb_covis_create: %d poses before the global BA: allocation failed", kf->capacity); delete g; return CORB_ERR_HIP;
     }
+    if (essgraph_loop_sets_create(g) != CORB_OK) { delete g; return CORB_ERR_HIP; }
     *out = g;
     return CORB_OK;
 }

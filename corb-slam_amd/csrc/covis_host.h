@@ -12,6 +12,7 @@ struct CorbCovis {
     DevMem mem, tree_mem;                    // what R and T point into
     DevMem bef_mem;                          // [capacity][16] mTcwBefGBA of slot r (C/include/KeyFrame.h:63); a fresh graph holds the identity
     float* bef() const { return bef_mem.as<float>(); }
+    DevMem loop_mem;                         // mspLoopEdges of every slot: [capacity][CORB_COVIS_MAX_LOOP_EDGES] ids, then [capacity] counts (corb_essgraph.cpp); a fresh graph holds empty sets
     std::mutex mu;
 };
 
@@ -21,11 +22,11 @@ struct CovisCall {
     RecordCall rec;
     std::unique_ptr<CorbScratch> scratch;            // taken after the stores' locks, as every store call does
     CovisStores S{};
-    int begin(CorbCovis* g, const char* who, bool need_points, CorbKfStore* frames = nullptr)
+    int begin(CorbCovis* g, const char* who, bool need_points, CorbKfStore* frames = nullptr, int lane = 0)
     {
         CorbKfStore* kf = g->kf; CorbMpStore* mp = g->mp;
         rec.hold(&g->mu, kf, frames, mp);
-        scratch.reset(new CorbScratch(0));
+        scratch.reset(new CorbScratch(lane));                // lane 1: the long optimisations (corb_essgraph.cpp)
         CorbScratch& pool = *scratch;
         if (!pool.stream) { corb_set_error("%s: no workspace stream", who); return CORB_ERR_HIP; }
         int rc = need_points ? record_need_index(who, mp) : CORB_OK; if (rc) return rc;
@@ -38,6 +39,8 @@ struct CovisCall {
         return CORB_OK;
     }
 };
+// the loop-edge sets of a new graph (corb_essgraph.cpp); CORB_ERR_HIP with the message set
+int essgraph_loop_sets_create(CorbCovis* g);
 inline int covis_slot_ok(CorbCovis* g, int slot, const char* who)
 {
     if (!g || slot < 0 || slot >= g->kf->capacity) { corb_set_error("%s: bad graph / slot", who); return CORB_ERR_ARG; }

@@ -27,6 +27,7 @@
 #include <corb_voc_train.h>
 #include <corb_keyframe_insert.h>
 #include <corb_map_publish.h>
+#include <corb_essential_graph.h>
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -1247,6 +1248,7 @@ private:
 //   AddChild / EraseChild / ChangeParent / GetChilds / GetParent / hasChild and the tree part of SetBadFlag      KeyFrame.cc:504-543, :607-668
 //   void Tracking::UpdateLocalMap()                                               Tracking.cc:1218-1366
 //   CorrectLoop's propagation and the map update of RunGlobalBundleAdjustment      GlobalOptimize.cpp:253-338, :463-532 (LoopClosing.cc:436-522, :684-753)
+//   AddLoopEdge / GetLoopEdges and Optimizer::OptimizeEssentialGraph                KeyFrame.cc:545-561, Optimizer.cc:840-1117 (include/corb_essential_graph.h)
 // The keyframes are named by the slots MapStoreT::PutKeyFrame filed them in (Bind).  The spanning tree lives in the graph (corb_covis_update keeps it as :493-499 do);
 // UpdateConnections still returns the front of the ordered list, which is mpParent on a keyframe's first connection.  Db (optional) is the place-recognition database of this header: its
 // UpdateConnections(KeyFrame*) is called for the keyframe and for every keyframe on its ordered list -- the rows an update can change the best ten of.
@@ -1403,6 +1405,64 @@ public:
                 if (!pRefKF || slot_.find(pRefKF) == slot_.end() || pRefKF->mnBAGlobalForKF != nLoopKF) continue;
             }
             pMP->SetWorldPos(adapt::MatFactory<Mat>::from_floats(3, 1, rec[m].world_pos)); pCacher->addUpdateMapPoint(pMP);                       // :504-505, :527-528
+        }
+        return r;
+    }
+    // ---- the loop edges and the essential graph on records (include/corb_essential_graph.h) ----
+    void AddLoopEdge(KeyFrame* pKF, KeyFrame* pOther) { check(corb_covis_add_loop_edge(h_, Slot(pKF), Slot(pOther)), "corb_covis_add_loop_edge"); }      // KeyFrame.cc:545-550
+    std::set<KeyFrame*> GetLoopEdges(KeyFrame* pKF)                                                                       // the ones without a slot dropped (:552-561)
+    {
+        uint64_t ids[CORB_COVIS_MAX_LOOP_EDGES]; int n = 0;
+        check(corb_covis_get_loop_edges(h_, Slot(pKF), ids, CORB_COVIS_MAX_LOOP_EDGES, &n), "corb_covis_get_loop_edges");
+        std::set<KeyFrame*> out; for (int i = 0; i < n; i++) if (KeyFrame* p = byId(ids[i])) out.insert(p);
+        return out;
+    }
+    // void Optimizer::OptimizeEssentialGraph(pCache, pLoopKF, pCurKF, NonCorrectedSim3, CorrectedSim3, LoopConnections, bFixScale) (Optimizer.cc:840-1117) through
+    // corb_essential_graph_store.  The two pose maps are read through toV8(const Sim3&, double* v8) (quaternion x y z w, t, s: what CorrectLoop's makeSim3 was given);
+    // a key of LoopConnections or a member of a set without a slot is a caller's error.  scaleFactor = mfScaleFactor (0: no UpdateNormalAndDepth); vpMP[m] is the
+    // object of map-point slot first + m.  The objects receive what :1074-1112 leave: SetPose + addUpdateKeyframe for every keyframe with a vertex that is not
+    // getFixed(), SetWorldPos + addUpdateMapPoint (+ normal and distances) for every point the call moved -- the points that are neither bad nor fixed and whose
+    // nIDr (:1087-1098) names a bound keyframe that is not bad.
+    template <class MapPoint, class Mat, class Cache, class PoseMap, class ToV8>
+    CorbEssentialGraphResult OptimizeEssentialGraph(KeyFrame* pLoopKF, KeyFrame* pCurKF, const PoseMap& NonCorrectedSim3, const PoseMap& CorrectedSim3,
+                                                    const std::map<KeyFrame*, std::set<KeyFrame*>>& LoopConnections, bool bFixScale, float scaleFactor, CorbKfStore* kfs,
+                                                    CorbMpStore* mps, int first, const std::vector<MapPoint*>& vpMP, Cache* pCacher, ToV8 toV8, int minFeat = 100, int nIterations = 20)
+    {
+        std::vector<int32_t> corrSlots, lcKf, lcOff(1, 0), lcSlots; std::vector<double> co, nc;
+        for (const auto& e : CorrectedSim3) {
+            const auto non = NonCorrectedSim3.find(e.first);
+            if (non == NonCorrectedSim3.end()) throw Error(CORB_ERR_ARG, "OptimizeEssentialGraph: CorrectedSim3 and NonCorrectedSim3 have different keys");
+            corrSlots.push_back(Slot(e.first)); co.resize(co.size() + 8); nc.resize(nc.size() + 8);
+            toV8(e.second, &co[co.size() - 8]); toV8(non->second, &nc[nc.size() - 8]);
+        }
+        for (const auto& e : LoopConnections) {
+            lcKf.push_back(Slot(e.first));
+            for (KeyFrame* p : e.second) lcSlots.push_back(Slot(p));
+            lcOff.push_back((int32_t)lcSlots.size());
+        }
+        CorbEssentialGraphInput in{};
+        in.loop_slot = Slot(pLoopKF); in.cur_slot = Slot(pCurKF); in.n_corr = (int32_t)corrSlots.size(); in.n_lc = (int32_t)lcKf.size();
+        in.corr_slots = corrSlots.data(); in.corrected = co.data(); in.non_corrected = nc.data();
+        in.lc_kf = lcKf.data(); in.lc_offset = lcOff.data(); in.lc_slots = lcSlots.data(); in.min_weight = minFeat;
+        CorbEssentialGraphResult r{};
+        check(corb_essential_graph_store(h_, &in, nIterations, bFixScale ? 1 : 0, scaleFactor, nullptr, nullptr, 0, &r), "corb_essential_graph_store");
+        for (size_t s = 0; s < kf_.size(); s++) {                                                                                                 // :1053-1076
+            KeyFrame* pKFi = kf_[s];
+            if (!pKFi || pKFi->isBad() || pKFi->getFixed()) continue;
+            CorbKeyFrameMeta m; check(corb_kf_store_get_meta(kfs, (int)s, &m), "corb_kf_store_get_meta");
+            pKFi->SetPose(adapt::MatFactory<Mat>::from_floats(4, 4, m.Tcw)); pCacher->addUpdateKeyframe(pKFi);
+        }
+        std::vector<CorbMapPointRecord> rec(vpMP.size());
+        if (!vpMP.empty()) check(corb_mp_store_get(mps, first, (int)vpMP.size(), rec.data(), nullptr, nullptr), "corb_mp_store_get");
+        for (size_t m = 0; m < vpMP.size(); m++) {                                                                                                // :1079-1115
+            MapPoint* pMP = vpMP[m];
+            if (!pMP || pMP->isBad() || pMP->getFixed()) continue;
+            KeyFrame* pRef = nullptr;
+            if (pMP->mnCorrectedByKF == pCurKF->mnId) pRef = byId((uint64_t)pMP->mnCorrectedReference);
+            else if (KeyFrame* p = pMP->GetReferenceKeyFrame()) pRef = slot_.find(p) != slot_.end() ? p : nullptr;
+            if (!pRef || pRef->isBad()) continue;
+            pMP->SetWorldPos(adapt::MatFactory<Mat>::from_floats(3, 1, rec[m].world_pos)); pCacher->addUpdateMapPoint(pMP);                       // :1109-1111
+            if (scaleFactor > 0.f) pMP->SetNormalAndDistances(adapt::MatFactory<Mat>::from_floats(3, 1, rec[m].normal), rec[m].min_distance, rec[m].max_distance);   // :1112
         }
         return r;
     }
