@@ -1,279 +1,24 @@
-"""corb_slam_amd -- thin ctypes harness over libcorb_accel.so (the MI355X-native CORB-SLAM hot path).
+"""corb_slam_amd -- the ctypes harness over libcorb_accel.so (the MI355X-native CORB-SLAM hot path).
 
-The product is the C-ABI library (include/corb_accel.h) plus the C++ adapter in host/; this module only
-drives it from tests/, bench.py and __graft_entry__.py.  Class / method names mirror the reference
-(ORBextractor::operator(), ORBmatcher::SearchByBoW / SearchForTriangulation,
-Optimizer::GlobalBundleAdjustemnt).  There is NO fallback: if the HIP library is missing or no gfx950
-device is visible, every call raises CorbError.
+The product is the C-ABI library (include/*.h) plus the C++ adapter in host/; this package only drives it
+from tests/, bench.py and __graft_entry__.py.  It has two layers:
+  _abi.py      the mirror of the C ABI, stated once: constants, structures, record dtypes, one prototype
+               per exported function, and bind() that puts the prototypes onto an opened library
+  __init__.py  (this file) load(), the handle owner, and the classes and functions that marshal numpy
+               arrays into the calls -- about 1900 lines, most of them array marshalling
+Class / method names mirror the reference (ORBextractor::operator(), ORBmatcher::SearchByBoW /
+SearchForTriangulation, Optimizer::GlobalBundleAdjustemnt).  Every C call looks `load` up in this module at
+call time (`load().corb_...`) and no object keeps the library, so a test that replaces `load` sees every call.
+There is NO fallback: if the HIP library is missing or no gfx950 device is visible, every call raises CorbError.
 """
 import ctypes as C
 import os
 import numpy as np
 
+from ._abi import *         # noqa: F401,F403 -- every name of the mirror, the underscore ones included (_abi.__all__)
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libcorb_accel.so")
-
-KP_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4"),
-                     ("response", "<f4"), ("octave", "<i4"), ("class_id", "<i4")])
-EDGE_DTYPE = np.dtype([("pose", "<i4"), ("point", "<i4"), ("u", "<f4"), ("v", "<f4"),
-                       ("ur", "<f4"), ("inv_sigma2", "<f4")])
-
-EXPORTS = [
-    "corb_last_error", "corb_device_count", "corb_version", "corb_abi_version", "corb_warmup", "corb_release_scratch", "corb_pinned_alloc", "corb_pinned_free",
-    "corb_orb_create", "corb_orb_destroy", "corb_orb_extract", "corb_orb_tables", "corb_orb_pyramid_level",
-    "corb_orb_upload", "corb_orb_run", "corb_orb_sync", "corb_orb_fetch", "corb_orb_fetch_candidates",
-    "corb_orb_device_image", "corb_orb_upload_batch", "corb_orb_capacity", "corb_orb_fetch_batch", "corb_stereo_upload_batch", "corb_stereo_fetch_matches_batch", "corb_orb_profile", "corb_orb_profile_read",
-    "corb_stereo_create", "corb_stereo_destroy", "corb_stereo_orb", "corb_stereo_upload", "corb_stereo_run",
-    "corb_stereo_sync", "corb_stereo_fetch_matches", "corb_stereo_frame_layout", "corb_stereo_frames", "corb_track_search_reloc", "corb_search_by_sim3_store", "corb_mp_store_set_counters", "corb_mp_store_get_counters", "corb_mp_store_set_scratch", "corb_mp_store_get_scratch", "corb_mp_store_replace",
-    "corb_descriptor_distance", "corb_search_by_bow", "corb_search_for_triangulation", "corb_ba_solve", "corb_ba_solve_ex", "corb_ba_solve_staged",
-    "corb_search_by_projection_map", "corb_search_by_projection_frame", "corb_pose_optimization_batch",
-    "corb_search_by_projection_reloc", "corb_search_by_projection_scw", "corb_search_for_initialization", "corb_fuse", "corb_search_by_sim3", "corb_distinctive_descriptors", "corb_rebase_map", "corb_optimize_sim3", "corb_optimize_essential_graph",
-    "corb_kf_store_create", "corb_kf_store_destroy", "corb_kf_store_record_bytes", "corb_kf_store_put_from_stereo", "corb_kf_store_put_host", "corb_kf_store_set_bow",
-    "corb_kf_store_set_flags", "corb_kf_store_get", "corb_search_by_bow_slots", "corb_search_for_triangulation_slots",
-    "corb_comm_unique_id", "corb_comm_create", "corb_comm_destroy", "corb_map_push",
-    "corb_kf_store_set_meta", "corb_kf_store_get_meta", "corb_kf_store_set_map_points", "corb_kf_store_get_map_points",
-    "corb_mp_store_create", "corb_mp_store_destroy", "corb_mp_store_record_bytes", "corb_mp_store_put_host", "corb_mp_store_get",
-    "corb_comm_create_local", "corb_comm_rank", "corb_comm_world", "corb_map_push_ex", "corb_map_push_plan", "corb_map_push_messages", "corb_comm_test_rccl_exchange", "corb_map_push_setup", "corb_map_push_begin", "corb_map_push_wait", "corb_rebase_map_store", "corb_ba_solve_store", "corb_local_ba_store", "corb_fuse_store", "corb_search_by_projection_scw_store", "corb_ba_solve_devflat", "corb_kf_store_put_batch", "corb_spd_solve",
-    "corb_mp_store_build_index", "corb_kf_store_count", "corb_track_search_last_frame", "corb_track_pose_optimization", "corb_track_search_local_points", "corb_kf_store_put_frame",
-    "corb_rgbd_create", "corb_rgbd_destroy", "corb_rgbd_orb", "corb_rgbd_upload_batch", "corb_rgbd_run", "corb_rgbd_sync", "corb_rgbd_fetch_batch",
-    "corb_rgbd_frame_layout", "corb_rgbd_frames", "corb_rgbd_image_bounds", "corb_kf_store_put_from_rgbd",
-    "corb_triangulate_pairs", "corb_create_new_map_points_store",
-    "corb_sim3_ransac", "corb_sim3_ransac_store",
-    "corb_pnp_ransac", "corb_pnp_ransac_store",
-    "corb_mono_initialize",
-    "corb_voc_create", "corb_voc_load_text", "corb_voc_destroy", "corb_voc_info", "corb_voc_transform", "corb_kf_store_compute_bow",
-    "corb_kfdb_create", "corb_kfdb_destroy", "corb_kfdb_set_bow", "corb_kfdb_get_bow", "corb_kfdb_add", "corb_kfdb_erase", "corb_kfdb_clear", "corb_kfdb_set_neighbours",
-    "corb_kfdb_get_state", "corb_kfdb_score", "corb_kfdb_detect", "corb_bow_profile", "corb_bow_profile_read",
-    "corb_covis_create", "corb_covis_destroy", "corb_covis_update", "corb_covis_erase", "corb_covis_get", "corb_covis_query", "corb_covis_weight",
-    "corb_covis_keyframe_culling", "corb_covis_local_window",
-    "corb_covis_set_tree", "corb_covis_get_tree", "corb_covis_add_child", "corb_covis_erase_child", "corb_covis_change_parent", "corb_covis_reparent_children",
-    "corb_track_update_local_map",
-    "corb_loop_correct_store", "corb_fuse_sim3_store", "corb_gba_propagate_store", "corb_covis_set_pose_before_gba", "corb_covis_get_pose_before_gba",
-    "corb_scratch_fill", "corb_scratch_report", "corb_scratch_read",
-]
-
-# include/corb_voc_train.h: vocabulary training and export, an offline tool beside the drop-in boundary (exported from the same library)
-TRAIN_EXPORTS = ("corb_voc_train", "corb_voc_train_store", "corb_voc_get", "corb_voc_save_text")
-# include/corb_keyframe_insert.h: keyframe insertion on records, bound the same way
-KFINSERT_EXPORTS = ("corb_kfi_create", "corb_kfi_destroy", "corb_kfi_create_stereo_points", "corb_kfi_need_keyframe_counts", "corb_kfi_process_new_keyframe",
-                    "corb_kfi_map_point_culling")
-# include/corb_map_publish.h: the server -> clients publish on records, bound the same way
-PUBLISH_EXPORTS = ("corb_pub_create", "corb_pub_destroy", "corb_pub_message_layout", "corb_pub_pack", "corb_pub_message", "corb_pub_message_read", "corb_pub_apply",
-                   "corb_map_publish_plan", "corb_map_publish_messages", "corb_map_publish")
-# include/corb_stereo_rectify.h: stereo rectification in front of the stereo front-end, bound the same way
-# the essential graph on records (include/corb_essential_graph.h)
-ESSGRAPH_EXPORTS = ("corb_covis_add_loop_edge", "corb_covis_get_loop_edges", "corb_covis_clear_loop_edges", "corb_essential_graph_plan", "corb_essential_graph_store")
-RECTIFY_EXPORTS = ("corb_rect_create", "corb_rect_destroy", "corb_rect_maps", "corb_rect_set_maps", "corb_rect_upload_batch", "corb_rect_frames")
-
-
-class CorbError(RuntimeError):
-    pass
-
-
-class VocTrainOptions(C.Structure):
-    _fields_ = [("k", C.c_int32), ("L", C.c_int32), ("max_iterations", C.c_int32), ("reserved", C.c_int32), ("seed", C.c_uint64)]
-
-
-class VocTrainStats(C.Structure):
-    _fields_ = [(f, C.c_int32) for f in ("nodes", "words", "kmeans_nodes", "trivial_nodes", "short_nodes", "max_iterations_seen", "capped_nodes", "empty_cluster_events")] + \
-               [(f, C.c_int32 * 10) for f in ("level_nodes", "level_max_iterations", "level_launches", "level_small_nodes", "level_large_nodes")] + \
-               [("launches", C.c_int32), ("small_limit", C.c_int32), ("elapsed_ms", C.c_double)]
-
-    def as_dict(self):
-        return dict((f, list(getattr(self, f)) if f.startswith("level_") else getattr(self, f)) for f, _ in self._fields_)
-
-
-class LocalMap(C.Structure):
-    """CorbLocalMap: what corb_track_update_local_map reports beside its lists"""
-    _fields_ = [("n_kf", C.c_int32), ("n_voted", C.c_int32), ("n_mp", C.c_int32), ("ref_slot", C.c_int32), ("ref_id", C.c_uint64), ("counter_empty", C.c_int32), ("n_cleared", C.c_int32)]
-
-
-class _EssentialGraphInput(C.Structure):
-    _fields_ = [("loop_slot", C.c_int32), ("cur_slot", C.c_int32), ("n_corr", C.c_int32), ("n_lc", C.c_int32), ("corr_slots", C.c_void_p), ("corrected", C.c_void_p),
-                ("non_corrected", C.c_void_p), ("lc_kf", C.c_void_p), ("lc_offset", C.c_void_p), ("lc_slots", C.c_void_p), ("min_weight", C.c_int32), ("pad", C.c_int32)]
-
-
-class EssentialGraphCounts(C.Structure):
-    """CorbEssentialGraphCounts; n_kind: loop connection, tree, loop edge, covisibility; n_suppressed: parent, child, loop edge, bad, not of smaller id, inserted"""
-    _fields_ = [("n_vertices", C.c_int32), ("n_edges", C.c_int32), ("n_kind", C.c_int32 * 4), ("n_dropped", C.c_int32), ("n_lc_below_weight", C.c_int32),
-                ("n_suppressed", C.c_int32 * 6)]
-
-    def as_dict(self):
-        return dict(n_vertices=self.n_vertices, n_edges=self.n_edges, n_kind=list(self.n_kind), n_dropped=self.n_dropped, n_lc_below_weight=self.n_lc_below_weight,
-                    n_suppressed=list(self.n_suppressed))
-
-
-class EssentialGraphResult(C.Structure):
-    _fields_ = [("graph", EssentialGraphCounts), ("iters_done", C.c_int32), ("n_poses_set", C.c_int32), ("n_points_moved", C.c_int32), ("n_points_kept", C.c_int32),
-                ("n_points_skipped", C.c_int32), ("n_points_fixed_ref", C.c_int32)]
-
-
-class GbaPropagation(C.Structure):
-    """CorbGbaPropagation: the counts of corb_gba_propagate_store"""
-    _fields_ = [(k, C.c_int32) for k in ("n_popped", "n_reached", "n_propagated", "n_revisited", "n_points_set", "n_points_moved", "n_points_skipped")]
-
-
-class OrbConfig(C.Structure):
-    _fields_ = [("nfeatures", C.c_int32), ("scale_factor", C.c_float), ("nlevels", C.c_int32),
-                ("ini_th_fast", C.c_int32), ("min_th_fast", C.c_int32), ("width", C.c_int32), ("height", C.c_int32),
-                ("max_images", C.c_int32), ("device", C.c_int32)]
-
-
-class StereoConfig(C.Structure):
-    _fields_ = [("orb", OrbConfig), ("max_frames", C.c_int32), ("fx", C.c_float), ("bf", C.c_float)]
-
-
-SENSOR_MONOCULAR, SENSOR_RGBD = 0, 2            # include/corb_accel.h: CORB_SENSOR_*
-DEPTH_U16, DEPTH_F32 = 0, 1                     # CORB_DEPTH_*
-
-
-class CameraConfig(C.Structure):
-    _fields_ = [("orb", OrbConfig), ("max_frames", C.c_int32), ("sensor", C.c_int32), ("channels", C.c_int32), ("rgb", C.c_int32)] + \
-               [(k, C.c_float) for k in ("fx", "fy", "cx", "cy", "k1", "k2", "p1", "p2", "k3", "bf", "depth_map_factor")] + [("depth_format", C.c_int32)]
-
-
-class RgbdFrameLayout(C.Structure):
-    _fields_ = [(k, C.c_int32) for k in ("capacity", "frame_bytes", "input_bytes", "off_keys", "off_keys_un", "off_desc", "off_u_right", "off_depth")]
-
-
-class KernelTime(C.Structure):
-    _fields_ = [("name", C.c_char * 48), ("total_ms", C.c_double), ("launches", C.c_int64)]
-
-
-class _FeatVec(C.Structure):
-    _fields_ = [("n_nodes", C.c_int32), ("node_id", C.c_void_p), ("offset", C.c_void_p), ("idx", C.c_void_p)]
-
-
-class _VocDesc(C.Structure):
-    _fields_ = [("k", C.c_int32), ("L", C.c_int32), ("scoring", C.c_int32), ("weighting", C.c_int32), ("n_nodes", C.c_int32),
-                ("parent", C.c_void_p), ("is_leaf", C.c_void_p), ("descriptor", C.c_void_p), ("weight", C.c_void_p)]
-
-
-class _BowSide(C.Structure):
-    _fields_ = [("desc", C.c_void_p), ("angle", C.c_void_p), ("valid", C.c_void_p), ("n", C.c_int32), ("fv", _FeatVec)]
-
-
-class _TriSide(C.Structure):
-    _fields_ = [("desc", C.c_void_p), ("kp", C.c_void_p), ("u_right", C.c_void_p), ("has_mappoint", C.c_void_p),
-                ("n", C.c_int32), ("fv", _FeatVec)]
-
-
-MP_DTYPE = np.dtype([("world", "<f4", 3), ("normal", "<f4", 3), ("min_distance", "<f4"), ("max_distance", "<f4"), ("angle", "<f4"),
-                     ("valid", "u1"), ("pad", "u1", 3)])
-
-
-class _KeyFrameView(C.Structure):
-    _fields_ = [("keys_un", C.c_void_p), ("u_right", C.c_void_p), ("desc", C.c_void_p), ("n", C.c_int32),
-                ("min_x", C.c_float), ("min_y", C.c_float), ("max_x", C.c_float), ("max_y", C.c_float),
-                ("scale", C.c_void_p), ("inv_level_sigma2", C.c_void_p), ("nlevels", C.c_int32), ("log_scale_factor", C.c_float),
-                ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("bf", C.c_float)]
-
-
-class _Sim3Problem(C.Structure):
-    _fields_ = [("n", C.c_int32), ("p1c", C.c_void_p), ("p2c", C.c_void_p), ("obs1", C.c_void_p), ("obs2", C.c_void_p),
-                ("inv_sigma2_1", C.c_void_p), ("inv_sigma2_2", C.c_void_p)] + [(k, C.c_float) for k in ("fx1", "fy1", "cx1", "cy1", "fx2", "fy2", "cx2", "cy2")]
-
-
-class _PoseOptFrame(C.Structure):
-    _fields_ = [("Tcw", C.c_void_p), ("n_obs", C.c_int32), ("points", C.c_void_p), ("u", C.c_void_p), ("v", C.c_void_p),
-                ("u_right", C.c_void_p), ("inv_sigma2", C.c_void_p),
-                ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("bf", C.c_float)]
-
-
-class _BAProblem(C.Structure):
-    _fields_ = [("n_poses", C.c_int32), ("n_points", C.c_int32), ("n_edges", C.c_int32),
-                ("poses", C.c_void_p), ("pose_fixed", C.c_void_p), ("points", C.c_void_p),
-                ("point_fixed", C.c_void_p), ("edges", C.c_void_p),
-                ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("bf", C.c_float), ("intr", C.c_void_p)]
-
-
-class StereoFrameLayout(C.Structure):
-    _fields_ = [("capacity", C.c_int32), ("frame_bytes", C.c_int32), ("off_kp_left", C.c_int32), ("off_kp_right", C.c_int32),
-                ("off_desc_left", C.c_int32), ("off_desc_right", C.c_int32), ("off_u_right", C.c_int32), ("off_depth", C.c_int32)]
-
-
-class StereoFrameTiming(C.Structure):
-    _fields_ = [("ms_upload", C.c_float), ("ms_kernels", C.c_float), ("ms_download", C.c_float)]
-
-
-class RectifyEye(C.Structure):
-    _fields_ = [("K", C.c_double * 9), ("D", C.c_double * 8), ("R", C.c_double * 9), ("P", C.c_double * 12)]
-
-
-class RectifyConfig(C.Structure):
-    _fields_ = [("raw_width", C.c_int32), ("raw_height", C.c_int32), ("left", RectifyEye), ("right", RectifyEye)]
-
-
-class _BAResult(C.Structure):
-    _fields_ = [("poses", C.c_void_p), ("points", C.c_void_p), ("chi2", C.c_void_p), ("lam", C.c_void_p),
-                ("iters_done", C.c_int32), ("trials_total", C.c_int32),
-                ("ms_total", C.c_double), ("ms_build", C.c_double), ("ms_schur", C.c_double),
-                ("ms_solve", C.c_double), ("ms_update", C.c_double), ("solver_used", C.c_int32), ("pcg_iterations", C.c_int32),
-                ("free_poses", C.c_int32), ("free_points", C.c_int32), ("active_edges", C.c_int32), ("nnz_blocks", C.c_int64), ("schur_pairs", C.c_int64),
-                ("pc_block", C.c_int32), ("pc_levels", C.c_int32),
-                ("pcg_residual_max", C.c_double), ("pcg_residual_last", C.c_double), ("grad_inf", C.c_double), ("pcg_refined_trials", C.c_int32), ("reserved0", C.c_int32)]
-
-
-KF_META_DTYPE = np.dtype([("id", "<u8"), ("client_id", "<i4"), ("flags", "<u4"), ("fx", "<f4"), ("fy", "<f4"), ("cx", "<f4"), ("cy", "<f4"), ("bf", "<f4"),
-                          ("nlevels", "<i4"), ("Tcw", "<f4", 16), ("TcwGBA", "<f4", 16), ("ba_global_for_kf", "<u8"), ("inv_level_sigma2", "<f4", 16)])
-MP_RECORD_DTYPE = np.dtype([("id", "<u8"), ("ref_kf_id", "<u8"), ("descriptor", "u1", 32), ("client_id", "<i4"), ("n_obs", "<i4"), ("flags", "<u4"), ("world_pos", "<f4", 3),
-                            ("normal", "<f4", 3), ("min_distance", "<f4"), ("max_distance", "<f4"), ("pos_gba", "<f4", 3), ("ba_global_for_kf", "<u8")], align=True)
-assert KF_META_DTYPE.itemsize == 240 and MP_RECORD_DTYPE.itemsize == 112 and MP_RECORD_DTYPE.fields["descriptor"][1] == 16
-MP_COUNTERS_DTYPE = np.dtype([("n_visible", "<i4"), ("n_found", "<i4"), ("replaced_by", "<u8")])
-MP_SCRATCH_DTYPE = np.dtype([("first_kf_id", "<i8"), ("first_frame", "<i8"), ("track_reference_for_frame", "<u8"), ("last_frame_seen", "<u8"), ("ba_local_for_kf", "<u8"),
-                             ("fuse_candidate_for_kf", "<u8"), ("loop_point_for_kf", "<u8"), ("corrected_by_kf", "<u8"), ("corrected_reference", "<u8"),
-                             ("track_proj_x", "<f4"), ("track_proj_y", "<f4"), ("track_proj_xr", "<f4"), ("track_view_cos", "<f4"), ("track_scale_level", "<i4"),
-                             ("n_obs_weight", "<i4"), ("track_in_view", "u1"), ("pad", "u1", 7)])      # CorbMapPointScratch (104 bytes)
-PUSH_HEADER_DTYPE = np.dtype([("status", "<i4"), ("n_kf", "<i4"), ("n_mp", "<i4"), ("kf_record_bytes", "<i4"), ("mp_record_bytes", "<i4")])
-NO_MAP_POINT = 0xFFFFFFFFFFFFFFFF
-KF_BAD, KF_FIXED, MP_BAD, MP_FIXED = 1, 2, 1, 2
-
-
-KF_POSE_PACKET_DTYPE = np.dtype([("id", "<u8"), ("Tcw", "<f4", 16)])                                                     # CorbKeyFramePosePacket (72 bytes)
-MP_POSE_PACKET_DTYPE = np.dtype([("id", "<u8"), ("pos", "<f4", 3), ("pad", "<u4")])                                    # CorbMapPointPosePacket (24 bytes)
-PUBLISH_TRANSFORM_DTYPE = np.dtype([("client_id", "<i4"), ("pad", "<i4"), ("T", "<f4", 16), ("Tinv", "<f4", 16)])      # CorbPublishTransform (136 bytes)
-PUBLISH_HEADER_DTYPE = np.dtype([("status", "<i4"), ("kf_record_bytes", "<i4"), ("mp_record_bytes", "<i4"), ("counts", "<i4", 5)])
-assert KF_POSE_PACKET_DTYPE.itemsize == 72 and MP_POSE_PACKET_DTYPE.itemsize == 24 and PUBLISH_TRANSFORM_DTYPE.itemsize == 136 and PUBLISH_HEADER_DTYPE.itemsize == 32
-
-
-class _PublishOutputs(C.Structure):
-    _fields_ = [("kind_kf_new", C.c_void_p), ("kind_mp_new", C.c_void_p), ("kind_kf_upd", C.c_void_p), ("kind_mp_upd", C.c_void_p), ("kf_new_slots", C.c_void_p),
-                ("mp_new_slots", C.c_void_p), ("n_kf_inserted", C.c_int32), ("n_mp_inserted", C.c_int32), ("n_kf_updated", C.c_int32), ("n_mp_updated", C.c_int32),
-                ("no_transform", C.c_int32)]
-
-
-class _PublishPack(C.Structure):
-    _fields_ = [("kf", C.c_void_p), ("new_kf_slots", C.c_void_p), ("n_new_kf", C.c_int32), ("upd_kf_slots", C.c_void_p), ("n_upd_kf", C.c_int32),
-                ("mp", C.c_void_p), ("new_mp_slots", C.c_void_p), ("n_new_mp", C.c_int32), ("upd_mp_slots", C.c_void_p), ("n_upd_mp", C.c_int32),
-                ("trans_client_id", C.c_void_p), ("trans", C.c_void_p), ("n_trans", C.c_int32)]
-
-
-class _PublishApply(C.Structure):
-    _fields_ = [("client_id", C.c_int32), ("dst_kf", C.c_void_p), ("kf_first", C.c_int32), ("kf_n", C.c_int32), ("kf_free_first", C.c_int32), ("kf_room", C.c_int32),
-                ("dst_mp", C.c_void_p), ("mp_first", C.c_int32), ("mp_n", C.c_int32), ("mp_free_first", C.c_int32), ("mp_room", C.c_int32), ("apply", C.c_int32),
-                ("out", C.POINTER(_PublishOutputs))]
-
-
-class _MapPush(C.Structure):
-    _fields_ = [("kf", C.c_void_p), ("kf_slots", C.c_void_p), ("n_kf", C.c_int32), ("mp", C.c_void_p), ("mp_slots", C.c_void_p), ("n_mp", C.c_int32),
-                ("kf_dst_first", C.c_void_p), ("mp_dst_first", C.c_void_p), ("kf_recv_counts", C.c_void_p), ("mp_recv_counts", C.c_void_p)]
-
-
-TRACKED_DTYPE = np.dtype([("proj_x", "<f4"), ("proj_y", "<f4"), ("proj_xr", "<f4"), ("view_cos", "<f4"), ("level", "<i4"),
-                          ("valid", "u1"), ("claims", "u1"), ("pad", "u1", 2)])
-LAST_DTYPE = np.dtype([("world", "<f4", 3), ("angle", "<f4"), ("octave", "<i4"), ("valid", "u1"), ("claims", "u1"), ("pad", "u1", 2)])
-
-
-class _FrameView(C.Structure):
-    _fields_ = [("keys_un", C.c_void_p), ("u_right", C.c_void_p), ("desc", C.c_void_p), ("n", C.c_int32), ("claimed", C.c_void_p),
-                ("min_x", C.c_float), ("min_y", C.c_float), ("max_x", C.c_float), ("max_y", C.c_float), ("scale", C.c_void_p), ("nlevels", C.c_int32)]
-
-
-class BAStage(C.Structure):
-    _fields_ = [("iterations", C.c_int32), ("robust", C.c_int32), ("chi2_mono", C.c_float), ("chi2_stereo", C.c_float),
-                ("check_depth", C.c_int32), ("recompute_inactive", C.c_int32), ("allow_reactivate", C.c_int32),
-                ("reset_estimates", C.c_int32), ("float_compare", C.c_int32), ("huber_mono", C.c_float), ("huber_stereo", C.c_float)]
-
 
 # Optimizer::LocalBundleAdjustment (Optimizer.cc:487-838) and Optimizer::PoseOptimization (272-485) as stage lists
 _HM, _HS = float(np.float32(np.sqrt(5.991))), float(np.float32(np.sqrt(7.815)))
@@ -282,239 +27,55 @@ _HM, _HS = float(np.float32(np.sqrt(5.991))), float(np.float32(np.sqrt(7.815)))
 LOCAL_BA_STAGES = [(5, 1, 5.991, 7.815, 1, 0, 0, 0, 0, _HM, _HS), (10, 0, 5.991, 7.815, 1, 0, 1, 0, 0, _HM, _HS)]
 POSE_OPT_STAGES = [(10, 1, 5.991, 7.815, 0, 1, 1, 1, 1, _HM, _HS)] * 3 + [(10, 0, 5.991, 7.815, 0, 1, 1, 1, 1, _HM, _HS)]
 
-
-class BAOptions(C.Structure):
-    _fields_ = [("solver", C.c_int32), ("pcg_tol", C.c_double), ("pcg_max_iter", C.c_int32), ("pc_block", C.c_int32), ("pc_multilevel", C.c_int32), ("scale_factor", C.c_float)]
-
-
 _lib = None
 
 
-ABI_VERSION = 6          # = CORB_ABI_VERSION of the header the ctypes structures below mirror
-
-
 def load():
-    """dlopen libcorb_accel.so; raises CorbError if the HIP extension has not been built."""
+    """dlopen libcorb_accel.so and bind the prototypes (once); raises CorbError if the HIP extension has not been built."""
     global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(LIB_PATH):
-        raise CorbError("libcorb_accel.so is not built (run `python -c 'import __graft_entry__ as g; g.build()'`); "
-                        "there is no CPU fallback")
-    L = C.CDLL(LIB_PATH)
-    if not hasattr(L, "corb_abi_version") or L.corb_abi_version() != ABI_VERSION:       # include/corb_accel.h: CORB_ABI_VERSION -- the structs carry no size fields
-        raise CorbError("libcorb_accel.so was built from another corb_accel.h (struct layout version %s, this harness mirrors %d): rebuild it"
-                        % (L.corb_abi_version() if hasattr(L, "corb_abi_version") else "< 5", ABI_VERSION))
-    L.corb_last_error.restype = C.c_char_p
-    L.corb_stereo_orb.restype = C.c_void_p
-    L.corb_stereo_orb.argtypes = [C.c_void_p]
-    L.corb_orb_create.argtypes = [C.POINTER(OrbConfig), C.POINTER(C.c_void_p)]
-    L.corb_orb_destroy.argtypes = [C.c_void_p]
-    L.corb_orb_destroy.restype = None
-    L.corb_orb_extract.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
-    L.corb_orb_tables.argtypes = [C.c_void_p] + [C.c_void_p] * 6
-    L.corb_orb_pyramid_level.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_int)]
-    L.corb_orb_upload.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
-    L.corb_orb_run.argtypes = [C.c_void_p, C.c_int]
-    L.corb_orb_sync.argtypes = [C.c_void_p]
-    L.corb_orb_fetch.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
-    L.corb_orb_fetch_candidates.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
-    L.corb_orb_upload_batch.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
-    L.corb_orb_capacity.argtypes = [C.c_void_p]
-    L.corb_orb_fetch_batch.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.corb_stereo_upload_batch.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
-    L.corb_stereo_frame_layout.argtypes = [C.c_void_p, C.POINTER(StereoFrameLayout)]
-    L.corb_stereo_frames.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.corb_stereo_fetch_matches_batch.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.corb_orb_device_image.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
-    L.corb_orb_profile.argtypes = [C.c_void_p, C.c_int]
-    L.corb_orb_profile_read.argtypes = [C.c_void_p, C.POINTER(KernelTime), C.c_int, C.POINTER(C.c_int)]
-    L.corb_stereo_create.argtypes = [C.POINTER(StereoConfig), C.POINTER(C.c_void_p)]
-    L.corb_stereo_destroy.argtypes = [C.c_void_p]
-    L.corb_stereo_destroy.restype = None
-    L.corb_stereo_upload.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
-    L.corb_stereo_run.argtypes = [C.c_void_p, C.c_int]
-    L.corb_stereo_sync.argtypes = [C.c_void_p]
-    L.corb_stereo_fetch_matches.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
-    L.corb_descriptor_distance.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int]
-    L.corb_search_by_bow.argtypes = [C.c_int, C.POINTER(_BowSide), C.POINTER(_BowSide), C.c_float, C.c_int, C.c_void_p, C.POINTER(C.c_int), C.c_int]
-    L.corb_search_for_triangulation.argtypes = [C.POINTER(_TriSide), C.POINTER(_TriSide), C.c_void_p, C.c_float, C.c_float,
-                                                C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_int), C.c_int]
-    L.corb_search_by_projection_map.argtypes = [C.POINTER(_FrameView), C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_void_p, C.POINTER(C.c_int), C.c_int]
-    L.corb_search_by_projection_frame.argtypes = [C.POINTER(_FrameView), C.c_void_p, C.c_void_p] + [C.c_float] * 6 + [C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_int), C.c_int]
-    L.corb_ba_solve.argtypes = [C.POINTER(_BAProblem), C.c_int, C.c_int, C.c_void_p, C.POINTER(_BAResult), C.c_int]
-    L.corb_ba_solve_ex.argtypes = [C.POINTER(_BAProblem), C.c_int, C.c_int, C.c_void_p, C.POINTER(_BAResult), C.c_int, C.POINTER(BAOptions)]
-    L.corb_ba_solve_devflat.argtypes = [C.POINTER(_BAProblem), C.c_int, C.c_int, C.POINTER(_BAResult), C.c_int, C.POINTER(BAOptions)]
-    L.corb_spd_solve.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.c_int]
-    L.corb_scratch_fill.argtypes = [C.c_int, C.c_int, C.c_uint32, C.c_uint64, C.POINTER(C.c_uint64)]
-    L.corb_scratch_report.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_int), C.POINTER(C.c_uint64)]
-    L.corb_scratch_read.argtypes = [C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.c_void_p]
-    L.corb_ba_solve_staged.argtypes = [C.POINTER(_BAProblem), C.POINTER(BAStage), C.c_int, C.c_void_p, C.POINTER(_BAResult), C.c_void_p, C.c_int, C.POINTER(BAOptions)]
-    L.corb_search_by_projection_reloc.restype = C.c_int
-    L.corb_search_by_projection_reloc.argtypes = [C.POINTER(_KeyFrameView), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_int), C.c_int]
-    L.corb_search_for_initialization.restype = C.c_int
-    L.corb_search_for_initialization.argtypes = [C.POINTER(_FrameView), C.POINTER(_FrameView), C.c_void_p, C.c_int, C.c_float, C.c_int, C.c_void_p, C.POINTER(C.c_int), C.c_int]
-    L.corb_search_by_projection_scw.restype = C.c_int
-    L.corb_search_by_projection_scw.argtypes = [C.POINTER(_KeyFrameView), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.POINTER(C.c_int), C.c_int]
-    L.corb_fuse.restype = C.c_int
-    L.corb_fuse.argtypes = [C.POINTER(_KeyFrameView), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.c_int]
-    L.corb_search_by_sim3.restype = C.c_int
-    L.corb_search_by_sim3.argtypes = [C.POINTER(_KeyFrameView), C.POINTER(_KeyFrameView)] + [C.c_void_p] * 6 + [C.c_float, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.POINTER(C.c_int), C.c_int]
-    L.corb_distinctive_descriptors.restype = C.c_int
-    L.corb_distinctive_descriptors.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int]
-    L.corb_rebase_map.restype = C.c_int
-    L.corb_rebase_map.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int]
-    L.corb_optimize_essential_graph.restype = C.c_int
-    L.corb_optimize_essential_graph.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int,
-                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_int]
-    L.corb_optimize_sim3.restype = C.c_int
-    L.corb_optimize_sim3.argtypes = [C.POINTER(_Sim3Problem), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
-    L.corb_pose_optimization_batch.restype = C.c_int
-    L.corb_pose_optimization_batch.argtypes = [C.POINTER(_PoseOptFrame), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
-    L.corb_kf_store_create.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
-    L.corb_kf_store_destroy.argtypes = [C.c_void_p]; L.corb_kf_store_destroy.restype = None
-    L.corb_kf_store_record_bytes.argtypes = [C.c_void_p]
-    L.corb_kf_store_put_from_stereo.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_uint64]
-    L.corb_kf_store_put_host.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_uint64]
-    L.corb_kf_store_set_bow.argtypes = [C.c_void_p, C.c_int, C.POINTER(_FeatVec)]
-    L.corb_kf_store_set_flags.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
-    L.corb_kf_store_get.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 5 + [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_uint64), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]
-    L.corb_search_by_bow_slots.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_float, C.c_int, C.c_void_p, C.POINTER(C.c_int)]
-    L.corb_search_for_triangulation_slots.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
-                                                      C.c_void_p, C.POINTER(C.c_int)]
-    L.corb_comm_unique_id.argtypes = [C.c_void_p]
-    L.corb_comm_create.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
-    L.corb_comm_destroy.argtypes = [C.c_void_p]; L.corb_comm_destroy.restype = None
-    L.corb_map_push.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
-    L.corb_kf_store_set_meta.argtypes = [C.c_void_p, C.c_int, C.c_void_p]; L.corb_kf_store_get_meta.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
-    L.corb_kf_store_set_map_points.argtypes = [C.c_void_p, C.c_int, C.c_void_p]; L.corb_kf_store_get_map_points.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
-    L.corb_kf_store_put_batch.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 7
-    L.corb_mp_store_create.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
-    L.corb_mp_store_destroy.argtypes = [C.c_void_p]; L.corb_mp_store_destroy.restype = None
-    L.corb_mp_store_record_bytes.argtypes = [C.c_void_p]
-    L.corb_mp_store_put_host.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.corb_mp_store_get.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.corb_comm_create_local.argtypes = [C.c_int, C.c_void_p, C.c_void_p]
-    L.corb_comm_rank.argtypes = [C.c_void_p]; L.corb_comm_world.argtypes = [C.c_void_p]
-    L.corb_map_push_ex.argtypes = [C.c_void_p, C.POINTER(_MapPush), C.c_int]
-    L.corb_map_push_plan.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
-    L.corb_rebase_map_store.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
-    L.corb_ba_solve_store.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_uint64, C.POINTER(_BAResult), C.POINTER(BAOptions)]
-    L.corb_fuse_store.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(TrackCamera), C.c_void_p, C.c_float, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
-    L.corb_local_ba_store.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(BAStage), C.c_int, C.c_float, C.c_int, C.c_void_p,
-                                      C.POINTER(_BAResult), C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(BAOptions)]
-    L.corb_rgbd_create.argtypes = [C.POINTER(CameraConfig), C.POINTER(C.c_void_p)]
-    L.corb_rgbd_destroy.argtypes = [C.c_void_p]; L.corb_rgbd_destroy.restype = None
-    L.corb_rgbd_orb.argtypes = [C.c_void_p]; L.corb_rgbd_orb.restype = C.c_void_p
-    L.corb_rgbd_upload_batch.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
-    L.corb_rgbd_run.argtypes = [C.c_void_p, C.c_int]
-    L.corb_rgbd_sync.argtypes = [C.c_void_p]
-    L.corb_rgbd_fetch_batch.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 6
-    L.corb_rgbd_frame_layout.argtypes = [C.c_void_p, C.POINTER(RgbdFrameLayout)]
-    L.corb_rgbd_frames.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.corb_rgbd_image_bounds.argtypes = [C.c_void_p, C.c_void_p]
-    L.corb_kf_store_put_from_rgbd.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_uint64]
-    L.corb_triangulate_pairs.argtypes = [C.POINTER(_NewPointSide), C.POINTER(_NewPointSide), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.c_int]
-    L.corb_create_new_map_points_store.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(TrackCamera), C.c_int, C.c_int, C.c_void_p, C.c_int,
-                                                   C.c_uint64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
-    L.corb_sim3_ransac.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 6 + [C.c_int]
-    L.corb_pnp_ransac.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 9 + [C.c_int]
-    L.corb_pnp_ransac_store.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(TrackCamera), C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int,
-                                        C.c_void_p, C.c_int] + [C.c_void_p] * 11
-    L.corb_sim3_ransac_store.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(TrackCamera), C.c_void_p, C.c_void_p, C.c_double, C.c_int, C.c_int, C.c_int,
-                                         C.c_void_p, C.c_int] + [C.c_void_p] * 8
-    L.corb_mono_initialize.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 6 + [C.c_int]
-    L.corb_voc_create.argtypes = [C.POINTER(_VocDesc), C.c_int, C.POINTER(C.c_void_p)]
-    L.corb_voc_load_text.argtypes = [C.c_char_p, C.c_int, C.POINTER(C.c_void_p)]
-    L.corb_voc_destroy.argtypes = [C.c_void_p]
-    L.corb_voc_destroy.restype = None
-    L.corb_voc_info.argtypes = [C.c_void_p] + [C.POINTER(C.c_int32)] * 4
-    L.corb_voc_transform.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 9
-    L.corb_kfdb_create.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
-    L.corb_kfdb_destroy.argtypes = [C.c_void_p]
-    L.corb_kfdb_destroy.restype = None
-    L.corb_kfdb_set_bow.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
-    L.corb_kfdb_get_bow.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
-    L.corb_kfdb_add.argtypes = [C.c_void_p, C.c_int]
-    L.corb_kfdb_erase.argtypes = [C.c_void_p, C.c_int]
-    L.corb_kfdb_clear.argtypes = [C.c_void_p]
-    L.corb_kfdb_set_neighbours.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
-    L.corb_kfdb_get_state.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
-    L.corb_kfdb_score.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
-    L.corb_kfdb_detect.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_uint64, C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
-    L.corb_covis_create.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]
-    L.corb_covis_destroy.argtypes = [C.c_void_p]
-    L.corb_covis_destroy.restype = None
-    L.corb_covis_update.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
-    L.corb_covis_erase.argtypes = [C.c_void_p, C.c_int]
-    L.corb_covis_get.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.c_int]
-    L.corb_covis_query.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
-    L.corb_covis_weight.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int)]
-    L.corb_covis_keyframe_culling.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
-    L.corb_covis_local_window.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p, C.c_int, C.POINTER(C.c_int)]
-    L.corb_covis_set_tree.argtypes = [C.c_void_p, C.c_int, C.c_uint64, C.c_int, C.c_void_p, C.c_int]
-    L.corb_covis_get_tree.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_int), C.c_void_p, C.c_int, C.POINTER(C.c_int)]
-    L.corb_covis_add_child.argtypes = [C.c_void_p, C.c_int, C.c_int]
-    L.corb_covis_erase_child.argtypes = [C.c_void_p, C.c_int, C.c_int]
-    L.corb_covis_change_parent.argtypes = [C.c_void_p, C.c_int, C.c_int]
-    L.corb_covis_reparent_children.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
-    L.corb_track_update_local_map.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(LocalMap)]
-    L.corb_bow_profile.argtypes = [C.c_int, C.c_int]
-    L.corb_bow_profile_read.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int)]
-    L.corb_kf_store_compute_bow.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-    for name in TRAIN_EXPORTS:
-        if not hasattr(L, name):
-            raise CorbError("libcorb_accel.so lacks %s (include/corb_voc_train.h): rebuild it" % name)
-    L.corb_voc_train.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(VocTrainOptions), C.c_int, C.POINTER(C.c_void_p), C.POINTER(VocTrainStats)]
-    L.corb_voc_train_store.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(VocTrainOptions), C.POINTER(C.c_void_p), C.POINTER(VocTrainStats)]
-    L.corb_voc_get.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
-    L.corb_voc_save_text.argtypes = [C.c_void_p, C.c_char_p, C.c_int]
-    for name in KFINSERT_EXPORTS:
-        if not hasattr(L, name):
-            raise CorbError("libcorb_accel.so lacks %s (include/corb_keyframe_insert.h): rebuild it" % name)
-    L.corb_kfi_create.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
-    L.corb_kfi_destroy.argtypes = [C.c_void_p]; L.corb_kfi_destroy.restype = None
-    L.corb_kfi_create_stereo_points.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(TrackCamera), C.c_float, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_int32,
-                                                C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
-    L.corb_kfi_need_keyframe_counts.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_float, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
-                                                C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
-    L.corb_kfi_process_new_keyframe.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_void_p,
-                                                C.POINTER(C.c_int), C.POINTER(C.c_int)]
-    L.corb_kfi_map_point_culling.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_uint64, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
-                                             C.POINTER(C.c_int), C.POINTER(C.c_int)]
-    for name in PUBLISH_EXPORTS:
-        if not hasattr(L, name):
-            raise CorbError("libcorb_accel.so lacks %s (include/corb_map_publish.h): rebuild it" % name)
-    L.corb_pub_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
-    L.corb_pub_destroy.argtypes = [C.c_void_p]; L.corb_pub_destroy.restype = None
-    L.corb_pub_message_layout.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
-    L.corb_pub_pack.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
-    L.corb_pub_message.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
-    L.corb_pub_message_read.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
-    L.corb_pub_apply.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int32, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
-                                 C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_PublishOutputs)]
-    L.corb_map_publish_plan.argtypes = [C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_int)]
-    L.corb_map_publish_messages.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.c_void_p, C.POINTER(C.c_int)]
-    L.corb_map_publish.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(_PublishPack), C.POINTER(_PublishApply)]
-    for name in ESSGRAPH_EXPORTS:
-        if not hasattr(L, name):
-            raise CorbError("libcorb_accel.so lacks %s (include/corb_essential_graph.h): rebuild it" % name)
-    L.corb_covis_add_loop_edge.argtypes = [C.c_void_p, C.c_int, C.c_int]
-    L.corb_covis_get_loop_edges.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
-    L.corb_covis_clear_loop_edges.argtypes = [C.c_void_p, C.c_int]
-    L.corb_essential_graph_plan.argtypes = [C.c_void_p, C.POINTER(_EssentialGraphInput), C.c_int, C.c_int] + [C.c_void_p] * 8 + [C.POINTER(EssentialGraphCounts)]
-    L.corb_essential_graph_store.argtypes = [C.c_void_p, C.POINTER(_EssentialGraphInput), C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(EssentialGraphResult)]
-    for name in RECTIFY_EXPORTS:
-        if not hasattr(L, name):
-            raise CorbError("libcorb_accel.so lacks %s (include/corb_stereo_rectify.h): rebuild it" % name)
-    L.corb_rect_create.argtypes = [C.POINTER(RectifyConfig), C.c_void_p, C.POINTER(C.c_void_p)]
-    L.corb_rect_destroy.argtypes = [C.c_void_p]; L.corb_rect_destroy.restype = None
-    L.corb_rect_maps.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-    L.corb_rect_set_maps.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-    L.corb_rect_upload_batch.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
-    L.corb_rect_frames.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-    _lib = L
-    return L
+    if _lib is None:
+        if not os.path.exists(LIB_PATH):
+            raise CorbError("libcorb_accel.so is not built (run `python -c 'import __graft_entry__ as g; g.build()'`); "
+                            "there is no CPU fallback")
+        _lib = bind(C.CDLL(LIB_PATH))
+    return _lib
+
+
+class _Handle:
+    """The one owner of a library handle: `h` (a c_void_p, null once closed), the name of the function that destroys it, and whether this object owns the
+    handle or borrows it from another object (a borrowed handle is never destroyed)."""
+    _destroy = None
+    h, _owned = None, False         # of an object whose create never ran (immutable: no c_void_p is shared between objects)
+
+    def _create(self, what, *args):
+        """call the create function `what`, whose last parameter receives the handle, and own the result"""
+        self.h, self._owned = C.c_void_p(), True
+        _chk(getattr(load(), what)(*args, C.byref(self.h)), what)
+
+    @classmethod
+    def _adopt(cls, handle, owned=True, **attributes):
+        """an object of the class around an existing handle (no __init__), with the attributes given"""
+        self = cls.__new__(cls)
+        self.h, self._owned = handle if isinstance(handle, C.c_void_p) else C.c_void_p(handle), owned
+        self.__dict__.update(attributes)
+        return self
+
+    def close(self):
+        h, self.h = self.h, C.c_void_p()
+        if h and self._owned:
+            getattr(load(), self._destroy)(h)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
 
 
 def _chk(rc, what):
@@ -530,43 +91,29 @@ def device_count():
     return load().corb_device_count()
 
 
-class ORBextractor:
-    """Mirror of ORB_SLAM2::ORBextractor (corbslam_client/include/ORBextractor.h:45-114)."""
+class ORBextractor(_Handle):
+    """Mirror of ORB_SLAM2::ORBextractor (corbslam_client/include/ORBextractor.h:45-114).  _handle: the extractor of a front-end, borrowed."""
+    _destroy = "corb_orb_destroy"
 
     def __init__(self, nfeatures=2000, scaleFactor=1.2, nlevels=8, iniThFAST=20, minThFAST=7,
                  width=1241, height=376, max_images=1, device=0, _handle=None):
-        self.L = load()
         self.nlevels, self.width, self.height, self.max_images = nlevels, width, height, max_images
-        self._owned = _handle is None
         if _handle is None:
             cfg = OrbConfig(nfeatures, scaleFactor, nlevels, iniThFAST, minThFAST, width, height, max_images, device)
-            h = C.c_void_p()
-            _chk(self.L.corb_orb_create(C.byref(cfg), C.byref(h)), "corb_orb_create")
-            self.h = h
+            self._create("corb_orb_create", C.byref(cfg))
         else:
-            self.h = C.c_void_p(_handle)
+            self.h, self._owned = C.c_void_p(_handle), False
         self.cap = self._out_cap(nfeatures)
 
     def _out_cap(self, nfeatures):
         return nfeatures + 16 * self.nlevels + 256
-
-    def close(self):
-        if self._owned and self.h:
-            self.L.corb_orb_destroy(self.h)
-        self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     # getters (ORBextractor.h:62-82)
     def tables(self):
         n = self.nlevels
         sc, isc, s2, is2 = (np.zeros(n, np.float32) for _ in range(4))
         quota = np.zeros(n, np.int32); umax = np.zeros(16, np.int32)
-        _chk(self.L.corb_orb_tables(self.h, _p(sc), _p(isc), _p(s2), _p(is2), _p(quota), _p(umax)), "corb_orb_tables")
+        _chk(load().corb_orb_tables(self.h, _p(sc), _p(isc), _p(s2), _p(is2), _p(quota), _p(umax)), "corb_orb_tables")
         return dict(scale=sc, inv_scale=isc, sigma2=s2, inv_sigma2=is2, quota=quota, umax=umax)
 
     def GetScaleFactors(self):
@@ -580,49 +127,50 @@ class ORBextractor:
         image = np.ascontiguousarray(image, np.uint8)
         kps = np.zeros(self.cap, KP_DTYPE); desc = np.zeros((self.cap, 32), np.uint8); n = C.c_int()
         if image.size == 0:
-            _chk(self.L.corb_orb_extract(self.h, None, 0, 0, 0, _p(kps), _p(desc), self.cap, C.byref(n)), "corb_orb_extract")
+            _chk(load().corb_orb_extract(self.h, None, 0, 0, 0, _p(kps), _p(desc), self.cap, C.byref(n)), "corb_orb_extract")
         else:
             h, w = image.shape
-            _chk(self.L.corb_orb_extract(self.h, _p(image), w, h, w, _p(kps), _p(desc), self.cap, C.byref(n)), "corb_orb_extract")
+            _chk(load().corb_orb_extract(self.h, _p(image), w, h, w, _p(kps), _p(desc), self.cap, C.byref(n)), "corb_orb_extract")
         return kps[: n.value].copy(), desc[: n.value].copy()
 
     # batched path
     def upload(self, slot, image):
         image = np.ascontiguousarray(image, np.uint8)
         assert image.shape == (self.height, self.width)
-        _chk(self.L.corb_orb_upload(self.h, slot, _p(image), self.width), "corb_orb_upload")
+        _chk(load().corb_orb_upload(self.h, slot, _p(image), self.width), "corb_orb_upload")
         self._keep = image
 
     def run(self, n_images):
-        _chk(self.L.corb_orb_run(self.h, n_images), "corb_orb_run")
+        _chk(load().corb_orb_run(self.h, n_images), "corb_orb_run")
 
     def sync(self):
-        _chk(self.L.corb_orb_sync(self.h), "corb_orb_sync")
+        _chk(load().corb_orb_sync(self.h), "corb_orb_sync")
 
     def fetch(self, slot):
         kps = np.zeros(self.cap, KP_DTYPE); desc = np.zeros((self.cap, 32), np.uint8); n = C.c_int()
-        _chk(self.L.corb_orb_fetch(self.h, slot, _p(kps), _p(desc), self.cap, C.byref(n)), "corb_orb_fetch")
+        _chk(load().corb_orb_fetch(self.h, slot, _p(kps), _p(desc), self.cap, C.byref(n)), "corb_orb_fetch")
         return kps[: n.value].copy(), desc[: n.value].copy()
 
     def pyramid_level(self, slot, level, blurred=False):
         w, h = C.c_int(), C.c_int()
-        _chk(self.L.corb_orb_pyramid_level(self.h, slot, level, int(blurred), None, 0, C.byref(w), C.byref(h)), "pyramid_level")
+        _chk(load().corb_orb_pyramid_level(self.h, slot, level, bool(blurred), None, 0, C.byref(w), C.byref(h)), "pyramid_level")
         out = np.zeros((h.value, w.value), np.uint8)
-        _chk(self.L.corb_orb_pyramid_level(self.h, slot, level, int(blurred), _p(out), out.size, C.byref(w), C.byref(h)), "pyramid_level")
+        _chk(load().corb_orb_pyramid_level(self.h, slot, level, bool(blurred), _p(out), out.size, C.byref(w), C.byref(h)), "pyramid_level")
         return out
 
     def candidates(self, slot, level):
         cap = 1 << 20
         out = np.zeros(cap, KP_DTYPE); n = C.c_int()
-        _chk(self.L.corb_orb_fetch_candidates(self.h, slot, level, _p(out), cap, C.byref(n)), "fetch_candidates")
+        _chk(load().corb_orb_fetch_candidates(self.h, slot, level, _p(out), cap, C.byref(n)), "fetch_candidates")
         return out[: n.value].copy()
 
     def profile(self, enable=True):
-        _chk(self.L.corb_orb_profile(self.h, int(enable)), "corb_orb_profile")
+        """corb_orb_profile: a mode, not a flag -- 0 off, 1 (True) time the product sequence, 2 time every kernel unsplit on one stream"""
+        _chk(load().corb_orb_profile(self.h, int(enable)), "corb_orb_profile")
 
     def profile_read(self):
         arr = (KernelTime * 64)(); n = C.c_int()
-        _chk(self.L.corb_orb_profile_read(self.h, arr, 64, C.byref(n)), "corb_orb_profile_read")
+        _chk(load().corb_orb_profile_read(self.h, arr, 64, C.byref(n)), "corb_orb_profile_read")
         return {arr[i].name.decode(): (arr[i].total_ms, arr[i].launches) for i in range(n.value)}
 
 
@@ -631,13 +179,13 @@ _pinned_keep = []
 
 def warmup(device=0):
     """corb_warmup: create the two workspace lanes (stream, events, pinned block) now instead of inside the first optimisation of the process."""
-    _chk(load().corb_warmup(int(device)), "corb_warmup")
+    _chk(load().corb_warmup(device), "corb_warmup")
 
 
 def release_scratch(device=0):
     """corb_release_scratch: the workspace arenas and the host-array staging of `device` back to the runtime; returns the bytes freed."""
     n = C.c_uint64(0)
-    _chk(load().corb_release_scratch(int(device), C.byref(n)), "corb_release_scratch")
+    _chk(load().corb_release_scratch(device, C.byref(n)), "corb_release_scratch")
     return int(n.value)
 
 
@@ -645,96 +193,81 @@ def scratch_fill(lane, word, min_bytes, device=0):
     """corb_scratch_fill (test aid): the lane's arena as one chunk of at least `min_bytes`, every 32-bit word of it, of the staging and of the pinned block = `word`;
     returns the chunk's capacity."""
     cap = C.c_uint64(0)
-    _chk(load().corb_scratch_fill(int(device), int(lane), C.c_uint32(int(word)), C.c_uint64(int(min_bytes)), C.byref(cap)), "corb_scratch_fill")
+    _chk(load().corb_scratch_fill(device, lane, word, min_bytes, C.byref(cap)), "corb_scratch_fill")
     return int(cap.value)
 
 
 def scratch_report(lane, device=0):
     """corb_scratch_report (test aid): (arena capacity, number of chunks, staging capacity) of the lane"""
     cap = C.c_uint64(0); n = C.c_int(0); st = C.c_uint64(0)
-    _chk(load().corb_scratch_report(int(device), int(lane), C.byref(cap), C.byref(n), C.byref(st)), "corb_scratch_report")
+    _chk(load().corb_scratch_report(device, lane, C.byref(cap), C.byref(n), C.byref(st)), "corb_scratch_report")
     return int(cap.value), int(n.value), int(st.value)
 
 
 def scratch_read(lane, offset, nbytes, device=0):
     """corb_scratch_read (test aid): `nbytes` bytes at `offset` of the lane's single arena chunk as a uint8 array"""
     out = np.empty(int(nbytes), np.uint8)
-    _chk(load().corb_scratch_read(int(device), int(lane), C.c_uint64(int(offset)), C.c_uint64(int(nbytes)), _p(out)), "corb_scratch_read")
+    _chk(load().corb_scratch_read(device, lane, offset, nbytes, _p(out)), "corb_scratch_read")
     return out
 
 
 def pinned_empty(shape, dtype):
     """numpy array in page-locked host memory (hipHostMalloc): copies to / from it are DMA transfers and asynchronous on the handle's stream.
     The allocation lives until the process exits."""
-    L = load()                                              # (through the library: the HIP runtime IT is linked with must own the allocation)
     nbytes = int(np.prod(shape)) * np.dtype(dtype).itemsize
-    ptr = C.c_void_p()
-    L.corb_pinned_alloc.argtypes = [C.c_size_t, C.POINTER(C.c_void_p)]
-    _chk(L.corb_pinned_alloc(C.c_size_t(max(nbytes, 1)), C.byref(ptr)), "corb_pinned_alloc")
+    ptr = C.c_void_p()                                      # (through the library: the HIP runtime IT is linked with must own the allocation)
+    _chk(load().corb_pinned_alloc(max(nbytes, 1), C.byref(ptr)), "corb_pinned_alloc")
     buf = (C.c_uint8 * max(nbytes, 1)).from_address(ptr.value)
     _pinned_keep.append(buf)
     return np.frombuffer(buf, np.uint8, nbytes).view(dtype).reshape(shape)
 
 
-class StereoFrontend:
+class StereoFrontend(_Handle):
     """Frame::Frame(stereo) hot path (corbslam_client/src/Frame.cc:61-117): left/right extraction +
     ComputeStereoMatches for a batch of frames."""
+    _destroy = "corb_stereo_destroy"
 
     def __init__(self, nfeatures=2000, scaleFactor=1.2, nlevels=8, iniThFAST=20, minThFAST=7,
                  width=1241, height=376, max_frames=1, fx=718.856, bf=386.1448, device=0):
-        self.L = load()
         cfg = StereoConfig(OrbConfig(nfeatures, scaleFactor, nlevels, iniThFAST, minThFAST, width, height, 0, device),
                            max_frames, fx, bf)
-        h = C.c_void_p()
-        _chk(self.L.corb_stereo_create(C.byref(cfg), C.byref(h)), "corb_stereo_create")
-        self.h = h
+        self._create("corb_stereo_create", C.byref(cfg))
         self.max_frames = max_frames
         self.orb = ORBextractor(nfeatures, scaleFactor, nlevels, iniThFAST, minThFAST, width, height, 2 * max_frames,
-                                device, _handle=self.L.corb_stereo_orb(h))
+                                device, _handle=load().corb_stereo_orb(self.h))
         self._keep = []
-
-    def close(self):
-        if self.h:
-            self.L.corb_stereo_destroy(self.h)
-        self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def upload(self, frame, left, right):
         left = np.ascontiguousarray(left, np.uint8); right = np.ascontiguousarray(right, np.uint8)
-        _chk(self.L.corb_stereo_upload(self.h, frame, _p(left), _p(right), left.shape[1]), "corb_stereo_upload")
+        _chk(load().corb_stereo_upload(self.h, frame, _p(left), _p(right), left.shape[1]), "corb_stereo_upload")
         self._keep.append((left, right))
 
     def run(self, n_frames):
-        _chk(self.L.corb_stereo_run(self.h, n_frames), "corb_stereo_run")
+        _chk(load().corb_stereo_run(self.h, n_frames), "corb_stereo_run")
 
     def sync(self):
-        _chk(self.L.corb_stereo_sync(self.h), "corb_stereo_sync")
+        _chk(load().corb_stereo_sync(self.h), "corb_stereo_sync")
         self._keep = []
 
     def upload_batch(self, first, packed):
         """packed: uint8 array [n_frames][2][height][width] (left, right), C-contiguous; pinned memory makes it a DMA."""
         assert packed.flags["C_CONTIGUOUS"] and packed.dtype == np.uint8
-        _chk(self.L.corb_stereo_upload_batch(self.h, first, packed.shape[0], _p(packed)), "corb_stereo_upload_batch")
+        _chk(load().corb_stereo_upload_batch(self.h, first, packed.shape[0], _p(packed)), "corb_stereo_upload_batch")
 
     def fetch_batch(self, first, n, out=None):
         """All results of frames first .. first+n-1 in one set of copies.  Returns dict of strided arrays:
         kp [2n][cap], desc [2n][cap][32], counts [2n], u_right / depth [n][cap], n_matched [n]  (image 2f = left, 2f+1 = right)."""
-        cap = self.L.corb_orb_capacity(self.orb.h)
+        cap = load().corb_orb_capacity(self.orb.h)
         if out is None:
             out = dict(kp=np.zeros((2 * n, cap), KP_DTYPE), desc=np.zeros((2 * n, cap, 32), np.uint8), counts=np.zeros(2 * n, np.int32),
                        u_right=np.zeros((n, cap), np.float32), depth=np.zeros((n, cap), np.float32), n_matched=np.zeros(n, np.int32))
-        _chk(self.L.corb_orb_fetch_batch(self.orb.h, 2 * first, 2 * n, _p(out["kp"]), _p(out["desc"]), _p(out["counts"])), "corb_orb_fetch_batch")
-        _chk(self.L.corb_stereo_fetch_matches_batch(self.h, first, n, _p(out["u_right"]), _p(out["depth"]), _p(out["n_matched"])), "corb_stereo_fetch_matches_batch")
+        _chk(load().corb_orb_fetch_batch(self.orb.h, 2 * first, 2 * n, _p(out["kp"]), _p(out["desc"]), _p(out["counts"])), "corb_orb_fetch_batch")
+        _chk(load().corb_stereo_fetch_matches_batch(self.h, first, n, _p(out["u_right"]), _p(out["depth"]), _p(out["n_matched"])), "corb_stereo_fetch_matches_batch")
         return out
 
     def frame_layout(self):
         lay = StereoFrameLayout()
-        _chk(self.L.corb_stereo_frame_layout(self.h, C.byref(lay)), "corb_stereo_frame_layout")
+        _chk(load().corb_stereo_frame_layout(self.h, C.byref(lay)), "corb_stereo_frame_layout")
         return lay
 
     def frames(self, packed, result=None, timing=None):
@@ -745,7 +278,7 @@ class StereoFrontend:
         n = packed.shape[0]
         if result is None:
             result = np.zeros(n * self.frame_layout().frame_bytes, np.uint8)
-        _chk(self.L.corb_stereo_frames(self.h, n, _p(packed), _p(result), C.byref(timing) if timing is not None else None), "corb_stereo_frames")
+        _chk(load().corb_stereo_frames(self.h, n, _p(packed), _p(result), C.byref(timing) if timing is not None else None), "corb_stereo_frames")
         return result
 
     def unpack_frame(self, result, f=0):
@@ -763,17 +296,18 @@ class StereoFrontend:
         kr, dr = self.orb.fetch(2 * frame + 1)
         ur = np.zeros(self.orb.cap, np.float32); dp = np.zeros(self.orb.cap, np.float32)
         n, nm = C.c_int(), C.c_int()
-        _chk(self.L.corb_stereo_fetch_matches(self.h, frame, _p(ur), _p(dp), self.orb.cap, C.byref(n), C.byref(nm)), "fetch_matches")
+        _chk(load().corb_stereo_fetch_matches(self.h, frame, _p(ur), _p(dp), self.orb.cap, C.byref(n), C.byref(nm)), "fetch_matches")
         return dict(kl=kl, dl=dl, kr=kr, dr=dr, u_right=ur[: n.value].copy(), depth=dp[: n.value].copy(), n_matched=nm.value)
 
 
-class StereoRectifier:
+class StereoRectifier(_Handle):
     """What the reference's stereo mains for unrectified cameras do before TrackStereo (Examples/Stereo/stereo_euroc.cc:64-98,136-137): the maps of
     cv::initUndistortRectifyMap from LEFT / RIGHT {K, D, R, P}, and cv::remap(INTER_LINEAR) of every raw pair, on the device in front of a StereoFrontend
     (include/corb_stereo_rectify.h).  left / right: (K, D, R, P) with K, R 3x3, P 3x4 and D of 4, 5 or 8 coefficients.  Close it before its front-end."""
 
+    _destroy = "corb_rect_destroy"
+
     def __init__(self, stereo_frontend, left, right, raw_width, raw_height):
-        self.L = load()
         self.sf = stereo_frontend
         self.width, self.height, self.raw_width, self.raw_height = stereo_frontend.orb.width, stereo_frontend.orb.height, int(raw_width), int(raw_height)
         cfg = RectifyConfig(); cfg.raw_width = self.raw_width; cfg.raw_height = self.raw_height
@@ -781,9 +315,7 @@ class StereoRectifier:
             d = np.zeros(8); dd = np.asarray(D, np.float64).reshape(-1); d[: len(dd)] = dd
             for name, v, n in (("K", K, 9), ("D", d, 8), ("R", R, 9), ("P", P, 12)):
                 setattr(eye, name, (C.c_double * n)(*np.asarray(v, np.float64).reshape(n)))
-        h = C.c_void_p()
-        _chk(self.L.corb_rect_create(C.byref(cfg), stereo_frontend.h, C.byref(h)), "corb_rect_create")
-        self.h = h
+        self._create("corb_rect_create", C.byref(cfg), stereo_frontend.h)
 
     @staticmethod
     def read_settings(path):
@@ -807,26 +339,15 @@ class StereoRectifier:
         eye = lambda e: (s[e + ".K"], s[e + ".D"], s[e + ".R"], s[e + ".P"])
         return cls(stereo_frontend, eye("LEFT"), eye("RIGHT"), int(s["LEFT.width"]), int(s["LEFT.height"]))
 
-    def close(self):
-        if self.h:
-            self.L.corb_rect_destroy(self.h)
-        self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
     def maps(self, eye):
         mx = np.zeros((self.height, self.width), np.float32); my = np.zeros((self.height, self.width), np.float32)
-        _chk(self.L.corb_rect_maps(self.h, eye, _p(mx), _p(my)), "corb_rect_maps")
+        _chk(load().corb_rect_maps(self.h, eye, _p(mx), _p(my)), "corb_rect_maps")
         return mx, my
 
     def set_maps(self, eye, map_x, map_y):
         mx = np.ascontiguousarray(map_x, np.float32); my = np.ascontiguousarray(map_y, np.float32)
         assert mx.shape == (self.height, self.width) and my.shape == mx.shape
-        _chk(self.L.corb_rect_set_maps(self.h, eye, _p(mx), _p(my)), "corb_rect_set_maps")
+        _chk(load().corb_rect_set_maps(self.h, eye, _p(mx), _p(my)), "corb_rect_set_maps")
 
     def _raw(self, packed):
         assert packed.flags["C_CONTIGUOUS"] and packed.dtype == np.uint8 and packed.shape[1:] == (2, self.raw_height, self.raw_width)
@@ -834,47 +355,34 @@ class StereoRectifier:
 
     def upload_batch(self, first, packed):
         """packed: uint8 [n_frames][2][raw_height][raw_width] (raw left, raw right); afterwards the front-end's run / sync / fetch work unchanged"""
-        _chk(self.L.corb_rect_upload_batch(self.h, first, self._raw(packed), _p(packed)), "corb_rect_upload_batch")
+        _chk(load().corb_rect_upload_batch(self.h, first, self._raw(packed), _p(packed)), "corb_rect_upload_batch")
 
     def frames(self, packed, result=None, timing=None):
         """corb_rect_frames: StereoFrontend.frames for raw input; returns the result block that StereoFrontend.unpack_frame parses"""
         n = self._raw(packed)
         if result is None:
             result = np.zeros(n * self.sf.frame_layout().frame_bytes, np.uint8)
-        _chk(self.L.corb_rect_frames(self.h, n, _p(packed), _p(result), C.byref(timing) if timing is not None else None), "corb_rect_frames")
+        _chk(load().corb_rect_frames(self.h, n, _p(packed), _p(result), C.byref(timing) if timing is not None else None), "corb_rect_frames")
         return result
 
 
-class RgbdFrontend:
+class RgbdFrontend(_Handle):
     """Frame::Frame(RGB-D) / Frame::Frame(monocular) hot path (corbslam_client/src/Frame.cc:119-228) with the input conversions of
     Tracking::GrabImageRGBD / GrabImageMonocular (Tracking.cc:206-264): colour -> grey, extraction, UndistortKeyPoints, ComputeStereoFromRGBD.
     Defaults: TUM1's RGB-D settings file.  One frame of input = colour [height][width][channels] (or [height][width] grey) followed by the depth image
     [height][width] (uint16 or float32, RGB-D only); pack_input builds the block."""
+    _destroy = "corb_rgbd_destroy"
 
     def __init__(self, nfeatures=1000, scaleFactor=1.2, nlevels=8, iniThFAST=20, minThFAST=7, width=640, height=480, max_frames=1,
                  sensor=SENSOR_RGBD, channels=3, rgb=1, fx=517.306408, fy=516.469215, cx=318.643040, cy=255.313989,
                  k1=0.262383, k2=-0.953104, p1=-0.005358, p2=0.002628, k3=1.163314, bf=40.0, depth_map_factor=5000.0, depth_format=DEPTH_U16, device=0):
-        self.L = load()
         cfg = CameraConfig(OrbConfig(nfeatures, scaleFactor, nlevels, iniThFAST, minThFAST, width, height, 0, device), max_frames, sensor, channels, rgb,
                            fx, fy, cx, cy, k1, k2, p1, p2, k3, bf, depth_map_factor, depth_format)
-        h = C.c_void_p()
-        _chk(self.L.corb_rgbd_create(C.byref(cfg), C.byref(h)), "corb_rgbd_create")
-        self.h = h
+        self._create("corb_rgbd_create", C.byref(cfg))
         self.max_frames, self.width, self.height, self.channels = max_frames, width, height, channels
         self.sensor, self.depth_format = sensor, depth_format
-        self.orb = ORBextractor(nfeatures, scaleFactor, nlevels, iniThFAST, minThFAST, width, height, max_frames, device, _handle=self.L.corb_rgbd_orb(h))
+        self.orb = ORBextractor(nfeatures, scaleFactor, nlevels, iniThFAST, minThFAST, width, height, max_frames, device, _handle=load().corb_rgbd_orb(self.h))
         self.layout = self.frame_layout()
-
-    def close(self):
-        if self.h:
-            self.L.corb_rgbd_destroy(self.h)
-        self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def pack_input(self, frames):
         """frames: list of (colour, depth) pairs (depth None for monocular) -> uint8 [n][input_bytes]"""
@@ -890,20 +398,20 @@ class RgbdFrontend:
     def upload_batch(self, first, packed):
         """packed: uint8 [n][input_bytes], C-contiguous (pack_input)"""
         assert packed.flags["C_CONTIGUOUS"] and packed.dtype == np.uint8 and packed.size == packed.shape[0] * self.layout.input_bytes
-        _chk(self.L.corb_rgbd_upload_batch(self.h, first, packed.shape[0], _p(packed)), "corb_rgbd_upload_batch")
+        _chk(load().corb_rgbd_upload_batch(self.h, first, packed.shape[0], _p(packed)), "corb_rgbd_upload_batch")
 
     def run(self, n_frames):
-        _chk(self.L.corb_rgbd_run(self.h, n_frames), "corb_rgbd_run")
+        _chk(load().corb_rgbd_run(self.h, n_frames), "corb_rgbd_run")
 
     def sync(self):
-        _chk(self.L.corb_rgbd_sync(self.h), "corb_rgbd_sync")
+        _chk(load().corb_rgbd_sync(self.h), "corb_rgbd_sync")
 
     def fetch_batch(self, first, n):
         """strided results of frames first .. first+n-1: keys / keys_un [n][cap], desc [n][cap][32], u_right / depth [n][cap], counts [n]"""
         cap = self.layout.capacity
         out = dict(keys=np.zeros((n, cap), KP_DTYPE), keys_un=np.zeros((n, cap), KP_DTYPE), desc=np.zeros((n, cap, 32), np.uint8),
                    u_right=np.zeros((n, cap), np.float32), depth=np.zeros((n, cap), np.float32), counts=np.zeros(n, np.int32))
-        _chk(self.L.corb_rgbd_fetch_batch(self.h, first, n, _p(out["keys"]), _p(out["keys_un"]), _p(out["desc"]), _p(out["u_right"]), _p(out["depth"]),
+        _chk(load().corb_rgbd_fetch_batch(self.h, first, n, _p(out["keys"]), _p(out["keys_un"]), _p(out["desc"]), _p(out["u_right"]), _p(out["depth"]),
                                           _p(out["counts"])), "corb_rgbd_fetch_batch")
         return out
 
@@ -916,7 +424,7 @@ class RgbdFrontend:
 
     def frame_layout(self):
         lay = RgbdFrameLayout()
-        _chk(self.L.corb_rgbd_frame_layout(self.h, C.byref(lay)), "corb_rgbd_frame_layout")
+        _chk(load().corb_rgbd_frame_layout(self.h, C.byref(lay)), "corb_rgbd_frame_layout")
         return lay
 
     def frames(self, packed, result=None, timing=None):
@@ -926,7 +434,7 @@ class RgbdFrontend:
         n = packed.shape[0]
         if result is None:
             result = np.zeros(n * self.layout.frame_bytes, np.uint8)
-        _chk(self.L.corb_rgbd_frames(self.h, n, _p(packed), _p(result), C.byref(timing) if timing is not None else None), "corb_rgbd_frames")
+        _chk(load().corb_rgbd_frames(self.h, n, _p(packed), _p(result), C.byref(timing) if timing is not None else None), "corb_rgbd_frames")
         return result
 
     def unpack_frame(self, result, f=0):
@@ -942,7 +450,7 @@ class RgbdFrontend:
     def bounds(self):
         """Frame::ComputeImageBounds: (mnMinX, mnMaxX, mnMinY, mnMaxY) as float32"""
         out = np.zeros(4, np.float32)
-        _chk(self.L.corb_rgbd_image_bounds(self.h, _p(out)), "corb_rgbd_image_bounds")
+        _chk(load().corb_rgbd_image_bounds(self.h, _p(out)), "corb_rgbd_image_bounds")
         return out
 
 
@@ -959,7 +467,7 @@ class ORBmatcher:
 
     def __init__(self, nnratio=0.6, checkOri=True, device=0):
         self.nnratio, self.checkOri, self.device = float(nnratio), bool(checkOri), device
-        self.L = load()
+        load()                                                  # (a missing library is reported here, not by the first search)
 
     @staticmethod
     def DescriptorDistance(a, b, device=0):
@@ -977,7 +485,7 @@ class ORBmatcher:
         B = _BowSide(_p(d2), _p(a2), _p(v2), len(d2), _fv(*fv2, keep))
         nslots = len(d2) if variant == 0 else len(d1)
         match = np.zeros(max(nslots, 1), np.int32); n = C.c_int()
-        _chk(self.L.corb_search_by_bow(variant, C.byref(A), C.byref(B), self.nnratio, int(self.checkOri), _p(match),
+        _chk(load().corb_search_by_bow(variant, C.byref(A), C.byref(B), self.nnratio, self.checkOri, _p(match),
                                        C.byref(n), self.device), "corb_search_by_bow")
         return match[:nslots], n.value
 
@@ -1004,7 +512,7 @@ class ORBmatcher:
         keep = []; fv = self._frame_view(frame, keep)
         mps = np.ascontiguousarray(mps, TRACKED_DTYPE); mp_desc = np.ascontiguousarray(mp_desc, np.uint8)
         match = np.zeros(max(len(frame["keys_un"]), 1), np.int32); n = C.c_int()
-        _chk(self.L.corb_search_by_projection_map(C.byref(fv), _p(mps), _p(mp_desc), len(mps), float(th), self.nnratio, _p(match), C.byref(n), self.device),
+        _chk(load().corb_search_by_projection_map(C.byref(fv), _p(mps), _p(mp_desc), len(mps), th, self.nnratio, _p(match), C.byref(n), self.device),
              "corb_search_by_projection_map")
         return match[: len(frame["keys_un"])].copy(), n.value
 
@@ -1014,8 +522,8 @@ class ORBmatcher:
         Tcw = np.ascontiguousarray(Tcw, np.float32).reshape(16); Tlw = np.ascontiguousarray(Tlw, np.float32).reshape(16)
         last = np.ascontiguousarray(last, LAST_DTYPE); last_desc = np.ascontiguousarray(last_desc, np.uint8)
         match = np.zeros(max(len(cur["keys_un"]), 1), np.int32); n = C.c_int()
-        _chk(self.L.corb_search_by_projection_frame(C.byref(fv), _p(Tcw), _p(Tlw), fx, fy, cx, cy, bf, mb, _p(last), _p(last_desc), len(last),
-                                                    float(th), int(bMono), int(self.checkOri), _p(match), C.byref(n), self.device),
+        _chk(load().corb_search_by_projection_frame(C.byref(fv), _p(Tcw), _p(Tlw), fx, fy, cx, cy, bf, mb, _p(last), _p(last_desc), len(last),
+                                                    th, bool(bMono), self.checkOri, _p(match), C.byref(n), self.device),
              "corb_search_by_projection_frame")
         return match[: len(cur["keys_un"])].copy(), n.value
 
@@ -1033,7 +541,7 @@ class ORBmatcher:
         claimed = np.ascontiguousarray(claimed, np.uint8); Tcw = np.ascontiguousarray(Tcw, np.float32).reshape(16)
         pts = np.ascontiguousarray(pts, MP_DTYPE); desc = np.ascontiguousarray(desc, np.uint8)
         match = np.zeros(max(len(cur["keys_un"]), 1), np.int32); n = C.c_int()
-        _chk(self.L.corb_search_by_projection_reloc(C.byref(kv), _p(claimed), _p(Tcw), _p(pts), _p(desc), len(pts), float(th), int(ORBdist), int(self.checkOri),
+        _chk(load().corb_search_by_projection_reloc(C.byref(kv), _p(claimed), _p(Tcw), _p(pts), _p(desc), len(pts), th, ORBdist, self.checkOri,
                                                     _p(match), C.byref(n), self.device), "corb_search_by_projection_reloc")
         return match[: len(cur["keys_un"])].copy(), n.value
 
@@ -1046,7 +554,7 @@ class ORBmatcher:
         v1, v2 = fv(f1), fv(f2)
         pm = np.array(prev_matched, np.float32, copy=True).reshape(-1, 2); assert len(pm) == len(f1["keys_un"])
         m = np.zeros(max(len(pm), 1), np.int32); n = C.c_int()
-        _chk(self.L.corb_search_for_initialization(C.byref(v1), C.byref(v2), _p(pm), int(window_size), float(self.nnratio), int(self.checkOri), _p(m), C.byref(n), self.device),
+        _chk(load().corb_search_for_initialization(C.byref(v1), C.byref(v2), _p(pm), window_size, self.nnratio, self.checkOri, _p(m), C.byref(n), self.device),
              "corb_search_for_initialization")
         return m[: len(pm)].copy(), pm, n.value
 
@@ -1059,7 +567,7 @@ class ORBmatcher:
         Scw = np.ascontiguousarray(Scw, np.float32).reshape(16)
         pts = np.ascontiguousarray(pts, MP_DTYPE); desc = np.ascontiguousarray(desc, np.uint8)
         match = np.zeros(max(nk, 1), np.int32); n = C.c_int()
-        _chk(self.L.corb_search_by_projection_scw(C.byref(kv), _p(claimed), _p(Scw), _p(pts), _p(desc), len(pts), float(th), _p(match), C.byref(n), self.device),
+        _chk(load().corb_search_by_projection_scw(C.byref(kv), _p(claimed), _p(Scw), _p(pts), _p(desc), len(pts), th, _p(match), C.byref(n), self.device),
              "corb_search_by_projection_scw")
         return match[:nk].copy(), n.value
 
@@ -1070,7 +578,7 @@ class ORBmatcher:
         T = np.ascontiguousarray(T, np.float32).reshape(16); Ow = np.ascontiguousarray(Ow if Ow is not None else np.zeros(3), np.float32)
         pts = np.ascontiguousarray(pts, MP_DTYPE); desc = np.ascontiguousarray(desc, np.uint8)
         bi = np.zeros(max(len(pts), 1), np.int32); bd = np.zeros(max(len(pts), 1), np.int32); n = C.c_int()
-        _chk(self.L.corb_fuse(C.byref(kv), _p(T), _p(Ow), int(sim3), _p(pts), _p(desc), len(pts), float(th), _p(bi), _p(bd), C.byref(n), self.device), "corb_fuse")
+        _chk(load().corb_fuse(C.byref(kv), _p(T), _p(Ow), bool(sim3), _p(pts), _p(desc), len(pts), th, _p(bi), _p(bd), C.byref(n), self.device), "corb_fuse")
         return bi[: len(pts)].copy(), bd[: len(pts)].copy(), n.value
 
     def SearchBySim3(self, kf1, kf2, T1w, T2w, pts1, desc1, pts2, desc2, s12, R12, t12, th):
@@ -1080,8 +588,8 @@ class ORBmatcher:
         desc1 = np.ascontiguousarray(desc1, np.uint8); desc2 = np.ascontiguousarray(desc2, np.uint8)
         R12 = np.ascontiguousarray(R12, np.float32).reshape(9); t12 = np.ascontiguousarray(t12, np.float32).reshape(3)
         m = np.zeros(max(len(pts1), 1), np.int32); n = C.c_int()
-        _chk(self.L.corb_search_by_sim3(C.byref(k1), C.byref(k2), _p(T1w), _p(T2w), _p(pts1), _p(desc1), _p(pts2), _p(desc2), float(np.float32(s12)),
-                                        _p(R12), _p(t12), float(th), _p(m), C.byref(n), self.device), "corb_search_by_sim3")
+        _chk(load().corb_search_by_sim3(C.byref(k1), C.byref(k2), _p(T1w), _p(T2w), _p(pts1), _p(desc1), _p(pts2), _p(desc2), s12,
+                                        _p(R12), _p(t12), th, _p(m), C.byref(n), self.device), "corb_search_by_sim3")
         return m[: len(pts1)].copy(), n.value
 
     def SearchForTriangulation(self, kf1, kf2, F12, ex, ey, scale2, sigma2_2, bOnlyStereo):
@@ -1095,19 +603,10 @@ class ORBmatcher:
         F = np.ascontiguousarray(F12, np.float32).reshape(9)
         sc = np.ascontiguousarray(scale2, np.float32); sg = np.ascontiguousarray(sigma2_2, np.float32)
         pairs = np.zeros((max(len(kf1["desc"]), 1), 2), np.int32); n = C.c_int()
-        _chk(self.L.corb_search_for_triangulation(C.byref(A), C.byref(B), _p(F), float(np.float32(ex)), float(np.float32(ey)),
-                                                  _p(sc), _p(sg), len(sc), int(bOnlyStereo), int(self.checkOri), _p(pairs),
+        _chk(load().corb_search_for_triangulation(C.byref(A), C.byref(B), _p(F), ex, ey,
+                                                  _p(sc), _p(sg), len(sc), bool(bOnlyStereo), self.checkOri, _p(pairs),
                                                   C.byref(n), self.device), "corb_search_for_triangulation")
         return pairs[: n.value].copy(), n.value
-
-
-# status of a pair in CreateNewMapPoints (include/corb_accel.h: CORB_NP_*)
-NP_OK, NP_NO_PARALLAX, NP_W_ZERO, NP_BEHIND_1, NP_BEHIND_2, NP_REPROJ_1, NP_REPROJ_2, NP_SCALE = range(8)
-
-
-class _NewPointSide(C.Structure):
-    _fields_ = [("keys_un", C.c_void_p), ("u_right", C.c_void_p), ("depth", C.c_void_p), ("n", C.c_int32), ("Tcw", C.c_float * 16)] + \
-               [(k, C.c_float) for k in ("fx", "fy", "cx", "cy", "bf", "mb")] + [("scale", C.c_void_p), ("nlevels", C.c_int32)]
 
 
 def TriangulatePairs(kf1, kf2, pairs, device=0):
@@ -1132,14 +631,6 @@ def TriangulatePairs(kf1, kf2, pairs, device=0):
     return x3d[:n], st[:n], src[:n], nn.value
 
 
-class _Sim3RansacProblem(C.Structure):
-    _fields_ = [("n", C.c_int32), ("p1c", C.c_void_p), ("p2c", C.c_void_p), ("sigma2_1", C.c_void_p), ("sigma2_2", C.c_void_p)] + \
-               [(k, C.c_float) for k in ("fx1", "fy1", "cx1", "cy1", "fx2", "fy2", "cx2", "cy2")]
-
-
-SIM3_EVENT_DTYPE = np.dtype([("iteration", "<i4"), ("n_inliers", "<i4"), ("R12", "<f4", 9), ("t12", "<f4", 3), ("s12", "<f4")])      # CorbSim3RansacEvent
-
-
 def _sim3_ransac_result(c, n_ev, max_events, cap, events, flags, counts, q):
     k = min(int(n_ev[c]), max_events)
     return dict(ransac_max_its=int(cap[c]), n_events=int(n_ev[c]), events=events[c, :k].copy(), inliers=flags[c, :k].astype(bool),
@@ -1162,7 +653,7 @@ def Sim3Ransac(problems, rand_values, probability=0.99, min_inliers=20, max_iter
     assert len(rv) == n * max_iterations * 3
     cap = np.zeros(max(n, 1), np.int32); n_ev = np.zeros(max(n, 1), np.int32); ev = np.zeros((max(n, 1), max(max_events, 1)), SIM3_EVENT_DTYPE)
     fl = np.zeros((max(n, 1), max(max_events, 1), stride), np.uint8); cnt = np.zeros((max(n, 1), max_iterations), np.int32); qo = np.zeros((max(n, 1), max_iterations, 4), np.float32)
-    _chk(load().corb_sim3_ransac(C.cast(arr, C.c_void_p), n, float(probability), int(min_inliers), int(max_iterations), int(bool(fix_scale)), _p(rv), max_events, stride,
+    _chk(load().corb_sim3_ransac(C.cast(arr, C.c_void_p), n, probability, min_inliers, max_iterations, bool(fix_scale), _p(rv), max_events, stride,
                                  _p(cap), _p(n_ev), _p(ev), _p(fl), _p(cnt), _p(qo), device), "corb_sim3_ransac")
     out = [_sim3_ransac_result(c, n_ev, max_events, cap, ev, fl, cnt, qo) for c in range(n)]
     for c, r in enumerate(out):
@@ -1232,14 +723,6 @@ class Sim3Solver:
         return None if self._last is None else float(self._last["s12"])
 
 
-class _PnPRansacProblem(C.Structure):
-    _fields_ = [("n", C.c_int32), ("p3dw", C.c_void_p), ("p2d", C.c_void_p), ("sigma2", C.c_void_p)] + [(k, C.c_float) for k in ("fx", "fy", "cx", "cy")]
-
-
-PNP_RECORD_DTYPE = np.dtype([("iteration", "<i4"), ("n_inliers", "<i4"), ("Tcw_best", "<f4", 12), ("n_refined", "<i4"), ("refine_ok", "<i4"),
-                             ("Tcw_refined", "<f4", 12)])                                                              # CorbPnPRansacRecord
-
-
 def PnPRansac(problems, rand_values, probability=0.99, min_inliers=8, max_iterations=300, min_set=4, epsilon=0.4, th2=5.991, tail_iterations=0, max_records=None, device=0):
     """PnPsolver's RANSAC, Refine() included, for a list of candidates in one call (corb_pnp_ransac).  problems: dicts(p3dw [n, 3], p2d [n, 2], sigma2 [n], K = (fx, fy,
     cx, cy)); rand_values [n_problems, max_iterations + tail_iterations, min_set] results of rand().  Returns per problem dict(ransac_max_its, ransac_min_inliers,
@@ -1259,8 +742,8 @@ def PnPRansac(problems, rand_values, probability=0.99, min_inliers=8, max_iterat
     cap = np.zeros(n1, np.int32); mi = np.zeros(n1, np.int32); n_rec = np.zeros(n1, np.int32); rec = np.zeros((n1, r1), PNP_RECORD_DTYPE)
     bf = np.zeros((n1, r1, stride), np.uint8); rf = np.zeros((n1, r1, stride), np.uint8); cnt = np.zeros((n1, max(stride_its, 1)), np.int32)
     po = np.zeros((n1, max(stride_its, 1), 16), np.float64); rpo = np.zeros((n1, r1, 16), np.float64)
-    _chk(load().corb_pnp_ransac(C.cast(arr, C.c_void_p), n, float(probability), int(min_inliers), int(max_iterations), int(min_set), float(epsilon), float(th2),
-                                int(tail_iterations), _p(rv), max_records, stride, _p(cap), _p(mi), _p(n_rec), _p(rec), _p(bf), _p(rf), _p(cnt), _p(po), _p(rpo), device),
+    _chk(load().corb_pnp_ransac(C.cast(arr, C.c_void_p), n, probability, min_inliers, max_iterations, min_set, epsilon, th2,
+                                tail_iterations, _p(rv), max_records, stride, _p(cap), _p(mi), _p(n_rec), _p(rec), _p(bf), _p(rf), _p(cnt), _p(po), _p(rpo), device),
          "corb_pnp_ransac")
     out = []
     for c in range(n):
@@ -1279,7 +762,7 @@ def PnPRansacStore(frames, slot, mp_store, cam, matched_ids, rand_values, probab
     """PnPsolver's constructor, RANSAC and Refine() on records (corb_pnp_ransac_store): the frame = record `slot` of the KeyFrameStore `frames`, matched_ids [n_candidates,
     n(slot)] = one row of vvpMapPointMatches per candidate as MapPoint ids.  Returns per candidate what PnPRansac returns (both inlier sets per feature of the frame =
     vbInliers) plus n_corr and index = mvKeyPointIndices."""
-    n1 = load().corb_kf_store_count(frames.h, int(slot))          # the host-known count: an empty slot (-1) is the library's error to report
+    n1 = load().corb_kf_store_count(frames.h, slot)          # the host-known count: an empty slot (-1) is the library's error to report
     ids = np.ascontiguousarray(matched_ids, np.uint64); ids = ids.reshape(len(ids), -1); n = len(ids)
     assert n == 0 or n1 <= 0 or ids.shape[1] == n1
     stride_its = int(max_iterations) + int(tail_iterations); max_records = stride_its if max_records is None else int(max_records)
@@ -1289,8 +772,8 @@ def PnPRansacStore(frames, slot, mp_store, cam, matched_ids, rand_values, probab
     cap = np.zeros(nn, np.int32); mi = np.zeros(nn, np.int32); n_rec = np.zeros(nn, np.int32); rec = np.zeros((nn, r1), PNP_RECORD_DTYPE)
     bf = np.zeros((nn, r1, s1), np.uint8); rf = np.zeros((nn, r1, s1), np.uint8); cnt = np.zeros((nn, max(stride_its, 1)), np.int32)
     po = np.zeros((nn, max(stride_its, 1), 16), np.float64); rpo = np.zeros((nn, r1, 16), np.float64); ncorr = np.zeros(nn, np.int32); index = np.full((nn, s1), -1, np.int32)
-    _chk(load().corb_pnp_ransac_store(frames.h, int(slot), mp_store.h, C.byref(cam), _p(ids), n, float(probability), int(min_inliers), int(max_iterations), int(min_set),
-                                      float(epsilon), float(th2), int(tail_iterations), _p(rv), max_records, _p(cap), _p(mi), _p(n_rec), _p(rec), _p(bf), _p(rf), _p(ncorr),
+    _chk(load().corb_pnp_ransac_store(frames.h, slot, mp_store.h, C.byref(cam), _p(ids), n, probability, min_inliers, max_iterations, min_set,
+                                      epsilon, th2, tail_iterations, _p(rv), max_records, _p(cap), _p(mi), _p(n_rec), _p(rec), _p(bf), _p(rf), _p(ncorr),
                                       _p(index), _p(cnt), _p(po), _p(rpo)), "corb_pnp_ransac_store")
     out = []
     for c in range(n):
@@ -1366,17 +849,6 @@ class PnPsolver:
         return T, vb, n
 
 
-class _InitProblem(C.Structure):
-    _fields_ = [("keys1", C.c_void_p), ("n1", C.c_int32), ("keys2", C.c_void_p), ("n2", C.c_int32), ("matches12", C.c_void_p)] + [(k, C.c_float) for k in ("fx", "fy", "cx", "cy")]
-
-
-INIT_RESULT_DTYPE = np.dtype([("status", "<i4"), ("model", "<i4"), ("n_matches", "<i4"), ("score_h", "<f4"), ("score_f", "<f4"), ("rh", "<f4"), ("best_it_h", "<i4"),
-                              ("best_it_f", "<i4"), ("H21", "<f4", 9), ("F21", "<f4", 9), ("n_inliers", "<i4"), ("n_good", "<i4", 8), ("cos_parallax", "<f4", 8),
-                              ("parallax", "<f4", 8), ("best_hypothesis", "<i4"), ("second_best_good", "<i4"), ("R21", "<f4", 9), ("t21", "<f4", 3),
-                              ("n_triangulated", "<i4")])                                                             # CorbInitResult
-INIT_OK, INIT_NO_MODEL, INIT_H_DEGENERATE, INIT_AMBIGUOUS, INIT_FEW_POINTS, INIT_LOW_PARALLAX = range(6)                # CORB_INIT_*
-
-
 def _keys(k):
     """keypoints as KP_DTYPE records: a KP_DTYPE array, or [n, 2] coordinates"""
     k = np.asarray(k)
@@ -1404,7 +876,7 @@ def MonoInitialize(problems, rand_values, sigma=1.0, max_iterations=200, min_par
     n1 = max(n, 1)
     res = np.zeros(n1, INIT_RESULT_DTYPE); p3d = np.zeros((n1, ps, 3), np.float32); tri = np.zeros((n1, ps), np.uint8)
     ih = np.zeros((n1, fs), np.uint8); i_f = np.zeros((n1, fs), np.uint8); sc = np.zeros((n1, int(max_iterations), 2), np.float32)
-    _chk(load().corb_mono_initialize(C.cast(arr, C.c_void_p), n, float(sigma), int(max_iterations), float(min_parallax), int(min_triangulated), _p(rv), ps, fs, _p(res), _p(p3d),
+    _chk(load().corb_mono_initialize(C.cast(arr, C.c_void_p), n, sigma, max_iterations, min_parallax, min_triangulated, _p(rv), ps, fs, _p(res), _p(p3d),
                                      _p(tri), _p(ih), _p(i_f), _p(sc), device), "corb_mono_initialize")
     return [dict(result=res[c].copy(), p3d=p3d[c, :len(keep[c][0])].copy(), triangulated=tri[c, :len(keep[c][0])].astype(bool), inliers_h=ih[c, :Ns[c]].astype(bool),
                  inliers_f=i_f[c, :Ns[c]].astype(bool), scores=sc[c].copy(), raw=dict(p3d=p3d[c], triangulated=tri[c], inliers_h=ih[c], inliers_f=i_f[c])) for c in range(n)]
@@ -1468,9 +940,9 @@ class Optimizer:
         res = _BAResult(_p(oposes), _p(opoints), _p(chi2), _p(lam), 0, 0, 0, 0, 0, 0, 0, 0, 0)
         opt = BAOptions(solver, pcg_tol, pcg_max_iter, pc_block, pc_multilevel)
         if devflat:          # the graph flattening on the device (the path of corb_ba_solve_store)
-            _chk(load().corb_ba_solve_devflat(C.byref(prob), nIterations, int(bRobust), C.byref(res), device, C.byref(opt)), "corb_ba_solve_devflat")
+            _chk(load().corb_ba_solve_devflat(C.byref(prob), nIterations, bool(bRobust), C.byref(res), device, C.byref(opt)), "corb_ba_solve_devflat")
         else:
-            _chk(load().corb_ba_solve_ex(C.byref(prob), nIterations, int(bRobust), None, C.byref(res), device, C.byref(opt)), "corb_ba_solve_ex")
+            _chk(load().corb_ba_solve_ex(C.byref(prob), nIterations, bool(bRobust), None, C.byref(res), device, C.byref(opt)), "corb_ba_solve_ex")
         return dict(poses=oposes.reshape(-1, 4, 4), points=opoints, chi2=chi2[: res.iters_done + 1],
                     lam=lam[: res.iters_done], iters_done=res.iters_done, trials=res.trials_total,
                     solver=res.solver_used, pcg_iterations=res.pcg_iterations, reserved0=res.reserved0,
@@ -1532,7 +1004,7 @@ class Optimizer:
         meas = np.ascontiguousarray(g["meas"], np.float64)
         Tiw = np.zeros((len(S), 16), np.float32); pts = np.ascontiguousarray(g["points"], np.float32).copy(); ref = np.ascontiguousarray(g["ref"], np.int32)
         chi2 = np.zeros(iterations + 1, np.float64); it = C.c_int32()
-        _chk(load().corb_optimize_essential_graph(len(S), _p(S), _p(fixed), len(vi), _p(vi), _p(vj), _p(meas), iterations, int(bFixScale), _p(Tiw), len(pts),
+        _chk(load().corb_optimize_essential_graph(len(S), _p(S), _p(fixed), len(vi), _p(vi), _p(vj), _p(meas), iterations, bool(bFixScale), _p(Tiw), len(pts),
                                                   _p(ref), _p(pts), _p(chi2), C.byref(it), device), "corb_optimize_essential_graph")
         return dict(S=S, chi2=chi2[: it.value + 1], iters_done=it.value, Tiw=Tiw.reshape(-1, 4, 4), points=pts)
 
@@ -1540,7 +1012,7 @@ class Optimizer:
     def OptimizeSim3(problems, th2=10.0, bFixScale=False, device=0):
         """Optimizer::OptimizeSim3 for a list of loop-closure candidates (dicts like synth.sim3_problem).  Returns a list of
         dict(R, t, s, removed, n_in, iters_done)."""
-        L = load(); n = len(problems)
+        n = len(problems)
         arr = (_Sim3Problem * n)(); keep = []; rem = []
         R = np.zeros((n, 9), np.float64); t = np.zeros((n, 3), np.float64); s = np.zeros(n, np.float64)
         for f, q in enumerate(problems):
@@ -1551,14 +1023,13 @@ class Optimizer:
             R[f] = np.asarray(q["R12"], np.float64).reshape(9); t[f] = np.asarray(q["t12"], np.float64).reshape(3); s[f] = q["s12"]
         rptr = (C.c_void_p * n)(*[r.ctypes.data for r in rem])
         nin = np.zeros(n, np.int32); its = np.zeros(n, np.int32)
-        _chk(L.corb_optimize_sim3(arr, n, _p(R), _p(t), _p(s), float(np.float32(th2)), int(bFixScale), C.cast(rptr, C.c_void_p), _p(nin), _p(its), device), "corb_optimize_sim3")
+        _chk(load().corb_optimize_sim3(arr, n, _p(R), _p(t), _p(s), th2, bool(bFixScale), C.cast(rptr, C.c_void_p), _p(nin), _p(its), device), "corb_optimize_sim3")
         return [dict(R=R[f].reshape(3, 3).copy(), t=t[f].copy(), s=float(s[f]), removed=rem[f][: len(keep[f][0])].copy(), n_in=int(nin[f]), iters_done=int(its[f])) for f in range(n)]
 
     @staticmethod
     def PoseOptimizationBatch(frames, fx, fy, cx, cy, bf, device=0):
         """corb_pose_optimization_batch: frames = list of (Tcw, points, obs, inv_sigma2).  Returns a list of
         (Tcw, mvbOutlier, n_inliers) -- one workgroup per frame, one launch for the whole batch."""
-        L = load()
         n = len(frames)
         arr = (_PoseOptFrame * n)()
         keep = []
@@ -1574,17 +1045,12 @@ class Optimizer:
         Tout = np.zeros((n, 16), np.float32)
         ninl = np.zeros(n, np.int32)
         optr = (C.c_void_p * n)(*[o.ctypes.data for o in outl])
-        _chk(L.corb_pose_optimization_batch(arr, n, _p(Tout), C.cast(optr, C.c_void_p), _p(ninl), device), "corb_pose_optimization_batch")
+        _chk(load().corb_pose_optimization_batch(arr, n, _p(Tout), C.cast(optr, C.c_void_p), _p(ninl), device), "corb_pose_optimization_batch")
         return [(Tout[f].reshape(4, 4).copy(), outl[f][: len(keep[f][1])].astype(bool), int(ninl[f])) for f in range(n)]
 
 
-
-BOW_MAX_FEATURES = 8192                          # CORB_BOW_MAX_FEATURES
-KFDB_STATE_DTYPE = np.dtype([("loop_query", "<u8"), ("loop_words", "<i4"), ("loop_score", "<f4"), ("reloc_query", "<u8"), ("reloc_words", "<i4"), ("reloc_score", "<f4")])
-
-
 def bow_profile(enable, device=0):
-    _chk(load().corb_bow_profile(int(enable), device), "corb_bow_profile")
+    _chk(load().corb_bow_profile(bool(enable), device), "corb_bow_profile")
 
 
 def bow_profile_read():
@@ -1594,24 +1060,25 @@ def bow_profile_read():
     return dict((out[i].name.decode(), (out[i].total_ms, out[i].launches)) for i in range(min(n.value, 32)))
 
 
-class Vocabulary:
+class Vocabulary(_Handle):
     """ORBVocabulary (DBoW2::TemplatedVocabulary, L1_NORM / TF_IDF) on the device (corb_voc_*): flat arrays in -- node ids 1 .. n in array order, the root is node 0 -- or
     the text format of loadFromTextFile."""
+    _destroy = "corb_voc_destroy"
 
     def __init__(self, k, L, parent, is_leaf, descriptor, weight, scoring=0, weighting=0, device=0):
         p = np.ascontiguousarray(parent, np.int32); lf = np.ascontiguousarray(is_leaf, np.int32); d = np.ascontiguousarray(descriptor, np.uint8).reshape(-1, 32)
         w = np.ascontiguousarray(weight, np.float64)
         if not (len(p) == len(lf) == len(d) == len(w)):
             raise CorbError("Vocabulary: the node arrays differ in length")
-        self.h = C.c_void_p(); self.device = device
+        self.device = device
         c = _VocDesc(int(k), int(L), int(scoring), int(weighting), len(p), _p(p), _p(lf), _p(d), _p(w))
-        _chk(load().corb_voc_create(C.byref(c), device, C.byref(self.h)), "corb_voc_create")
+        self._create("corb_voc_create", C.byref(c), device)
 
     @classmethod
     def from_text(cls, path, device=0):
-        self = cls.__new__(cls); self.h = C.c_void_p(); self.device = device
-        _chk(load().corb_voc_load_text(os.fsencode(path), device, C.byref(self.h)), "corb_voc_load_text")
-        return self
+        h = C.c_void_p()
+        _chk(load().corb_voc_load_text(os.fsencode(path), device, C.byref(h)), "corb_voc_load_text")
+        return cls._adopt(h, device=device)
 
     train_stats = None          # of a trained vocabulary: CorbVocTrainStats as a dict
 
@@ -1625,21 +1092,18 @@ class Vocabulary:
 
     @classmethod
     def _train_raw(cls, desc, off, k, L, seed, max_iterations, device):
-        self = cls.__new__(cls); self.h = C.c_void_p(); self.device = device
+        h = C.c_void_p()
         opt = VocTrainOptions(int(k), int(L), int(max_iterations), 0, int(seed) & (2 ** 64 - 1)); st = VocTrainStats()
-        _chk(load().corb_voc_train(_p(desc), _p(np.ascontiguousarray(off, np.int32)), len(off) - 1, C.byref(opt), device, C.byref(self.h), C.byref(st)), "corb_voc_train")
-        self.train_stats = st.as_dict()
-        return self
+        _chk(load().corb_voc_train(_p(desc), _p(np.ascontiguousarray(off, np.int32)), len(off) - 1, C.byref(opt), device, C.byref(h), C.byref(st)), "corb_voc_train")
+        return cls._adopt(h, device=device, train_stats=st.as_dict())
 
     @classmethod
     def train_store(cls, store, slots, k, L, seed, max_iterations=100):
         """corb_voc_train_store: every slot of a KeyFrameStore is one training image; the descriptors stay on the device"""
-        self = cls.__new__(cls); self.h = C.c_void_p(); self.device = getattr(store, "device", 0)
-        sl = np.ascontiguousarray(slots, np.int32)
+        h = C.c_void_p(); sl = np.ascontiguousarray(slots, np.int32)
         opt = VocTrainOptions(int(k), int(L), int(max_iterations), 0, int(seed) & (2 ** 64 - 1)); st = VocTrainStats()
-        _chk(load().corb_voc_train_store(store.h, _p(sl), len(sl), C.byref(opt), C.byref(self.h), C.byref(st)), "corb_voc_train_store")
-        self.train_stats = st.as_dict()
-        return self
+        _chk(load().corb_voc_train_store(store.h, _p(sl), len(sl), C.byref(opt), C.byref(h), C.byref(st)), "corb_voc_train_store")
+        return cls._adopt(h, device=getattr(store, "device", 0), train_stats=st.as_dict())
 
     def flat(self, cap_nodes=None):
         """corb_voc_get: the flat arrays of the vocabulary, as dbow_reference.Vocabulary.flat() names them"""
@@ -1650,17 +1114,7 @@ class Vocabulary:
 
     def save_text(self, path, digits=0):
         """corb_voc_save_text: the reference's saveToTextFile; digits = 17 reloads bit for bit"""
-        _chk(load().corb_voc_save_text(self.h, os.fsencode(path), int(digits)), "corb_voc_save_text")
-
-    def close(self):
-        if self.h:
-            load().corb_voc_destroy(self.h); self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        _chk(load().corb_voc_save_text(self.h, os.fsencode(path), digits), "corb_voc_save_text")
 
     def info(self):
         v = [C.c_int32(0) for _ in range(4)]
@@ -1675,7 +1129,7 @@ class Vocabulary:
         desc = np.concatenate(sets) if sets else np.zeros((0, 32), np.uint8)
         word = np.zeros(t, np.uint32); val = np.zeros(t, np.float64); bc = np.zeros(ns, np.int32); node = np.zeros(t, np.uint32); fo = np.zeros(t + ns, np.int32)
         idx = np.zeros(t, np.uint32); nn = np.zeros(ns, np.int32); fw = np.zeros(t, np.int32) if per_feature else None; fn = np.zeros(t, np.uint32) if per_feature else None
-        _chk(load().corb_voc_transform(self.h, _p(np.ascontiguousarray(desc)), _p(off), ns, int(levelsup), _p(word), _p(val), _p(bc), _p(node), _p(fo), _p(idx), _p(nn), _p(fw), _p(fn)),
+        _chk(load().corb_voc_transform(self.h, _p(np.ascontiguousarray(desc)), _p(off), ns, levelsup, _p(word), _p(val), _p(bc), _p(node), _p(fo), _p(idx), _p(nn), _p(fw), _p(fn)),
              "corb_voc_transform")
         out = []
         for s in range(ns):
@@ -1689,40 +1143,32 @@ class Vocabulary:
         return self.transform_sets([desc], levelsup, per_feature)[0]
 
 
-class KeyFrameDatabase:
+class KeyFrameDatabase(_Handle):
     """KeyFrameDatabase (C/src/KeyFrameDatabase.cc) over entries of a device-resident table (corb_kfdb_*).  The detect functions take (query entry, query id); the loop
     variant also the connected keyframes as entries and minScore.  They return the candidates as entries, in the reference's order."""
 
+    _destroy = "corb_kfdb_destroy"
+
     def __init__(self, voc, capacity, max_words):
-        self.h = C.c_void_p(); self.voc = voc; self.capacity = capacity; self.max_words = max_words
-        _chk(load().corb_kfdb_create(voc.h, capacity, max_words, C.byref(self.h)), "corb_kfdb_create")
-
-    def close(self):
-        if self.h:
-            load().corb_kfdb_destroy(self.h); self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self.voc = voc; self.capacity = capacity; self.max_words = max_words
+        self._create("corb_kfdb_create", voc.h, capacity, max_words)
 
     def set_bow(self, entry, word, value):
         w = np.ascontiguousarray(word, np.uint32); v = np.ascontiguousarray(value, np.float64)
         if len(w) != len(v):
             raise CorbError("KeyFrameDatabase.set_bow: words and values differ in length")
-        _chk(load().corb_kfdb_set_bow(self.h, int(entry), _p(w), _p(v), len(w)), "corb_kfdb_set_bow")
+        _chk(load().corb_kfdb_set_bow(self.h, entry, _p(w), _p(v), len(w)), "corb_kfdb_set_bow")
 
     def get_bow(self, entry):
         w = np.zeros(self.max_words, np.uint32); v = np.zeros(self.max_words, np.float64); n = C.c_int(0)
-        _chk(load().corb_kfdb_get_bow(self.h, int(entry), _p(w), _p(v), self.max_words, C.byref(n)), "corb_kfdb_get_bow")
+        _chk(load().corb_kfdb_get_bow(self.h, entry, _p(w), _p(v), self.max_words, C.byref(n)), "corb_kfdb_get_bow")
         return w[:n.value].copy(), v[:n.value].copy()
 
     def add(self, entry):
-        _chk(load().corb_kfdb_add(self.h, int(entry)), "corb_kfdb_add")
+        _chk(load().corb_kfdb_add(self.h, entry), "corb_kfdb_add")
 
     def erase(self, entry):
-        _chk(load().corb_kfdb_erase(self.h, int(entry)), "corb_kfdb_erase")
+        _chk(load().corb_kfdb_erase(self.h, entry), "corb_kfdb_erase")
 
     def clear(self):
         _chk(load().corb_kfdb_clear(self.h), "corb_kfdb_clear")
@@ -1734,18 +1180,18 @@ class KeyFrameDatabase:
     def state(self, first=0, n=None):
         n = self.capacity - first if n is None else n
         out = np.zeros(n, KFDB_STATE_DTYPE)
-        _chk(load().corb_kfdb_get_state(self.h, int(first), int(n), _p(out)), "corb_kfdb_get_state")
+        _chk(load().corb_kfdb_get_state(self.h, first, n, _p(out)), "corb_kfdb_get_state")
         return out
 
     def score(self, entry_a, entries_b):
         b = np.ascontiguousarray(entries_b, np.int32); out = np.zeros(len(b), np.float64)
-        _chk(load().corb_kfdb_score(self.h, int(entry_a), _p(b), len(b), _p(out)), "corb_kfdb_score")
+        _chk(load().corb_kfdb_score(self.h, entry_a, _p(b), len(b), _p(out)), "corb_kfdb_score")
         return out
 
     def detect(self, kind, query_entry, query_id, connected=(), min_score=0.0, cap=None):
         cap = self.capacity if cap is None else cap
         c = np.ascontiguousarray(list(connected), np.int32); out = np.zeros(max(cap, 1), np.int32); n = C.c_int(0)
-        rc = load().corb_kfdb_detect(self.h, int(kind), int(query_entry), int(query_id), _p(c), len(c), C.c_float(min_score), _p(out), int(cap), C.byref(n))
+        rc = load().corb_kfdb_detect(self.h, kind, query_entry, query_id, _p(c), len(c), min_score, _p(out), cap, C.byref(n))
         self.last_count = n.value
         _chk(rc, "corb_kfdb_detect")
         return out[:n.value].copy()
@@ -1760,46 +1206,35 @@ class KeyFrameDatabase:
         return self.detect(2, query_entry, query_id)
 
 
-NO_ID = 0xFFFFFFFFFFFFFFFF       # CORB_NO_MAP_POINT: "none"
-
-
-class Covisibility:
+class Covisibility(_Handle):
     """The covisibility graph over a KeyFrameStore and a MapPointStore (corb_covis_*): KeyFrame::UpdateConnections, the covisibility queries, LocalMapping::KeyFrameCulling
     and the window of Optimizer::LocalBundleAdjustment on records.  Keyframes are named by their slots; the queries answer slots."""
 
+    _destroy = "corb_covis_destroy"
+
     def __init__(self, kf_store, mp_store, max_connections=0):
-        self.h = C.c_void_p(); self.kf = kf_store; self.mp = mp_store; self.M = max_connections if max_connections > 0 else 512
-        _chk(load().corb_covis_create(kf_store.h, mp_store.h, int(max_connections), C.byref(self.h)), "corb_covis_create")
-
-    def close(self):
-        if self.h:
-            load().corb_covis_destroy(self.h); self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self.kf = kf_store; self.mp = mp_store; self.M = max_connections if max_connections > 0 else 512
+        self._create("corb_covis_create", kf_store.h, mp_store.h, max_connections)
 
     def UpdateConnections(self, slots, th=15):
         """corb_covis_update for the slots in list order; returns the front of each keyframe's ordered list (its id, NO_ID if none)"""
         s = np.ascontiguousarray(np.atleast_1d(slots), np.int32); fp = np.full(max(len(s), 1), NO_ID, np.uint64)
-        _chk(load().corb_covis_update(self.h, _p(s), len(s), int(th), _p(fp)), "corb_covis_update")
+        _chk(load().corb_covis_update(self.h, _p(s), len(s), th, _p(fp)), "corb_covis_update")
         return fp[:len(s)].copy()
 
     def EraseConnections(self, slot):
-        _chk(load().corb_covis_erase(self.h, int(slot)), "corb_covis_erase")
+        _chk(load().corb_covis_erase(self.h, slot), "corb_covis_erase")
 
     def get(self, slot):
         """the row of a slot: (ids, weights) of the weight map in descending (weight, id), and (ids, weights) of the ordered list"""
         M = self.M; ai = np.zeros(M, np.uint64); aw = np.zeros(M, np.int32); oi = np.zeros(M, np.uint64); ow = np.zeros(M, np.int32); na = C.c_int(0); no = C.c_int(0)
-        _chk(load().corb_covis_get(self.h, int(slot), _p(ai), _p(aw), C.byref(na), _p(oi), _p(ow), C.byref(no), M), "corb_covis_get")
+        _chk(load().corb_covis_get(self.h, slot, _p(ai), _p(aw), C.byref(na), _p(oi), _p(ow), C.byref(no), M), "corb_covis_get")
         return (ai[:na.value].copy(), aw[:na.value].copy()), (oi[:no.value].copy(), ow[:no.value].copy())
 
     def query(self, slot, N=0, min_weight=0, cap=None):
         cap = self.M if cap is None else cap
         out = np.zeros(max(cap, 1), np.int32); w = np.zeros(max(cap, 1), np.int32); n = C.c_int(0)
-        _chk(load().corb_covis_query(self.h, int(slot), int(N), int(min_weight), _p(out), _p(w), int(cap), C.byref(n)), "corb_covis_query")
+        _chk(load().corb_covis_query(self.h, slot, N, min_weight, _p(out), _p(w), cap, C.byref(n)), "corb_covis_query")
         return out[:n.value].copy(), w[:n.value].copy()
 
     def GetVectorCovisibleKeyFrames(self, slot):
@@ -1813,14 +1248,14 @@ class Covisibility:
 
     def GetWeight(self, slot_a, slot_b):
         w = C.c_int(0)
-        _chk(load().corb_covis_weight(self.h, int(slot_a), int(slot_b), C.byref(w)), "corb_covis_weight")
+        _chk(load().corb_covis_weight(self.h, slot_a, slot_b, C.byref(w)), "corb_covis_weight")
         return w.value
 
     def KeyFrameCulling(self, cur_slot, monocular, th_depth, cap=None):
         """per covisible keyframe of cur_slot: (slots, nMPs, nRedundantObservations, cull)"""
         cap = self.M if cap is None else cap; m = max(cap, 1)
         ks = np.zeros(m, np.int32); nm = np.zeros(m, np.int32); nr = np.zeros(m, np.int32); cu = np.zeros(m, np.uint8); n = C.c_int(0)
-        _chk(load().corb_covis_keyframe_culling(self.h, int(cur_slot), int(bool(monocular)), C.c_float(th_depth), _p(ks), _p(nm), _p(nr), _p(cu), int(cap), C.byref(n)),
+        _chk(load().corb_covis_keyframe_culling(self.h, cur_slot, bool(monocular), th_depth, _p(ks), _p(nm), _p(nr), _p(cu), cap, C.byref(n)),
              "corb_covis_keyframe_culling")
         k = n.value
         return ks[:k].copy(), nm[:k].copy(), nr[:k].copy(), cu[:k].copy()
@@ -1828,33 +1263,33 @@ class Covisibility:
     def LocalWindow(self, slot, kf_cap, mp_cap):
         """(kf_slots, n_local, mp_slots): lLocalKeyFrames + lFixedCameras and lLocalMapPoints as corb_local_ba_store takes them"""
         ks = np.zeros(max(kf_cap, 1), np.int32); ms = np.zeros(max(mp_cap, 1), np.int32); nl = C.c_int(0); nk = C.c_int(0); nm = C.c_int(0)
-        _chk(load().corb_covis_local_window(self.h, int(slot), _p(ks), int(kf_cap), C.byref(nl), C.byref(nk), _p(ms), int(mp_cap), C.byref(nm)), "corb_covis_local_window")
+        _chk(load().corb_covis_local_window(self.h, slot, _p(ks), kf_cap, C.byref(nl), C.byref(nk), _p(ms), mp_cap, C.byref(nm)), "corb_covis_local_window")
         return ks[:nk.value].copy(), nl.value, ms[:nm.value].copy()
 
     # ---- the spanning tree (mpParent, mbFirstConnection, mspChildrens per slot) ----
     def SetTree(self, slot, parent_id=NO_ID, first_connection=True, children=()):
         ch = np.ascontiguousarray(children, np.uint64)
-        _chk(load().corb_covis_set_tree(self.h, int(slot), C.c_uint64(int(parent_id)), int(bool(first_connection)), _p(ch) if len(ch) else None, len(ch)), "corb_covis_set_tree")
+        _chk(load().corb_covis_set_tree(self.h, slot, parent_id, bool(first_connection), _p(ch) if len(ch) else None, len(ch)), "corb_covis_set_tree")
 
     def GetTree(self, slot):
         """(parent id or NO_ID, mbFirstConnection, children ids ascending)"""
         ch = np.zeros(self.M, np.uint64); p = C.c_uint64(0); f = C.c_int(0); n = C.c_int(0)
-        _chk(load().corb_covis_get_tree(self.h, int(slot), C.byref(p), C.byref(f), _p(ch), self.M, C.byref(n)), "corb_covis_get_tree")
+        _chk(load().corb_covis_get_tree(self.h, slot, C.byref(p), C.byref(f), _p(ch), self.M, C.byref(n)), "corb_covis_get_tree")
         return int(p.value), bool(f.value), ch[:n.value].copy()
 
     def AddChild(self, slot, child_slot):
-        _chk(load().corb_covis_add_child(self.h, int(slot), int(child_slot)), "corb_covis_add_child")
+        _chk(load().corb_covis_add_child(self.h, slot, child_slot), "corb_covis_add_child")
 
     def EraseChild(self, slot, child_slot):
-        _chk(load().corb_covis_erase_child(self.h, int(slot), int(child_slot)), "corb_covis_erase_child")
+        _chk(load().corb_covis_erase_child(self.h, slot, child_slot), "corb_covis_erase_child")
 
     def ChangeParent(self, slot, other_slot):
-        _chk(load().corb_covis_change_parent(self.h, int(slot), int(other_slot)), "corb_covis_change_parent")
+        _chk(load().corb_covis_change_parent(self.h, slot, other_slot), "corb_covis_change_parent")
 
     def ReparentChildren(self, slot):
         """the tree part of KeyFrame::SetBadFlag, after EraseConnections(slot): (ChangeParent calls, whether the reference sets mbBad)"""
         n = C.c_int(0); b = C.c_int(0)
-        _chk(load().corb_covis_reparent_children(self.h, int(slot), C.byref(n), C.byref(b)), "corb_covis_reparent_children")
+        _chk(load().corb_covis_reparent_children(self.h, slot, C.byref(n), C.byref(b)), "corb_covis_reparent_children")
         return n.value, bool(b.value)
 
     # ---- CorrectLoop's propagation on records ----
@@ -1864,7 +1299,7 @@ class Covisibility:
         cap = self.M + 1 if cap is None else int(cap); m = max(cap, 1)
         S = np.ascontiguousarray(Scw, np.float64).reshape(8)
         ks = np.zeros(m, np.int32); co = np.zeros((m, 8), np.float64); nc = np.zeros((m, 8), np.float64); n = C.c_int(0); npt = C.c_int(0)
-        _chk(load().corb_loop_correct_store(self.h, int(cur_slot), _p(S), C.c_float(scale_factor), _p(ks), _p(co), _p(nc), cap, C.byref(n), C.byref(npt)), "corb_loop_correct_store")
+        _chk(load().corb_loop_correct_store(self.h, cur_slot, _p(S), scale_factor, _p(ks), _p(co), _p(nc), cap, C.byref(n), C.byref(npt)), "corb_loop_correct_store")
         k = n.value
         return ks[:k].copy(), co[:k].copy(), nc[:k].copy(), npt.value
 
@@ -1872,24 +1307,24 @@ class Covisibility:
     def PropagateGlobalBA(self, origin_slots, loop_kf, queue_cap=0):
         """corb_gba_propagate_store: TcwGBA / pos_gba become Tcw / world_pos, unmarked keyframes are corrected through the child sets; returns the counts"""
         o = np.ascontiguousarray(np.atleast_1d(origin_slots), np.int32); out = GbaPropagation()
-        _chk(load().corb_gba_propagate_store(self.h, _p(o) if len(o) else None, len(o), C.c_uint64(int(loop_kf)), int(queue_cap), C.byref(out)), "corb_gba_propagate_store")
+        _chk(load().corb_gba_propagate_store(self.h, _p(o) if len(o) else None, len(o), loop_kf, queue_cap, C.byref(out)), "corb_gba_propagate_store")
         return out
 
     # ---- the loop edges (mspLoopEdges per slot) and Optimizer::OptimizeEssentialGraph on records (include/corb_essential_graph.h) ----
     MAX_LOOP_EDGES = 32          # CORB_COVIS_MAX_LOOP_EDGES
 
     def AddLoopEdge(self, slot, other_slot):
-        _chk(load().corb_covis_add_loop_edge(self.h, int(slot), int(other_slot)), "corb_covis_add_loop_edge")
+        _chk(load().corb_covis_add_loop_edge(self.h, slot, other_slot), "corb_covis_add_loop_edge")
 
     def GetLoopEdges(self, slot, cap=None):
         """the ids of the set, ascending"""
         cap = self.MAX_LOOP_EDGES if cap is None else int(cap)
         ids = np.zeros(max(cap, 1), np.uint64); n = C.c_int(0)
-        _chk(load().corb_covis_get_loop_edges(self.h, int(slot), _p(ids), cap, C.byref(n)), "corb_covis_get_loop_edges")
+        _chk(load().corb_covis_get_loop_edges(self.h, slot, _p(ids), cap, C.byref(n)), "corb_covis_get_loop_edges")
         return ids[:n.value].copy()
 
     def ClearLoopEdges(self, slot):
-        _chk(load().corb_covis_clear_loop_edges(self.h, int(slot)), "corb_covis_clear_loop_edges")
+        _chk(load().corb_covis_clear_loop_edges(self.h, slot), "corb_covis_clear_loop_edges")
 
     @staticmethod
     def _essential_graph_input(loop_slot, cur_slot, corr_slots, corrected, non_corrected, loop_connections, min_weight):
@@ -1907,16 +1342,16 @@ class Covisibility:
         """corb_essential_graph_plan: dict(v_slots, S, fixed, snc, vi, vj, kind, meas, counts).  v_cap / e_cap None: sized by a first call that asks for the counts.
         A cap too small raises CorbError with (-2); the counts of that call are in self.last_plan_counts."""
         inp, keep = self._essential_graph_input(loop_slot, cur_slot, corr_slots, corrected, non_corrected, loop_connections, min_weight)
-        cnt = EssentialGraphCounts(); L = load()
+        cnt = EssentialGraphCounts()
         if v_cap is None or e_cap is None:
-            rc = L.corb_essential_graph_plan(self.h, C.byref(inp), 0, 0, *([None] * 8), C.byref(cnt))
+            rc = load().corb_essential_graph_plan(self.h, C.byref(inp), 0, 0, *([None] * 8), C.byref(cnt))
             if rc not in (0, ERR_CAPACITY):
                 _chk(rc, "corb_essential_graph_plan")
             v_cap = cnt.n_vertices if v_cap is None else v_cap; e_cap = cnt.n_edges if e_cap is None else e_cap
         K = max(v_cap, 1); E = max(e_cap, 1)
         vs = np.zeros(K, np.int32); S = np.zeros((K, 8), np.float64); fx = np.zeros(K, np.uint8); snc = np.zeros((K, 8), np.float64)
         vi = np.zeros(E, np.int32); vj = np.zeros(E, np.int32); kind = np.zeros(E, np.uint8); meas = np.zeros((E, 8), np.float64)
-        rc = L.corb_essential_graph_plan(self.h, C.byref(inp), int(v_cap), int(e_cap), _p(vs), _p(S), _p(fx), _p(snc), _p(vi), _p(vj), _p(kind), _p(meas), C.byref(cnt))
+        rc = load().corb_essential_graph_plan(self.h, C.byref(inp), v_cap, e_cap, _p(vs), _p(S), _p(fx), _p(snc), _p(vi), _p(vj), _p(kind), _p(meas), C.byref(cnt))
         self.last_plan_counts = cnt.as_dict()
         _chk(rc, "corb_essential_graph_plan")
         k, e = cnt.n_vertices, cnt.n_edges
@@ -1930,54 +1365,31 @@ class Covisibility:
         inp, keep = self._essential_graph_input(loop_slot, cur_slot, corr_slots, corrected, non_corrected, loop_connections, min_weight)
         v_cap = self.kf.capacity if v_cap is None else int(v_cap)
         chi2 = np.zeros(iterations + 1, np.float64); S = np.zeros((max(v_cap, 1), 8), np.float64); out = EssentialGraphResult()
-        rc = load().corb_essential_graph_store(self.h, C.byref(inp), int(iterations), int(bool(bFixScale)), C.c_float(scale_factor), _p(chi2), _p(S), v_cap, C.byref(out))
+        rc = load().corb_essential_graph_store(self.h, C.byref(inp), iterations, bool(bFixScale), scale_factor, _p(chi2), _p(S), v_cap, C.byref(out))
         self.last_result = out
         _chk(rc, "corb_essential_graph_store")
         return dict(result=out, chi2=chi2[:out.iters_done + 1].copy(), S=S[:out.graph.n_vertices].copy())
 
     def SetPoseBeforeGBA(self, slot, T):
         a = np.ascontiguousarray(T, np.float32).reshape(16)
-        _chk(load().corb_covis_set_pose_before_gba(self.h, int(slot), _p(a)), "corb_covis_set_pose_before_gba")
+        _chk(load().corb_covis_set_pose_before_gba(self.h, slot, _p(a)), "corb_covis_set_pose_before_gba")
 
     def GetPoseBeforeGBA(self, slot):
         a = np.zeros(16, np.float32)
-        _chk(load().corb_covis_get_pose_before_gba(self.h, int(slot), _p(a)), "corb_covis_get_pose_before_gba")
+        _chk(load().corb_covis_get_pose_before_gba(self.h, slot, _p(a)), "corb_covis_get_pose_before_gba")
         return a.reshape(4, 4)
 
 
-class TrackCamera(C.Structure):
-    """CorbTrackCamera: Frame intrinsics, image bounds and mvScaleFactors"""
-    _fields_ = [("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("bf", C.c_float), ("mb", C.c_float),
-                ("min_x", C.c_float), ("max_x", C.c_float), ("min_y", C.c_float), ("max_y", C.c_float), ("nlevels", C.c_int32), ("scale", C.c_float * 16)]
-
-    @classmethod
-    def make(cls, fx, fy, cx, cy, bf, mb, min_x, max_x, min_y, max_y, scale):
-        c = cls(); c.fx, c.fy, c.cx, c.cy, c.bf, c.mb = fx, fy, cx, cy, bf, mb
-        c.min_x, c.max_x, c.min_y, c.max_y = min_x, max_x, min_y, max_y
-        c.nlevels = len(scale)
-        for i, v in enumerate(scale):
-            c.scale[i] = float(v)
-        return c
-
-
-class KeyFrameStore:
+class KeyFrameStore(_Handle):
     """Device-resident keyframe store (corb_kf_store_*): one fixed-size SoA record per keyframe in HBM -- what the reference serialises per KeyFrame for
     the client -> server push (corbslam_client/include/KeyFrame.h:59-87).  Slots are filled device-to-device from a StereoFrontend, matched without
     uploads (SearchByBoW / SearchForTriangulation on slots) and pushed to the server rank over RCCL (map_push)."""
 
+    _destroy = "corb_kf_store_destroy"
+
     def __init__(self, capacity, max_features, device=0):
-        self.h = C.c_void_p(); self.capacity = capacity; self.F = max_features; self.device = device
-        _chk(load().corb_kf_store_create(device, capacity, max_features, C.byref(self.h)), "corb_kf_store_create")
-
-    def close(self):
-        if self.h:
-            load().corb_kf_store_destroy(self.h); self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self.capacity = capacity; self.F = max_features; self.device = device
+        self._create("corb_kf_store_create", device, capacity, max_features)
 
     def record_bytes(self):
         return load().corb_kf_store_record_bytes(self.h)
@@ -2010,7 +1422,7 @@ class KeyFrameStore:
         sl = np.ascontiguousarray(np.atleast_1d(slots), np.int32); en = None if entries is None else np.ascontiguousarray(np.atleast_1d(entries), np.int32)
         if db is not None and (en is None or len(en) != len(sl)):
             raise CorbError("compute_bow: one database entry per slot")
-        _chk(load().corb_kf_store_compute_bow(self.h, _p(sl), len(sl), voc.h, int(levelsup), db.h if db is not None else None, _p(en)), "corb_kf_store_compute_bow")
+        _chk(load().corb_kf_store_compute_bow(self.h, _p(sl), len(sl), voc.h, levelsup, db.h if db is not None else None, _p(en)), "corb_kf_store_compute_bow")
 
     def set_flags(self, slot, flags):
         f = None if flags is None else np.ascontiguousarray(flags, np.uint8)
@@ -2038,15 +1450,15 @@ class KeyFrameStore:
         n = self._n_features(cur_slot)
         m = np.full(n, -1, np.int32) if want_match else None; cnt = C.c_int(0)
         a = np.ascontiguousarray(Tcw, np.float32).reshape(16); b = np.ascontiguousarray(Tlw, np.float32).reshape(16)
-        _chk(load().corb_track_search_last_frame(self.h, int(cur_slot), int(last_slot), mp_store.h, _p(a), _p(b), C.byref(cam), C.c_float(th), int(bool(mono)),
-                                                 C.c_float(nnratio), int(bool(check_orientation)), _p(m), C.byref(cnt)), "corb_track_search_last_frame")
+        _chk(load().corb_track_search_last_frame(self.h, cur_slot, last_slot, mp_store.h, _p(a), _p(b), C.byref(cam), th, bool(mono),
+                                                 nnratio, bool(check_orientation), _p(m), C.byref(cnt)), "corb_track_search_last_frame")
         return m, cnt.value
 
     def TrackPoseOptimization(self, slot, mp_store, cam, Tcw, discard_outliers=False, want_outliers=True):
         """Optimizer::PoseOptimization(Frame*) (Optimizer.cc:272-485) on the record: returns (Tcw, mvbOutlier, inliers); pose and outlier flags stay in the record"""
         n = self._n_features(slot)
         a = np.ascontiguousarray(Tcw, np.float32).reshape(16); out = np.zeros(16, np.float32); fl = np.zeros(n, np.uint8) if want_outliers else None; inl = C.c_int32(0)
-        _chk(load().corb_track_pose_optimization(self.h, int(slot), mp_store.h, C.byref(cam), _p(a), _p(out), int(bool(discard_outliers)), _p(fl), C.byref(inl)), "corb_track_pose_optimization")
+        _chk(load().corb_track_pose_optimization(self.h, slot, mp_store.h, C.byref(cam), _p(a), _p(out), bool(discard_outliers), _p(fl), C.byref(inl)), "corb_track_pose_optimization")
         return out.reshape(4, 4), (fl.astype(bool) if want_outliers else None), inl.value
 
     def TrackSearchLocalPoints(self, slot, mp_store, local_ids, cam, Tcw, log_scale_factor, th=1.0, nnratio=0.8, want_match=True, want_tracked=False):
@@ -2057,8 +1469,8 @@ class KeyFrameStore:
         m = np.full(n, -1, np.int32) if want_match else None; tr = np.zeros(len(ids), TRACKED_DTYPE) if want_tracked else None
         cnt = C.c_int(0); inv = C.c_int(0)
         a = np.ascontiguousarray(Tcw, np.float32).reshape(16)
-        _chk(load().corb_track_search_local_points(self.h, int(slot), mp_store.h, _p(ids), len(ids), C.byref(cam), _p(a), C.c_float(log_scale_factor), C.c_float(th),
-                                                   C.c_float(nnratio), _p(m), _p(tr), C.byref(cnt), C.byref(inv)), "corb_track_search_local_points")
+        _chk(load().corb_track_search_local_points(self.h, slot, mp_store.h, _p(ids), len(ids), C.byref(cam), _p(a), log_scale_factor, th,
+                                                   nnratio, _p(m), _p(tr), C.byref(cnt), C.byref(inv)), "corb_track_search_local_points")
         return (m, cnt.value, inv.value, tr) if want_tracked else (m, cnt.value, inv.value)
 
     def TrackUpdateLocalMap(self, slot, covis, prev_kf_slots=(), kf_cap=None, mp_cap=None):
@@ -2072,7 +1484,7 @@ class KeyFrameStore:
         kf_cap = max(min(covis.M, 128), 83, len(prev)) if kf_cap is None else int(kf_cap)
         mp_cap = min(covis.mp.capacity, kf_cap * covis.kf.F, 16384) if mp_cap is None else int(mp_cap)
         ks = np.zeros(max(kf_cap, 1), np.int32); ms = np.zeros(max(mp_cap, 1), np.int32); ids = np.zeros(max(mp_cap, 1), np.uint64); info = LocalMap()
-        _chk(load().corb_track_update_local_map(covis.h, self.h, int(slot), _p(prev) if len(prev) else None, len(prev), _p(ks), kf_cap, _p(ms), _p(ids), mp_cap, C.byref(info)),
+        _chk(load().corb_track_update_local_map(covis.h, self.h, slot, _p(prev) if len(prev) else None, len(prev), _p(ks), kf_cap, _p(ms), _p(ids), mp_cap, C.byref(info)),
              "corb_track_update_local_map")
         return ks[:info.n_kf].copy(), ms[:info.n_mp].copy(), ids[:info.n_mp].copy(), info
 
@@ -2083,10 +1495,8 @@ class KeyFrameStore:
         ms = np.ascontiguousarray(mp_slots, np.int32); S = np.ascontiguousarray(Scw, np.float32).reshape(16)
         ids = np.array(matched_ids, np.uint64, copy=True); assert len(ids) == n
         m = np.full(max(n, 1), -1, np.int32); cnt = C.c_int(0)
-        L = load(); L.corb_search_by_projection_scw_store.restype = C.c_int
-        L.corb_search_by_projection_scw_store.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
-        _chk(L.corb_search_by_projection_scw_store(self.h, int(slot), mp_store.h, _p(ms), len(ms), C.byref(cam), _p(S), C.c_float(log_scale_factor), C.c_float(th),
-                                                   _p(ids), _p(m), C.byref(cnt)), "corb_search_by_projection_scw_store")
+        _chk(load().corb_search_by_projection_scw_store(self.h, slot, mp_store.h, _p(ms), len(ms), C.byref(cam), _p(S), log_scale_factor, th,
+                                                        _p(ids), _p(m), C.byref(cnt)), "corb_search_by_projection_scw_store")
         return ids, m[:n], cnt.value
 
     def Fuse(self, slot, mp_store, mp_slots, cam, Tcw, log_scale_factor, th=3.0, apply=False):
@@ -2094,7 +1504,7 @@ class KeyFrameStore:
         Returns (best_idx, best_dist, n_fused, action): action 1 = entered a feature without MapPoint (apply: records updated), 2 = Replace pending."""
         ms = np.ascontiguousarray(mp_slots, np.int32); T = np.ascontiguousarray(Tcw, np.float32).reshape(16)
         bi = np.full(max(len(ms), 1), -1, np.int32); bd = np.full(max(len(ms), 1), 256, np.int32); act = np.zeros(max(len(ms), 1), np.uint8); n = C.c_int(0)
-        _chk(load().corb_fuse_store(self.h, int(slot), mp_store.h, _p(ms), len(ms), C.byref(cam), _p(T), C.c_float(log_scale_factor), C.c_float(th), int(bool(apply)),
+        _chk(load().corb_fuse_store(self.h, slot, mp_store.h, _p(ms), len(ms), C.byref(cam), _p(T), log_scale_factor, th, bool(apply),
                                     _p(bi), _p(bd), _p(act), C.byref(n)), "corb_fuse_store")
         return bi[: len(ms)], bd[: len(ms)], n.value, act[: len(ms)]
 
@@ -2103,7 +1513,7 @@ class KeyFrameStore:
         replace_slot): action 1 = entered an empty feature, 2 = replace_slot holds vpReplacePoint (Replace pending, -1: the id has no record), 4 = the feature's point is bad."""
         ms = np.ascontiguousarray(mp_slots, np.int32); T = np.ascontiguousarray(Scw, np.float32).reshape(16); k = max(len(ms), 1)
         bi = np.full(k, -1, np.int32); bd = np.full(k, 256, np.int32); act = np.zeros(k, np.uint8); rs = np.full(k, -1, np.int32); n = C.c_int(0)
-        _chk(load().corb_fuse_sim3_store(self.h, int(slot), mp_store.h, _p(ms), len(ms), C.byref(cam), _p(T), C.c_float(log_scale_factor), C.c_float(th), int(bool(apply)),
+        _chk(load().corb_fuse_sim3_store(self.h, slot, mp_store.h, _p(ms), len(ms), C.byref(cam), _p(T), log_scale_factor, th, bool(apply),
                                          _p(bi), _p(bd), _p(rs), _p(act), C.byref(n)), "corb_fuse_sim3_store")
         return bi[: len(ms)], bd[: len(ms)], n.value, act[: len(ms)], rs[: len(ms)]
 
@@ -2117,8 +1527,8 @@ class KeyFrameStore:
         cap = max(n_nb * n1, 1)
         off = np.zeros(n_nb + 1, np.int32); pr = np.zeros((cap, 2), np.int32); x3d = np.zeros((cap, 3), np.float32); st = np.zeros(cap, np.uint8); src = np.zeros(cap, np.uint8)
         nn = C.c_int(0)
-        _chk(load().corb_create_new_map_points_store(self.h, int(cur_slot), _p(nb), n_nb, _p(F), _p(ep), C.byref(cam), int(bool(only_stereo)), int(bool(apply)),
-                                                     mp_store.h if mp_store is not None else None, int(first_mp_slot), int(first_mp_id), int(client_id),
+        _chk(load().corb_create_new_map_points_store(self.h, cur_slot, _p(nb), n_nb, _p(F), _p(ep), C.byref(cam), bool(only_stereo), bool(apply),
+                                                     mp_store.h if mp_store is not None else None, first_mp_slot, first_mp_id, client_id,
                                                      _p(off), _p(pr), _p(x3d), _p(st), _p(src), C.byref(nn)), "corb_create_new_map_points_store")
         m = int(off[n_nb])
         return dict(pair_offset=off, pairs=pr[:m].copy(), x3d=x3d[:m].copy(), status=st[:m].copy(), source=src[:m].copy(), n_new=nn.value)
@@ -2128,9 +1538,8 @@ class KeyFrameStore:
         pKF = kf_slot of kf_store, sAlreadyFound = the MapPoints the frame holds.  Returns (match per frame feature = pKF feature or -1, matches); the ids go into the record."""
         n = self._n_features(cur_slot)
         m = np.full(n, -1, np.int32); cnt = C.c_int(0); a = np.ascontiguousarray(Tcw, np.float32).reshape(16)
-        L = load(); L.corb_track_search_reloc.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
-        _chk(L.corb_track_search_reloc(self.h, int(cur_slot), kf_store.h, int(kf_slot), mp_store.h, C.byref(cam), _p(a), C.c_float(log_scale_factor), C.c_float(th),
-                                       int(orb_dist), int(bool(check_orientation)), _p(m), C.byref(cnt)), "corb_track_search_reloc")
+        _chk(load().corb_track_search_reloc(self.h, cur_slot, kf_store.h, kf_slot, mp_store.h, C.byref(cam), _p(a), log_scale_factor, th,
+                                            orb_dist, bool(check_orientation), _p(m), C.byref(cnt)), "corb_track_search_reloc")
         return m, cnt.value
 
     def SearchBySim3(self, slot1, slot2, mp_store, cam, log_scale_factor, T1w, T2w, s12, R12, t12, th=7.5, matched12_ids=None):
@@ -2141,10 +1550,8 @@ class KeyFrameStore:
         a = np.ascontiguousarray(T1w, np.float32).reshape(16); b = np.ascontiguousarray(T2w, np.float32).reshape(16)
         R = np.ascontiguousarray(R12, np.float32).reshape(9); t = np.ascontiguousarray(t12, np.float32).reshape(3)
         mi = None if matched12_ids is None else np.ascontiguousarray(matched12_ids, np.uint64)
-        L = load(); L.corb_search_by_sim3_store.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p,
-                                                            C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
-        _chk(L.corb_search_by_sim3_store(self.h, int(slot1), int(slot2), mp_store.h, C.byref(cam), C.c_float(log_scale_factor), _p(a), _p(b), _p(mi) if mi is not None else None,
-                                         C.c_float(s12), _p(R), _p(t), C.c_float(th), _p(m), _p(ids), C.byref(cnt)), "corb_search_by_sim3_store")
+        _chk(load().corb_search_by_sim3_store(self.h, slot1, slot2, mp_store.h, C.byref(cam), log_scale_factor, _p(a), _p(b), _p(mi) if mi is not None else None,
+                                              s12, _p(R), _p(t), th, _p(m), _p(ids), C.byref(cnt)), "corb_search_by_sim3_store")
         return m, ids, cnt.value
 
     def Sim3Ransac(self, slot1, slots2, mp_store, cam1, cams2, matched12_ids, rand_values, probability=0.99, min_inliers=20, max_iterations=300, fix_scale=False, max_events=None):
@@ -2160,8 +1567,8 @@ class KeyFrameStore:
         cap = np.zeros(m, np.int32); n_ev = np.zeros(m, np.int32); ev = np.zeros((m, max(max_events, 1)), SIM3_EVENT_DTYPE)
         fl = np.zeros((m, max(max_events, 1), max(n1, 1)), np.uint8); cnt = np.zeros((m, max_iterations), np.int32); qo = np.zeros((m, max_iterations, 4), np.float32)
         nc = np.zeros(m, np.int32); ix = np.full((m, max(n1, 1)), -1, np.int32)
-        _chk(load().corb_sim3_ransac_store(self.h, int(slot1), _p(sl), n, mp_store.h, C.byref(cam1), C.cast(cams, C.c_void_p), _p(ids), float(probability), int(min_inliers),
-                                           int(max_iterations), int(bool(fix_scale)), _p(rv), max_events, _p(cap), _p(n_ev), _p(ev), _p(fl), _p(nc), _p(ix), _p(cnt), _p(qo)),
+        _chk(load().corb_sim3_ransac_store(self.h, slot1, _p(sl), n, mp_store.h, C.byref(cam1), C.cast(cams, C.c_void_p), _p(ids), probability, min_inliers,
+                                           max_iterations, bool(fix_scale), _p(rv), max_events, _p(cap), _p(n_ev), _p(ev), _p(fl), _p(nc), _p(ix), _p(cnt), _p(qo)),
              "corb_sim3_ransac_store")
         out = []
         for c in range(n):
@@ -2171,14 +1578,14 @@ class KeyFrameStore:
         return out
 
     def _n_features(self, slot):
-        n = load().corb_kf_store_count(self.h, int(slot))
+        n = load().corb_kf_store_count(self.h, slot)
         if n < 0:
             raise RuntimeError("slot %d holds no frame with a host-known feature count" % slot)
         return n
 
     def _n_any(self, slot):
         """feature count of a slot: the host's mirror, or (a slot filled from a device-side count) the record's"""
-        n = load().corb_kf_store_count(self.h, int(slot))
+        n = load().corb_kf_store_count(self.h, slot)
         return n if n >= 0 else len(self.get(slot)["kp"])
 
     def set_meta(self, slot, **kw):
@@ -2210,34 +1617,26 @@ class KeyFrameStore:
     def SearchByBoW(self, slot_a, other, slot_b, nnratio=0.6, checkOri=True, variant=0):
         na = self._n_any(slot_a); nb = other._n_any(slot_b)
         out = np.full(max(nb if variant == 0 else na, 1), -1, np.int32); n = C.c_int(0)
-        _chk(load().corb_search_by_bow_slots(variant, self.h, slot_a, other.h, slot_b, nnratio, int(checkOri), _p(out), C.byref(n)), "corb_search_by_bow_slots")
+        _chk(load().corb_search_by_bow_slots(variant, self.h, slot_a, other.h, slot_b, nnratio, bool(checkOri), _p(out), C.byref(n)), "corb_search_by_bow_slots")
         return out[: (nb if variant == 0 else na)], n.value
 
     def SearchForTriangulation(self, slot_a, other, slot_b, F12, ex, ey, scale2, sigma2_2, bOnlyStereo, checkOri=True):
         na = self._n_any(slot_a)
         F12 = np.ascontiguousarray(F12, np.float32); sc = np.ascontiguousarray(scale2, np.float32); sg = np.ascontiguousarray(sigma2_2, np.float32)
         pairs = np.zeros((max(na, 1), 2), np.int32); n = C.c_int(0)
-        _chk(load().corb_search_for_triangulation_slots(self.h, slot_a, other.h, slot_b, _p(F12), ex, ey, _p(sc), _p(sg), len(sc), int(bOnlyStereo), int(checkOri), _p(pairs), C.byref(n)),
+        _chk(load().corb_search_for_triangulation_slots(self.h, slot_a, other.h, slot_b, _p(F12), ex, ey, _p(sc), _p(sg), len(sc), bool(bOnlyStereo), bool(checkOri), _p(pairs), C.byref(n)),
              "corb_search_for_triangulation_slots")
         return pairs[: n.value].copy(), n.value
 
 
-class MapPointStore:
+class MapPointStore(_Handle):
     """Device-resident map-point store (corb_mp_store_*): one fixed-size record per MapPoint -- header (MapPoint.h:52-72) + observation list."""
 
+    _destroy = "corb_mp_store_destroy"
+
     def __init__(self, capacity, max_obs=32, device=0):
-        self.h = C.c_void_p(); self.capacity = capacity; self.O = max_obs; self.device = device
-        _chk(load().corb_mp_store_create(device, capacity, max_obs, C.byref(self.h)), "corb_mp_store_create")
-
-    def close(self):
-        if self.h:
-            load().corb_mp_store_destroy(self.h); self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self.capacity = capacity; self.O = max_obs; self.device = device
+        self._create("corb_mp_store_create", device, capacity, max_obs)
 
     def record_bytes(self):
         return load().corb_mp_store_record_bytes(self.h)
@@ -2256,60 +1655,44 @@ class MapPointStore:
         """mnVisible / mnFound / mpReplaced (0 = none, else id + 1) of the records first .. (the header's spare 16 bytes)"""
         n = len(visible); a = np.zeros(n, MP_COUNTERS_DTYPE); a["n_visible"] = visible; a["n_found"] = found
         if replaced_by is not None: a["replaced_by"] = replaced_by
-        L = load(); L.corb_mp_store_set_counters.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
-        _chk(L.corb_mp_store_set_counters(self.h, int(first), n, _p(a)), "corb_mp_store_set_counters")
+        _chk(load().corb_mp_store_set_counters(self.h, first, n, _p(a)), "corb_mp_store_set_counters")
 
     def get_counters(self, first, n):
         a = np.zeros(n, MP_COUNTERS_DTYPE)
-        L = load(); L.corb_mp_store_get_counters.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
-        _chk(L.corb_mp_store_get_counters(self.h, int(first), int(n), _p(a)), "corb_mp_store_get_counters")
+        _chk(load().corb_mp_store_get_counters(self.h, first, n, _p(a)), "corb_mp_store_get_counters")
         return a
 
     def set_scratch(self, first, scratch):
         """CorbMapPointScratch of the records first ..: the tracking / local-mapping / loop-closing fields of MapPoint's serialised state the header does not carry"""
         a = np.ascontiguousarray(scratch, MP_SCRATCH_DTYPE)
-        L = load(); L.corb_mp_store_set_scratch.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]; L.corb_mp_store_set_scratch.restype = C.c_int
-        _chk(L.corb_mp_store_set_scratch(self.h, int(first), len(a), _p(a)), "corb_mp_store_set_scratch")
+        _chk(load().corb_mp_store_set_scratch(self.h, first, len(a), _p(a)), "corb_mp_store_set_scratch")
 
     def get_scratch(self, first, n):
         a = np.zeros(n, MP_SCRATCH_DTYPE)
-        L = load(); L.corb_mp_store_get_scratch.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]; L.corb_mp_store_get_scratch.restype = C.c_int
-        _chk(L.corb_mp_store_get_scratch(self.h, int(first), int(n), _p(a)), "corb_mp_store_get_scratch")
+        _chk(load().corb_mp_store_get_scratch(self.h, first, n, _p(a)), "corb_mp_store_get_scratch")
         return a
 
     def Replace(self, slot_this, slot_into, kf_store, kf_first, kf_n):
         """MapPoint::Replace(pMP) on records (corb_mp_store_replace): returns 0 (done) or 1 (the same point)"""
         st = C.c_int(0)
-        L = load(); L.corb_mp_store_replace.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
-        _chk(L.corb_mp_store_replace(self.h, int(slot_this), int(slot_into), kf_store.h, int(kf_first), int(kf_n), C.byref(st)), "corb_mp_store_replace")
+        _chk(load().corb_mp_store_replace(self.h, slot_this, slot_into, kf_store.h, kf_first, kf_n, C.byref(st)), "corb_mp_store_replace")
         return st.value
 
     def build_index(self, first, n):
         """corb_mp_store_build_index: the mnId -> slot table the tracking calls on records look map points up in"""
-        _chk(load().corb_mp_store_build_index(self.h, int(first), int(n)), "corb_mp_store_build_index")
+        _chk(load().corb_mp_store_build_index(self.h, first, n), "corb_mp_store_build_index")
 
 
-ERR_CAPACITY = -2                # CORB_ERR_CAPACITY
-
-
-class KeyframeInserter:
+class KeyframeInserter(_Handle):
     """Keyframe insertion on records (include/corb_keyframe_insert.h): the stereo points of CreateNewKeyFrame / StereoInitialization / UpdateLastFrame, the counts of
     NeedNewKeyFrame, ProcessNewKeyFrame's association loop and MapPointCulling.  One handle per client: it owns the calls' device scratch and a stream.  A call that
     answers CORB_ERR_CAPACITY returns its complete outputs with capacity_error = True instead of raising (nothing was written)."""
 
+    _destroy = "corb_kfi_destroy"
+
     def __init__(self, max_features, max_recent, device=0):
-        self.h = C.c_void_p(); self.F = max_features; self.R = max_recent
-        _chk(load().corb_kfi_create(device, int(max_features), int(max_recent), C.byref(self.h)), "corb_kfi_create")
-
-    def close(self):
-        if self.h:
-            load().corb_kfi_destroy(self.h); self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self.F = max_features; self.R = max_recent
+        self._create("corb_kfi_create", device, max_features, max_recent)
 
     @staticmethod
     def _rc(rc, what):
@@ -2321,8 +1704,8 @@ class KeyframeInserter:
         """corb_kfi_create_stereo_points: dict(order, kind, x3d, n_visited, n_created, capacity_error)"""
         n = max(kf._n_features(slot), 1)
         order = np.zeros(n, np.int32); kind = np.zeros(n, np.uint8); x3d = np.zeros((n, 3), np.float32); nv = C.c_int(0); nc = C.c_int(0)
-        rc = load().corb_kfi_create_stereo_points(self.h, kf.h, int(slot), mp_store.h, C.byref(cam), C.c_float(th_depth), int(mode), int(bool(apply)), int(first_mp_slot),
-                                                  int(first_mp_id), int(client_id), int(frame_id), mirror.h if mirror is not None else None, int(mirror_slot),
+        rc = load().corb_kfi_create_stereo_points(self.h, kf.h, slot, mp_store.h, C.byref(cam), th_depth, mode, bool(apply), first_mp_slot,
+                                                  first_mp_id, client_id, frame_id, mirror.h if mirror is not None else None, mirror_slot,
                                                   _p(order), _p(kind), _p(x3d), C.byref(nv), C.byref(nc))
         full = self._rc(rc, "corb_kfi_create_stereo_points")
         return dict(order=order[: nv.value].copy(), kind=kind[: nv.value].copy(), x3d=x3d[: nc.value].copy(), n_visited=nv.value, n_created=nc.value, capacity_error=full)
@@ -2330,7 +1713,7 @@ class KeyframeInserter:
     def NeedKeyFrameCounts(self, frames, cur_slot, mp_store, th_depth, kf, ref_slot, min_obs, kf_first, kf_n):
         """corb_kfi_need_keyframe_counts: (nTrackedClose, nNonTrackedClose, nRefMatches)"""
         a = C.c_int(0); b = C.c_int(0); c = C.c_int(0)
-        _chk(load().corb_kfi_need_keyframe_counts(self.h, frames.h, int(cur_slot), mp_store.h, C.c_float(th_depth), kf.h, int(ref_slot), int(min_obs), int(kf_first), int(kf_n),
+        _chk(load().corb_kfi_need_keyframe_counts(self.h, frames.h, cur_slot, mp_store.h, th_depth, kf.h, ref_slot, min_obs, kf_first, kf_n,
                                                   C.byref(a), C.byref(b), C.byref(c)), "corb_kfi_need_keyframe_counts")
         return a.value, b.value, c.value
 
@@ -2338,7 +1721,7 @@ class KeyframeInserter:
         """corb_kfi_process_new_keyframe: dict(kind, recent_slots, n_added, capacity_error)"""
         n = max(kf._n_features(slot), 1)
         kind = np.zeros(n, np.uint8); recent = np.zeros(n, np.int32); na = C.c_int(0); nr = C.c_int(0)
-        rc = load().corb_kfi_process_new_keyframe(self.h, kf.h, int(slot), mp_store.h, int(kf_first), int(kf_n), C.c_float(scale_factor), int(bool(apply)), _p(kind), _p(recent),
+        rc = load().corb_kfi_process_new_keyframe(self.h, kf.h, slot, mp_store.h, kf_first, kf_n, scale_factor, bool(apply), _p(kind), _p(recent),
                                                   C.byref(na), C.byref(nr))
         full = self._rc(rc, "corb_kfi_process_new_keyframe")
         return dict(kind=kind[: kf._n_features(slot)].copy(), recent_slots=recent[: nr.value].copy(), n_added=na.value, capacity_error=full)
@@ -2347,7 +1730,7 @@ class KeyframeInserter:
         """corb_kfi_map_point_culling: dict(decision, kept_slots, n_culled)"""
         sl = np.ascontiguousarray(recent_slots, np.int32); n = len(sl)
         dec = np.zeros(max(n, 1), np.uint8); kept = np.zeros(max(n, 1), np.int32); nk = C.c_int(0); ncu = C.c_int(0)
-        _chk(load().corb_kfi_map_point_culling(self.h, mp_store.h, _p(sl) if n else None, n, int(cur_kf_id), int(th_obs), kf.h, int(kf_first), int(kf_n), int(bool(apply)),
+        _chk(load().corb_kfi_map_point_culling(self.h, mp_store.h, _p(sl) if n else None, n, cur_kf_id, th_obs, kf.h, kf_first, kf_n, bool(apply),
                                                _p(dec), _p(kept), C.byref(nk), C.byref(ncu)), "corb_kfi_map_point_culling")
         return dict(decision=dec[:n].copy(), kept_slots=kept[: nk.value].copy(), n_culled=ncu.value)
 
@@ -2355,7 +1738,7 @@ class KeyframeInserter:
 def publish_message_layout(counts, kf_record_bytes, mp_record_bytes):
     """corb_pub_message_layout: byte offsets of sections A..E and the message's size.  Pure host arithmetic."""
     c = np.ascontiguousarray(counts, np.int32); off = np.zeros(6, np.int64)
-    _chk(load().corb_pub_message_layout(_p(c), int(kf_record_bytes), int(mp_record_bytes), _p(off)), "corb_pub_message_layout")
+    _chk(load().corb_pub_message_layout(_p(c), kf_record_bytes, mp_record_bytes, _p(off)), "corb_pub_message_layout")
     return off
 
 
@@ -2377,24 +1760,16 @@ class _PublishResult:
                     capacity_error=capacity_error)
 
 
-class MapPublisher:
+class MapPublisher(_Handle):
     """The server -> clients publish on records (include/corb_map_publish.h): pack on the server's stores, apply on a client's.  One handle per rank: it owns the
     message buffer, the calls' device scratch and a stream.  An apply that answers CORB_ERR_CAPACITY returns its complete outputs with capacity_error = True
     instead of raising (nothing was written)."""
 
+    _destroy = "corb_pub_destroy"
+
     def __init__(self, device=0):
-        self.h = C.c_void_p(); self.device = device
-        _chk(load().corb_pub_create(device, C.byref(self.h)), "corb_pub_create")
-
-    def close(self):
-        if self.h:
-            load().corb_pub_destroy(self.h); self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self.device = device
+        self._create("corb_pub_create", device)
 
     @staticmethod
     def _pack_args(kf, new_kf_slots, upd_kf_slots, mp, new_mp_slots, upd_mp_slots, trans):
@@ -2427,8 +1802,8 @@ class MapPublisher:
         """corb_pub_apply of a message() dict (this handle's or another's on the same device): the outputs as a dict"""
         counts = np.ascontiguousarray(msg["counts"], np.int32)
         r = _PublishResult(counts, kf_room if kf is not None else 0, mp_room if mp is not None else 0)
-        rc = load().corb_pub_apply(self.h, msg["ptr"], _p(counts), msg["kf_record_bytes"], msg["mp_record_bytes"], int(client_id), kf.h if kf is not None else None, int(kf_first), int(kf_n),
-                                   int(kf_free_first), int(kf_room), mp.h if mp is not None else None, int(mp_first), int(mp_n), int(mp_free_first), int(mp_room), int(bool(apply)), C.byref(r.c))
+        rc = load().corb_pub_apply(self.h, msg["ptr"], _p(counts), msg["kf_record_bytes"], msg["mp_record_bytes"], client_id, kf.h if kf is not None else None, kf_first, kf_n,
+                                   kf_free_first, kf_room, mp.h if mp is not None else None, mp_first, mp_n, mp_free_first, mp_room, bool(apply), C.byref(r.c))
         if rc != ERR_CAPACITY:
             _chk(rc, "corb_pub_apply")
         return r.as_dict(capacity_error=rc == ERR_CAPACITY)
@@ -2437,7 +1812,7 @@ class MapPublisher:
 def map_publish_plan(headers, root):
     """corb_map_publish_plan: (verdict code, failing rank) of a publish from what the ranks contributed to the header all-gather.  Pure host arithmetic."""
     h = np.ascontiguousarray(headers, PUBLISH_HEADER_DTYPE); who = C.c_int(-1)
-    rc = load().corb_map_publish_plan(len(h), int(root), _p(h), C.byref(who))
+    rc = load().corb_map_publish_plan(len(h), root, _p(h), C.byref(who))
     return rc, who.value
 
 
@@ -2445,7 +1820,7 @@ def map_publish_messages(headers, rank, root):
     """corb_map_publish_messages: (sends, recvs) rank `rank` posts for a publish with these gathered headers.  Pure host arithmetic."""
     h = np.ascontiguousarray(headers, PUBLISH_HEADER_DTYPE); W = len(h)
     sends = np.zeros(max(W, 1), PUSH_MSG_DTYPE); recvs = np.zeros(1, PUSH_MSG_DTYPE); ns = C.c_int(0); nr = C.c_int(0)
-    _chk(load().corb_map_publish_messages(W, int(rank), int(root), _p(h), _p(sends), C.byref(ns), _p(recvs), C.byref(nr)), "corb_map_publish_messages")
+    _chk(load().corb_map_publish_messages(W, rank, root, _p(h), _p(sends), C.byref(ns), _p(recvs), C.byref(nr)), "corb_map_publish_messages")
     return sends[: ns.value].copy(), recvs[: nr.value].copy()
 
 
@@ -2458,23 +1833,13 @@ def map_push_plan(headers, root, kf_capacity, mp_capacity, kf_dst_first, mp_dst_
     return rc, who.value
 
 
-PUSH_MSG_DTYPE = np.dtype([("peer", "<i4"), ("kind", "<i4"), ("first_record", "<i4"), ("n_records", "<i4"), ("bytes", "<i8")])
-
-
 def map_push_messages(headers, rank, root, kf_dst_first=None, mp_dst_first=None):
     """corb_map_push_messages: (sends, recvs) rank `rank` posts for a push with these gathered headers.  Pure host arithmetic."""
     h = np.ascontiguousarray(headers, PUSH_HEADER_DTYPE); W = len(h)
     kd = None if kf_dst_first is None else np.ascontiguousarray(kf_dst_first, np.int32); md = None if mp_dst_first is None else np.ascontiguousarray(mp_dst_first, np.int32)
     sends = np.zeros(2, PUSH_MSG_DTYPE); recvs = np.zeros(2 * W, PUSH_MSG_DTYPE); ns = C.c_int(0); nr = C.c_int(0)
-    L = load(); L.corb_map_push_messages.restype = C.c_int
-    _chk(L.corb_map_push_messages(W, int(rank), int(root), _p(h), _p(kd), _p(md), _p(sends), C.byref(ns), _p(recvs), C.byref(nr)), "corb_map_push_messages")
+    _chk(load().corb_map_push_messages(W, rank, root, _p(h), _p(kd), _p(md), _p(sends), C.byref(ns), _p(recvs), C.byref(nr)), "corb_map_push_messages")
     return sends[: ns.value].copy(), recvs[: nr.value].copy()
-
-
-class _RcclFns(C.Structure):
-    _fields_ = [("group_start", C.CFUNCTYPE(C.c_int)), ("group_end", C.CFUNCTYPE(C.c_int)),
-                ("send", C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_void_p)),
-                ("recv", C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_void_p))]
 
 
 def rccl_exchange_with_fake(sends, recvs, fail_at=None):
@@ -2490,8 +1855,7 @@ def rccl_exchange_with_fake(sends, recvs, fail_at=None):
     f = _RcclFns(); keep = (_RcclFns._fields_[0][1](gs), _RcclFns._fields_[1][1](ge), _RcclFns._fields_[2][1](snd), _RcclFns._fields_[3][1](rcv))
     f.group_start, f.group_end, f.send, f.recv = keep
     sm = np.ascontiguousarray(sends, PUSH_MSG_DTYPE); rm = np.ascontiguousarray(recvs, PUSH_MSG_DTYPE)
-    L = load(); L.corb_comm_test_rccl_exchange.restype = C.c_int
-    rc = L.corb_comm_test_rccl_exchange(C.byref(f), _p(sm) if len(sm) else None, len(sm), _p(rm) if len(rm) else None, len(rm))
+    rc = load().corb_comm_test_rccl_exchange(C.byref(f), _p(sm) if len(sm) else None, len(sm), _p(rm) if len(rm) else None, len(rm))
     return rc, log
 
 
@@ -2510,7 +1874,7 @@ def GlobalBundleAdjustemntStore(kf, kf_slots, mp, mp_slots, nIterations=10, bRob
     chi2 = np.zeros(nIterations + 1, np.float64); lam = np.zeros(max(nIterations, 1), np.float64)
     res = _BAResult(_p(oposes), _p(opoints), _p(chi2), _p(lam), 0, 0, 0, 0, 0, 0, 0, 0, 0)
     opt = BAOptions(solver, pcg_tol, pcg_max_iter, pc_block, pc_multilevel, scale_factor)
-    _chk(load().corb_ba_solve_store(kf.h, _p(ks), len(ks), mp.h, _p(ms), len(ms), nIterations, int(bRobust), None, nLoopKF, C.byref(res), C.byref(opt)), "corb_ba_solve_store")
+    _chk(load().corb_ba_solve_store(kf.h, _p(ks), len(ks), mp.h, _p(ms), len(ms), nIterations, bool(bRobust), None, nLoopKF, C.byref(res), C.byref(opt)), "corb_ba_solve_store")
     return dict(poses=None if oposes is None else oposes.reshape(-1, 4, 4), points=opoints, chi2=chi2[: res.iters_done + 1], lam=lam[: res.iters_done], iters_done=res.iters_done,
                 trials=res.trials_total, solver=res.solver_used, pcg_iterations=res.pcg_iterations,
                 structure=dict(free_poses=res.free_poses, free_points=res.free_points, active_edges=res.active_edges, nnz_blocks=res.nnz_blocks, schur_pairs=res.schur_pairs, pc_block=res.pc_block, pc_levels=res.pc_levels),
@@ -2532,15 +1896,16 @@ def LocalBundleAdjustmentStore(kf, kf_slots, n_local, mp, mp_slots, scale_factor
     one = C.c_int(1)
     sp = None if stop is None else (C.cast(C.byref(one), C.c_void_p) if stop == "before" else C.cast(C.byref(res, _BAResult.iters_done.offset), C.c_void_p))
     opt = BAOptions(solver, 0.0, 0, 0, 0)
-    _chk(load().corb_local_ba_store(kf.h, _p(ks), int(n_local), len(ks), mp.h, _p(ms), len(ms), st, len(stages), C.c_float(scale_factor), int(bool(apply_erase)), sp,
+    _chk(load().corb_local_ba_store(kf.h, _p(ks), n_local, len(ks), mp.h, _p(ms), len(ms), st, len(stages), scale_factor, bool(apply_erase), sp,
                                     C.byref(res), _p(pairs), cap, C.byref(ne), C.byref(opt)), "corb_local_ba_store")
     return dict(poses=oposes.reshape(-1, 4, 4), points=opoints, erase=pairs[: ne.value].copy(), iters_done=res.iters_done, trials=res.trials_total, ms_total=res.ms_total,
                 structure=dict(free_poses=res.free_poses, free_points=res.free_points, active_edges=res.active_edges, nnz_blocks=res.nnz_blocks, schur_pairs=res.schur_pairs),
                 device_route=bool(res.reserved0))
 
 
-class Comm:
+class Comm(_Handle):
     """RCCL communicator of the client / server ranks (corb_comm_*): rank 0 creates the 128-byte id, every rank gets it by the job's own means."""
+    _destroy = "corb_comm_destroy"
 
     @staticmethod
     def unique_id():
@@ -2548,30 +1913,17 @@ class Comm:
         _chk(load().corb_comm_unique_id(b), "corb_comm_unique_id")
         return bytes(b)
 
-    def __init__(self, unique_id, rank, world, device=0, _handle=None):
-        self.h = C.c_void_p(); self.rank = rank; self.world = world
-        if _handle is not None:
-            self.h = C.c_void_p(_handle); return
-        buf = (C.c_char * 128).from_buffer_copy(unique_id)
-        _chk(load().corb_comm_create(buf, rank, world, device, C.byref(self.h)), "corb_comm_create")
+    def __init__(self, unique_id, rank, world, device=0):
+        self.rank = rank; self.world = world
+        self._create("corb_comm_create", (C.c_char * 128).from_buffer_copy(unique_id), rank, world, device)
 
-    @staticmethod
-    def local(world, devices=None):
+    @classmethod
+    def local(cls, world, devices=None):
         """corb_comm_create_local: `world` communicators over the in-process transport (one host thread per rank)"""
         arr = (C.c_void_p * world)()
         dv = None if devices is None else np.ascontiguousarray(devices, np.int32)
         _chk(load().corb_comm_create_local(world, _p(dv), arr), "corb_comm_create_local")
-        return [Comm(None, r, world, _handle=arr[r]) for r in range(world)]
-
-    def close(self):
-        if self.h:
-            load().corb_comm_destroy(self.h); self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return [cls._adopt(arr[r], rank=r, world=world) for r in range(world)]
 
     def map_push(self, store, slots, root=0, dst_first=None):
         """corb_map_push: every rank sends the records of `slots` to `root`, which files rank r's records from slot dst_first[r] on; returns the per-rank counts on the root"""
@@ -2601,14 +1953,14 @@ class Comm:
             kf, mp = pack.get("kf"), pack.get("mp")
             p = _PublishPack(kf.h if kf is not None else None, _p(a) if len(a) else None, len(a), _p(c) if len(c) else None, len(c), mp.h if mp is not None else None,
                              _p(b) if len(b) else None, len(b), _p(d) if len(d) else None, len(d), _p(ids) if len(ids) else None, _p(T) if len(ids) else None, len(ids))
-            _chk(load().corb_map_publish(self.h, pub.h, int(root), C.byref(p), None), "corb_map_publish")
+            _chk(load().corb_map_publish(self.h, pub.h, root, C.byref(p), None), "corb_map_publish")
             return None
         kf, mp = apply.get("kf"), apply.get("mp")
         r = _PublishResult(max_counts, apply.get("kf_room", 0) if kf is not None else 0, apply.get("mp_room", 0) if mp is not None else 0)
         q = _PublishApply(int(apply["client_id"]), kf.h if kf is not None else None, int(apply.get("kf_first", 0)), int(apply.get("kf_n", 0)), int(apply.get("kf_free_first", 0)),
                           int(apply.get("kf_room", 0)), mp.h if mp is not None else None, int(apply.get("mp_first", 0)), int(apply.get("mp_n", 0)), int(apply.get("mp_free_first", 0)),
-                          int(apply.get("mp_room", 0)), int(bool(apply.get("apply", True))), C.pointer(r.c))
-        rc = load().corb_map_publish(self.h, pub.h, int(root), None, C.byref(q))
+                          int(apply.get("mp_room", 0)), bool(apply.get("apply", True)), C.pointer(r.c))
+        rc = load().corb_map_publish(self.h, pub.h, root, None, C.byref(q))
         if rc != ERR_CAPACITY:
             _chk(rc, "corb_map_publish")
         return r.as_dict(capacity_error=rc == ERR_CAPACITY)
@@ -2616,8 +1968,7 @@ class Comm:
     def map_push_setup(self, root, kf=None, mp=None, kf_dst_first=None, mp_dst_first=None):
         """corb_map_push_setup (collective, once): the root's layout to every rank, for the asynchronous pushes"""
         kd = None if kf_dst_first is None else np.ascontiguousarray(kf_dst_first, np.int32); md = None if mp_dst_first is None else np.ascontiguousarray(mp_dst_first, np.int32)
-        L = load(); L.corb_map_push_setup.restype = C.c_int; L.corb_map_push_setup.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        _chk(L.corb_map_push_setup(self.h, int(root), kf.h if kf is not None else None, mp.h if mp is not None else None, _p(kd), _p(md)), "corb_map_push_setup")
+        _chk(load().corb_map_push_setup(self.h, root, kf.h if kf is not None else None, mp.h if mp is not None else None, _p(kd), _p(md)), "corb_map_push_setup")
 
     def map_push_begin(self, kf, kf_slots, mp=None, mp_slots=(), root=0):
         """corb_map_push_begin: one header all-gather, records enqueued; returns at once (map_push_wait completes it and returns the counts on the root)"""
@@ -2626,11 +1977,9 @@ class Comm:
         p = _MapPush(kf.h if kf is not None else None, _p(ks) if len(ks) else None, len(ks), mp.h if mp is not None else None, _p(ms) if len(ms) else None, len(ms),
                      None, None, _p(kc), _p(mc))
         self._flight = (ks, ms, kc, mc, p, root)                # (the arrays the C side keeps pointers to until the wait)
-        L = load(); L.corb_map_push_begin.restype = C.c_int; L.corb_map_push_begin.argtypes = [C.c_void_p, C.POINTER(_MapPush), C.c_int]
-        _chk(L.corb_map_push_begin(self.h, C.byref(p), int(root)), "corb_map_push_begin")
+        _chk(load().corb_map_push_begin(self.h, C.byref(p), root), "corb_map_push_begin")
 
     def map_push_wait(self):
-        L = load(); L.corb_map_push_wait.restype = C.c_int; L.corb_map_push_wait.argtypes = [C.c_void_p]
-        _chk(L.corb_map_push_wait(self.h), "corb_map_push_wait")
+        _chk(load().corb_map_push_wait(self.h), "corb_map_push_wait")
         fl = getattr(self, "_flight", None); self._flight = None
         return (fl[2], fl[3]) if fl is not None and self.rank == fl[5] else None

@@ -5,7 +5,7 @@ corb = corbload.load_pkg()
 from corb_slam_amd import synth
 l, r = synth.stereo_pair(0)
 ex = corb.ORBextractor(width=1241, height=376, max_images=1)
-L = ex.L; h = ex.h
+L = corb.load(); h = ex.h
 ex(l)
 kp = np.zeros(4000, corb.KP_DTYPE); desc = np.zeros((4000, 32), np.uint8); n = C.c_int()
 def t(f, reps=20):

@@ -30,7 +30,7 @@ def pinned(shape, dtype):
     buf = (ctypes.c_uint8 * nbytes).from_address(ptr.value)
     return np.frombuffer(buf, np.uint8).view(dtype).reshape(shape), buf
 packed = np.stack([np.stack([l, r]) for l, r in frames])
-cap = sf.L.corb_orb_capacity(sf.orb.h)
+cap = corb.load().corb_orb_capacity(sf.orb.h)
 for name, mk in (("pageable", lambda sh, dt: (np.zeros(sh, dt), None)), ("pinned", pinned)):
     inp, k0 = mk(packed.shape, np.uint8); inp[...] = packed
     keep = [k0]
