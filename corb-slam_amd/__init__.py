@@ -4,6 +4,7 @@ The product is the C-ABI library (include/*.h) plus the C++ adapter in host/; th
 from tests/, bench.py and __graft_entry__.py.  It has two layers:
   _abi.py      the mirror of the C ABI, stated once: constants, structures, record dtypes, one prototype
                per exported function, and bind() that puts the prototypes onto an opened library
+  _abi_fusion.py  the same for the seventh header, include/corb_map_fusion.h, as a table of its own (bind_fusion())
   __init__.py  (this file) load(), the handle owner, and the classes and functions that marshal numpy
                arrays into the calls -- about 1900 lines, most of them array marshalling
 Class / method names mirror the reference (ORBextractor::operator(), ORBmatcher::SearchByBoW /
@@ -16,6 +17,7 @@ import os
 import numpy as np
 
 from ._abi import *         # noqa: F401,F403 -- every name of the mirror, the underscore ones included (_abi.__all__)
+from ._abi_fusion import *  # noqa: F401,F403 -- include/corb_map_fusion.h: a table of its own beside the six headers' (see _abi_fusion.py)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libcorb_accel.so")
@@ -37,7 +39,7 @@ def load():
         if not os.path.exists(LIB_PATH):
             raise CorbError("libcorb_accel.so is not built (run `python -c 'import __graft_entry__ as g; g.build()'`); "
                             "there is no CPU fallback")
-        _lib = bind(C.CDLL(LIB_PATH))
+        _lib = bind_fusion(bind(C.CDLL(LIB_PATH)))
     return _lib
 
 
@@ -1196,6 +1198,19 @@ class KeyFrameDatabase(_Handle):
         _chk(rc, "corb_kfdb_detect")
         return out[:n.value].copy()
 
+    def detect_batch(self, kind, entries, ids, cap=None):
+        """corb_kfdb_detect_batch: the queries (entries[i], ids[i]) in list order, as `detect` called for one after the other -> (offsets[n + 1], candidates).
+        cap=None leaves room for every entry per query.  After a CorbError, last_rc / last_count hold the return code and the room needed."""
+        e = np.ascontiguousarray(entries, np.int32).reshape(-1); i = np.ascontiguousarray(ids, np.uint64).reshape(-1)
+        if len(e) != len(i):
+            raise CorbError("KeyFrameDatabase.detect_batch: entries and ids differ in length")
+        cap = len(e) * self.capacity if cap is None else cap
+        off = np.zeros(len(e) + 1, np.int32); out = np.zeros(max(cap, 1), np.int32); n = C.c_int(0)
+        rc = load().corb_kfdb_detect_batch(self.h, kind, _p(e), _p(i), len(e), _p(off), _p(out), cap, C.byref(n))
+        self.last_rc, self.last_count, self.last_offsets = rc, n.value, off
+        _chk(rc, "corb_kfdb_detect_batch")
+        return off, out[:n.value].copy()
+
     def DetectLoopCandidates(self, query_entry, query_id, connected, min_score):
         return self.detect(0, query_entry, query_id, connected, min_score)
 
@@ -1620,6 +1635,18 @@ class KeyFrameStore(_Handle):
         _chk(load().corb_search_by_bow_slots(variant, self.h, slot_a, other.h, slot_b, nnratio, bool(checkOri), _p(out), C.byref(n)), "corb_search_by_bow_slots")
         return out[: (nb if variant == 0 else na)], n.value
 
+    def SearchByBoW_batch(self, slots_a, other, slots_b, nnratio=0.6, checkOri=True, variant=0, stride=None):
+        """corb_search_by_bow_slots_batch: SearchByBoW for the pairs (slots_a[p], slots_b[p]) -> (match[n_pairs, stride], counts[n_pairs]); a row holds -1 behind its
+        length.  stride=None: the longest row."""
+        a = np.ascontiguousarray(slots_a, np.int32).reshape(-1); b = np.ascontiguousarray(slots_b, np.int32).reshape(-1)
+        if len(a) != len(b):
+            raise CorbError("KeyFrameStore.SearchByBoW_batch: the slot lists differ in length")
+        if stride is None:
+            stride = max([other._n_any(int(s)) for s in set(b.tolist())] if variant == 0 else [self._n_any(int(s)) for s in set(a.tolist())], default=0)
+        match = np.full((len(a), stride), -1, np.int32); counts = np.zeros(len(a), np.int32)
+        _chk(load().corb_search_by_bow_slots_batch(variant, self.h, _p(a), other.h, _p(b), len(a), nnratio, bool(checkOri), stride, _p(match), _p(counts)), "corb_search_by_bow_slots_batch")
+        return match, counts
+
     def SearchForTriangulation(self, slot_a, other, slot_b, F12, ex, ey, scale2, sigma2_2, bOnlyStereo, checkOri=True):
         na = self._n_any(slot_a)
         F12 = np.ascontiguousarray(F12, np.float32); sc = np.ascontiguousarray(scale2, np.float32); sg = np.ascontiguousarray(sigma2_2, np.float32)
@@ -1627,6 +1654,26 @@ class KeyFrameStore(_Handle):
         _chk(load().corb_search_for_triangulation_slots(self.h, slot_a, other.h, slot_b, _p(F12), ex, ey, _p(sc), _p(sg), len(sc), bool(bOnlyStereo), bool(checkOri), _p(pairs), C.byref(n)),
              "corb_search_for_triangulation_slots")
         return pairs[: n.value].copy(), n.value
+
+
+def map_fusion_candidates(db, sub, query_slots, query_entries, query_ids, glob, entry_slot, nnratio=0.75, checkOri=True, min_matches=15, cap_rows=None, cap_ids=None):
+    """corb_map_fusion_candidates_store: detectKeyFrameInServerMap's detection, matching and discarding for every keyframe of a submap -> (rows, offsets, ids):
+    rows (FUSION_ROW_DTYPE) in detection order, rows[offsets[i] : offsets[i + 1]] those of query i, ids the map-point ids of the kept rows (a row's start: ids_offset).
+    cap_rows=None / cap_ids=None leave room for every entry per query and for every row with a record."""
+    qs = np.ascontiguousarray(query_slots, np.int32).reshape(-1); qe = np.ascontiguousarray(query_entries, np.int32).reshape(-1); qi = np.ascontiguousarray(query_ids, np.uint64).reshape(-1)
+    es = np.ascontiguousarray(entry_slot, np.int32).reshape(-1)
+    if not (len(qs) == len(qe) == len(qi)) or len(es) != db.capacity:
+        raise CorbError("map_fusion_candidates: the query lists differ in length, or entry_slot does not have one entry per database entry")
+    cap_rows = len(qs) * db.capacity if cap_rows is None else cap_rows
+    if cap_ids is None:
+        cap_ids = int((es >= 0).sum()) * sum(max(sub._n_any(int(s)), 0) for s in qs)
+    off = np.zeros(len(qs) + 1, np.int32); rows = np.zeros(max(cap_rows, 1), FUSION_ROW_DTYPE); ids = np.zeros(max(cap_ids, 1), np.uint64)
+    n_rows = C.c_int(0); n_ids = C.c_int64(0)
+    rc = load().corb_map_fusion_candidates_store(db.h, sub.h, _p(qs), _p(qe), _p(qi), len(qs), glob.h, _p(es), nnratio, bool(checkOri), min_matches,
+                                                 _p(off), _p(rows), cap_rows, C.byref(n_rows), _p(ids), cap_ids, C.byref(n_ids))
+    map_fusion_candidates.last = (rc, n_rows.value, n_ids.value)
+    _chk(rc, "corb_map_fusion_candidates_store")
+    return rows[:n_rows.value].copy(), off, ids[:n_ids.value].copy()
 
 
 class MapPointStore(_Handle):

@@ -40,6 +40,23 @@ struct CorbVoc {
     DevList allocs;
 };
 int voc_finish(CorbVoc* v, int device, CorbVoc** out, const char* who);
+
+#include <mutex>
+#include <vector>
+// a keyframe database handle (corb_bow.cpp; the whole-submap calls of corb_fusion.cpp work on it too)
+struct CorbKfDb {
+    int device = 0;
+    CorbVoc* voc = nullptr;
+    BowDbDev d{};
+    OwnedStream stream;
+    std::mutex mu;
+    DevList allocs;
+    PinnedMem pinned;                           // [2 * capacity + 2] ints: connected list / entry lists up, candidates down
+    PinnedMem pinned_score;                     // [capacity] doubles
+    std::vector<int> n_words;                   // host mirror: words of an entry's BowVector, -1 = none
+    std::vector<char> live;
+    uint32_t next_seq = 1;
+};
 #define BOW_MAX_SETS 65535          // descriptor sets per transform call: the sets are one grid dimension
 
 // corb_bow_profile: event pairs per launch, and wall-clock ticks of the two in-order sums (ticks[0] the norm loop of bow_build_kernel, [1] that kernel's lane 0 in all;

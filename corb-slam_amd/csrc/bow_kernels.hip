@@ -16,16 +16,11 @@
 //   kfdb_score_list_kernel : corb_kfdb_score: one wavefront per listed entry, the same in-order sum
 // No scalar memory writes, no device-side printf / assert; every launch is on the caller's stream.
 #include "bow_internal.h"
+#include "bow_device.h"
 #include "lane_exchange.h"
 #include <mutex>
 
 namespace {
-
-__device__ __forceinline__ double bow_readlane(double v, int lane)
-{
-    const int lo = __builtin_amdgcn_readlane(__double2loint(v), lane), hi = __builtin_amdgcn_readlane(__double2hiint(v), lane);
-    return __hiloint2double(hi, lo);
-}
 
 template <int G> __global__ __launch_bounds__(256) void bow_descend_kernel(BowVocView v, const BowSetDev* sets, int levelsup, int32_t* feat_word, uint32_t* feat_node)
 {
@@ -53,23 +48,6 @@ template <int G> __global__ __launch_bounds__(256) void bow_descend_kernel(BowVo
         if (level == nid_level) nid = node;
     } while (v.child_count[node] > 0);
     if (c == 0) { feat_word[s.feat_off + f] = v.node_word[node]; feat_node[s.feat_off + f] = (uint32_t)(nid < 0 ? node : nid); }
-}
-
-// ascending bitonic sort of keys[0 .. P), P a power of two, by the whole workgroup
-template <class Swap> __device__ __forceinline__ void bow_bitonic(unsigned long long* keys, int P, Swap swap_payload)
-{
-    const int tid = threadIdx.x, T = blockDim.x;
-    for (int k2 = 2; k2 <= P; k2 <<= 1)
-        for (int j = k2 >> 1; j > 0; j >>= 1) {
-            for (int i = tid; i < P; i += T) {
-                const int x = i ^ j;
-                if (x > i) {
-                    const unsigned long long a = keys[i], b = keys[x];
-                    if ((a > b) == ((i & k2) == 0)) { keys[i] = b; keys[x] = a; swap_payload(i, x); }
-                }
-            }
-            __syncthreads();
-        }
 }
 
 __global__ __launch_bounds__(256) void bow_build_kernel(BowVocView v, const BowSetDev* sets, const int32_t* feat_word, const uint32_t* feat_node, unsigned long long* ticks)
@@ -157,42 +135,18 @@ __global__ void kfdb_scatter_kernel(BowDbDev d, int q, int nq, int n_conn, int s
     if (i < 2 && set) d.ctr[i] = 0;
 }
 
-// words the entry shares with the scattered query: count and the first of them (lane-uniform results)
+// words the entry shares with the scattered query: count and the first of them (lane-uniform results; the ballots are bow_device.h's)
 __device__ __forceinline__ int kfdb_wave_common(const BowDbDev& d, int e, int lane, uint32_t* first)
 {
-    const int nw = d.n_words[e];
-    const uint32_t* w = d.words + (size_t)e * d.max_words;
-    int common = 0; uint32_t fw = 0;
-    for (int base = 0; base < nw; base += 64) {
-        const int i = base + lane;
-        uint32_t wi = 0; bool c = false;
-        if (i < nw) { wi = w[i]; c = d.dense[wi] > 0.0; }
-        const unsigned long long m = __ballot(c);
-        if (m) {
-            if (!common) fw = (uint32_t)__builtin_amdgcn_readlane((int)wi, __ffsll((long long)m) - 1);
-            common += __popcll(m);
-        }
-    }
-    *first = fw;
-    return common;
+    const double* dense = d.dense;
+    return bow_wave_common(d.words + (size_t)e * d.max_words, d.n_words[e], lane, [dense](uint32_t w) { return dense[w] > 0.0; }, first);
 }
 
 // L1Scoring::score of the scattered query against entry e: the common words' terms in ascending word order (lane-uniform result)
 template <bool TIMED> __device__ __forceinline__ double kfdb_wave_score(const BowDbDev& d, int e, int lane, unsigned long long& sum_ticks)
 {
-    const int nw = d.n_words[e];
-    const uint32_t* w = d.words + (size_t)e * d.max_words; const double* val = d.values + (size_t)e * d.max_words;
-    double sum = 0.0;
-    for (int base = 0; base < nw; base += 64) {
-        const int i = base + lane;
-        double term = 0.0; bool c = false;
-        if (i < nw) { const double q = d.dense[w[i]]; if (q > 0.0) { c = true; term = bow_score_term(q, val[i]); } }
-        unsigned long long m = __ballot(c);
-        const unsigned long long t0 = TIMED ? wall_clock64() : 0;
-        while (m) { const int j = __ffsll((long long)m) - 1; m &= m - 1; sum += bow_readlane(term, j); }
-        if (TIMED) sum_ticks += wall_clock64() - t0;
-    }
-    return bow_score_finish(sum);
+    const double* dense = d.dense;
+    return bow_wave_score<TIMED>(d.words + (size_t)e * d.max_words, d.values + (size_t)e * d.max_words, d.n_words[e], lane, [dense](uint32_t w) { return dense[w]; }, sum_ticks);
 }
 
 __global__ __launch_bounds__(256) void kfdb_count_kernel(BowDbDev d, int kind, unsigned long long id)

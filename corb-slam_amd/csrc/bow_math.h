@@ -86,18 +86,24 @@ BOW_HD bool bow_visit_reloc(BowKfState& s, unsigned long long id, int common)
     s.reloc_words += common;
     return false;
 }
-// the covisibility accumulation of one scored keyframe (:143-165, :251-274): nb = its neighbours' entries (-1 padded)
-BOW_HD void bow_accumulate(int kind, const BowKfState* st, const int* nb, int entry, float si, unsigned long long id, int min_common, float* acc_out, int* best_out)
+// the covisibility accumulation of one scored keyframe (:143-165, :251-274): nb = its neighbours' entries (-1 padded).  counts(e2) says whether neighbour e2 takes
+// part for this query and score_of(e2) is the score it holds then -- for the relocalisation / map-fusion kinds that is whatever mRelocScore the last query that
+// scored it left there (a neighbour that shares a word with the query but was not scored for it adds a stale score; the reference does).
+template <class Counts, class ScoreOf> BOW_HD void bow_accumulate_by(const int* nb, int entry, float si, Counts counts, ScoreOf score_of, float* acc_out, int* best_out)
 {
     float best_score = si, acc = si; int best = entry;
     for (int j = 0; j < BOW_NEIGHBOURS; j++) {
         const int e2 = nb[j];
-        if (e2 < 0) continue;
-        const BowKfState& s2 = st[e2];
-        if (kind == 0) { if (!(s2.loop_query == id && s2.loop_words > min_common)) continue; acc += s2.loop_score; if (s2.loop_score > best_score) { best = e2; best_score = s2.loop_score; } }
-        else { if (s2.reloc_query != id) continue; acc += s2.reloc_score; if (s2.reloc_score > best_score) { best = e2; best_score = s2.reloc_score; } }
+        if (e2 < 0 || !counts(e2)) continue;
+        const float s2 = score_of(e2);
+        acc += s2; if (s2 > best_score) { best = e2; best_score = s2; }
     }
     *acc_out = acc; *best_out = best;
+}
+BOW_HD void bow_accumulate(int kind, const BowKfState* st, const int* nb, int entry, float si, unsigned long long id, int min_common, float* acc_out, int* best_out)
+{
+    if (kind == 0) bow_accumulate_by(nb, entry, si, [=](int e2) { return st[e2].loop_query == id && st[e2].loop_words > min_common; }, [=](int e2) { return st[e2].loop_score; }, acc_out, best_out);
+    else bow_accumulate_by(nb, entry, si, [=](int e2) { return st[e2].reloc_query == id; }, [=](int e2) { return st[e2].reloc_score; }, acc_out, best_out);
 }
 
 // ============================ host side: the vocabulary's construction (corb_bow.cpp and the host program share it) ============================

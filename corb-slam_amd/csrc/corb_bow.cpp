@@ -154,20 +154,7 @@ extern "C" int corb_voc_transform(CorbVoc* v, const uint8_t* desc, const int32_t
 }
 
 // ---------------------------------------------------------------- keyframe database ----------------------------------------------------------------
-struct CorbKfDb {
-    int device = 0;
-    CorbVoc* voc = nullptr;
-    BowDbDev d{};
-    OwnedStream stream;
-    std::mutex mu;
-    DevList allocs;
-    PinnedMem pinned;                           // [2 * capacity + 2] ints: connected list / entry lists up, candidates down
-    PinnedMem pinned_score;                     // [capacity] doubles
-    std::vector<int> n_words;                   // host mirror: words of an entry's BowVector, -1 = none
-    std::vector<char> live;
-    uint32_t next_seq = 1;
-};
-
+// (struct CorbKfDb: bow_internal.h)
 template <class T> static hipError_t db_alloc(CorbKfDb* db, T** out, size_t n, int fill)
 {
     hipError_t e = db->allocs.add(out, n); if (e != hipSuccess) return e;

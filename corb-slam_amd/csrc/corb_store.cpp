@@ -62,6 +62,13 @@ static int refresh_host(CorbKfStore* s, int slot)
     return CORB_OK;
 }
 
+// for calls on many slots outside this file (corb_fusion.cpp): the slot checked and its host mirror current; the caller holds s->mu
+int kf_store_slot_ready(CorbKfStore* s, int slot, const char* who)
+{
+    int rc = slot_ok(s, slot, who); if (rc) return rc;
+    return refresh_host(s, slot);
+}
+
 // slot <- a front-end frame's device arrays (device-to-device, on the front-end's stream)
 static int kf_put_device_frame(CorbKfStore* s, int slot, const CorbStereoDeviceFrame& f, uint64_t id, const char* who)
 {

@@ -35,6 +35,9 @@ struct CorbMpStore {
     char* rec(int slot) const { return base() + (size_t)slot * L.bytes; }
 };
 
+// slot in range and host[slot] current (counts and node ids read from the record once after a device-side fill); under s->mu (corb_store.cpp)
+int kf_store_slot_ready(CorbKfStore* s, int slot, const char* who);
+
 // the vocabulary nodes two FeatureVectors share (both ascend in the node id): positions in a and in b -- what the BoW-guided matchers on slots walk
 inline void common_nodes(const std::vector<uint32_t>& a, const std::vector<uint32_t>& b, std::vector<int>& pa, std::vector<int>& pb)
 {

@@ -600,6 +600,77 @@ private:
     CorbKfInsert* h_ = nullptr;
 };
 
+// ---- the server's detection loop on records (include/corb_map_fusion.h) ----
+//   bool MapFusion::detectKeyFrameInServerMap(pMap, tKF, Tcw, candidateKFs)        S/src/MapFusion.cpp:660-756, called per keyframe by mapFuseToGlobalMap / mapFuse :432-620
+// Detect() walks the keyframes of a submap as that loop walks them, with the argument meaning of the reference: for each keyframe the candidates of
+// DetectMapFusionCandidatesFromDB, SearchByBoWInServer(0.75, true) against each, the candidates that are bad / have fewer than 15 matches discarded, PnPsolver with
+// SetRansacParameters(0.99, 10, 300, 4, 0.5, 5.991) on the rest and iterate(5) round-robin until a solver returns a pose (a refined one, or with bNoMore its best
+// hypothesis on record: the reference takes any non-empty Tcw) -- and stops at the first keyframe that yields
+// one.  On records that is ONE corb_map_fusion_candidates_store for the whole submap, then one corb_pnp_ransac_store per keyframe in order (it takes the kept rows' ids
+// where the first call left them) with corb::pnp_replay answering the iterate(5) calls.  The keyframes are named by their records: subSlotOf(pKF) in `sub`,
+// entrySlot[e] in `global` for database entry e.  Pose refinement, SearchByProjection and ComputeSim3 after a pose stay where they are (corb_track_*, corb_sim3_*).
+template <class KeyFrame, class Db>
+class MapFusionDetectT {
+public:
+    struct Params { float nnratio = 0.75f; bool checkOrientation = true; int minMatches = 15; double probability = 0.99; int minInliers = 10, maxIterations = 300, minSet = 4;
+                    float epsilon = 0.5f, th2 = 5.991f; int nIterations = 5, tailIterations = 0; };
+    struct Detection {
+        FusionCandidates cand;                   // every keyframe's rows, whether the walk reached it or not
+        int iKeyFrame = -1;                      // the first keyframe that yielded a pose (-1: none), its row among all rows, and the solver's answer
+        int row = -1;
+        bool bRefined = false;                   // the pose is Refine()'s (mRefinedTcw); false: the running best returned with bNoMore (mBestTcw, PnPsolver.cc:286-299)
+        float Tcw[16] = {0};                     // the Tcw iterate() returned
+        std::vector<uint8_t> vbInliers;          // per feature of that keyframe: mvbRefinedInliers or mvbBestInliers
+        int nTried = 0;                          // keyframes that had a PnP call
+    };
+    // rand(k) -> the k-th draw of one keyframe's solvers (the reference draws from rand(); here the draws are data: RANSAC routes, DESIGN)
+    template <class SubSlotOf, class Rand>
+    Detection Detect(const std::vector<KeyFrame*>& vpKFs, SubSlotOf subSlotOf, Db& db, CorbKfStore* sub, CorbKfStore* global, const std::vector<int32_t>& entrySlot,
+                     CorbMpStore* map, const CorbTrackCamera& cam, Rand rand, int capRows, int64_t capIds, const Params& P = Params())
+    {
+        std::vector<int32_t> slots, entries; std::vector<uint64_t> ids;
+        for (KeyFrame* p : vpKFs) { slots.push_back((int32_t)subSlotOf(p)); entries.push_back(db.Entry(p)); ids.push_back((uint64_t)p->mnId); }
+        Detection d;
+        d.cand = MapFusionCandidates(db.handle(), sub, slots, entries, ids, global, entrySlot, capRows, capIds, P.nnratio, P.checkOrientation, P.minMatches);
+        const int stride = P.maxIterations + P.tailIterations;
+        for (size_t i = 0; i < vpKFs.size() && d.iKeyFrame < 0; i++) {
+            const int r0 = d.cand.rowOffset[i], r1 = d.cand.rowOffset[i + 1];
+            std::vector<int> kept; for (int r = r0; r < r1; r++) if (d.cand.rows[r].kept) kept.push_back(r);
+            if (kept.empty()) continue;                                                   // every candidate discarded (:700-707)
+            const int n = corb_kf_store_count(sub, slots[i]), nc = (int)kept.size();
+            if (n <= 0) continue;
+            std::vector<int32_t> rv((size_t)nc * stride * P.minSet); for (size_t k = 0; k < rv.size(); k++) rv[k] = (int32_t)rand(k);
+            std::vector<int32_t> cap(nc), mi(nc), nrec(nc), ncorr(nc), counts((size_t)nc * stride);
+            std::vector<CorbPnPRansacRecord> rec((size_t)nc * stride); std::vector<uint8_t> bf((size_t)nc * stride * n), rf((size_t)nc * stride * n);
+            check(corb_pnp_ransac_store(sub, slots[i], map, &cam, d.cand.ids.data() + d.cand.rows[kept[0]].ids_offset, nc, P.probability, P.minInliers, P.maxIterations, P.minSet,
+                                        P.epsilon, P.th2, P.tailIterations, rv.data(), stride, cap.data(), mi.data(), nrec.data(), rec.data(), bf.data(), rf.data(), ncorr.data(),
+                                        nullptr, counts.data(), nullptr, nullptr), "corb_pnp_ransac_store");
+            d.nTried++;
+            // the round-robin of :709-752: iterate(nIterations) per live solver until one returns a pose or all are discarded
+            std::vector<int> its(nc, 0); std::vector<char> dead(nc, 0); int alive = nc;
+            while (alive > 0 && d.iKeyFrame < 0)
+                for (int c = 0; c < nc && d.iKeyFrame < 0; c++) {
+                    if (dead[c]) continue;
+                    const int k = std::min(nrec[c], stride);
+                    const PnPReplay a = pnp_replay(counts.data() + (size_t)c * stride, stride, rec.data() + (size_t)c * stride, k, mi[c], cap[c], its[c], P.nIterations);
+                    its[c] = a.iterations;
+                    if (a.kind != PnPReplay::Refined) { dead[c] = 1; alive--; }           // bNoMore: vbDiscarded[i] = true (:728-732)
+                    if (a.kind == PnPReplay::None) continue;                              // an empty Tcw
+                    // any pose ends the walk (:735-741): Refine()'s, or -- with bNoMore -- the best hypothesis on record whose Refine() never succeeded
+                    d.bRefined = a.kind == PnPReplay::Refined;
+                    d.iKeyFrame = (int)i; d.row = kept[c];
+                    const size_t at = (size_t)c * stride + a.record;
+                    const float* T = d.bRefined ? rec[at].Tcw_refined : rec[at].Tcw_best;
+                    for (int j = 0; j < 12; j++) d.Tcw[j] = T[j];
+                    d.Tcw[12] = d.Tcw[13] = d.Tcw[14] = 0.f; d.Tcw[15] = 1.f;
+                    const std::vector<uint8_t>& fl = d.bRefined ? rf : bf;
+                    d.vbInliers.assign(fl.begin() + at * n, fl.begin() + (at + 1) * n);
+                }
+        }
+        return d;
+    }
+};
+
 // ---- the server -> clients publish on records (include/corb_map_publish.h) ----
 //   server: MapFusion::runPubTopic / resentGlobalMapToClient -> PubToClient::pub*ToClients             S/src/MapFusion.cpp:315-430, S/src/PubToClient.cpp:24-163
 //   client: Cache::subNewInsertKeyFramesFromServer / subNewInsertMapPointFromServer / subUpdated*      C/src/Cache.cc:446-634
@@ -1193,6 +1264,18 @@ public:
         return detect(0, entry(pKF), (uint64_t)pKF->mnId, conn, minScore);
     }
     std::vector<KeyFrame*> DetectMapFusionCandidatesFromDB(KeyFrame* pKF) { return detect(2, entry(pKF), (uint64_t)pKF->mnId, {}, 0.f); }
+    // DetectMapFusionCandidatesFromDB for every keyframe of a submap in one call (corb_kfdb_detect_batch): the lists the calls above give one after the other
+    std::vector<std::vector<KeyFrame*>> DetectMapFusionCandidatesFromDB(const std::vector<KeyFrame*>& vpKFs)
+    {
+        std::vector<int32_t> e; std::vector<uint64_t> ids;
+        for (KeyFrame* p : vpKFs) { e.push_back(entry(p)); ids.push_back((uint64_t)p->mnId); }
+        const CandidateLists c = DetectBatch(h_, 2, e, ids, (int)std::min<size_t>(vpKFs.size() * (size_t)cap_, 1u << 30));
+        std::vector<std::vector<KeyFrame*>> out(vpKFs.size());
+        for (size_t i = 0; i < vpKFs.size(); i++) for (int k = c.offset[i]; k < c.offset[i + 1]; k++) out[i].push_back(kf_[c.cand[k]]);
+        return out;
+    }
+    int Entry(KeyFrame* pKF) { return entry(pKF); }             // the keyframe's entry (its BowVector is uploaded at first sight)
+    int Capacity() const { return cap_; }
     std::vector<KeyFrame*> DetectRelocalizationCandidates(Frame* F)
     {
         set_bow(cap_ - 1, F->mBowVec);
@@ -1506,6 +1589,7 @@ using PnPsolver = corb::PnPsolver<Frame, KeyFrame, MapPoint>;
 using Initializer = corb::Initializer<Frame>;
 using ORBVocabulary = corb::ORBVocabulary;
 using KeyFrameDatabase = corb::KeyFrameDatabase<KeyFrame, Frame>;
+using MapFusionDetect = corb::adapt::MapFusionDetectT<KeyFrame, corb::KeyFrameDatabase<KeyFrame, Frame>>;
 using Covisibility = corb::Covisibility<KeyFrame, corb::KeyFrameDatabase<KeyFrame, Frame>>;
 }  // namespace accel
 }  // namespace ORB_SLAM2

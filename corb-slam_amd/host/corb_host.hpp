@@ -14,6 +14,7 @@
 #pragma once
 #include <corb_accel.h>
 #include <corb_stereo_rectify.h>
+#include <corb_map_fusion.h>
 #include <algorithm>
 #include <cstdint>
 #include <stdexcept>
@@ -498,5 +499,44 @@ inline PnPReplay pnp_replay(const int32_t* counts, int n_counts, const CorbPnPRa
         if (i >= s && counts[i] >= m && b >= 0 && records[b].refine_ok) return {PnPReplay::Refined, b, i + 1};
     }
     return {b >= 0 ? PnPReplay::Best : PnPReplay::None, b, std::max(end, s)};
+}
+// ---- map-fusion detection for a whole submap (include/corb_map_fusion.h).  This header holds no mirror class of the keyframe database or of the record stores (the
+// database's class with the reference's signatures is corb::KeyFrameDatabase of corb_adapter_orbslam.hpp, whose DetectMapFusionCandidatesFromDB(vector) calls DetectBatch
+// below; the stores are plain handles), so
+// the three calls are mirrored here as functions on the handles, sized and cut as the Python harness sizes and cuts them. ----
+struct CandidateLists { std::vector<int32_t> offset, cand; };      // cand[offset[i] .. offset[i + 1]) = the candidates of query i
+inline CandidateLists DetectBatch(CorbKfDb* db, int kind, const std::vector<int32_t>& entries, const std::vector<uint64_t>& ids, int cap)
+{
+    if (entries.size() != ids.size()) throw Error(CORB_ERR_ARG, "DetectBatch: entries and ids differ in length");
+    CandidateLists o; o.offset.assign(entries.size() + 1, 0); o.cand.assign((size_t)std::max(cap, 1), 0);
+    int n = 0;
+    check(corb_kfdb_detect_batch(db, kind, entries.data(), ids.data(), (int)entries.size(), o.offset.data(), o.cand.data(), cap, &n), "corb_kfdb_detect_batch");
+    o.cand.resize((size_t)n);
+    return o;
+}
+struct BowMatches { int stride = 0; std::vector<int32_t> match, count; };      // row p: match[p * stride ..], -1 behind the row's length
+inline BowMatches SearchByBoWSlotsBatch(int variant, CorbKfStore* a, const std::vector<int32_t>& slotsA, CorbKfStore* b, const std::vector<int32_t>& slotsB, float nnratio,
+                                        bool checkOrientation, int stride)
+{
+    if (slotsA.size() != slotsB.size()) throw Error(CORB_ERR_ARG, "SearchByBoWSlotsBatch: the slot lists differ in length");
+    BowMatches o; o.stride = stride; o.match.assign(std::max<size_t>(slotsA.size() * (size_t)stride, 1), -1); o.count.assign(std::max<size_t>(slotsA.size(), 1), 0);
+    check(corb_search_by_bow_slots_batch(variant, a, slotsA.data(), b, slotsB.data(), (int)slotsA.size(), nnratio, checkOrientation ? 1 : 0, stride, o.match.data(), o.count.data()),
+          "corb_search_by_bow_slots_batch");
+    o.count.resize(slotsA.size());
+    return o;
+}
+struct FusionCandidates { std::vector<int32_t> rowOffset; std::vector<CorbFusionRow> rows; std::vector<uint64_t> ids; };
+inline FusionCandidates MapFusionCandidates(CorbKfDb* db, CorbKfStore* sub, const std::vector<int32_t>& querySlots, const std::vector<int32_t>& queryEntries,
+                                            const std::vector<uint64_t>& queryIds, CorbKfStore* global, const std::vector<int32_t>& entrySlot, int capRows, int64_t capIds,
+                                            float nnratio = 0.75f, bool checkOrientation = true, int minMatches = 15)
+{
+    if (querySlots.size() != queryEntries.size() || querySlots.size() != queryIds.size()) throw Error(CORB_ERR_ARG, "MapFusionCandidates: the query lists differ in length");
+    FusionCandidates o; o.rowOffset.assign(querySlots.size() + 1, 0); o.rows.resize((size_t)std::max(capRows, 1)); o.ids.resize((size_t)std::max<int64_t>(capIds, 1));
+    int nRows = 0; int64_t nIds = 0;
+    check(corb_map_fusion_candidates_store(db, sub, querySlots.data(), queryEntries.data(), queryIds.data(), (int)querySlots.size(), global, entrySlot.data(), nnratio,
+                                           checkOrientation ? 1 : 0, minMatches, o.rowOffset.data(), o.rows.data(), capRows, &nRows, o.ids.data(), capIds, &nIds),
+          "corb_map_fusion_candidates_store");
+    o.rows.resize((size_t)nRows); o.ids.resize((size_t)nIds);
+    return o;
 }
 }  // namespace corb
