@@ -5,6 +5,7 @@ from tests/, bench.py and __graft_entry__.py.  It has two layers:
   _abi.py      the mirror of the C ABI, stated once: constants, structures, record dtypes, one prototype
                per exported function, and bind() that puts the prototypes onto an opened library
   _abi_fusion.py  the same for the seventh header, include/corb_map_fusion.h, as a table of its own (bind_fusion())
+  _abi_tracklocal.py  the same for the eighth header, include/corb_track_local_map.h (bind_tracklocal())
   __init__.py  (this file) load(), the handle owner, and the classes and functions that marshal numpy
                arrays into the calls -- about 1900 lines, most of them array marshalling
 Class / method names mirror the reference (ORBextractor::operator(), ORBmatcher::SearchByBoW /
@@ -18,6 +19,7 @@ import numpy as np
 
 from ._abi import *         # noqa: F401,F403 -- every name of the mirror, the underscore ones included (_abi.__all__)
 from ._abi_fusion import *  # noqa: F401,F403 -- include/corb_map_fusion.h: a table of its own beside the six headers' (see _abi_fusion.py)
+from ._abi_tracklocal import *  # noqa: F401,F403 -- include/corb_track_local_map.h: likewise (see _abi_tracklocal.py)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libcorb_accel.so")
@@ -39,7 +41,7 @@ def load():
         if not os.path.exists(LIB_PATH):
             raise CorbError("libcorb_accel.so is not built (run `python -c 'import __graft_entry__ as g; g.build()'`); "
                             "there is no CPU fallback")
-        _lib = bind_fusion(bind(C.CDLL(LIB_PATH)))
+        _lib = bind_tracklocal(bind_fusion(bind(C.CDLL(LIB_PATH))))
     return _lib
 
 
@@ -1502,6 +1504,35 @@ class KeyFrameStore(_Handle):
         _chk(load().corb_track_update_local_map(covis.h, self.h, slot, _p(prev) if len(prev) else None, len(prev), _p(ks), kf_cap, _p(ms), _p(ids), mp_cap, C.byref(info)),
              "corb_track_update_local_map")
         return ks[:info.n_kf].copy(), ms[:info.n_mp].copy(), ids[:info.n_mp].copy(), info
+
+    def TrackLocalMap(self, slot, covis, cam, Tcw, frame_id, log_scale_factor, prev_kf_slots=(), last_reloc_frame_id=0, max_frames=30, sensor=1, only_tracking=False,
+                      nnratio=0.8, th=0.0, kf_cap=None, mp_cap=None, want_match=True, want_outliers=True):
+        """bool Tracking::TrackLocalMap() (Tracking.cc:951-992) for the frame in `slot` of this store against the graph `covis` in one call (corb_track_local_map):
+        UpdateLocalMap, SearchLocalPoints, PoseOptimization and the tail, with mnVisible / mnFound and the tracking scratch written into the map-point records.
+        Returns a dict: ok (the reference's bool), kf_slots / mp_slots / mp_ids / local as TrackUpdateLocalMap, match (index into the local list per feature or -1),
+        outlier (mvbOutlier), n_in_view, n_matches, n_pose_inliers, n_matches_inliers, th_used, Tcw.  The caps default as TrackUpdateLocalMap's."""
+        n = max(load().corb_kf_store_count(self.h, slot), 0)          # (an empty slot is the call's to report)
+        prev = np.ascontiguousarray(prev_kf_slots, np.int32)
+        kf_cap = max(min(covis.M, 128), 83, len(prev)) if kf_cap is None else int(kf_cap)
+        mp_cap = min(covis.mp.capacity, kf_cap * covis.kf.F, 16384) if mp_cap is None else int(mp_cap)
+        ks = np.zeros(max(kf_cap, 1), np.int32); ms = np.zeros(max(mp_cap, 1), np.int32); ids = np.zeros(max(mp_cap, 1), np.uint64)
+        m = np.full(max(n, 1), -1, np.int32) if want_match else None; fl = np.zeros(max(n, 1), np.uint8) if want_outliers else None
+        a = np.ascontiguousarray(Tcw, np.float32).reshape(16)
+        par = TrackLocalMapParams(frame_id, last_reloc_frame_id, max_frames, sensor, int(bool(only_tracking)), log_scale_factor, nnratio, th); out = TrackLocalMapResult()
+        _chk(load().corb_track_local_map(covis.h, self.h, slot, C.byref(cam), _p(a), _p(prev) if len(prev) else None, len(prev), C.byref(par), _p(ks), kf_cap, _p(ms), _p(ids), mp_cap,
+                                         _p(m), _p(fl), C.byref(out)), "corb_track_local_map")
+        L = out.local
+        return dict(ok=bool(out.ok), kf_slots=ks[:L.n_kf].copy(), mp_slots=ms[:L.n_mp].copy(), mp_ids=ids[:L.n_mp].copy(), local=L, match=m[:n] if want_match else None,
+                    outlier=fl[:n].astype(bool) if want_outliers else None, n_in_view=out.n_in_view, n_matches=out.n_matches, n_pose_inliers=out.n_pose_inliers,
+                    n_matches_inliers=out.n_matches_inliers, th_used=out.th_used, Tcw=np.array(out.Tcw, np.float32).reshape(4, 4))
+
+    def TrackLocalMapStats(self, slot, mp_store, frame_id, last_reloc_frame_id=0, max_frames=30, sensor=1, only_tracking=False):
+        """The tail of TrackLocalMap (Tracking.cc:960-991) on a record TrackPoseOptimization(discard_outliers=False) has left (corb_track_local_map_stats): mnFound of
+        the inliers' points, the stereo outliers' points leave the frame; returns (mnMatchesInliers, the reference's bool)"""
+        cnt = C.c_int32(0); ok = C.c_int(0)
+        _chk(load().corb_track_local_map_stats(self.h, slot, mp_store.h, sensor, bool(only_tracking), frame_id, last_reloc_frame_id, max_frames, C.byref(cnt), C.byref(ok)),
+             "corb_track_local_map_stats")
+        return cnt.value, bool(ok.value)
 
     def SearchByProjectionScw(self, slot, mp_store, mp_slots, cam, Scw, log_scale_factor, matched_ids, th=10):
         """ORBmatcher::SearchByProjection(pKF, Scw, vpPoints, vpMatched, th) (ORBmatcher.cc:425-538) on records (corb_search_by_projection_scw_store): pKF = this store's `slot`,

@@ -4,12 +4,10 @@
 #include "track_internal.h"
 #include "record_call.h"
 #include "proj_host.h"
+#include "track_host.h"
 
 using namespace proj_host;
-
-void corb_pose_from_T(const float* T, double* out7);
-void corb_pose_to_T(const double* p7, float* T);
-void corb_pose_optimization_stages(CorbBAStage* st);
+using track_host::record_target;
 
 namespace {
 // A tracking call's opening (record_call.h): its argument checks, the device, the locks, and under them the counts and the id index
@@ -20,7 +18,7 @@ struct TrackCall : RecordCall {
     {
         if (!kf_ || !map_ || !cam || slot < 0 || slot >= kf_->capacity) { corb_set_error("%s: bad store / slot", who); return CORB_ERR_ARG; }
         if (kf_->device != map_->device) { corb_set_error("%s: the stores live on different devices", who); return CORB_ERR_ARG; }
-        if (cam->nlevels < 1 || cam->nlevels > CORB_MAX_LEVELS || !(cam->max_x > cam->min_x) || !(cam->max_y > cam->min_y)) { corb_set_error("%s: bad camera", who); return CORB_ERR_ARG; }
+        if (!track_host::camera_ok(cam)) { corb_set_error("%s: bad camera", who); return CORB_ERR_ARG; }
         if (!args_ok || (kf2_ && (slot2 < 0 || slot2 >= kf2_->capacity || kf2_->device != kf_->device || (kf2_ == kf_ && slot2 == slot)))) { corb_set_error("%s: bad argument", who); return CORB_ERR_ARG; }
         int rc = corb_select_device(kf_->device); if (rc) return rc;
         hold(nullptr, kf_, kf2_, map_);
@@ -35,15 +33,6 @@ int check_mp_slots(const char* who, const CorbMpStore* map, const int32_t* mp_sl
 {
     if (map && mp_slots) for (int i = 0; i < n_points; i++) if (mp_slots[i] < 0 || mp_slots[i] >= map->capacity) { corb_set_error("%s: map-point slot out of range", who); return CORB_ERR_ARG; }
     return CORB_OK;
-}
-// the target image of a matcher is a record: grid and level tables from the camera (mvInvLevelSigma2 = 1 / mvLevelSigma2, ORBextractor.cc:418-430), arrays of the record
-void record_target(CorbProjDev& d, const CorbTrackCamera* cam, const char* rec, const RecLayout& L, int n, int nq)
-{
-    const float bounds[4] = {cam->min_x, cam->min_y, cam->max_x, cam->max_y};
-    float inv_sigma2[CORB_MAX_LEVELS];
-    for (int l = 0; l < cam->nlevels; l++) inv_sigma2[l] = 1.0f / (cam->scale[l] * cam->scale[l]);
-    proj_grid(d, n, nq, bounds, cam->scale, inv_sigma2, cam->nlevels);
-    d.keys = reinterpret_cast<const CorbKeyPoint*>(rec + L.kp); d.u_right = reinterpret_cast<const float*>(rec + L.ur); d.desc = reinterpret_cast<const unsigned long long*>(rec + L.desc);
 }
 CorbProjTf tf_of(const CorbTrackCamera* cam, float log_scale_factor, float th) { return tf_intrinsics(cam->fx, cam->fy, cam->cx, cam->cy, cam->bf, log_scale_factor, th, cam->nlevels); }
 }  // namespace
@@ -111,33 +100,15 @@ extern "C" int corb_track_pose_optimization(CorbKfStore* frames, int slot, CorbM
     CorbScratch pool(0);
     TrackPoseDev t; memset(&t, 0, sizeof(t));
     t.cur = frames->rec(slot); t.F = frames->F; t.n_cur = n; t.mp_base = map->base(); t.mp_bytes = map->L.bytes; t.idt = map->idt;
-    double *dpose, *dcam, *dlast; unsigned char* dact; int* dcnt;
-    HIPCHK(pool.alloc(&t.edge_off, 2)); HIPCHK(pool.alloc(&t.stage_limit, 1)); HIPCHK(pool.alloc(&t.pt, (size_t)3 * n)); HIPCHK(pool.alloc(&t.obs, (size_t)3 * n)); HIPCHK(pool.alloc(&t.w, (size_t)n));
-    HIPCHK(pool.alloc(&t.dim, (size_t)n)); HIPCHK(pool.alloc(&t.efeat, (size_t)n)); HIPCHK(pool.alloc(&dlast, (size_t)n)); HIPCHK(pool.alloc(&dact, (size_t)n)); HIPCHK(pool.alloc(&dcnt, 4));
-    double h[12]; corb_pose_from_T(Tcw_in, h);
-    h[7] = cam->fx; h[8] = cam->fy; h[9] = cam->cx; h[10] = cam->cy; h[11] = cam->bf;
-    HIPCHK(pool.upload_block({{(void**)&dpose, h, sizeof(h)}}));
-    dcam = dpose + 7;
-    track_launch_pose_gather(t, pool.stream);
-    CorbPoseDev d; memset(&d, 0, sizeof(d));
-    d.n_problems = 1; d.n_stages = 4; corb_pose_optimization_stages(d.stages);
-    d.edge_off = t.edge_off; d.pt = t.pt; d.obs = t.obs; d.w = t.w; d.dim = t.dim; d.cam = dcam; d.pose = dpose; d.last_chi2 = dlast; d.active = dact; d.counters = dcnt;
-    d.stage_limit = t.stage_limit;                      // the edge count is on the device: the gather kernel turns it into the reference's early exits
-    pose_launch_optimize(d, n, pool.stream);
-    t.active = dact; t.pose = dpose; t.counters = dcnt; t.discard = discard_outliers ? 1 : 0;
-    struct Res { double pose[7]; int cnt[4]; int E[2]; };           // (the finish kernel packs it: one copy instead of three)
-    static_assert(sizeof(Res) == 80, "pose | counters | edge counts");
-    double* dres; HIPCHK(pool.alloc(&dres, 10)); t.result = dres;
-    if (outlier) HIPCHK(pool.alloc(&t.rejected, (size_t)n));
-    track_launch_pose_finish(t, pool.stream);
-    HIPCHK(hipGetLastError());
-    Res* r = static_cast<Res*>(pool.pinned());
-    HIPCHK(hipMemcpyAsync(r, dres, sizeof(Res), hipMemcpyDeviceToHost, pool.stream));
+    t.discard = discard_outliers ? 1 : 0;
+    rc = track_host::pose_enqueue(pool, t, cam, Tcw_in, outlier != nullptr, nullptr); if (rc) return rc;
+    track_host::PoseResult* r = static_cast<track_host::PoseResult*>(pool.pinned());
+    HIPCHK(hipMemcpyAsync(r, t.result, sizeof(*r), hipMemcpyDeviceToHost, pool.stream));
     std::vector<unsigned char> fl;
     if (outlier) { fl.resize((size_t)n); HIPCHK(pool.d2h(fl.data(), t.rejected, (size_t)n)); }
     HIPCHK(pool.fetch_finish());
     if (r->cnt[2]) corb_pose_to_T(r->pose, Tcw_out);
-    if (n_inliers) *n_inliers = r->E[1] < 3 ? 0 : r->cnt[3];          // `if(nInitialCorrespondences<3) return 0;`
+    if (n_inliers) *n_inliers = track_host::pose_inliers(*r);
     // (the features THIS call rejected, whether or not a discard then clears their mvbOutlier; a feature that an earlier call discarded carries no edge and is not one)
     if (outlier) memcpy(outlier, fl.data(), (size_t)n);
     return CORB_OK;

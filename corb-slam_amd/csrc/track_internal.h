@@ -35,6 +35,8 @@ struct TrackPoseDev {
     int discard;                                         // outliers lose their MapPoint (TrackWithMotionModel / TrackLocalMap's "Discard outliers")
     unsigned char* rejected;                             // [n_cur] or NULL: 1 for the features whose edge this call rejected (a feature discarded by an earlier call is not one)
     double* result;                                      // [10] what the host reads, as one block (one copy): pose[7] | counters[4] and edge_off[2] as six ints
+    const int* skip;                                     // NULL, or [2] words on the device (corb_track_local_map: the status / fail of its LocalMapHead): the finish
+                                                         // kernel writes nothing when either is set
 };
 // one edge per feature that holds a usable MapPoint, in feature order (Optimizer.cc:300-366); edge_off[1] = their number
 void track_launch_pose_gather(const TrackPoseDev& t, hipStream_t s);

@@ -1,6 +1,7 @@
 // track_kernels.hip -- gathers / scatters between store records and the flat views of the projection matcher and the single-pose optimiser
 // (Tracking::TrackWithMotionModel, C/src/Tracking.cc:868-940: SearchByProjection(CurrentFrame, LastFrame, th, mono) -> PoseOptimization(&CurrentFrame)).
 #include "track_internal.h"
+#include "track_device.h"
 #include "ba_math.h"
 
 __global__ __launch_bounds__(256) void track_index_kernel(const char* mp_base, size_t mp_bytes, int first, int n, CorbIdTable idt, int* dup)
@@ -13,20 +14,6 @@ __global__ __launch_bounds__(256) void track_index_kernel(const char* mp_base, s
 void track_launch_index_store(const char* mp_base, size_t mp_bytes, int first, int n, CorbIdTable idt, int* dup, hipStream_t s)
 {
     if (n > 0) hipLaunchKernelGGL(track_index_kernel, dim3((n + 255) / 256), dim3(256), 0, s, mp_base, mp_bytes, first, n, idt, dup);
-}
-
-__device__ __forceinline__ const CorbMapPointRecord* track_find_mp(const char* mp_base, size_t mp_bytes, const CorbIdTable& idt, unsigned long long id)
-{
-    if (id == CORB_NO_MAP_POINT) return nullptr;
-    const int slot = corb_idtab_find(idt, id);
-    return slot < 0 ? nullptr : reinterpret_cast<const CorbMapPointRecord*>(mp_base + (size_t)slot * mp_bytes);
-}
-
-// the MapPoint id a feature HOLDS (discarded ones hold none)
-__device__ __forceinline__ unsigned long long track_held_id(const char* rec, const RecLayout& L, int i)
-{
-    const unsigned char fl = reinterpret_cast<const unsigned char*>(rec + L.flags)[i];
-    return (fl & CORB_FEATURE_DISCARDED) ? CORB_NO_MAP_POINT : reinterpret_cast<const unsigned long long*>(rec + L.mp_id)[i];
 }
 
 __global__ __launch_bounds__(256) void track_prepare_last_kernel(TrackDev t)
@@ -123,6 +110,7 @@ __global__ __launch_bounds__(256) void track_pose_finish_kernel(TrackPoseDev t) 
     const RecLayout L(t.F);
     unsigned char* fl = reinterpret_cast<unsigned char*>(t.cur + L.flags);
     const int E = t.edge_off[1];
+    if (t.skip && (t.skip[0] | t.skip[1])) return;                                                        // (uniform) the chain's earlier step failed: the record stays as it is
     for (int i = threadIdx.x; i < t.n_cur; i += 256) { fl[i] &= (unsigned char)~CORB_FEATURE_OUTLIER; if (t.rejected) t.rejected[i] = 0; }       // mvbOutlier[i] = false where no edge says otherwise
     __syncthreads();
     // (one edge per feature: own byte)  discard: mvpMapPoints[i] = NULL, mvbOutlier[i] = false, pMP->mnLastFrameSeen = this frame (Tracking.cc:927-936)
@@ -160,7 +148,7 @@ __global__ __launch_bounds__(256) void track_local_frame_kernel(TrackLocalDev t)
     }
     t.claimed[i] = cl;
 }
-// (3x3 products = cv::gemm on CV_32F: double accumulation, one rounding; cv::norm / Mat::dot = double sums; PredictScale's log as in proj_kernels.hip)
+// Frame::isInFrustum(pMP, 0.5) of the local points the frame does not hold (track_device.h has the arithmetic)
 __global__ __launch_bounds__(256) void track_local_points_kernel(TrackLocalDev t)
 {
     const int q = blockIdx.x * 256 + threadIdx.x;
@@ -169,38 +157,11 @@ __global__ __launch_bounds__(256) void track_local_points_kernel(TrackLocalDev t
     unsigned long long dsc[4] = {0, 0, 0, 0};
     const unsigned long long id = t.ids[q];
     const CorbMapPointRecord* r = track_find_mp(t.mp_base, t.mp_bytes, t.idt, id);
-    if (r && !(r->flags & CORB_MP_BAD) && corb_idtab_find(t.inframe, id) < 0) {
-        const float* P = r->world_pos;
-        float Pc[3];
-#pragma unroll
-        for (int i = 0; i < 3; i++) {
-            const double s = __fma_rn((double)t.Tcw[i * 4 + 2], (double)P[2], __fma_rn((double)t.Tcw[i * 4 + 1], (double)P[1], __dmul_rn((double)t.Tcw[i * 4], (double)P[0])));
-            Pc[i] = (float)__dadd_rn(s, (double)t.Tcw[i * 4 + 3]);
-        }
-        if (Pc[2] > 0.0f) {
-            const float invz = __fdiv_rn(1.0f, Pc[2]);
-            const float u = __fadd_rn(__fmul_rn(__fmul_rn(t.fx, Pc[0]), invz), t.cx), v = __fadd_rn(__fmul_rn(__fmul_rn(t.fy, Pc[1]), invz), t.cy);
-            if (!(u < t.min_x || u > t.max_x || v < t.min_y || v > t.max_y)) {
-                const float maxD = __fmul_rn(1.2f, r->max_distance), minD = __fmul_rn(0.8f, r->min_distance);
-                const float PO[3] = { __fsub_rn(P[0], t.Ow[0]), __fsub_rn(P[1], t.Ow[1]), __fsub_rn(P[2], t.Ow[2]) };
-                const float dist = (float)sqrt(__fma_rn((double)PO[2], (double)PO[2], __fma_rn((double)PO[1], (double)PO[1], __dmul_rn((double)PO[0], (double)PO[0]))));
-                if (!(dist < minD || dist > maxD)) {
-                    const double dot = __fma_rn((double)PO[2], (double)r->normal[2], __fma_rn((double)PO[1], (double)r->normal[1], __dmul_rn((double)PO[0], (double)r->normal[0])));
-                    const float viewCos = (float)__ddiv_rn(dot, (double)dist);
-                    if (!(viewCos < t.cos_limit)) {
-                        const float ratio = __fdiv_rn(r->max_distance, dist);
-                        const float lg = (float)log((double)ratio);
-                        int lvl = (int)ceilf(__fdiv_rn(lg, t.log_scale));
-                        if (lvl < 0) lvl = 0; else if (lvl >= t.nlevels) lvl = t.nlevels - 1;
-                        o.proj_x = u; o.proj_y = v; o.proj_xr = __fsub_rn(u, __fmul_rn(t.bf, invz)); o.view_cos = viewCos; o.level = lvl;
-                        o.valid = 1; o.claims = r->n_obs > 0 ? 1 : 0;
-                        const unsigned long long* dp = reinterpret_cast<const unsigned long long*>(r->descriptor);
-                        dsc[0] = dp[0]; dsc[1] = dp[1]; dsc[2] = dp[2]; dsc[3] = dp[3];
-                        atomicAdd(t.n_in_view, 1);
-                    }
-                }
-            }
-        }
+    if (r && !(r->flags & CORB_MP_BAD) && corb_idtab_find(t.inframe, id) < 0 && track_in_frustum(t, r, o) == 0) {
+        o.valid = 1; o.claims = r->n_obs > 0 ? 1 : 0;
+        const unsigned long long* dp = reinterpret_cast<const unsigned long long*>(r->descriptor);
+        dsc[0] = dp[0]; dsc[1] = dp[1]; dsc[2] = dp[2]; dsc[3] = dp[3];
+        atomicAdd(t.n_in_view, 1);
     }
     t.tracked[q] = o;
 #pragma unroll

@@ -863,6 +863,28 @@ template <class Frame, class MapPoint, class Mat> struct FrameStoreT {
         if (nToMatch) *nToMatch = nv;
         return n;
     }
+    // bool Tracking::TrackLocalMap() (Tracking.cc:951-992) for the Frame in `slot` of `store` in ONE call (corb_track_local_map): UpdateLocalMap, SearchLocalPoints,
+    // PoseOptimization and the tail; mnVisible / mnFound and the tracking fields of the MapPoints are written on their records.  The Tracking members the function
+    // reads travel in `tracking` (mSensor as System::eSensor's value, mbOnlyTracking, mnLastRelocFrameId, mMaxFrames).  The Frame receives the pose and mvbOutlier;
+    // ReadBackMapPoints brings mvpMapPoints over.  *pOut (optional): the lists, the matches and the counts (mnMatchesInliers = result.n_matches_inliers).
+    struct TrackingState { int mSensor = 1; bool mbOnlyTracking = false; uint64_t mnLastRelocFrameId = 0; int mMaxFrames = 30; };
+    static bool TrackLocalMap(CorbCovis* graph, CorbKfStore* store, int slot, Frame* pFrame, const TrackingState& tracking, const std::vector<int32_t>& prevKfSlots,
+                              int maxKeyFrames, int maxMapPoints, TrackLocalMapOutput* pOut = nullptr, float nnratio = 0.8f)
+    {
+        float Tin[16];
+        for (int r = 0; r < 4; r++) for (int c = 0; c < 4; c++) Tin[4 * r + c] = matf(pFrame->mTcw, r, c);
+        const CorbTrackCamera cam = Camera(*pFrame);
+        CorbTrackLocalMapParams p; std::memset(&p, 0, sizeof(p));
+        p.frame_id = (uint64_t)pFrame->mnId; p.last_reloc_frame_id = tracking.mnLastRelocFrameId; p.max_frames = tracking.mMaxFrames; p.sensor = tracking.mSensor;
+        p.only_tracking = tracking.mbOnlyTracking ? 1 : 0; p.log_scale_factor = pFrame->mfLogScaleFactor; p.nnratio = nnratio; p.th = 0.f;
+        TrackLocalMapOutput o = corb::TrackLocalMap(graph, store, slot, cam, Tin, prevKfSlots, p, maxKeyFrames, maxMapPoints);
+        pFrame->SetPose(MatFactory<Mat>::from_floats(4, 4, o.result.Tcw));
+        pFrame->mvbOutlier.assign(pFrame->N, false);
+        for (int i = 0; i < pFrame->N; i++) if (o.outlier[i]) pFrame->mvbOutlier[i] = true;
+        const bool ok = o.result.ok != 0;
+        if (pOut) *pOut = std::move(o);
+        return ok;
+    }
     // the record's mvpMapPoints -> the Frame (ids resolved through the caller's id -> MapPoint* map; features whose point was discarded hold none)
     template <class Lookup> static void ReadBackMapPoints(CorbKfStore* store, int slot, Frame* pFrame, const Lookup& byId)
     {

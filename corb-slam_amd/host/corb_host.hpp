@@ -15,8 +15,10 @@
 #include <corb_accel.h>
 #include <corb_stereo_rectify.h>
 #include <corb_map_fusion.h>
+#include <corb_track_local_map.h>
 #include <algorithm>
 #include <cstdint>
+#include <cstring>
 #include <stdexcept>
 #include <string>
 #include <utility>
@@ -538,5 +540,30 @@ inline FusionCandidates MapFusionCandidates(CorbKfDb* db, CorbKfStore* sub, cons
           "corb_map_fusion_candidates_store");
     o.rows.resize((size_t)nRows); o.ids.resize((size_t)nIds);
     return o;
+}
+
+// ---- Tracking::TrackLocalMap on records (include/corb_track_local_map.h), mirrored as functions on the handles like the three above ----
+// what the one call leaves: the lists as slots and ids, the matches into the list, mvbOutlier, and the result struct (ok = the reference's bool)
+struct TrackLocalMapOutput { std::vector<int32_t> kfSlots, mpSlots, match; std::vector<uint64_t> mpIds; std::vector<uint8_t> outlier; CorbTrackLocalMapResult result; };
+inline TrackLocalMapOutput TrackLocalMap(CorbCovis* graph, CorbKfStore* frames, int slot, const CorbTrackCamera& cam, const float* Tcw /* 16 */, const std::vector<int32_t>& prevKfSlots,
+                                         const CorbTrackLocalMapParams& params, int maxKeyFrames, int maxMapPoints)
+{
+    TrackLocalMapOutput o; std::memset(&o.result, 0, sizeof(o.result));
+    const int n = std::max(corb_kf_store_count(frames, slot), 0);
+    o.kfSlots.resize((size_t)std::max(maxKeyFrames, 1)); o.mpSlots.resize((size_t)std::max(maxMapPoints, 1)); o.mpIds.resize((size_t)std::max(maxMapPoints, 1));
+    o.match.assign((size_t)std::max(n, 1), -1); o.outlier.assign((size_t)std::max(n, 1), 0);
+    check(corb_track_local_map(graph, frames, slot, &cam, Tcw, prevKfSlots.data(), (int)prevKfSlots.size(), &params, o.kfSlots.data(), maxKeyFrames, o.mpSlots.data(), o.mpIds.data(),
+                               maxMapPoints, o.match.data(), o.outlier.data(), &o.result), "corb_track_local_map");
+    o.kfSlots.resize((size_t)o.result.local.n_kf); o.mpSlots.resize((size_t)o.result.local.n_mp); o.mpIds.resize((size_t)o.result.local.n_mp);
+    o.match.resize((size_t)n); o.outlier.resize((size_t)n);
+    return o;
+}
+// the tail alone, after corb_track_pose_optimization(discard_outliers = 0): returns the reference's bool, *nMatchesInliers = mnMatchesInliers
+inline bool TrackLocalMapStats(CorbKfStore* frames, int slot, CorbMpStore* map, int sensor, bool onlyTracking, uint64_t frameId, uint64_t lastRelocFrameId, int maxFrames, int* nMatchesInliers = nullptr)
+{
+    int32_t n = 0; int ok = 0;
+    check(corb_track_local_map_stats(frames, slot, map, sensor, onlyTracking ? 1 : 0, frameId, lastRelocFrameId, maxFrames, &n, &ok), "corb_track_local_map_stats");
+    if (nMatchesInliers) *nMatchesInliers = n;
+    return ok != 0;
 }
 }  // namespace corb
