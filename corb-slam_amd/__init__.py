@@ -6,6 +6,7 @@ from tests/, bench.py and __graft_entry__.py.  It has two layers:
                per exported function, and bind() that puts the prototypes onto an opened library
   _abi_fusion.py  the same for the seventh header, include/corb_map_fusion.h, as a table of its own (bind_fusion())
   _abi_tracklocal.py  the same for the eighth header, include/corb_track_local_map.h (bind_tracklocal())
+  _abi_trackframe.py  the same for the ninth header, include/corb_track_frame.h (bind_trackframe())
   __init__.py  (this file) load(), the handle owner, and the classes and functions that marshal numpy
                arrays into the calls -- about 1900 lines, most of them array marshalling
 Class / method names mirror the reference (ORBextractor::operator(), ORBmatcher::SearchByBoW /
@@ -20,6 +21,7 @@ import numpy as np
 from ._abi import *         # noqa: F401,F403 -- every name of the mirror, the underscore ones included (_abi.__all__)
 from ._abi_fusion import *  # noqa: F401,F403 -- include/corb_map_fusion.h: a table of its own beside the six headers' (see _abi_fusion.py)
 from ._abi_tracklocal import *  # noqa: F401,F403 -- include/corb_track_local_map.h: likewise (see _abi_tracklocal.py)
+from ._abi_trackframe import *  # noqa: F401,F403 -- include/corb_track_frame.h: likewise (see _abi_trackframe.py)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libcorb_accel.so")
@@ -41,7 +43,7 @@ def load():
         if not os.path.exists(LIB_PATH):
             raise CorbError("libcorb_accel.so is not built (run `python -c 'import __graft_entry__ as g; g.build()'`); "
                             "there is no CPU fallback")
-        _lib = bind_tracklocal(bind_fusion(bind(C.CDLL(LIB_PATH))))
+        _lib = bind_trackframe(bind_tracklocal(bind_fusion(bind(C.CDLL(LIB_PATH)))))
     return _lib
 
 
@@ -1533,6 +1535,47 @@ class KeyFrameStore(_Handle):
         _chk(load().corb_track_local_map_stats(self.h, slot, mp_store.h, sensor, bool(only_tracking), frame_id, last_reloc_frame_id, max_frames, C.byref(cnt), C.byref(ok)),
              "corb_track_local_map_stats")
         return cnt.value, bool(ok.value)
+
+    def _track_frame_result(self, out, n, m, fl):
+        T = lambda a: np.array(a, np.float32).reshape(4, 4)
+        return dict(ok=bool(out.ok), vo=bool(out.vo), n_matches_first=out.n_matches_first, searched_wide=bool(out.searched_wide), n_matches=out.n_matches, th_used=out.th_used,
+                    n_pose_inliers=out.n_pose_inliers, n_matches_kept=out.n_matches_kept, n_matches_map=out.n_matches_map, Tlw=T(out.Tlw), Tcw_pred=T(out.Tcw_pred), Tcw=T(out.Tcw),
+                    match=None if m is None else m[:n], outlier=None if fl is None else fl[:n].astype(bool))
+
+    def TrackWithMotionModel(self, cur_slot, last_slot, kf_store, ref_slot, mp_store, cam, velocity, frame_id, Tlr=None, sensor=1, only_tracking=False, check_replaced=False,
+                             nnratio=0.9, check_orientation=True, th=0.0, want_match=True, want_outliers=True):
+        """bool Tracking::TrackWithMotionModel() (Tracking.cc:886-949) in one call (corb_track_with_motion_model): CheckReplacedInLastFrame when asked, UpdateLastFrame's
+        pose from Tlr and the reference keyframe's record (ref_slot of kf_store) when Tlr is given, SetPose(velocity * Tlw), the fill, SearchByProjection at th and --
+        decided on the device -- at 2 th, PoseOptimization, the "Discard outliers" loop with its writes into the map points.  Returns a dict: ok (the reference's bool),
+        vo (mbVO), n_matches_first, searched_wide, n_matches, th_used, n_pose_inliers, n_matches_kept, n_matches_map, Tlw, Tcw_pred, Tcw, match (the last frame's
+        feature per feature, or -1), outlier (the features the optimisation rejected)."""
+        n = max(load().corb_kf_store_count(self.h, cur_slot), 0)          # (an empty slot is the call's to report)
+        m = np.full(max(n, 1), -1, np.int32) if want_match else None; fl = np.zeros(max(n, 1), np.uint8) if want_outliers else None
+        v = np.ascontiguousarray(velocity, np.float32).reshape(16); r = None if Tlr is None else np.ascontiguousarray(Tlr, np.float32).reshape(16)
+        par = TrackFrameParams(frame_id, sensor, int(bool(only_tracking)), int(bool(check_replaced)), int(bool(check_orientation)), nnratio, th); out = TrackFrameResult()
+        _chk(load().corb_track_with_motion_model(self.h, cur_slot, last_slot, kf_store.h, ref_slot, mp_store.h, C.byref(cam), _p(v), _p(r), C.byref(par), _p(m), _p(fl), C.byref(out)),
+             "corb_track_with_motion_model")
+        return self._track_frame_result(out, n, m, fl)
+
+    def TrackReferenceKeyFrame(self, cur_slot, last_slot, kf_store, ref_slot, mp_store, cam, frame_id, voc=None, sensor=1, check_replaced=False, nnratio=0.7,
+                               check_orientation=True, want_match=True, want_outliers=True):
+        """bool Tracking::TrackReferenceKeyFrame() (Tracking.cc:775-817) in one call (corb_track_reference_keyframe): ComputeBoW when `voc` is given and the record has no
+        FeatureVector, SearchByBoW against the reference keyframe (ref_slot of kf_store) with the validity of its features taken from the map, and from 15 matches on
+        setMapPointMatches, SetPose(the last record's pose), PoseOptimization and the "Discard outliers" loop.  The dict of TrackWithMotionModel; match = the keyframe's
+        feature per feature, or -1."""
+        n = max(load().corb_kf_store_count(self.h, cur_slot), 0)
+        m = np.full(max(n, 1), -1, np.int32) if want_match else None; fl = np.zeros(max(n, 1), np.uint8) if want_outliers else None
+        par = TrackFrameParams(frame_id, sensor, 0, int(bool(check_replaced)), int(bool(check_orientation)), nnratio, 0.0); out = TrackFrameResult()
+        _chk(load().corb_track_reference_keyframe(self.h, cur_slot, last_slot, kf_store.h, ref_slot, mp_store.h, C.byref(cam), voc.h if voc is not None else None, C.byref(par),
+                                                  _p(m), _p(fl), C.byref(out)), "corb_track_reference_keyframe")
+        return self._track_frame_result(out, n, m, fl)
+
+    def TrackFrameFinish(self, cur_slot, kf_store, ref_slot, mp_store, stage):
+        """The per-feature loops at the end of Tracking::Track (corb_track_frame_finish).  stage 0: "Clean VO matches" (Tracking.cc:438-447), asynchronous, returns None.
+        stage 1: the outliers' points leave the frame (:463-467); returns Tcr = Tcw * GetPoseInverse(reference keyframe) (:491), what the next frame passes as Tlr."""
+        Tcr = np.zeros(16, np.float32) if stage else None
+        _chk(load().corb_track_frame_finish(self.h, cur_slot, kf_store.h, ref_slot, mp_store.h, stage, _p(Tcr)), "corb_track_frame_finish")
+        return Tcr.reshape(4, 4) if stage else None
 
     def SearchByProjectionScw(self, slot, mp_store, mp_slots, cam, Scw, log_scale_factor, matched_ids, th=10):
         """ORBmatcher::SearchByProjection(pKF, Scw, vpPoints, vpMatched, th) (ORBmatcher.cc:425-538) on records (corb_search_by_projection_scw_store): pKF = this store's `slot`,

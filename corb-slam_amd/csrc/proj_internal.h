@@ -49,8 +49,13 @@ struct CorbProjDev {
     int* match; int* n_matches; int* status;
     int* best_idx; int* best_dist;    // [nq] independent best candidate per query (Fuse, SearchBySim3)
     int cand_cap;                     // candidates kept per query: 0 = PROJ_CAND_CAP (every matcher but SearchForInitialization, whose windows are 100 px wide)
+    const int* gate; int gate_below;  // gate NULL, or a count on the device (corb_track_with_motion_model's wide search reads the first search's matches): the query
+                                      // preparation, the candidate and the resolve kernels return at once unless *gate < gate_below, and write nothing
 };
 
 void corb_launch_projection_points(const CorbProjDev& d, const CorbMapPointView* pts, const CorbProjTf& tf, int greedy, hipStream_t s);
 void corb_launch_search_for_initialization(const CorbProjDev& d, const CorbKeyPoint* keys1, float* prev_matched, float window, hipStream_t s);
 void corb_launch_projection(const CorbProjDev& d, const CorbTrackedPoint* mp, const CorbLastPoint* last, const CorbProjPose* pose, float th, hipStream_t s);
+// SearchByProjection(Frame, Frame) inside a chain: the pose block is read from device memory (an earlier kernel of the stream wrote it); with_grid = 0 when an earlier
+// launch on the same target has left feat_cell / cell_off / cell_idx where d points; d.gate as above
+void corb_launch_projection_frame_dev(const CorbProjDev& d, const CorbLastPoint* last, const CorbProjPose* dev_pose, float th, int with_grid, hipStream_t s);

@@ -70,13 +70,11 @@ __global__ __launch_bounds__(256) void proj_prepare_map_kernel(CorbProjDev d, co
     d.query[q] = o;
 }
 
-// query preparation, SearchByProjection(Frame, Frame): project the last frame's map points into the current frame
-__global__ __launch_bounds__(256) void proj_prepare_frame_kernel(CorbProjDev d, const CorbLastPoint* last, CorbProjPose pose, float th)
+// query preparation, SearchByProjection(Frame, Frame): project the last frame's map points into the current frame (stated once: the pose comes as a kernel
+// argument in the separate call and from device memory in a chain)
+__device__ __forceinline__ CorbProjQuery proj_frame_query(const CorbProjDev& d, const CorbLastPoint& p, const CorbProjPose& pose, float th)
 {
-    const int q = blockIdx.x * 256 + threadIdx.x;
-    if (q >= d.nq) return;
-    const CorbLastPoint p = last[q];
-    CorbProjQuery o; o.valid = 0; o.claims = p.claims; o.angle = p.angle; o.x = o.y = o.r = o.ur_ref = 0.f; o.min_level = o.max_level = 0;
+    CorbProjQuery o; o.valid = 0; o.claims = p.claims; o.angle = p.angle; o.x = o.y = o.r = o.ur_ref = 0.f; o.min_level = o.max_level = 0; o.pad[0] = o.pad[1] = 0;
     if (p.valid) {
         float x3[3];
 #pragma unroll
@@ -97,7 +95,20 @@ __global__ __launch_bounds__(256) void proj_prepare_frame_kernel(CorbProjDev d, 
             }
         }
     }
-    d.query[q] = o;
+    return o;
+}
+__global__ __launch_bounds__(256) void proj_prepare_frame_kernel(CorbProjDev d, const CorbLastPoint* last, CorbProjPose pose, float th)
+{
+    const int q = blockIdx.x * 256 + threadIdx.x;
+    if (q >= d.nq) return;
+    d.query[q] = proj_frame_query(d, last[q], pose, th);
+}
+__global__ __launch_bounds__(256) void proj_prepare_frame_dev_kernel(CorbProjDev d, const CorbLastPoint* last, const CorbProjPose* dev_pose, float th)
+{
+    const int q = blockIdx.x * 256 + threadIdx.x;
+    if (q >= d.nq || (d.gate && *d.gate >= d.gate_below)) return;
+    const CorbProjPose pose = *dev_pose;
+    d.query[q] = proj_frame_query(d, last[q], pose, th);
 }
 
 // GetFeaturesInArea + DescriptorDistance for every candidate of a query (one wavefront per query).  Lanes sweep the cells of
@@ -105,7 +116,7 @@ __global__ __launch_bounds__(256) void proj_prepare_frame_kernel(CorbProjDev d, 
 __global__ __launch_bounds__(256) void proj_candidates_kernel(CorbProjDev d)
 {
     const int q = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (q >= d.nq) return;
+    if (q >= d.nq || (d.gate && *d.gate >= d.gate_below)) return;
     const CorbProjQuery Q = d.query[q];
     const int cap = d.cand_cap ? d.cand_cap : PROJ_CAND_CAP;
     int total = 0;
@@ -162,6 +173,7 @@ __global__ __launch_bounds__(1024) void proj_resolve_kernel(CorbProjDev d)
     unsigned char* fin = claimed + ((d.n + 3) & ~3);      // [nq]
     __shared__ int remaining, nmatches, hist[CORB_HISTO_LENGTH], ind[3];
     const int tid = threadIdx.x;
+    if (d.gate && *d.gate >= d.gate_below) return;                   // (uniform) a chain's search that is not taken: nothing is read or written
     for (int f = tid; f < d.n; f += 1024) { match[f] = -1; claimed[f] = d.claimed[f]; }
     for (int q = tid; q < d.nq; q += 1024) { fin[q] = (!d.query[q].valid || d.cand_cnt[q] == 0) ? 1 : 0; d.ev_feat[q] = -1; }
     if (tid < CORB_HISTO_LENGTH) hist[tid] = 0;
@@ -520,6 +532,17 @@ void corb_launch_projection(const CorbProjDev& d, const CorbTrackedPoint* mp, co
     if (d.nq > 0) {
         if (mp) hipLaunchKernelGGL(proj_prepare_map_kernel, dim3((d.nq + 255) / 256), dim3(256), 0, s, d, mp, th);
         else hipLaunchKernelGGL(proj_prepare_frame_kernel, dim3((d.nq + 255) / 256), dim3(256), 0, s, d, last, *pose, th);
+        hipLaunchKernelGGL(proj_candidates_kernel, dim3((d.nq + 3) / 4), dim3(256), 0, s, d);
+    }
+    const size_t lds = (size_t)d.n * 8 + ((d.n + 3) & ~3) + ((d.nq + 3) & ~3) + 16;
+    hipLaunchKernelGGL(proj_resolve_kernel, dim3(1), dim3(1024), lds, s, d);
+}
+
+void corb_launch_projection_frame_dev(const CorbProjDev& d, const CorbLastPoint* last, const CorbProjPose* dev_pose, float th, int with_grid, hipStream_t s)
+{
+    if (with_grid) hipLaunchKernelGGL(proj_grid_kernel, dim3(1), dim3(1024), 0, s, d);
+    if (d.nq > 0) {
+        hipLaunchKernelGGL(proj_prepare_frame_dev_kernel, dim3((d.nq + 255) / 256), dim3(256), 0, s, d, last, dev_pose, th);
         hipLaunchKernelGGL(proj_candidates_kernel, dim3((d.nq + 3) / 4), dim3(256), 0, s, d);
     }
     const size_t lds = (size_t)d.n * 8 + ((d.n + 3) & ~3) + ((d.nq + 3) & ~3) + 16;

@@ -30,17 +30,20 @@ inline int pose_inliers(const PoseResult& r) { return r.E[1] < 3 ? 0 : r.cnt[3];
 
 // Optimizer::PoseOptimization(Frame*) on the record t.cur, n = t.n_cur > 0 features, from Tcw_in: gather, the four rounds, finish, all on the pool's stream.  The
 // caller has set t.cur / F / n_cur / mp_base / mp_bytes / idt / discard (/ skip); result: where the finish kernel leaves a PoseResult, NULL = allocated here
-// (t.result either way); t.rejected is allocated when want_rejected
-inline int pose_enqueue(CorbScratch& pool, TrackPoseDev& t, const CorbTrackCamera* cam, const float* Tcw_in, bool want_rejected, double* result)
+// (t.result either way); t.rejected is allocated when want_rejected.  dev_Tcw: NULL, or the start pose as 16 floats on the device (a chain that computed it
+// there); Tcw_in is then not read
+inline int pose_enqueue(CorbScratch& pool, TrackPoseDev& t, const CorbTrackCamera* cam, const float* Tcw_in, bool want_rejected, double* result, const float* dev_Tcw = nullptr)
 {
     const int n = t.n_cur;
     double *dpose, *dcam, *dlast; unsigned char* dact; int* dcnt;
     HIPCHK(pool.alloc(&t.edge_off, 2)); HIPCHK(pool.alloc(&t.stage_limit, 1)); HIPCHK(pool.alloc(&t.pt, (size_t)3 * n)); HIPCHK(pool.alloc(&t.obs, (size_t)3 * n)); HIPCHK(pool.alloc(&t.w, (size_t)n));
     HIPCHK(pool.alloc(&t.dim, (size_t)n)); HIPCHK(pool.alloc(&t.efeat, (size_t)n)); HIPCHK(pool.alloc(&dlast, (size_t)n)); HIPCHK(pool.alloc(&dact, (size_t)n)); HIPCHK(pool.alloc(&dcnt, 4));
-    double h[12]; corb_pose_from_T(Tcw_in, h);
+    double h[12] = {0, 0, 0, 1, 0, 0, 0};
+    if (!dev_Tcw) corb_pose_from_T(Tcw_in, h);
     h[7] = cam->fx; h[8] = cam->fy; h[9] = cam->cx; h[10] = cam->cy; h[11] = cam->bf;
     HIPCHK(pool.upload_block({{(void**)&dpose, h, sizeof(h)}}));
     dcam = dpose + 7;
+    if (dev_Tcw) track_launch_pose_start(dev_Tcw, dpose, pool.stream);
     track_launch_pose_gather(t, pool.stream);
     CorbPoseDev d; memset(&d, 0, sizeof(d));
     d.n_problems = 1; d.n_stages = 4; corb_pose_optimization_stages(d.stages);

@@ -35,13 +35,16 @@ struct TrackPoseDev {
     int discard;                                         // outliers lose their MapPoint (TrackWithMotionModel / TrackLocalMap's "Discard outliers")
     unsigned char* rejected;                             // [n_cur] or NULL: 1 for the features whose edge this call rejected (a feature discarded by an earlier call is not one)
     double* result;                                      // [10] what the host reads, as one block (one copy): pose[7] | counters[4] and edge_off[2] as six ints
-    const int* skip;                                     // NULL, or [2] words on the device (corb_track_local_map: the status / fail of its LocalMapHead): the finish
-                                                         // kernel writes nothing when either is set
+    const int* skip;                                     // NULL, or [2] words on the device (corb_track_local_map: the status / fail of its LocalMapHead; the chains of
+                                                         // corb_track_frame.h: their `return false` before the optimisation): when either is set the gather kernel
+                                                         // leaves stage_limit = 0 and the finish kernel writes nothing
 };
 // one edge per feature that holds a usable MapPoint, in feature order (Optimizer.cc:300-366); edge_off[1] = their number
 void track_launch_pose_gather(const TrackPoseDev& t, hipStream_t s);
 // mvbOutlier -> record flags, the optimised pose -> the record's Tcw (when the graph had an active edge: counters[2])
 void track_launch_pose_finish(const TrackPoseDev& t, hipStream_t s);
+// Converter::toSE3Quat of a pose that lives on the device (a record's Tcw, 16 floats): pose7 <- corb_pose_from_T's value, operation for operation
+void track_launch_pose_start(const float* dev_Tcw, double* pose7, hipStream_t s);
 // id table of a map-point store: slots [first, first + n)
 void track_launch_index_store(const char* mp_base, size_t mp_bytes, int first, int n, CorbIdTable idt, int* dup, hipStream_t s);
 

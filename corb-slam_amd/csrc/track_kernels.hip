@@ -101,9 +101,34 @@ __global__ __launch_bounds__(1024) void track_pose_gather_kernel(TrackPoseDev t)
         if (tid == 0) { int tot = 0; for (int w = 0; w < 16; w++) tot += wsum[w]; base += tot; }
         __syncthreads();
     }
-    if (tid == 0) { t.edge_off[0] = 0; t.edge_off[1] = base; t.stage_limit[0] = base < 3 ? 0 : base < 10 ? 1 : 4; }
+    if (tid == 0) { t.edge_off[0] = 0; t.edge_off[1] = base; t.stage_limit[0] = (t.skip && (t.skip[0] | t.skip[1])) ? 0 : base < 3 ? 0 : base < 10 ? 1 : 4; }
 }
 void track_launch_pose_gather(const TrackPoseDev& t, hipStream_t s) { hipLaunchKernelGGL(track_pose_gather_kernel, dim3(1), dim3(1024), 0, s, t); }
+
+// corb_pose_from_T (corb_pose.cpp) on the device: Eigen::Quaterniond(Matrix3d) from the float entries widened to double, the sign and the normalisation, every
+// operation explicit and in the host's order (the host side is built without contraction)
+__global__ __launch_bounds__(64) void track_pose_start_kernel(const float* T, double* out7)
+{
+    if (threadIdx.x != 0) return;
+    const double R[9] = { (double)T[0], (double)T[1], (double)T[2], (double)T[4], (double)T[5], (double)T[6], (double)T[8], (double)T[9], (double)T[10] };
+    double q[4];
+    double t = __dadd_rn(__dadd_rn(R[0], R[4]), R[8]);
+    if (t > 0) {
+        t = __dsqrt_rn(__dadd_rn(t, 1.0)); q[3] = __dmul_rn(0.5, t); t = __ddiv_rn(0.5, t);
+        q[0] = __dmul_rn(__dsub_rn(R[7], R[5]), t); q[1] = __dmul_rn(__dsub_rn(R[2], R[6]), t); q[2] = __dmul_rn(__dsub_rn(R[3], R[1]), t);
+    } else {
+        int i = 0; if (R[4] > R[0]) i = 1; if (R[8] > R[i * 3 + i]) i = 2;
+        const int j = (i + 1) % 3, k = (j + 1) % 3;
+        t = __dsqrt_rn(__dadd_rn(__dsub_rn(__dsub_rn(R[i * 3 + i], R[j * 3 + j]), R[k * 3 + k]), 1.0));
+        q[i] = __dmul_rn(0.5, t); t = __ddiv_rn(0.5, t);
+        q[3] = __dmul_rn(__dsub_rn(R[k * 3 + j], R[j * 3 + k]), t); q[j] = __dmul_rn(__dadd_rn(R[j * 3 + i], R[i * 3 + j]), t); q[k] = __dmul_rn(__dadd_rn(R[k * 3 + i], R[i * 3 + k]), t);
+    }
+    if (q[3] < 0) { q[0] = -q[0]; q[1] = -q[1]; q[2] = -q[2]; q[3] = -q[3]; }
+    const double n = __dsqrt_rn(__dadd_rn(__dadd_rn(__dadd_rn(__dmul_rn(q[0], q[0]), __dmul_rn(q[1], q[1])), __dmul_rn(q[2], q[2])), __dmul_rn(q[3], q[3])));
+    out7[0] = __ddiv_rn(q[0], n); out7[1] = __ddiv_rn(q[1], n); out7[2] = __ddiv_rn(q[2], n); out7[3] = __ddiv_rn(q[3], n);
+    out7[4] = (double)T[3]; out7[5] = (double)T[7]; out7[6] = (double)T[11];
+}
+void track_launch_pose_start(const float* dev_Tcw, double* pose7, hipStream_t s) { hipLaunchKernelGGL(track_pose_start_kernel, dim3(1), dim3(64), 0, s, dev_Tcw, pose7); }
 
 __global__ __launch_bounds__(256) void track_pose_finish_kernel(TrackPoseDev t)          // ONE workgroup
 {

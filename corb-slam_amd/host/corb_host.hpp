@@ -16,6 +16,7 @@
 #include <corb_stereo_rectify.h>
 #include <corb_map_fusion.h>
 #include <corb_track_local_map.h>
+#include <corb_track_frame.h>
 #include <algorithm>
 #include <cstdint>
 #include <cstring>
@@ -565,5 +566,61 @@ inline bool TrackLocalMapStats(CorbKfStore* frames, int slot, CorbMpStore* map, 
     check(corb_track_local_map_stats(frames, slot, map, sensor, onlyTracking ? 1 : 0, frameId, lastRelocFrameId, maxFrames, &n, &ok), "corb_track_local_map_stats");
     if (nMatchesInliers) *nMatchesInliers = n;
     return ok != 0;
+}
+
+// ---- the initial pose of a tracked frame on records (include/corb_track_frame.h), mirrored as functions on the handles ----
+// what either call leaves: the matches (the last frame's / the keyframe's feature per feature, or -1), the features the optimisation rejected, the result struct
+struct TrackFrameOutput { std::vector<int32_t> match; std::vector<uint8_t> outlier; CorbTrackFrameResult result; };
+// bool Tracking::TrackWithMotionModel() (Tracking.cc:886-949); Tlr = the last entry of mlRelativeFramePoses (16 floats), or nullptr: the last record's pose stands
+inline TrackFrameOutput TrackWithMotionModel(CorbKfStore* frames, int curSlot, int lastSlot, CorbKfStore* kfs, int refSlot, CorbMpStore* map, const CorbTrackCamera& cam,
+                                             const float* velocity /* 16 */, const float* Tlr, const CorbTrackFrameParams& params)
+{
+    TrackFrameOutput o; std::memset(&o.result, 0, sizeof(o.result));
+    const int n = std::max(corb_kf_store_count(frames, curSlot), 0);
+    o.match.assign((size_t)std::max(n, 1), -1); o.outlier.assign((size_t)std::max(n, 1), 0);
+    check(corb_track_with_motion_model(frames, curSlot, lastSlot, kfs, refSlot, map, &cam, velocity, Tlr, &params, o.match.data(), o.outlier.data(), &o.result), "corb_track_with_motion_model");
+    o.match.resize((size_t)n); o.outlier.resize((size_t)n);
+    return o;
+}
+// bool Tracking::TrackReferenceKeyFrame() (Tracking.cc:775-817); voc = nullptr: the frame's record holds its FeatureVector already
+inline TrackFrameOutput TrackReferenceKeyFrame(CorbKfStore* frames, int curSlot, int lastSlot, CorbKfStore* kfs, int refSlot, CorbMpStore* map, const CorbTrackCamera& cam,
+                                               CorbVoc* voc, const CorbTrackFrameParams& params)
+{
+    TrackFrameOutput o; std::memset(&o.result, 0, sizeof(o.result));
+    const int n = std::max(corb_kf_store_count(frames, curSlot), 0);
+    o.match.assign((size_t)std::max(n, 1), -1); o.outlier.assign((size_t)std::max(n, 1), 0);
+    check(corb_track_reference_keyframe(frames, curSlot, lastSlot, kfs, refSlot, map, &cam, voc, &params, o.match.data(), o.outlier.data(), &o.result), "corb_track_reference_keyframe");
+    o.match.resize((size_t)n); o.outlier.resize((size_t)n);
+    return o;
+}
+// the host's choice of Tracking.cc:301-316 (mState == OK, local mapping active): TrackReferenceKeyFrame when there is no velocity (velocity == nullptr) or the frame
+// comes right after a relocalisation; otherwise TrackWithMotionModel, then TrackReferenceKeyFrame if it failed.  CheckReplacedInLastFrame (:304) runs once, in the
+// first call made.  *usedMotionModel (optional) = the call whose result is returned was TrackWithMotionModel
+inline TrackFrameOutput TrackInitialPose(CorbKfStore* frames, int curSlot, int lastSlot, CorbKfStore* kfs, int refSlot, CorbMpStore* map, const CorbTrackCamera& cam,
+                                         const float* velocity, const float* Tlr, CorbVoc* voc, uint64_t frameId, uint64_t lastRelocFrameId, int sensor, bool* usedMotionModel = nullptr)
+{
+    CorbTrackFrameParams p; std::memset(&p, 0, sizeof(p));
+    p.frame_id = frameId; p.sensor = sensor; p.only_tracking = 0; p.check_replaced = 1; p.check_orientation = 1;
+    const bool reference_first = !velocity || frameId < lastRelocFrameId + 2;        // if(mVelocity.empty() || mCurrentFrame.mnId<mnLastRelocFrameId+2)
+    if (usedMotionModel) *usedMotionModel = !reference_first;
+    if (!reference_first) {
+        p.nnratio = 0.9f; p.th = 0.f;
+        TrackFrameOutput o = TrackWithMotionModel(frames, curSlot, lastSlot, kfs, refSlot, map, cam, velocity, Tlr, p);
+        if (o.result.ok) return o;
+        p.check_replaced = 0;
+        if (usedMotionModel) *usedMotionModel = false;
+    }
+    p.nnratio = 0.7f; p.th = 0.f;
+    return TrackReferenceKeyFrame(frames, curSlot, lastSlot, kfs, refSlot, map, cam, voc, p);
+}
+// the loops at the end of Tracking::Track: "Clean VO matches" (:438-447), asynchronous; then, after NeedNewKeyFrame / CreateNewKeyFrame, the outliers' points leave
+// the frame (:463-467) and Tcr = mTcw * mpReferenceKF->GetPoseInverse() (:491) comes back: the next frame's Tlr
+inline void CleanVOMatches(CorbKfStore* frames, int curSlot, CorbKfStore* kfs, int refSlot, CorbMpStore* map)
+{
+    check(corb_track_frame_finish(frames, curSlot, kfs, refSlot, map, 0, nullptr), "corb_track_frame_finish");
+}
+inline void TrackFrameFinish(CorbKfStore* frames, int curSlot, CorbKfStore* kfs, int refSlot, CorbMpStore* map, float* Tcr /* 16 */)
+{
+    check(corb_track_frame_finish(frames, curSlot, kfs, refSlot, map, 1, Tcr), "corb_track_frame_finish");
 }
 }  // namespace corb
