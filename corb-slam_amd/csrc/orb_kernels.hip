@@ -12,6 +12,7 @@
 // (__fmul_rn/__fadd_rn/...), so results do not depend on compiler contraction.
 #include "corb_internal.h"
 #include "lane_exchange.h"
+#include "orb_fast_tile.h"
 #include <atomic>
 #include <cstring>
 #include <cstdlib>
@@ -329,20 +330,13 @@ __global__ __launch_bounds__(PYR_T, 8) void orb_pyramid_kernel(const CorbOrbPara
 // ---- packed FAST-9/16 ----
 // score(p) = max( max_arcs min_arc(ring) - p , p - min_arcs max_arc(ring) ) - 1   (cv::FAST cornerScore: the centre is a
 // monotone shift, so the 9-of-16 sliding min/max run on the raw ring bytes).  Two horizontally adjacent pixels are
-// processed per 32-bit register: ring bytes are gathered from the tile dwords with v_perm_b32 into the two 16-bit
-// halves [b,0 | b',0] and reduced with gfx950's packed 3-input v_pk_minimum3_f16 / v_pk_maximum3_f16 -- the halves
+// processed per 32-bit register: the LDS tile keeps a pixel per 16-bit slot, so a tile dword already holds the two 16-bit
+// halves [b,0 | b',0] once its score bytes are masked off (orb_fast_kernel below); they are reduced with gfx950's packed 3-input v_pk_minimum3_f16 / v_pk_maximum3_f16 -- the halves
 // 0x0000..0x00ff are non-negative f16 denormals (kernel FP mode keeps f16 denormals), whose order is the integer order.
 __device__ __forceinline__ uint32_t pk_min3(uint32_t a, uint32_t b, uint32_t c)
 { uint32_t d; asm("v_pk_minimum3_f16 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "v"(c)); return d; }
 __device__ __forceinline__ uint32_t pk_max3(uint32_t a, uint32_t b, uint32_t c)
 { uint32_t d; asm("v_pk_maximum3_f16 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "v"(c)); return d; }
-// bytes K, K+1 of the 12-byte window {w[0], w[1], w[2]} -> [b_K, 0, b_K+1, 0]   (K compile-time, 0..10)
-template <int K> __device__ __forceinline__ uint32_t pk_pair(const uint32_t (&w)[3])
-{
-    static_assert(K >= 0 && K <= 10, "window");
-    if constexpr (K <= 6) return __builtin_amdgcn_perm(w[1], w[0], 0x0c000c00u | (uint32_t)K | ((uint32_t)(K + 1) << 16));
-    else return __builtin_amdgcn_perm(w[2], w[1], 0x0c000c00u | (uint32_t)(K - 4) | ((uint32_t)(K - 3) << 16));
-}
 typedef short corb_short2 __attribute__((ext_vector_type(2)));
 
 // The 9-of-16 sliding chain of one polarity on packed ring values v[i] = [ring_i(A), 0 | ring_i(B), 0]: 16 3-windows, 16 9-windows, the reduction
@@ -361,7 +355,7 @@ template <bool BRIGHT> __device__ __forceinline__ uint32_t fast_arc_chain(const 
     return out3(out3(r5[0], r5[1], r5[2]), out3(r5[3], r5[4], w9[15]), r5[0]);
 }
 
-// Scores of the two pixels J (= 0: window bytes 4,5; 1: bytes 6,7) of a 4-pixel group; R[dy+3] = window of row y+dy; 0 = below the threshold t.
+// Scores of the two pixels of a pair from its 16 packed ring values v[i] = [ring_i(A),0 | ring_i(B),0] (cv::FAST order) and centres cpk; 0 = below the threshold t.
 // cornerScore = max(B - c, c - D) - 1 with B = max_arcs min_arc(ring), D = min_arcs max_arc(ring).  Every arc of 9 holds two adjacent compass
 // points, so B <= m and D >= n of fast_compass: a side whose compass test fails at t stays below t and cannot be the score of a pixel that
 // scores >= t.  Nearly every listed pixel passes on one side only (both: 0.3 % of the passing pixels on the synthetic frames), and the dark
@@ -369,15 +363,8 @@ template <bool BRIGHT> __device__ __forceinline__ uint32_t fast_arc_chain(const 
 // that pass on the dark side only and ONE chain scores both halves.  When a half of any lane passes on both sides the wave also runs the dual
 // chain on the same values (wave-uniform branch) and takes the maximum, which is the two-sided score whatever the halves' masks are.
 // kb = t + 0x200, kd = 0x200 - t - 1 in both halves: the side tests as plain 32-bit adds whose halves stay in 1 .. 0x3fe (no borrow across).
-template <int J> __device__ __forceinline__ uint32_t fast_pair_score(const uint32_t (&R)[7][3], uint32_t th2, uint32_t kb, uint32_t kd)
+__device__ __forceinline__ uint32_t fast_pair_score(uint32_t (&v)[16], uint32_t cpk, uint32_t th2, uint32_t kb, uint32_t kd)
 {
-    constexpr int C = 4 + 2 * J;
-    uint32_t v[16];
-    v[0] = pk_pair<C>(R[6]);      v[1] = pk_pair<C + 1>(R[6]);  v[2] = pk_pair<C + 2>(R[5]);  v[3] = pk_pair<C + 3>(R[4]);
-    v[4] = pk_pair<C + 3>(R[3]);  v[5] = pk_pair<C + 3>(R[2]);  v[6] = pk_pair<C + 2>(R[1]);  v[7] = pk_pair<C + 1>(R[0]);
-    v[8] = pk_pair<C>(R[0]);      v[9] = pk_pair<C - 1>(R[0]);  v[10] = pk_pair<C - 2>(R[1]); v[11] = pk_pair<C - 3>(R[2]);
-    v[12] = pk_pair<C - 3>(R[3]); v[13] = pk_pair<C - 3>(R[4]); v[14] = pk_pair<C - 2>(R[5]); v[15] = pk_pair<C - 1>(R[6]);
-    const uint32_t cpk = pk_pair<C>(R[3]);
     const uint32_t e0 = pk_max3(v[0], v[8], v[8]), e1 = pk_max3(v[4], v[12], v[12]), f0 = pk_min3(v[0], v[8], v[8]), f1 = pk_min3(v[4], v[12], v[12]);
     const uint32_t m = pk_min3(e0, e1, e1), n = pk_max3(f0, f1, f1);                // as in fast_compass
     const uint32_t nbright = (cpk + kb) - m;                                       // 0x200 + c + t - m     : bit 9 <=> NOT m - c > t
@@ -393,17 +380,15 @@ template <int J> __device__ __forceinline__ uint32_t fast_pair_score(const uint3
     return __builtin_bit_cast(uint32_t, (corb_short2)(s & keep));                  // [s,0 | s',0]
 }
 
-// Compass test of the two pixels J (= 0: window bytes 4,5; 1: bytes 6,7) of a 4-pixel group: any arc of 9 contiguous circle pixels holds two
+// Compass test of a pixel pair from its packed compass values v0, v4, v8, v12 (circle positions 0, 4, 8, 12) and centres cpk: any arc of 9 contiguous circle pixels holds two
 // ADJACENT compass points (circle positions 0, 4, 8, 12), so   corner at t  =>  max over adjacent compass pairs of min(v_i, v_i+1) > c + t
 // or c - t > min over the pairs of max(v_i, v_i+1).  With a, b, c', d the four compass values in circle order the max over the four adjacent
 // pairs of their minima is min(max(a, c'), max(b, d)) (max[min(a,b), min(a,d)] = min(a, max(b,d)), the same for c', and
 // max[min(a,M), min(c',M)] = min(max(a,c'), M)), and the min over the pairs of their maxima is max(min(a, c'), min(b, d)): 6 min/max instead
 // of 12.  Returns Q = max(that max-min - c, c - that min-max) per half: "Q > t" is an EXACT necessary condition (never rejects a corner),
-// 14 instructions per pixel pair and 3 tile rows instead of 109 and 7.
-template <int J> __device__ __forceinline__ uint32_t fast_compass(const uint32_t (&R0)[3], const uint32_t (&R3)[3], const uint32_t (&R6)[3])
+// 9 instructions per pixel pair and 3 tile rows instead of 109 and 7.
+__device__ __forceinline__ uint32_t fast_compass(uint32_t v0, uint32_t v4, uint32_t v8, uint32_t v12, uint32_t cpk)
 {
-    constexpr int C = 4 + 2 * J;
-    const uint32_t v0 = pk_pair<C>(R6), v4 = pk_pair<C + 3>(R3), v8 = pk_pair<C>(R0), v12 = pk_pair<C - 3>(R3), cpk = pk_pair<C>(R3);
     const uint32_t m = pk_min3(pk_max3(v0, v8, v8), pk_max3(v4, v12, v12), pk_max3(v4, v12, v12));
     const uint32_t n = pk_max3(pk_min3(v0, v8, v8), pk_min3(v4, v12, v12), pk_min3(v4, v12, v12));
     const corb_short2 c = __builtin_bit_cast(corb_short2, cpk);
@@ -411,23 +396,28 @@ template <int J> __device__ __forceinline__ uint32_t fast_compass(const uint32_t
 }
 __device__ __forceinline__ int mbcnt64(unsigned long long m) { return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u)); }
 
-// One WAVEFRONT per cell (64-thread workgroups: barriers are free, ~25 cells in flight per CU).
-// LDS tile: the cell's interior (scored pixels) starts at the dword-aligned column 4, its 3-px halo at column 1;
-// the global row is fetched as aligned dwords and re-aligned with v_alignbyte.  TP = compile-time tile pitch.
+// One WAVEFRONT per cell (64-thread workgroups: barriers are free).
+// LDS tile (orb_fast_tile.h): one 16-bit slot per pixel, pixel | score << 8, so an aligned dword of a row is a pixel pair [b,s | b',s'] and the
+// byte-to-pair conversion is paid once per loaded dword when the tile is written (two v_perm_b32 that also re-align the global dword, one
+// ds_write_b64) instead of once per ring value of every window.  The score lives in the slot's high byte -- a separate tile of score bytes
+// would take the cell from 4.2 to 5.7 KB of LDS and the compute unit from 32 cells to 28, which costs more than the shuffles save
+// (profiles/HISTORY_r10.md) -- and is masked off where pixels are read.  The cell's interior (scored pixels) starts at column 4 = byte 8 of a row, its
+// 3-px halo at column 1; a 4-pixel group is one aligned 8-byte word.  Ring and compass values at an even dx are dwords as they stand (one
+// v_and_b32 drops the scores; phase 1 skips it while no score has been written), those at an odd dx one v_perm_b32 of two adjacent dwords whose
+// zero selectors drop them.  TP = compile-time tile pitch in slots.
 //
 // The two cv::FAST calls of the reference (C/src/ORBextractor.cc:809-816) are two PASSES of the same three phases, the second one only for a
 // cell without a corner at iniThFAST (< 2 % of the cells):
 //   1. compass test at the pass' threshold for every pixel (a lane owns a group of 4 pixels = two packed pairs, lanes are an ng x (64/ng)
 //      patch sliding down the cell); the pixel PAIRS with a pixel that passes (11 % of the pairs at t = 20 on the synthetic KITTI-size frames) are
 //      appended to a list in LDS (two ballots and lane-prefix counts per sweep, no atomics);
-//   2. the 9-of-16 arc score only for the listed pairs and only on the side each pixel passed on (fast_pair_score), one pair per lane (the second pair of a group is the first pair's window two
-//      bytes further: one v_alignbyte per window dword); scores >= threshold go to the score bytes (everything else stays 0 -- for
-//      cv::FAST's NMS a non-corner scores 0);
-//   3. strict 8-neighbour NMS on the score bytes, over the listed pairs, survivors as per-row bit masks, compacted in row-major order.
+//   2. the 9-of-16 arc score only for the listed pairs and only on the side each pixel passed on (fast_pair_score), one pair per lane (the pair's
+//      position enters the LDS address only: 23 dword reads, 10 v_perm_b32, 7 v_and_b32); scores >= threshold go to the slots' high bytes (everything else stays
+//      0 -- for cv::FAST's NMS a non-corner scores 0);
+//   3. strict 8-neighbour NMS on the slots' score bytes (9 v_perm_b32 per pair), over the listed pairs, survivors as per-row bit masks, compacted in row-major order.
 // Scoring every pixel at minThFAST (round 1: one pass, 218 VALU per 4 px, the kernel sat on its VALU issue bound) computed 10x more arc scores
 // than the reference's first call needs; a list of 4-pixel groups (first form of round 2) scored 306 pixels per cell in 1.7 trips of the wave,
 // the pair list scores 202 in 2.1 half-cost trips.
-#define FAST_LIST_CAP 512
 // inclusive prefix sum over the wavefront in 6 DPP adds (row_shr 1, 2, 4, 8 inside the rows of 16, then row_bcast 15 / 31 across them) -- a
 // shuffle-based scan costs an LDS permute and ~6 VALU per step
 __device__ __forceinline__ int wave_incl_scan(int v)
@@ -444,16 +434,17 @@ __device__ __forceinline__ int wave_incl_scan(int v)
 template <int TP>
 __global__ __launch_bounds__(64) void orb_fast_kernel(const CorbOrbParams p)
 {
-    constexpr int P = TP / 4;                           // tile pitch in dwords
+    constexpr int P = TP / 4;                           // pitch of the 16-bit tile in 8-byte words
+    constexpr int PD = TP / 2;                          // pitch of the 16-bit tile in dwords (fast_tile_row_dwords)
     extern __shared__ __attribute__((aligned(16))) uint8_t fast_smem[];
     __shared__ uint16_t plist[FAST_LIST_CAP];           // pixel pairs with a pixel that passed the compass test: (y << 6) | (g << 1) | pair   (y = tile row)
     uint32_t* tile = reinterpret_cast<uint32_t*>(fast_smem);
-    uint32_t* sc = tile + P * p.fast_th;                // score bytes, 0 = not a corner at the pass' threshold
-    // per interior row: NMS survivors of the current pass (fast_th - 6 rows: the kernel's LDS decides how many cells a CU holds -- 5.5 KB per cell
-    // admit 28, the 7 KB of a 1 024-entry list and 64 mask rows admitted 22: FAST alone 520 -> 480 us per 256 images)
-    uint32_t (*rowm)[2] = reinterpret_cast<uint32_t (*)[2]>(sc + P * p.fast_th);
+    // per interior row: NMS survivors of the current pass (fast_th - 6 rows).  The kernel's LDS decides how many cells a CU holds (the launch
+    // requests fast_dynamic_lds_bytes; figures per pitch in profiles/HISTORY_r10.md): the 7 KB of a 1 024-entry list and 64 mask rows admitted
+    // 22 cells where 5.5 KB admitted 28, FAST alone 520 -> 480 us per 256 images
+    uint32_t (*rowm)[2] = reinterpret_cast<uint32_t (*)[2]>(tile + PD * p.fast_th);
     const int nrowm = p.fast_th - 6;
-    uint8_t* scb = reinterpret_cast<uint8_t*>(sc);
+    uint8_t* tb = reinterpret_cast<uint8_t*>(tile);   // a slot's high byte is the pixel's score (0 = not a corner at the pass' threshold)
     int cell, img; corb_xcd_remap(cell, img); img += p.img_base;
     const int lane = threadIdx.x;
     // the cell's geometry depends on the handle alone: one record per cell, built at create (CorbFastCell), read through the scalar cache
@@ -473,6 +464,9 @@ __global__ __launch_bounds__(64) void orb_fast_kernel(const CorbOrbParams p)
         const int jlast = (int)(rec.w >> 20);            // aligned dword holding the last cell pixel
         const int r0 = lane / P, wc = lane - r0 * P;
         constexpr int RPI = 64 / P;
+        // bytes a .. a+3 of the two loaded dwords, spread to four slots: columns 4 wc, 4 wc + 1 | 4 wc + 2, 4 wc + 3 (wave-uniform selectors).
+        // Every lane wc < P of every row y < ch stores: all TP slots of the rows 0 .. ch-1 are byte-valued (the padding rule of orb_fast_tile.h)
+        const uint32_t sel_lo = 0x0c000c00u | a | ((a + 1u) << 16), sel_hi = sel_lo + 0x00020002u;
         if (r0 < RPI) {
             const int j0 = min(wc, jlast), j1 = min(wc + 1, jlast);
             for (int y = r0; y < ch; y += 4 * RPI) {        // four row groups per trip: eight loads in flight, then the stores
@@ -484,7 +478,10 @@ __global__ __launch_bounds__(64) void orb_fast_kernel(const CorbOrbParams p)
                 }
 #pragma unroll
                 for (int k = 0; k < 4; k++)
-                    if (y + k * RPI < ch) { tile[(y + k * RPI) * P + wc] = __builtin_amdgcn_alignbyte(w1[k], w0[k], a); sc[(y + k * RPI) * P + wc] = 0u; }
+                    if (y + k * RPI < ch) {
+                        const int yy = y + k * RPI;
+                        reinterpret_cast<uint2*>(tile)[yy * P + wc] = make_uint2(__builtin_amdgcn_perm(w1[k], w0[k], sel_lo), __builtin_amdgcn_perm(w1[k], w0[k], sel_hi));
+                    }
             }
         }
     }
@@ -495,6 +492,8 @@ __global__ __launch_bounds__(64) void orb_fast_kernel(const CorbOrbParams p)
     const int nvalid = min(4, iw - 4 * g);               // pixels of this group inside the interior
     const uint32_t smask0 = nvalid >= 2 ? 0x80008000u : nvalid == 1 ? 0x00008000u : 0u, smask1 = nvalid >= 4 ? 0x80008000u : nvalid == 3 ? 0x00008000u : 0u;
     unsigned long long mine = 0;
+    auto odd = [](uint32_t hi, uint32_t lo) { return __builtin_amdgcn_perm(hi, lo, 0x0c040c02u); };   // [pixel of lo's high slot | pixel of hi's low slot], score bytes dropped
+    bool dirty = false;                                  // scores may stand in the slots' high bytes
     for (int pass = 0; pass < 2; pass++) {
         const int th = pass == 0 ? p.ini_th : p.min_th;
         const uint32_t th2 = (uint32_t)th * 0x00010001u;
@@ -505,19 +504,24 @@ __global__ __launch_bounds__(64) void orb_fast_kernel(const CorbOrbParams p)
             nbatch++;
             // ---- phase 1: compass test; the pixel PAIRS with a survivor are appended to plist (room for a whole sweep of the patch: 128) ----
             base = 0;
-            for (; y0 < ch - 3 && base + 128 <= FAST_LIST_CAP; y0 += rstep) {
+            for (; y0 < ch - 3 && base + FAST_LIST_SWEEP <= FAST_LIST_CAP; y0 += rstep) {
                 const int y = y0 + r;
-                bool hit0 = false, hit1 = false;
+                uint32_t d0 = 0u, d1 = 0u;                       // idle lanes keep 0: the ballots below compare d0, d1 themselves (no 0/1 flag carried out of the branch)
                 if (active && y < ch - 3) {
-                    const uint32_t* t = tile + y * P + g;        // dword left of the group
-                    uint32_t R0[3], R3[3], R6[3];
-#pragma unroll
-                    for (int k = 0; k < 3; k++) { R0[k] = t[-3 * P + k]; R3[k] = t[k]; R6[k] = t[3 * P + k]; }
+                    const uint2* t = reinterpret_cast<const uint2*>(tile + y * PD) + g;      // 8-byte word left of the group: columns 4g .. 4g+3
+                    uint2 up = t[-3 * P + 1], dn = t[3 * P + 1];                              // the group's own columns 4g+4 .. 4g+7, rows y - 3 / y + 3
+                    const uint2 wl = t[0], wr = t[2]; uint2 wc = t[1];                      // row y: columns 4g .. 4g+11
+                    if (dirty) { up.x &= 0x00ff00ffu; up.y &= 0x00ff00ffu; dn.x &= 0x00ff00ffu; dn.y &= 0x00ff00ffu; }
+                    const uint2 wcm = make_uint2(wc.x & 0x00ff00ffu, wc.y & 0x00ff00ffu);
+                    // pair 0 (columns 4g+4, 4g+5): dx = -3 is columns 4g+1, 4g+2, dx = +3 columns 4g+7, 4g+8; pair 1 the same two columns further
+                    const uint32_t q0 = fast_compass(dn.x, odd(wr.x, wc.y), up.x, odd(wl.y, wl.x), dirty ? wcm.x : wc.x);
+                    const uint32_t q1 = fast_compass(dn.y, odd(wr.y, wr.x), up.y, odd(wc.x, wl.y), dirty ? wcm.y : wc.y);
                     // Q > th  <=>  (th - Q) < 0 per half: the sign bits of the four pixels, those past the interior masked off
-                    const uint32_t d0 = __builtin_bit_cast(uint32_t, (corb_short2)(__builtin_bit_cast(corb_short2, th2) - __builtin_bit_cast(corb_short2, fast_compass<0>(R0, R3, R6))));
-                    const uint32_t d1 = __builtin_bit_cast(uint32_t, (corb_short2)(__builtin_bit_cast(corb_short2, th2) - __builtin_bit_cast(corb_short2, fast_compass<1>(R0, R3, R6))));
-                    hit0 = (d0 & smask0) != 0u; hit1 = (d1 & smask1) != 0u;
+                    d0 = __builtin_bit_cast(uint32_t, (corb_short2)(__builtin_bit_cast(corb_short2, th2) - __builtin_bit_cast(corb_short2, q0))) & smask0;
+                    d1 = __builtin_bit_cast(uint32_t, (corb_short2)(__builtin_bit_cast(corb_short2, th2) - __builtin_bit_cast(corb_short2, q1))) & smask1;
                 }
+                asm("" : "+v"(d0), "+v"(d1));                   // keeps the two compares below the join: sunk into the branch they come back as v_cndmask 0/1 + v_cmp_ne each
+                const bool hit0 = d0 != 0u, hit1 = d1 != 0u;
                 const unsigned long long b0 = __ballot(hit0), b1 = __ballot(hit1);
                 const int n0 = __popcll(b0);
                 const uint32_t ent = (uint32_t)((y << 6) | (g << 1));
@@ -537,79 +541,69 @@ __global__ __launch_bounds__(64) void orb_fast_kernel(const CorbOrbParams p)
                 e = plist[i];
                 const int y = e >> 6, ge = (e >> 1) & 31;
                 const uint32_t sh = (e & 1u) * 2u;
-                const uint32_t* t = tile + y * P + ge;
-                uint32_t R[7][3];
-#pragma unroll
-                for (int dy = 0; dy < 7; dy++) {
-                    const uint32_t w0 = t[(dy - 3) * P], w1 = t[(dy - 3) * P + 1], w2 = t[(dy - 3) * P + 2];
-                    R[dy][0] = __builtin_amdgcn_alignbyte(w1, w0, sh); R[dy][1] = __builtin_amdgcn_alignbyte(w2, w1, sh); R[dy][2] = __builtin_amdgcn_alignbyte(0u, w2, sh);
+                // the pair's own dword (fast_tile_pair_dword(ge, e & 1) = 2 + the entry's low 6 bits): which pair of the group it is enters the address only
+                const uint32_t* t = tile + y * PD + 2 + (e & 63u);
+                constexpr uint32_t PX = 0x00ff00ffu;
+                uint32_t v[16];
+                {
+                    const uint32_t* u = t + 3 * PD;               // row y + 3: dx = 0, 1 and -1
+                    const uint32_t a = u[-1], b = u[0], c = u[1];
+                    v[0] = b & PX; v[1] = odd(c, b); v[15] = odd(b, a);
                 }
-                const uint32_t s0 = fast_pair_score<0>(R, th2, kb, kd);                    // [s,0 | s',0]
+                { const uint32_t* u = t + 2 * PD; v[14] = u[-1] & PX; v[2] = u[1] & PX; }                              // row y + 2: dx = -2, 2
+                { const uint32_t* u = t + PD; v[13] = odd(u[-1], u[-2]); v[3] = odd(u[2], u[1]); }           // row y + 1: dx = -3, 3
+                const uint32_t cpk = t[0] & PX;
+                v[12] = odd(t[-1], t[-2]); v[4] = odd(t[2], t[1]);                                           // row y
+                { const uint32_t* u = t - PD; v[11] = odd(u[-1], u[-2]); v[5] = odd(u[2], u[1]); }           // row y - 1
+                { const uint32_t* u = t - 2 * PD; v[10] = u[-1] & PX; v[6] = u[1] & PX; }                              // row y - 2
+                {
+                    const uint32_t* u = t - 3 * PD;               // row y - 3: dx = 1, 0, -1
+                    const uint32_t a = u[-1], b = u[0], c = u[1];
+                    v[7] = odd(c, b); v[8] = b & PX; v[9] = odd(b, a);
+                }
+                const uint32_t s0 = fast_pair_score(v, cpk, th2, kb, kd);                  // [s,0 | s',0]
                 const int px = 4 * ge + (int)sh;                                  // interior column of the pair's first pixel (< iw: it passed the mask)
-                uint32_t v = __builtin_amdgcn_perm(0u, s0, 0x0c0c0200u);          // s | s' << 8
-                if (px + 1 >= iw) v &= 0xFFu;
-                reinterpret_cast<uint16_t*>(scb)[(y * TP + 4 + px) >> 1] = (uint16_t)v;
-                has = v != 0u;
+                const uint32_t s2 = px + 1 >= iw ? s0 & 0xFFu : s0;
+                uint8_t* sb = tb + 4 * (t - tile);
+                sb[1] = (uint8_t)s2; sb[3] = (uint8_t)(s2 >> 16);
+                has = s2 != 0u;
                 }
                 const unsigned long long bs = __ballot(has);
                 if (has) plist[nscore + mbcnt64(bs)] = (uint16_t)e;
                 nscore += __popcll(bs);
             }
+            dirty = true;
             __syncthreads();
         }
         // ---- phase 3: strict 8-neighbour NMS (non-corners score 0).  Only listed groups can hold a corner: when the whole cell went through one
         // list (the usual case) the sweep runs over the list instead of over every group of the cell ----
-        auto nms_group = [&](int y, int ge) {
-            const uint32_t* t = sc + y * P + ge;
-            if (t[1] == 0u) return;                          // no corner in this group
-            uint32_t S[3][3];
-#pragma unroll
-            for (int dy = 0; dy < 3; dy++)
-#pragma unroll
-                for (int k = 0; k < 3; k++) S[dy][k] = t[(dy - 1) * P + k];
-            uint32_t bits = 0;
-#pragma unroll
-            for (int j = 0; j < 2; j++) {
-                uint32_t ctr, nb;
-                if (j == 0) {
-                    ctr = pk_pair<4>(S[1]);
-                    nb = pk_max3(pk_max3(pk_pair<3>(S[0]), pk_pair<4>(S[0]), pk_pair<5>(S[0])),
-                                 pk_max3(pk_pair<3>(S[2]), pk_pair<4>(S[2]), pk_pair<5>(S[2])),
-                                 pk_max3(pk_pair<3>(S[1]), pk_pair<5>(S[1]), pk_pair<5>(S[1])));
-                } else {
-                    ctr = pk_pair<6>(S[1]);
-                    nb = pk_max3(pk_max3(pk_pair<5>(S[0]), pk_pair<6>(S[0]), pk_pair<7>(S[0])),
-                                 pk_max3(pk_pair<5>(S[2]), pk_pair<6>(S[2]), pk_pair<7>(S[2])),
-                                 pk_max3(pk_pair<5>(S[1]), pk_pair<7>(S[1]), pk_pair<7>(S[1])));
-                }
-                // strict 8-neighbour maximum: ctr > nb  <=>  (nb - ctr) < 0 per half
-                const uint32_t dm = __builtin_bit_cast(uint32_t, (corb_short2)(__builtin_bit_cast(corb_short2, nb) - __builtin_bit_cast(corb_short2, ctr)));
-                bits |= (((dm >> 15) & 1u) | ((dm >> 30) & 2u)) << (2 * j);
-            }
-            if (bits) atomicOr(&rowm[y - 3][ge >> 3], bits << (4 * (ge & 7)));
+        // scores of the pair at dword q of row y against their 8 neighbours: bit 0 / 1 = the first / second pixel is a strict maximum
+        auto nms_pair = [&](const uint32_t* t) -> uint32_t {
+            auto mid = [](uint32_t d) { return __builtin_amdgcn_perm(0u, d, 0x0c030c01u); };                    // [s, 0 | s', 0] of a dword's two slots
+            auto lft = [](uint32_t d, uint32_t dm) { return __builtin_amdgcn_perm(d, dm, 0x0c050c03u); };       // the pair one column left of d (dm = the dword before d)
+            const uint32_t a0 = t[-PD - 1], a1 = t[-PD], a2 = t[-PD + 1], b0 = t[-1], b1 = t[0], b2 = t[1], c0 = t[PD - 1], c1 = t[PD], c2 = t[PD + 1];
+            const uint32_t ctr = mid(b1);
+            const uint32_t nb = pk_max3(pk_max3(lft(a1, a0), mid(a1), lft(a2, a1)), pk_max3(lft(c1, c0), mid(c1), lft(c2, c1)), pk_max3(lft(b1, b0), lft(b2, b1), lft(b2, b1)));
+            // strict 8-neighbour maximum: ctr > nb  <=>  (nb - ctr) < 0 per half
+            const uint32_t dm = __builtin_bit_cast(uint32_t, (corb_short2)(__builtin_bit_cast(corb_short2, nb) - __builtin_bit_cast(corb_short2, ctr)));
+            return ((dm >> 15) & 1u) | ((dm >> 30) & 2u);
         };
         if (nbatch == 1) {
             for (int i = lane; i < nscore; i += 64) {
-                const uint32_t e = plist[i];
+                const uint32_t e = plist[i];                       // only the pairs that scored are listed
                 const int y = e >> 6, ge = (e >> 1) & 31;
                 const uint32_t sh = (e & 1u) * 2u;
-                const uint32_t* t = sc + y * P + ge;
-                uint32_t S[3][3];
-#pragma unroll
-                for (int dy = 0; dy < 3; dy++) {
-                    const uint32_t w0 = t[(dy - 1) * P], w1 = t[(dy - 1) * P + 1], w2 = t[(dy - 1) * P + 2];
-                    S[dy][0] = __builtin_amdgcn_alignbyte(w1, w0, sh); S[dy][1] = __builtin_amdgcn_alignbyte(w2, w1, sh); S[dy][2] = 0u;
-                }
-                const uint32_t ctr = pk_pair<4>(S[1]);             // non-zero: only the pairs that scored are listed
-                const uint32_t nb = pk_max3(pk_max3(pk_pair<3>(S[0]), pk_pair<4>(S[0]), pk_pair<5>(S[0])),
-                                            pk_max3(pk_pair<3>(S[2]), pk_pair<4>(S[2]), pk_pair<5>(S[2])),
-                                            pk_max3(pk_pair<3>(S[1]), pk_pair<5>(S[1]), pk_pair<5>(S[1])));
-                const uint32_t dm = __builtin_bit_cast(uint32_t, (corb_short2)(__builtin_bit_cast(corb_short2, nb) - __builtin_bit_cast(corb_short2, ctr)));
-                const uint32_t bits = ((dm >> 15) & 1u) | ((dm >> 30) & 2u);
+                const uint32_t bits = nms_pair(tile + y * PD + 2 + (e & 63u));
                 if (bits) atomicOr(&rowm[y - 3][ge >> 3], bits << (4 * (ge & 7) + sh));
             }
         } else if (active) {
-            for (int y = 3 + r; y < ch - 3; y += rstep) nms_group(y, g);
+            for (int y = 3 + r; y < ch - 3; y += rstep) {
+                const uint32_t* t = tile + y * PD + 2 * g + 2;
+                uint32_t bits = 0;
+                if (t[0] & 0xff00ff00u) bits = nms_pair(t);
+                if (t[1] & 0xff00ff00u) bits |= nms_pair(t + 1) << 2;
+                if (bits) atomicOr(&rowm[y - 3][g >> 3], bits << (4 * (g & 7)));
+            }
         }
         __syncthreads();
         mine = lane < ih ? ((unsigned long long)rowm[lane][1] << 32) | rowm[lane][0] : 0ull;
@@ -627,7 +621,7 @@ __global__ __launch_bounds__(64) void orb_fast_kernel(const CorbOrbParams p)
         mask &= mask - 1;
         if (off < L.cell_cap)
             out[off] = (uint32_t)(ox + x) | ((uint32_t)(oy + lane) << 12) |
-                       ((uint32_t)scb[(lane + 3) * TP + x + 4] << 24);
+                       ((uint32_t)tb[2 * ((lane + 3) * TP + x + 4) + 1] << 24);
         off++;
     }
     if (lane == 0) { *out_count = min(total, L.cell_cap); if (total > L.cell_cap) p.status[img] = CORB_ERR_OVERFLOW; }
@@ -1505,11 +1499,11 @@ void corb_launch_orb_pipeline(const CorbOrbParams& p0, int img_base, int n_image
                                     // profiles/r04_variants_stage.txt): 93.3 k / 103.4 k / 90.6 k / 90.3 k stereo fps
 #endif
     if (CORB_STAGE_AFTER == 0 && after_fast) (void)hipEventRecord(after_fast, stream);
-    // (cells up to 32 px wide -- KITTI's 31 / 32 -- fit a 40-byte tile pitch: 4.8 KB of LDS per cell instead of 5.5)
+    // (cells up to 32 px wide -- KITTI's 31 / 32 -- fit a 40-slot tile pitch; the LDS of a cell is fast_cell_lds_bytes(TP, fast_th), orb_fast_tile.h)
     if (skip("fast")) {}
-    else if (p.fast_tp <= 40) CORB_LAUNCH(prof, "orb_fast_kernel", orb_fast_kernel<40>, dim3(p.cells_per_image, n_images), dim3(64), (size_t)2 * 40 * p.fast_th + 8 * (size_t)(p.fast_th - 6), stream, p);
-    else if (p.fast_tp <= 48) CORB_LAUNCH(prof, "orb_fast_kernel", orb_fast_kernel<48>, dim3(p.cells_per_image, n_images), dim3(64), (size_t)2 * 48 * p.fast_th + 8 * (size_t)(p.fast_th - 6), stream, p);
-    else CORB_LAUNCH(prof, "orb_fast_kernel", orb_fast_kernel<80>, dim3(p.cells_per_image, n_images), dim3(64), (size_t)2 * 80 * p.fast_th + 8 * (size_t)(p.fast_th - 6), stream, p);
+    else if (fast_tile_pitch_class(p.fast_tp) == 40) CORB_LAUNCH(prof, "orb_fast_kernel", orb_fast_kernel<40>, dim3(p.cells_per_image, n_images), dim3(64), (size_t)fast_dynamic_lds_bytes(40, p.fast_th), stream, p);
+    else if (fast_tile_pitch_class(p.fast_tp) == 48) CORB_LAUNCH(prof, "orb_fast_kernel", orb_fast_kernel<48>, dim3(p.cells_per_image, n_images), dim3(64), (size_t)fast_dynamic_lds_bytes(48, p.fast_th), stream, p);
+    else CORB_LAUNCH(prof, "orb_fast_kernel", orb_fast_kernel<80>, dim3(p.cells_per_image, n_images), dim3(64), (size_t)fast_dynamic_lds_bytes(80, p.fast_th), stream, p);
     if (CORB_STAGE_AFTER == 1 && after_fast) (void)hipEventRecord(after_fast, stream);      // the next part-batch of the run starts here (corb_orb.cpp: corb_run_parts)
     if (!skip("octree")) {
         // two level groups: [0, split) with OT_BIG threads per (image, level), [split, nlevels) with one wavefront; LDS carved per group
