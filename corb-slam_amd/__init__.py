@@ -7,6 +7,7 @@ from tests/, bench.py and __graft_entry__.py.  It has two layers:
   _abi_fusion.py  the same for the seventh header, include/corb_map_fusion.h, as a table of its own (bind_fusion())
   _abi_tracklocal.py  the same for the eighth header, include/corb_track_local_map.h (bind_tracklocal())
   _abi_trackframe.py  the same for the ninth header, include/corb_track_frame.h (bind_trackframe())
+  _abi_traj.py        the same for the tenth header, include/corb_trajectory.h (bind_traj())
   __init__.py  (this file) load(), the handle owner, and the classes and functions that marshal numpy
                arrays into the calls -- about 1900 lines, most of them array marshalling
 Class / method names mirror the reference (ORBextractor::operator(), ORBmatcher::SearchByBoW /
@@ -22,6 +23,7 @@ from ._abi import *         # noqa: F401,F403 -- every name of the mirror, the u
 from ._abi_fusion import *  # noqa: F401,F403 -- include/corb_map_fusion.h: a table of its own beside the six headers' (see _abi_fusion.py)
 from ._abi_tracklocal import *  # noqa: F401,F403 -- include/corb_track_local_map.h: likewise (see _abi_tracklocal.py)
 from ._abi_trackframe import *  # noqa: F401,F403 -- include/corb_track_frame.h: likewise (see _abi_trackframe.py)
+from ._abi_traj import *  # noqa: F401,F403 -- include/corb_trajectory.h: likewise (see _abi_traj.py)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libcorb_accel.so")
@@ -43,7 +45,7 @@ def load():
         if not os.path.exists(LIB_PATH):
             raise CorbError("libcorb_accel.so is not built (run `python -c 'import __graft_entry__ as g; g.build()'`); "
                             "there is no CPU fallback")
-        _lib = bind_trackframe(bind_tracklocal(bind_fusion(bind(C.CDLL(LIB_PATH)))))
+        _lib = bind_traj(bind_trackframe(bind_tracklocal(bind_fusion(bind(C.CDLL(LIB_PATH))))))
     return _lib
 
 
@@ -1397,6 +1399,96 @@ class Covisibility(_Handle):
         a = np.zeros(16, np.float32)
         _chk(load().corb_covis_get_pose_before_gba(self.h, slot, _p(a)), "corb_covis_get_pose_before_gba")
         return a.reshape(4, 4)
+
+
+class Trajectory(_Handle):
+    """The camera trajectory on records (corb_traj_*, include/corb_trajectory.h): the per-frame log of Tracking::Track, KeyFrame::mTcp and mTimeStamp per slot of the
+    graph's keyframe store, and System::SaveTrajectoryKITTI / SaveTrajectoryTUM / SaveKeyFrameTrajectoryTUM.  sensor: System::eSensor (0 MONOCULAR), for the refusal
+    of the two frame dumps (System.cc:256, :352), which the C calls leave to their caller."""
+
+    _destroy = "corb_traj_destroy"
+
+    def __init__(self, covis, capacity_frames, sensor=1):
+        self.g = covis; self.capacity = int(capacity_frames); self.n_slots = covis.kf.capacity; self.sensor = sensor
+        self._create("corb_traj_create", covis.h, self.capacity)
+
+    def reset(self):
+        _chk(load().corb_traj_reset(self.h), "corb_traj_reset")
+
+    def append(self, frames, cur_slot, ref_slot, Tcr=None, timestamp=0.0, lost=False):
+        """the end of Tracking::Track: Tcr given (what TrackFrameFinish returned), or None: computed on the device from the two records; cur_slot = -1 repeats the last entry"""
+        a = None if Tcr is None else np.ascontiguousarray(Tcr, np.float32).reshape(16)
+        _chk(load().corb_traj_append(self.h, frames.h if frames is not None else None, cur_slot, ref_slot, _p(a), float(timestamp), bool(lost)), "corb_traj_append")
+
+    def set_keyframe_time(self, slot, timestamp):
+        _chk(load().corb_traj_set_keyframe_time(self.h, slot, float(timestamp)), "corb_traj_set_keyframe_time")
+
+    def get_keyframe_time(self, slot):
+        v = C.c_double(0)
+        _chk(load().corb_traj_get_keyframe_time(self.h, slot, C.byref(v)), "corb_traj_get_keyframe_time")
+        return v.value
+
+    def set_bad_pose(self, slot):
+        """KeyFrame.cc:666, before the caller sets CORB_KF_BAD"""
+        _chk(load().corb_traj_set_bad_pose(self.h, slot), "corb_traj_set_bad_pose")
+
+    def set_tcp(self, slot, Tcp):
+        a = np.ascontiguousarray(Tcp, np.float32).reshape(16)
+        _chk(load().corb_traj_set_tcp(self.h, slot, _p(a)), "corb_traj_set_tcp")
+
+    def get_tcp(self, slot):
+        a = np.zeros(16, np.float32)
+        _chk(load().corb_traj_get_tcp(self.h, slot, _p(a)), "corb_traj_get_tcp")
+        return a.reshape(4, 4)
+
+    def get_entries(self):
+        e = np.zeros(self.capacity, TRAJ_ENTRY_DTYPE); n = C.c_int(0)
+        _chk(load().corb_traj_get_entries(self.h, e.ctypes.data_as(C.POINTER(TrajEntry)), self.capacity, C.byref(n)), "corb_traj_get_entries")
+        return e[:n.value].copy()
+
+    def frames(self, origin_slot=-1, format=TRAJ_KITTI, cap=None):
+        """(rows [n][12 | 7], times [n], entry_index [n], TrajStats) of corb_traj_frames"""
+        cap = self.capacity if cap is None else cap; w = 12 if format == TRAJ_KITTI else 7
+        rows = np.zeros((max(cap, 1), w), np.float32); times = np.zeros(max(cap, 1), np.float64); idx = np.zeros(max(cap, 1), np.int32); n = C.c_int(0); st = TrajStats()
+        _chk(load().corb_traj_frames(self.h, origin_slot, format, _p(rows), _p(times), _p(idx), cap, C.byref(n), C.byref(st)), "corb_traj_frames")
+        return rows[:n.value].copy(), times[:n.value].copy(), idx[:n.value].copy(), st
+
+    def keyframes(self, cap=None):
+        """(rows [n][7], times [n], ids [n]) of corb_traj_keyframes"""
+        cap = self.n_slots if cap is None else cap
+        rows = np.zeros((max(cap, 1), 7), np.float32); times = np.zeros(max(cap, 1), np.float64); ids = np.zeros(max(cap, 1), np.uint64); n = C.c_int(0)
+        _chk(load().corb_traj_keyframes(self.h, _p(rows), _p(times), _p(ids), cap, C.byref(n)), "corb_traj_keyframes")
+        return rows[:n.value].copy(), times[:n.value].copy(), ids[:n.value].copy()
+
+    def save(self, kind, path, origin_slot=-1):
+        _chk(load().corb_traj_save(self.h, origin_slot, kind, os.fsencode(path)), "corb_traj_save")
+
+    def _not_monocular(self, what):
+        if self.sensor == 0:
+            raise CorbError("ERROR: %s cannot be used for monocular." % what)
+
+    def SaveTrajectoryKITTI(self, path, origin_slot=-1):
+        self._not_monocular("SaveTrajectoryKITTI"); self.save(TRAJ_KITTI, path, origin_slot)
+
+    def SaveTrajectoryTUM(self, path, origin_slot=-1):
+        self._not_monocular("SaveTrajectoryTUM"); self.save(TRAJ_TUM, path, origin_slot)
+
+    def SaveKeyFrameTrajectoryTUM(self, path):
+        self.save(TRAJ_KEYFRAME_TUM, path)
+
+
+def traj_format_rows(kind, rows, times=None):
+    """corb_traj_format_rows: the text of the reference's streams for the rows (bytes); host code, no device"""
+    w = 12 if kind == TRAJ_KITTI else 7
+    r = np.ascontiguousarray(rows, np.float32).reshape(-1, w); t = None if times is None else np.ascontiguousarray(times, np.float64)
+    n = C.c_size_t(0)
+    rc = load().corb_traj_format_rows(kind, _p(r), _p(t), len(r), None, 0, C.byref(n))
+    if rc != -2:
+        _chk(rc, "corb_traj_format_rows")
+    buf = C.create_string_buffer(max(n.value, 1))
+    if n.value:
+        _chk(load().corb_traj_format_rows(kind, _p(r), _p(t), len(r), buf, n.value, C.byref(n)), "corb_traj_format_rows")
+    return buf.raw[:n.value]
 
 
 class KeyFrameStore(_Handle):

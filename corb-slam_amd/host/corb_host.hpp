@@ -17,6 +17,7 @@
 #include <corb_map_fusion.h>
 #include <corb_track_local_map.h>
 #include <corb_track_frame.h>
+#include <corb_trajectory.h>
 #include <algorithm>
 #include <cstdint>
 #include <cstring>
@@ -623,4 +624,65 @@ inline void TrackFrameFinish(CorbKfStore* frames, int curSlot, CorbKfStore* kfs,
 {
     check(corb_track_frame_finish(frames, curSlot, kfs, refSlot, map, 1, Tcr), "corb_track_frame_finish");
 }
+
+// ---- the camera trajectory (include/corb_trajectory.h): the log Tracking::Track appends, KeyFrame::mTcp, and System's three dumps under the reference's names ----
+struct TrajectoryRows { int width = 0; std::vector<float> rows; std::vector<double> times; std::vector<int32_t> entry; std::vector<uint64_t> ids; CorbTrajStats stats{}; int n() const { return (int)times.size(); } };
+class Trajectory {
+    CorbTrajectory* h_ = nullptr; int capacity_, sensor_;
+public:
+    // sensor: System::eSensor (0 MONOCULAR, 1 STEREO, 2 RGBD): SaveTrajectoryTUM / KITTI refuse a monocular system (System.cc:256, :352)
+    Trajectory(CorbCovis* graph, int capacityFrames, int sensor) : capacity_(capacityFrames), sensor_(sensor) { check(corb_traj_create(graph, capacityFrames, &h_), "corb_traj_create"); }
+    ~Trajectory() { corb_traj_destroy(h_); }
+    Trajectory(const Trajectory&) = delete;
+    Trajectory& operator=(const Trajectory&) = delete;
+    CorbTrajectory* handle() const { return h_; }
+    void Reset() { check(corb_traj_reset(h_), "corb_traj_reset"); }
+    // the end of Tracking::Track (:485-504): Tcr as TrackFrameFinish returned it, or nullptr: computed on the device from the two records
+    void Append(CorbKfStore* frames, int curSlot, int refSlot, const float* Tcr, double timestamp, bool lost) { check(corb_traj_append(h_, frames, curSlot, refSlot, Tcr, timestamp, lost ? 1 : 0), "corb_traj_append"); }
+    void AppendLost(bool lost = true) { check(corb_traj_append(h_, nullptr, -1, 0, nullptr, 0.0, lost ? 1 : 0), "corb_traj_append"); }       // the `else`: mlbLost.push_back(mState==LOST)
+    void SetKeyFrameTime(int slot, double t) { check(corb_traj_set_keyframe_time(h_, slot, t), "corb_traj_set_keyframe_time"); }
+    double KeyFrameTime(int slot) const { double t = 0; check(corb_traj_get_keyframe_time(h_, slot, &t), "corb_traj_get_keyframe_time"); return t; }
+    // KeyFrame::SetBadFlag (:666), after corb_covis_reparent_children answered reference_sets_bad and before the caller sets CORB_KF_BAD
+    void SetBadPose(int slot) { check(corb_traj_set_bad_pose(h_, slot), "corb_traj_set_bad_pose"); }
+    void SetTcp(int slot, const float* Tcp) { check(corb_traj_set_tcp(h_, slot, Tcp), "corb_traj_set_tcp"); }
+    void GetTcp(int slot, float* Tcp) const { check(corb_traj_get_tcp(h_, slot, Tcp), "corb_traj_get_tcp"); }
+    std::vector<CorbTrajEntry> Entries() const
+    {
+        std::vector<CorbTrajEntry> e((size_t)capacity_); int n = 0;
+        check(corb_traj_get_entries(h_, e.data(), capacity_, &n), "corb_traj_get_entries");
+        e.resize((size_t)n);
+        return e;
+    }
+    TrajectoryRows Frames(int format, int originSlot = -1) const
+    {
+        TrajectoryRows o; o.width = format == 0 ? 12 : 7;
+        o.rows.resize((size_t)capacity_ * o.width); o.times.resize((size_t)capacity_); o.entry.resize((size_t)capacity_);
+        int n = 0;
+        check(corb_traj_frames(h_, originSlot, format, o.rows.data(), o.times.data(), o.entry.data(), capacity_, &n, &o.stats), "corb_traj_frames");
+        o.rows.resize((size_t)n * o.width); o.times.resize((size_t)n); o.entry.resize((size_t)n);
+        return o;
+    }
+    TrajectoryRows KeyFrames(int maxKeyFrames) const
+    {
+        TrajectoryRows o; o.width = 7;
+        o.rows.resize((size_t)maxKeyFrames * 7); o.times.resize((size_t)maxKeyFrames); o.ids.resize((size_t)maxKeyFrames);
+        int n = 0;
+        check(corb_traj_keyframes(h_, o.rows.data(), o.times.data(), o.ids.data(), maxKeyFrames, &n), "corb_traj_keyframes");
+        o.rows.resize((size_t)n * 7); o.times.resize((size_t)n); o.ids.resize((size_t)n);
+        return o;
+    }
+    static std::string Format(int kind, const TrajectoryRows& r)
+    {
+        size_t len = 0;
+        const int rc = corb_traj_format_rows(kind, r.rows.data(), r.times.data(), r.n(), nullptr, 0, &len);
+        if (rc != CORB_ERR_CAPACITY) check(rc, "corb_traj_format_rows");
+        std::string s(len, '\0');
+        if (len) check(corb_traj_format_rows(kind, r.rows.data(), r.times.data(), r.n(), &s[0], len, &len), "corb_traj_format_rows");
+        return s;
+    }
+    // false: "ERROR: SaveTrajectoryTUM cannot be used for monocular." -- nothing is written
+    bool SaveTrajectoryTUM(const std::string& filename, int originSlot = -1) { if (sensor_ == 0) return false; check(corb_traj_save(h_, originSlot, 1, filename.c_str()), "corb_traj_save"); return true; }
+    bool SaveTrajectoryKITTI(const std::string& filename, int originSlot = -1) { if (sensor_ == 0) return false; check(corb_traj_save(h_, originSlot, 0, filename.c_str()), "corb_traj_save"); return true; }
+    void SaveKeyFrameTrajectoryTUM(const std::string& filename) { check(corb_traj_save(h_, -1, 2, filename.c_str()), "corb_traj_save"); }
+};
 }  // namespace corb
