@@ -8,6 +8,7 @@ from tests/, bench.py and __graft_entry__.py.  It has two layers:
   _abi_tracklocal.py  the same for the eighth header, include/corb_track_local_map.h (bind_tracklocal())
   _abi_trackframe.py  the same for the ninth header, include/corb_track_frame.h (bind_trackframe())
   _abi_traj.py        the same for the tenth header, include/corb_trajectory.h (bind_traj())
+  _abi_loopdetect.py  the same for the eleventh header, include/corb_loop_detect.h (bind_loopdetect())
   __init__.py  (this file) load(), the handle owner, and the classes and functions that marshal numpy
                arrays into the calls -- about 1900 lines, most of them array marshalling
 Class / method names mirror the reference (ORBextractor::operator(), ORBmatcher::SearchByBoW /
@@ -24,6 +25,7 @@ from ._abi_fusion import *  # noqa: F401,F403 -- include/corb_map_fusion.h: a ta
 from ._abi_tracklocal import *  # noqa: F401,F403 -- include/corb_track_local_map.h: likewise (see _abi_tracklocal.py)
 from ._abi_trackframe import *  # noqa: F401,F403 -- include/corb_track_frame.h: likewise (see _abi_trackframe.py)
 from ._abi_traj import *  # noqa: F401,F403 -- include/corb_trajectory.h: likewise (see _abi_traj.py)
+from ._abi_loopdetect import *  # noqa: F401,F403 -- include/corb_loop_detect.h: likewise (see _abi_loopdetect.py)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libcorb_accel.so")
@@ -45,7 +47,7 @@ def load():
         if not os.path.exists(LIB_PATH):
             raise CorbError("libcorb_accel.so is not built (run `python -c 'import __graft_entry__ as g; g.build()'`); "
                             "there is no CPU fallback")
-        _lib = bind_traj(bind_trackframe(bind_tracklocal(bind_fusion(bind(C.CDLL(LIB_PATH))))))
+        _lib = bind_loopdetect(bind_traj(bind_trackframe(bind_tracklocal(bind_fusion(bind(C.CDLL(LIB_PATH)))))))
     return _lib
 
 
@@ -1489,6 +1491,74 @@ def traj_format_rows(kind, rows, times=None):
     if n.value:
         _chk(load().corb_traj_format_rows(kind, _p(r), _p(t), len(r), buf, n.value, C.byref(n)), "corb_traj_format_rows")
     return buf.raw[:n.value]
+
+
+class LoopDetector(_Handle):
+    """LoopClosing::DetectLoop on records (corb_loop_detector_*, corb_loop_detect*, include/corb_loop_detect.h) over a Covisibility graph and a KeyFrameDatabase:
+    mLastLoopKFid, mnCovisibilityConsistencyTh and mvConsistentGroups live on the device.  A detect call answers one dict per consumed keyframe:
+    outcome (LOOP_*), min_score_bits, cand_entries, cand_slots, enough (positions in the candidate list), n_groups."""
+
+    _destroy = "corb_loop_detector_destroy"
+
+    def __init__(self, covis, db, max_candidates=64, max_groups=128):
+        self.g = covis; self.db = db; self.max_candidates = int(max_candidates); self.max_groups = int(max_groups); self.n_slots = covis.kf.capacity
+        self._create("corb_loop_detector_create", covis.h, db.h, self.max_candidates, self.max_groups)
+
+    def bind(self, slots, entries):
+        s = np.ascontiguousarray(np.atleast_1d(slots), np.int32); e = np.ascontiguousarray(np.atleast_1d(entries), np.int32)
+        if len(s) != len(e):
+            raise CorbError("LoopDetector.bind: slots and entries differ in length")
+        _chk(load().corb_loop_detector_bind(self.h, _p(s), _p(e), len(s)), "corb_loop_detector_bind")
+
+    def set_last_loop(self, kf_id):
+        _chk(load().corb_loop_detector_set_last_loop(self.h, int(kf_id)), "corb_loop_detector_set_last_loop")
+
+    def get_last_loop(self):
+        v = C.c_uint64(0)
+        _chk(load().corb_loop_detector_get_last_loop(self.h, C.byref(v)), "corb_loop_detector_get_last_loop")
+        return int(v.value)
+
+    def reset(self):
+        _chk(load().corb_loop_detector_reset(self.h), "corb_loop_detector_reset")
+
+    def clear_groups(self):
+        _chk(load().corb_loop_detector_clear_groups(self.h), "corb_loop_detector_clear_groups")
+
+    def drop_slot(self, slot):
+        _chk(load().corb_loop_detector_drop_slot(self.h, int(slot)), "corb_loop_detector_drop_slot")
+
+    def get_groups(self):
+        """mvConsistentGroups in order: [(member slots ascending, counter)]"""
+        G = self.max_groups; cnt = np.zeros(G, np.int32); off = np.zeros(G + 1, np.int32); mem = np.zeros(max(G * self.n_slots, 1), np.int32)
+        ng = C.c_int(0); nm = C.c_int(0)
+        _chk(load().corb_loop_detector_get_groups(self.h, _p(cnt), _p(off), _p(mem), G, G * self.n_slots, C.byref(ng), C.byref(nm)), "corb_loop_detector_get_groups")
+        return [(mem[off[g]:off[g + 1]].tolist(), int(cnt[g])) for g in range(ng.value)]
+
+    @staticmethod
+    def _answer(r, ce, cs, en):
+        nc, ne = int(r["n_candidates"]), int(r["n_enough"])
+        return dict(outcome=int(r["outcome"]), min_score_bits=int(r["min_score_bits"]), cand_entries=ce[:nc].tolist(), cand_slots=cs[:nc].tolist(), enough=en[:ne].tolist(),
+                    n_groups=int(r["n_groups"]))
+
+    def detect(self, slot):
+        """corb_loop_detect for mpCurrentKF = the record in `slot`.  After a CorbError, last_result holds what the call reported (n_candidates on a capacity error)."""
+        MC = self.max_candidates
+        r = np.zeros(1, LOOP_RESULT_DTYPE); ce = np.zeros(MC, np.int32); cs = np.zeros(MC, np.int32); en = np.zeros(MC, np.int32)
+        rc = load().corb_loop_detect(self.h, int(slot), r.ctypes.data_as(C.POINTER(LoopDetectResult)), _p(ce), _p(cs), _p(en))
+        self.last_result = r[0].copy()
+        _chk(rc, "corb_loop_detect")
+        return self._answer(r[0], ce, cs, en)
+
+    def detect_queue(self, slots):
+        """corb_loop_detect_queue for mlpLoopKeyFrameQueue = slots: the answers of the consumed keyframes.  A CorbError leaves them in last_answers."""
+        s = np.ascontiguousarray(np.atleast_1d(slots), np.int32); n = len(s); MC = self.max_candidates
+        r = np.zeros(max(n, 1), LOOP_RESULT_DTYPE); ce = np.zeros((max(n, 1), MC), np.int32); cs = np.zeros_like(ce); en = np.zeros_like(ce); done = C.c_int(0)
+        rc = load().corb_loop_detect_queue(self.h, _p(s), n, r.ctypes.data_as(C.POINTER(LoopDetectResult)), _p(ce), _p(cs), _p(en), C.byref(done))
+        self.last_answers = [self._answer(r[k], ce[k], cs[k], en[k]) for k in range(done.value)]
+        _chk(rc, "corb_loop_detect_queue")
+        return self.last_answers
+
+    DetectLoop = detect
 
 
 class KeyFrameStore(_Handle):

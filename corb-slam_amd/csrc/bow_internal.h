@@ -68,3 +68,16 @@ void corb_launch_bow_transform(const BowVocView& v, const BowSetDev* sets, int n
 void corb_launch_bow_descend(const BowVocView& v, const BowSetDev* sets, int n_sets, int max_n, int32_t* feat_word, uint32_t* feat_node, hipStream_t s);      // the descent alone, levelsup 0
 void corb_launch_kfdb_detect(const BowDbDev& d, int kind, int query_entry, int query_words, unsigned long long query_id, int n_connected, float min_score, hipStream_t s);
 void corb_launch_kfdb_score(const BowDbDev& d, int entry_a, int words_a, const int* entries_b, int n, hipStream_t s);
+
+// The loop query of LoopClosing::DetectLoop with everything but the query entry in device memory (corb_loopdetect.cpp).  The kernel that fills it has also set
+// d.conn for conn_list[0 .. n_conn).  skip != 0: every kernel of the launch returns at once and nothing of d changes.
+struct BowLoopQuery {
+    int skip;
+    int n_score;                        // entries of score_entries: the covisible keyframes minScore is taken over
+    int n_conn;                         // entries of d.conn_list whose d.conn flag is set
+    float min_score;                    // written by the launch: min over float(score(query, score_entries[i])), from 1.0f (LoopClosing.cc:124-137)
+    unsigned long long id;              // the query's mnId
+};
+// scatter, the scores of score_entries (at most max_score of them) with their minimum into q->min_score, then count / score / select as corb_launch_kfdb_detect(kind 0)
+// runs them with q->id and q->min_score, then the unscatter, which also clears the d.conn flags.  d.out holds the candidates as after corb_launch_kfdb_detect
+void corb_launch_kfdb_loop_query(const BowDbDev& d, int query_entry, int query_words, BowLoopQuery* q, const int* score_entries, int max_score, hipStream_t s);

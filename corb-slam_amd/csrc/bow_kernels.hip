@@ -14,6 +14,8 @@
 //   kfdb_select_kernel     : one workgroup: bitonic sort of the kept entries by that key (the reference's list order), bow_accumulate per entry, the maximum, the 0.75
 //                            threshold, first appearance per best keyframe by an atomic minimum of positions, and an ordered ballot compaction of the candidates
 //   kfdb_score_list_kernel : corb_kfdb_score: one wavefront per listed entry, the same in-order sum
+//   kfdb_*_q_kernel        : the same bodies for the loop query of corb_loop_detect, whose id, minScore and connected set never visit the host: read from a
+//                            BowLoopQuery in device memory, every kernel a no-op while its skip flag is set; kfdb_min_score_q_kernel is the minScore loop itself
 // No scalar memory writes, no device-side printf / assert; every launch is on the caller's stream.
 #include "bow_internal.h"
 #include "bow_device.h"
@@ -149,7 +151,7 @@ template <bool TIMED> __device__ __forceinline__ double kfdb_wave_score(const Bo
     return bow_wave_score<TIMED>(d.words + (size_t)e * d.max_words, d.values + (size_t)e * d.max_words, d.n_words[e], lane, [dense](uint32_t w) { return dense[w]; }, sum_ticks);
 }
 
-__global__ __launch_bounds__(256) void kfdb_count_kernel(BowDbDev d, int kind, unsigned long long id)
+__device__ __forceinline__ void kfdb_count_body(const BowDbDev& d, int kind, unsigned long long id)
 {
     const int e = blockIdx.x * 4 + (int)threadIdx.x / 64, lane = threadIdx.x & 63;
     if (e >= d.capacity) return;
@@ -166,7 +168,9 @@ __global__ __launch_bounds__(256) void kfdb_count_kernel(BowDbDev d, int kind, u
     if (lane == 0) { d.pushed[e] = pushed ? 1 : 0; d.first_word[e] = first; }
 }
 
-__global__ __launch_bounds__(256) void kfdb_score_kernel(BowDbDev d, int kind, float min_score, unsigned long long* ticks)
+__global__ __launch_bounds__(256) void kfdb_count_kernel(BowDbDev d, int kind, unsigned long long id) { kfdb_count_body(d, kind, id); }
+
+__device__ __forceinline__ void kfdb_score_body(const BowDbDev& d, int kind, float min_score, unsigned long long* ticks)
 {
     const unsigned long long t_begin = ticks ? wall_clock64() : 0; unsigned long long t_sum = 0;
     const int e = blockIdx.x * 4 + (int)threadIdx.x / 64, lane = threadIdx.x & 63;
@@ -184,7 +188,9 @@ __global__ __launch_bounds__(256) void kfdb_score_kernel(BowDbDev d, int kind, f
     if (ticks) { atomicAdd(&ticks[2], t_sum); atomicAdd(&ticks[3], wall_clock64() - t_begin); }
 }
 
-__global__ __launch_bounds__(1024) void kfdb_select_kernel(BowDbDev d, int kind, unsigned long long id, float min_score)
+__global__ __launch_bounds__(256) void kfdb_score_kernel(BowDbDev d, int kind, float min_score, unsigned long long* ticks) { kfdb_score_body(d, kind, min_score, ticks); }
+
+__device__ __forceinline__ void kfdb_select_body(const BowDbDev& d, int kind, unsigned long long id, float min_score)
 {
     __shared__ float red[1024]; __shared__ int wave_count[16];
     const int tid = threadIdx.x, T = blockDim.x, S = d.ctr[1];
@@ -226,7 +232,9 @@ __global__ __launch_bounds__(1024) void kfdb_select_kernel(BowDbDev d, int kind,
     if (tid == 0) d.out[0] = n_out;
 }
 
-__global__ __launch_bounds__(256) void kfdb_score_list_kernel(BowDbDev d, const int* entries, int n)
+__global__ __launch_bounds__(1024) void kfdb_select_kernel(BowDbDev d, int kind, unsigned long long id, float min_score) { kfdb_select_body(d, kind, id, min_score); }
+
+__device__ __forceinline__ void kfdb_score_list_body(const BowDbDev& d, const int* entries, int n)
 {
     const int i = blockIdx.x * 4 + (int)threadIdx.x / 64, lane = threadIdx.x & 63;
     if (i >= n) return;
@@ -235,6 +243,31 @@ __global__ __launch_bounds__(256) void kfdb_score_list_kernel(BowDbDev d, const 
     const double s = d.n_words[e] > 0 ? kfdb_wave_score<false>(d, e, lane, unused) : bow_score_finish(0.0);
     if (lane == 0) d.score_out[i] = s;
 }
+
+__global__ __launch_bounds__(256) void kfdb_score_list_kernel(BowDbDev d, const int* entries, int n) { kfdb_score_list_body(d, entries, n); }
+
+// ---- the loop query with its id, minScore and connected set in device memory (BowLoopQuery, bow_internal.h): the bodies above behind q->skip ----
+__global__ void kfdb_scatter_q_kernel(BowDbDev d, int q, int nq, const BowLoopQuery* p, int set)
+{
+    if (p->skip) return;
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < nq) d.dense[d.words[(size_t)q * d.max_words + i]] = set ? d.values[(size_t)q * d.max_words + i] : 0.0;
+    if (i < 2 && set) d.ctr[i] = 0;
+    if (!set) for (int j = i; j < p->n_conn; j += gridDim.x * blockDim.x) d.conn[d.conn_list[j]] = 0;
+}
+__global__ __launch_bounds__(256) void kfdb_score_list_q_kernel(BowDbDev d, const int* entries, const BowLoopQuery* p) { if (!p->skip) kfdb_score_list_body(d, entries, p->n_score); }
+// minScore (LoopClosing.cc:124-137): each score rounded to float, the minimum from 1.0f (one wavefront)
+__global__ __launch_bounds__(64) void kfdb_min_score_q_kernel(BowDbDev d, BowLoopQuery* p)
+{
+    if (p->skip) return;
+    float m = 1.0f;
+    for (int i = threadIdx.x; i < p->n_score; i += 64) { const float s = (float)d.score_out[i]; if (s < m) m = s; }
+    for (int o = 32; o > 0; o >>= 1) { const float t = __shfl_xor(m, o); if (t < m) m = t; }
+    if (threadIdx.x == 0) p->min_score = m;
+}
+__global__ __launch_bounds__(256) void kfdb_count_q_kernel(BowDbDev d, const BowLoopQuery* p) { if (!p->skip) kfdb_count_body(d, 0, p->id); }
+__global__ __launch_bounds__(256) void kfdb_score_q_kernel(BowDbDev d, const BowLoopQuery* p) { if (!p->skip) kfdb_score_body(d, 0, p->min_score, nullptr); }
+__global__ __launch_bounds__(1024) void kfdb_select_q_kernel(BowDbDev d, const BowLoopQuery* p) { if (!p->skip) kfdb_select_body(d, 0, p->id, p->min_score); }
 
 // hipFuncAttributeMaxDynamicSharedMemorySize is a per-device attribute of a kernel: opt in once on every device that launches it
 hipError_t bow_opt_in_lds()
@@ -293,4 +326,17 @@ void corb_launch_kfdb_score(const BowDbDev& d, int a, int na, const int* entries
     hipLaunchKernelGGL(kfdb_scatter_kernel, dim3(g_sc), dim3(256), 0, s, d, a, na, 0, 1);
     hipLaunchKernelGGL(kfdb_score_list_kernel, dim3((n + 3) / 4), dim3(256), 0, s, d, entries_b, n);
     hipLaunchKernelGGL(kfdb_scatter_kernel, dim3(g_sc), dim3(256), 0, s, d, a, na, 0, 0);
+}
+
+void corb_launch_kfdb_loop_query(const BowDbDev& d, int q, int nq, BowLoopQuery* p, const int* score_entries, int max_score, hipStream_t s)
+{
+    const int g_sc = ((nq > 2 ? nq : 2) + 255) / 256, g_e = (d.capacity + 3) / 4;
+    const BowProfile pf = corb_bow_profile_state();
+    CORB_LAUNCH(pf.prof, "kfdb_scatter_kernel", kfdb_scatter_q_kernel, dim3(g_sc), dim3(256), 0, s, d, q, nq, p, 1);
+    if (max_score > 0) CORB_LAUNCH(pf.prof, "kfdb_score_list_kernel", kfdb_score_list_q_kernel, dim3((max_score + 3) / 4), dim3(256), 0, s, d, score_entries, p);
+    CORB_LAUNCH(pf.prof, "kfdb_min_score_kernel", kfdb_min_score_q_kernel, dim3(1), dim3(64), 0, s, d, p);
+    CORB_LAUNCH(pf.prof, "kfdb_count_kernel", kfdb_count_q_kernel, dim3(g_e), dim3(256), 0, s, d, p);
+    CORB_LAUNCH(pf.prof, "kfdb_score_kernel", kfdb_score_q_kernel, dim3(g_e), dim3(256), 0, s, d, p);
+    CORB_LAUNCH(pf.prof, "kfdb_select_kernel", kfdb_select_q_kernel, dim3(1), dim3(1024), 0, s, d, p);
+    CORB_LAUNCH(pf.prof, "kfdb_scatter_kernel", kfdb_scatter_q_kernel, dim3(g_sc), dim3(256), 0, s, d, q, nq, p, 0);
 }

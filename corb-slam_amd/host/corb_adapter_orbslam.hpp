@@ -33,6 +33,7 @@
 #include <chrono>
 #include <cstdlib>
 #include <cstring>
+#include <deque>
 #include <functional>
 #include <list>
 #include <map>
@@ -1343,6 +1344,68 @@ private:
     CorbKfDb* h_ = nullptr; int cap_, next_ = 0;
     std::map<KeyFrame*, int> entry_; std::vector<KeyFrame*> kf_;
 };
+
+// ---- LoopClosing's queue and DetectLoop (C/src/LoopClosing.cc:87-231) on records: include/corb_loop_detect.h through corb::LoopDetector ----
+//   void InsertKeyFrame(KeyFrame*)  :87-92 (mnId 0 is dropped)     bool CheckNewKeyFrames()  :94-98     bool DetectLoop()  :100-231
+// The keyframes are named by their records: slotOf(pKF) in the graph's keyframe store; the database is the adapter above, whose entry of a keyframe is bound to its
+// slot when the keyframe is first met here (InsertKeyFrame, or Bind for a keyframe that never passes the queue, such as mnId 0: every keyframe that can be covisible
+// with a queued one needs its entry).  DetectLoop() hands the queue's front, up to maxQueue keyframes, to ONE corb_loop_detect_queue call and pops what that call
+// consumed: it stops at the first detection, so a true return leaves mpCurrentKF and mvpEnoughConsistentCandidates as the reference's DetectLoop() leaves them for
+// ComputeSim3, and the keyframes behind it still queued.  A false return means the chunk held no detection (more may be queued: CheckNewKeyFrames()).
+// mvpEnoughConsistentCandidates is cleared where the reference clears it (:157): by a keyframe that had candidates.  GetBestCovisibilityKeyFrames(10) of the queued
+// keyframes is read before the call, as KeyFrameDatabase::add reads it.  SetNotErase / SetErase stay with the caller.
+namespace adapt {
+template <class KeyFrame, class Db>
+class LoopDetectT {
+public:
+    KeyFrame* mpCurrentKF = nullptr;
+    std::vector<KeyFrame*> mvpEnoughConsistentCandidates;
+    std::vector<KeyFrame*> vpCandidateKFs;               // of mpCurrentKF
+    std::vector<LoopDetection> consumed;                 // what the last DetectLoop() call processed, in queue order
+    template <class SlotOf>
+    LoopDetectT(CorbCovis* graph, Db& db, SlotOf slotOf, int nSlots, int maxCandidates, int maxGroups, int maxQueue = 8)
+        : det_(graph, db.handle(), maxCandidates, maxGroups), db_(db), slotOf_(slotOf), kfOfSlot_((size_t)nSlots, nullptr), maxQueue_(std::min(std::max(maxQueue, 1), CORB_LOOP_DETECT_MAX_QUEUE)) {}
+    LoopDetector& detector() { return det_; }
+    void Bind(KeyFrame* pKF)
+    {
+        const int s = slotOf_(pKF);
+        if (s < 0 || s >= (int)kfOfSlot_.size()) throw Error(CORB_ERR_ARG, "LoopDetectT::Bind: the keyframe has no slot");
+        if (kfOfSlot_[(size_t)s] == pKF) return;
+        if (kfOfSlot_[(size_t)s]) det_.DropSlot(s);      // another keyframe takes the slot: the one before can never match again
+        det_.Bind({s}, {db_.Entry(pKF)}); kfOfSlot_[(size_t)s] = pKF;
+    }
+    void InsertKeyFrame(KeyFrame* pKF) { Bind(pKF); if (pKF->mnId != 0) queue_.push_back(pKF); }        // :90
+    bool CheckNewKeyFrames() const { return !queue_.empty(); }
+    size_t QueueSize() const { return queue_.size(); }
+    void SetLastLoop(KeyFrame* pKF) { det_.SetLastLoop((uint64_t)pKF->mnId); }                          // mLastLoopKFid = mpCurrentKF->mnId (:591)
+    void ResetIfRequested() { queue_.clear(); det_.Reset(); }                                           // :644-648
+    bool DetectLoop()
+    {
+        consumed.clear();
+        if (queue_.empty()) return false;
+        const size_t n = std::min(queue_.size(), (size_t)maxQueue_);
+        std::vector<int32_t> slots;
+        for (size_t k = 0; k < n; k++) { db_.UpdateConnections(queue_[k]); slots.push_back(slotOf_(queue_[k])); }
+        consumed = det_.DetectLoopQueue(slots);
+        bool detected = false;
+        for (size_t k = 0; k < consumed.size(); k++) {
+            const LoopDetection& d = consumed[k];
+            mpCurrentKF = queue_[k];
+            vpCandidateKFs.clear();
+            for (int32_t s : d.candSlots) vpCandidateKFs.push_back(s >= 0 && s < (int)kfOfSlot_.size() ? kfOfSlot_[(size_t)s] : nullptr);
+            if (d.result.n_candidates > 0) {
+                mvpEnoughConsistentCandidates.clear();
+                for (int32_t i : d.enough) mvpEnoughConsistentCandidates.push_back(vpCandidateKFs[(size_t)i]);
+            }
+            detected = d.detected();
+        }
+        queue_.erase(queue_.begin(), queue_.begin() + (std::ptrdiff_t)consumed.size());
+        return detected;
+    }
+private:
+    LoopDetector det_; Db& db_; std::function<int(KeyFrame*)> slotOf_; std::vector<KeyFrame*> kfOfSlot_; std::deque<KeyFrame*> queue_; int maxQueue_;
+};
+}  // namespace adapt
 }  // namespace corb
 
 // ---- covisibility graph: what KeyFrame::UpdateConnections and its readers do, on the records (corb_covis_*) ----
@@ -1612,6 +1675,7 @@ using Initializer = corb::Initializer<Frame>;
 using ORBVocabulary = corb::ORBVocabulary;
 using KeyFrameDatabase = corb::KeyFrameDatabase<KeyFrame, Frame>;
 using MapFusionDetect = corb::adapt::MapFusionDetectT<KeyFrame, corb::KeyFrameDatabase<KeyFrame, Frame>>;
+using LoopDetect = corb::adapt::LoopDetectT<KeyFrame, corb::KeyFrameDatabase<KeyFrame, Frame>>;
 using Covisibility = corb::Covisibility<KeyFrame, corb::KeyFrameDatabase<KeyFrame, Frame>>;
 }  // namespace accel
 }  // namespace ORB_SLAM2

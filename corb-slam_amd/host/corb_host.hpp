@@ -18,6 +18,7 @@
 #include <corb_track_local_map.h>
 #include <corb_track_frame.h>
 #include <corb_trajectory.h>
+#include <corb_loop_detect.h>
 #include <algorithm>
 #include <cstdint>
 #include <cstring>
@@ -684,5 +685,69 @@ public:
     bool SaveTrajectoryTUM(const std::string& filename, int originSlot = -1) { if (sensor_ == 0) return false; check(corb_traj_save(h_, originSlot, 1, filename.c_str()), "corb_traj_save"); return true; }
     bool SaveTrajectoryKITTI(const std::string& filename, int originSlot = -1) { if (sensor_ == 0) return false; check(corb_traj_save(h_, originSlot, 0, filename.c_str()), "corb_traj_save"); return true; }
     void SaveKeyFrameTrajectoryTUM(const std::string& filename) { check(corb_traj_save(h_, -1, 2, filename.c_str()), "corb_traj_save"); }
+};
+
+// ---- LoopClosing::DetectLoop on records (include/corb_loop_detect.h): a plain mirror over the C calls ----
+// one keyframe's DetectLoop: the outcome and counts, vpCandidateKFs as database entries and store slots, mvpEnoughConsistentCandidates as positions in them
+struct LoopDetection { CorbLoopDetectResult result{}; std::vector<int32_t> candEntries, candSlots, enough; bool detected() const { return result.outcome == CORB_LOOP_DETECTED; } };
+struct ConsistentGroups { std::vector<int32_t> counters, offsets, members; int n() const { return (int)counters.size(); } };
+class LoopDetector {
+    CorbLoopDetector* h_ = nullptr; int maxCandidates_, maxGroups_;
+    LoopDetection take(const CorbLoopDetectResult& r, const int32_t* ce, const int32_t* cs, const int32_t* en) const
+    {
+        LoopDetection d; d.result = r;
+        const int nc = std::min(std::max(r.n_candidates, 0), maxCandidates_), ne = std::min(std::max(r.n_enough, 0), maxCandidates_);
+        d.candEntries.assign(ce, ce + nc); d.candSlots.assign(cs, cs + nc); d.enough.assign(en, en + ne);
+        return d;
+    }
+public:
+    LoopDetector(CorbCovis* graph, CorbKfDb* db, int maxCandidates, int maxGroups) : maxCandidates_(maxCandidates), maxGroups_(maxGroups)
+    {
+        check_abi();
+        check(corb_loop_detector_create(graph, db, maxCandidates, maxGroups, &h_), "corb_loop_detector_create");
+    }
+    ~LoopDetector() { corb_loop_detector_destroy(h_); }
+    LoopDetector(const LoopDetector&) = delete;
+    LoopDetector& operator=(const LoopDetector&) = delete;
+    CorbLoopDetector* handle() const { return h_; }
+    int maxCandidates() const { return maxCandidates_; }
+    void Bind(const std::vector<int32_t>& slots, const std::vector<int32_t>& entries)
+    {
+        if (slots.size() != entries.size()) throw std::invalid_argument("LoopDetector::Bind: slots and entries differ in length");
+        check(corb_loop_detector_bind(h_, slots.data(), entries.data(), (int)slots.size()), "corb_loop_detector_bind");
+    }
+    void SetLastLoop(uint64_t id) { check(corb_loop_detector_set_last_loop(h_, id), "corb_loop_detector_set_last_loop"); }       // mLastLoopKFid = mpCurrentKF->mnId (:591)
+    uint64_t LastLoop() const { uint64_t id = 0; check(corb_loop_detector_get_last_loop(h_, &id), "corb_loop_detector_get_last_loop"); return id; }
+    void Reset() { check(corb_loop_detector_reset(h_), "corb_loop_detector_reset"); }                                            // :647
+    void ClearGroups() { check(corb_loop_detector_clear_groups(h_), "corb_loop_detector_clear_groups"); }
+    void DropSlot(int slot) { check(corb_loop_detector_drop_slot(h_, slot), "corb_loop_detector_drop_slot"); }
+    ConsistentGroups Groups(int maxSlots) const
+    {
+        ConsistentGroups g; g.counters.resize((size_t)maxGroups_); g.offsets.resize((size_t)maxGroups_ + 1); g.members.resize((size_t)maxGroups_ * (size_t)std::max(maxSlots, 1));
+        int ng = 0, nm = 0;
+        check(corb_loop_detector_get_groups(h_, g.counters.data(), g.offsets.data(), g.members.data(), maxGroups_, (int)g.members.size(), &ng, &nm), "corb_loop_detector_get_groups");
+        g.counters.resize((size_t)ng); g.offsets.resize((size_t)ng + 1); g.members.resize((size_t)nm);
+        return g;
+    }
+    // bool LoopClosing::DetectLoop() for mpCurrentKF = the record in `slot`
+    LoopDetection DetectLoop(int slot)
+    {
+        const size_t mc = (size_t)maxCandidates_;
+        std::vector<int32_t> ce(mc), cs(mc), en(mc); CorbLoopDetectResult r; std::memset(&r, 0, sizeof(r));
+        check(corb_loop_detect(h_, slot, &r, ce.data(), cs.data(), en.data()), "corb_loop_detect");
+        return take(r, ce.data(), cs.data(), en.data());
+    }
+    // DetectLoop for the queue in order, up to and with the first detection: one entry per consumed keyframe
+    std::vector<LoopDetection> DetectLoopQueue(const std::vector<int32_t>& slots)
+    {
+        const size_t n = slots.size(), mc = (size_t)maxCandidates_;
+        std::vector<CorbLoopDetectResult> r(std::max(n, (size_t)1)); std::vector<int32_t> ce(std::max(n, (size_t)1) * mc), cs(ce.size()), en(ce.size());
+        std::memset(r.data(), 0, r.size() * sizeof(CorbLoopDetectResult));
+        int done = 0;
+        check(corb_loop_detect_queue(h_, slots.data(), (int)n, r.data(), ce.data(), cs.data(), en.data(), &done), "corb_loop_detect_queue");
+        std::vector<LoopDetection> out;
+        for (int k = 0; k < done; k++) out.push_back(take(r[(size_t)k], ce.data() + (size_t)k * mc, cs.data() + (size_t)k * mc, en.data() + (size_t)k * mc));
+        return out;
+    }
 };
 }  // namespace corb

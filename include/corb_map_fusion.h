@@ -19,7 +19,7 @@ extern "C" {
  * for i = 0 .. n_queries - 1 in list order.  cand[cand_offset[i] .. cand_offset[i + 1]) = the candidates of query i in the reference's order; afterwards the six
  * fields of every entry (corb_kfdb_get_state) are what that sequence of single calls leaves, the stale mRelocScore a neighbour adds included (an entry's fields at
  * query i come from the most recent earlier query that shared a word with it, of this call or before it).
- * CORB_ERR_ARG with nothing changed: kind 0 (one query per keyframe by nature: it needs a connected set and a minScore each), more than
+ * CORB_ERR_ARG with nothing changed: kind 0 (one query per keyframe by nature: it needs a connected set and a minScore each; corb_loop_detect.h takes both from the device), more than
  * CORB_KFDB_BATCH_MAX_QUERIES queries, a query entry outside the database or without a BowVector (it may be in the database or not, and may be listed twice under
  * different ids), two equal query_ids.  n_queries == 0: CORB_OK, cand_offset[0] = 0.  More than cap candidates in all: CORB_ERR_OVERFLOW with *n_total = the room
  * needed, cand_offset complete and the fields updated all the same (as the single call does).
